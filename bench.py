@@ -28,11 +28,18 @@ MPN_BENCH_SHARE_GPU=1 (test only, stated in config.parallelism) maps every rank 
 gloo, so that `--gpus 2` exercises the launch / rank / drift-stream / reduction logic on a one-GPU box (RCCL refuses two ranks on
 one device).
 
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step
+(the time of one timed step), the config and the per-rank rates.  `--dump-outputs DIR` writes what the last timed step handed its
+caller (rank 0): DIR/detections.npy = the kept rows {x1,y1,x2,y2,score,class} [min(n, top_cap), 6] float32 and
+DIR/n_detections.npy = n (the untruncated survivor count) float64; the inputs are seeded, so two builds compare output for output.
+
+`--full` adds the auxiliary legs below (never the metric; each takes runs of its own after the timed region).
+
 After the timed K steps a `sustained` leg repeats the same host-fed step for >= 3 s (>= 800 steps) with the GPU's clock and power
 sampled beside it (sysfs hwmon of the device's PCI function, else rocm-smi): SURVEY §8(d) says "steady state", and a 70 ms timed
 region cannot show what DVFS does over a dataset-length run (Tester_FRCNN.lua:150-157).  `--sustained-seconds 0` skips it.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+With --full, ONE JSON line (rank 0) with extra objects:
   "roofline"      dominant kernel group (the Winograd convolutions), fp32-MFMA bound.  `achieved` / `frac` count the FLOPs the
                   matrix pipe EXECUTES (Winograd F(2x2,3x3): 16 multiplies per 4 outputs instead of 36 => direct-conv FLOPs /
                   2.25), so frac <= 1; `algorithmic_equiv_*` is the direct-convolution-equivalent rate (can exceed the peak).
@@ -698,6 +705,15 @@ def pin_to_gpu_numa_node(dev_index):
         return "none (%s)" % str(e).splitlines()[-1][:80]
 
 
+def dump_outputs(path, dets, n_dets):
+    """--dump-outputs: the (d_dets, *d_n_dets) pair of the last timed step, rows clamped to top_cap as include/mpn.h asks a caller to"""
+    os.makedirs(path, exist_ok=True)
+    n = int(n_dets.reshape(-1)[0].item())
+    rows = max(0, min(n, dets.size(0)))
+    np.save(os.path.join(path, "detections.npy"), dets[:rows].detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "n_detections.npy"), np.array([n], np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with no launcher: run N ranks of this script under torch.distributed.run."""
     s = socket.socket()
@@ -735,6 +751,8 @@ def latency_mode(args, torch, dist, models, parallel, comm, rank, world, dev, sh
         im_dev.copy_(im_host, non_blocking=True)
         boxes_dev.copy_(boxes_host, non_blocking=True)
 
+    last = {}
+
     def timed(fn, with_upload=True):
         for _ in range(args.warmup):
             upload(); fn()
@@ -745,7 +763,7 @@ def latency_mode(args, torch, dist, models, parallel, comm, rank, world, dev, sh
         for _ in range(args.steps):
             if with_upload:
                 upload()
-            fn()
+            last["out"] = fn()
             torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -782,6 +800,8 @@ def latency_mode(args, torch, dist, models, parallel, comm, rank, world, dev, sh
         def gather_final(d, n):
             return comm.gather_dets(d, n)
     ms = timed(sharded)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last["out"])
     ms_res = timed(sharded, with_upload=False)
     # outside the timed loops: every rank must hold the SAME final detections (one extra gather of the ~11-KB record), checked on rank 0
     dets_f, n_f = sharded()
@@ -927,13 +947,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="throughput mode: after the timed steps, also the auxiliary legs (inputs-resident passes, `sustained`, the profiled roofline / "
+                         "kernels leg, `power_sensitivity`, `fc_split3_aux`, `cpu_baseline`).  Off: the line carries only what the timed steps measure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's detections (detections.npy, n_detections.npy) to DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rois", type=int, default=250)
     ap.add_argument("--config", default="c2", choices=sorted(OTHER_CONFIGS) + ["c2"],
                     help="c2 (default) = the headline line, BASELINE configs[1].  c1 / c3 / c4 / c5 = the other BASELINE configs, each with its "
                          "own metric string (never the headline): same timed loop, whole-path rates only")
     ap.add_argument("--dtype", default=None, choices=["f32", "bf16"], help="c4 only (c5 is bf16, the rest fp32)")
-    ap.add_argument("--no-fc-split3-leg", action="store_true", help="c2 only: skip the auxiliary `fc_split3_aux` leg (the same model with MPN_FC_SPLIT3)")
+    ap.add_argument("--no-fc-split3-leg", action="store_true", help="c2 only, --full: skip the auxiliary `fc_split3_aux` leg (the same model with MPN_FC_SPLIT3)")
     ap.add_argument("--fc-arith", default="fp32", choices=["fp32", "split3"],
                     help="c2 / c3 only.  split3 = fc6 / fc7 on the bf16 matrix pipe (both operands as exact three-plane bf16 splits, six products, fp32 accumulate: "
                          "include/mpn.h MPN_FC_SPLIT3) — an AUXILIARY line with its own metric string and dtype, never the headline")
@@ -943,12 +968,12 @@ def main():
     ap.add_argument("--mixed-sizes", action="store_true",
                     help="c2 only: after the headline legs, a sustained leg over a dataset-shaped stream of DIFFERENT image sizes (bench.MIXED_SIZES, getImages' "
                          "rescale on the device) -> the `mixed_sizes` object; never the headline")
-    ap.add_argument("--no-power-sensitivity", action="store_true", help="c2 only: skip the `power_sensitivity` leg (fc6 alone, back to back; debug-flavour library)")
+    ap.add_argument("--no-power-sensitivity", action="store_true", help="c2 only, --full: skip the `power_sensitivity` leg (fc6 alone, back to back; debug-flavour library)")
     ap.add_argument("--mode", default="throughput", choices=["throughput", "latency"],
                     help="throughput (default) = the headline metric, images sharded over the ranks.  latency = ONE image's proposals and classes "
                          "sharded over the ranks (mpn_frcnn_test_one_sharded); its own metric string, never the headline")
     ap.add_argument("--sustained-seconds", type=float, default=3.0,
-                    help="after the timed region: the same host-fed step for at least this long (and >= 800 steps at the default), clock / power "
+                    help="--full: after the timed region, the same host-fed step for at least this long (and >= 800 steps at the default), clock / power "
                          "sampled beside it -> the `sustained` object of the JSON line; 0 = skip")
     ap.add_argument("--emulate-world", type=int, default=8,
                     help="latency mode on one GPU: also time rank 0's share of a world of this size (no all-gather), as a projection")
@@ -1077,7 +1102,7 @@ def main():
             b = (state["seq"] + rank) % n_rot
             cur = net.test_one_pipelined_host(im_host[b], boxes_host[b]) if host_fed else net.test_one_pipelined(im_dev, boxes_dev)
             gather(state["pending"])
-            state["pending"] = cur
+            state["pending"] = state["last"] = cur
             state["seq"] += 1
         return step
 
@@ -1143,15 +1168,51 @@ def main():
         out_s.update(sampler.summary())
         return out_s
 
+    def finish():
+        if comm is not None:
+            comm.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
     dt = timed(make_step(True))            # the metric: host image + boxes in, H2D inside the timed region
+    if args.dump_outputs and rank == 0:    # before any other leg reuses the handle's result buffers
+        dump_outputs(args.dump_outputs, *state["last"])
     per_rank = [args.steps * n_rois_cfg / t for t in state["per_rank_s"]]
     ranks_info = {"rccl_ranks": comm.rccl_ranks if comm is not None else 0,
                   "rccl_ranks_what": "ncclCommCount of the C-ABI communicator, cross-checked with ncclCommUserRank at init (mpn_comm_rccl_ranks); "
                                      "0 = no RCCL communicator (one rank, or the fallback / share-GPU test paths); -1 = this RCCL has no ncclCommCount: unverified",
                   "per_rank_proposals_per_s": {"min": round(min(per_rank), 1), "max": round(max(per_rank), 1),
                                                "all": [round(v, 1) for v in per_rank]}}
-    dt_res = min(timed(make_step(False)) for _ in range(2))  # inputs already resident in HBM (auxiliary figure: best of two passes)
     value = args.steps * n_rois_cfg * world / dt
+    if other is not None:
+        metric, dtype = other["metric"], other["dtype"]
+        config = {"workload": other["workload"] + "; host image + boxes uploaded inside the step",
+                  "parallelism": "image-sharded over %d rank%s, all-gather of scored boxes only via %s; cpu affinity: %s"
+                                 % (world, "" if world == 1 else "s", gather_via, affinity)}
+    else:
+        metric, dtype = "proposals/sec (1000 ROIs, 600x1000 img) VGG-16 Fast R-CNN", "f32"
+        config = {"workload": "VGG-16 Fast R-CNN, 1 image 600x1000 x 1000 ROIs per GPU per step, 21 classes, NMS 0.3, top-100 (BASELINE configs[1]); "
+                              "host image + boxes uploaded inside the step (pinned, copy stream, three staging sets)",
+                  "parallelism": "image-sharded over %d rank%s (one process per GPU), all-gather of scored boxes only via %s; cpu affinity: %s; "
+                                 "4 different pinned (image, proposals) sets in rotation, offset by rank"
+                                 % (world, "" if world == 1 else "s", gather_via, affinity)}
+    head = {"metric": metric, "value": round(value, 1), "unit": "proposals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": dtype, "data": "synthetic", "config": config}
+    if not args.full:  # the plain line: what the timed steps measured (and the opt-in mixed-size leg), no leg of its own
+        mixed = None
+        if args.mixed_sizes and other is None:
+            mixed = mixed_sizes_leg(torch, dist, models, P, dev, dev_index, world, rank, max(args.sustained_seconds, 1.0),
+                                    pin=mixed_pin if os.environ.get("MPN_BENCH_MIXED_PIN_LATE") != "1" else None)
+        if rank == 0:
+            out = dict(head, ranks=ranks_info)
+            if mixed is not None:
+                out["mixed_sizes"] = mixed
+            print(json.dumps(out))
+            sys.stdout.flush()
+        return finish()
+    dt_res = min(timed(make_step(False)) for _ in range(2))  # inputs already resident in HBM (auxiliary figure: best of two passes)
     value_res = args.steps * n_rois_cfg * world / dt_res
     sus = sustained(make_step(True), dt / args.steps)
     if sus is not None:
@@ -1196,13 +1257,8 @@ def main():
                 tj = json.load(open(tpath)).get(other["key"])
                 if tj and "dominant" in tj:
                     traffic, traffic_src = tj["dominant"], tj.get("_source")
-            out = {"metric": other["metric"], "value": round(value, 1), "unit": "proposals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                   "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                   "dtype": other["dtype"], "data": "synthetic",
-                   "config": {"workload": other["workload"] + "; host image + boxes uploaded inside the step",
-                              "parallelism": "image-sharded over %d rank%s, all-gather of scored boxes only via %s; cpu affinity: %s"
-                                             % (world, "" if world == 1 else "s", gather_via, affinity)},
-                   "value_inputs_resident": round(value_res, 1),
+            out = dict(head)
+            out.update({"value_inputs_resident": round(value_res, 1),
                    "sustained": sus, "ranks": ranks_info,
                    "whole_path": {"algorithmic_gflop_per_image": round(tot_alg / 1e9, 2), "executed_gflop_per_image": round(tot_ex / 1e9, 2),
                                   "executed_frac_of_%s_mfma_peak" % pk: round(value / world * (tot_ex / n_rois_cfg) / peak, 4),
@@ -1225,7 +1281,7 @@ def main():
                                 "how": "HIP events on the launch stream around each kernel group of the un-pipelined call, %d profiled steps after the timed "
                                        "region; achieved / frac count the FLOPs the matrix pipe EXECUTES (layers on the Winograd kernel: direct FLOPs / 2.25), "
                                        "algorithmic_equiv_frac the direct-convolution FLOPs" % args.steps},
-                   "kernels": kernels}
+                   "kernels": kernels})
             if world == 1 and not args.no_cpu_baseline and other.get("cpu_baseline"):
                 out["cpu_baseline"] = other["cpu_baseline"](im_np, boxes_np)
             if "split3" in other["key"] and "fc6" in kernels:
@@ -1237,12 +1293,7 @@ def main():
                                              "the six bf16 products run on the bf16 pipe (16x the fp32 MFMA rate)"}
             print(json.dumps(out))
             sys.stdout.flush()
-        if comm is not None:
-            comm.close()
-        if world > 1:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
+        return finish()
 
     # ---- roofline leg: same number of steps with HIP events around every kernel group (un-pipelined, single stream)
     net.set_profiling(True)
@@ -1314,16 +1365,8 @@ def main():
         achieved = executed[dom] / sec / 1e12
         total_flops = sum(f for f, _ in cf) + N_ROIS * 2.0 * (25088 * 4096 + 4096 * 4096 + 4096 * 105)
         total_exec = total_flops - flops["conv_wino"] + executed["conv_wino"]
-        out = {
-            "metric": "proposals/sec (1000 ROIs, 600x1000 img) VGG-16 Fast R-CNN",
-            "value": round(value, 1), "unit": "proposals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "VGG-16 Fast R-CNN, 1 image 600x1000 x 1000 ROIs per GPU per step, 21 classes, NMS 0.3, top-100 (BASELINE configs[1]); "
-                                   "host image + boxes uploaded inside the step (pinned, copy stream, three staging sets)",
-                       "parallelism": "image-sharded over %d rank%s (one process per GPU), all-gather of scored boxes only via %s; cpu affinity: %s; "
-                                      "4 different pinned (image, proposals) sets in rotation, offset by rank"
-                                      % (world, "" if world == 1 else "s", gather_via, affinity)},
+        out = dict(head)
+        out.update({
             "value_inputs_resident": round(value_res, 1), "ms_per_step_inputs_resident": round(dt_res / args.steps * 1e3, 4),
             "sustained": sus, "ranks": ranks_info,
             "whole_path": {"algorithmic_gflop_per_image": round(total_flops / 1e9, 2), "executed_gflop_per_image": round(total_exec / 1e9, 2),
@@ -1336,7 +1379,7 @@ def main():
                          "how": "HIP events on the launch stream around each kernel group (a layer's split-K reduce kernel included), "
                                 "%d profiled steps after the timed region" % args.steps},
             "kernels": kernels,
-        }
+        })
         if dom == "conv_wino":
             out["roofline"]["algorithm"] = ("Winograd F(2x2,3x3) in fp32: achieved / frac count the FLOPs the matrix pipe executes "
                                             "(direct-convolution FLOPs / 2.25); algorithmic_equiv_* is the direct-convolution-equivalent rate")
@@ -1360,11 +1403,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(P, im_np, boxes_np, args.cpu_rois)
         print(json.dumps(out))
         sys.stdout.flush()
-    if comm is not None:
-        comm.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

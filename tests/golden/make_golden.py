@@ -10,6 +10,8 @@ frcnn_small.npz a tiny VGG-shaped Fast R-CNN image: inputs, weights seed and the
 nms_dense.npz   (round 3; `python tests/golden/make_golden.py nms_dense` writes only this file) utils.nms_dense (utils.lua:402-462) as
                 restated by the oracle — a REGRESSION PIN of the restatement, not a reference vector (no Lua runtime exists here; the
                 order among bit-equal scores is the oracle's stable sort, unpinned against TH's quicksort).
+nms_ref_cases.npz (`python tests/golden/make_golden.py nms_ref_cases` writes only this file) inputs + outputs of the compiled nms.c on
+                the cases of tests/test_oracle_nms.py, which check them always and the live library too where oracle/_ref/ is built.
 """
 import os
 import sys
@@ -19,7 +21,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from conftest import random_scored_boxes  # noqa: E402
+from conftest import case_seed, random_scored_boxes  # noqa: E402
 from oracle import mpn_oracle as O  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,12 +41,38 @@ def make_nms_dense():
     np.savez_compressed(os.path.join(HERE, "nms_dense.npz"), **out)
 
 
+def make_nms_ref_cases():
+    """the cases of tests/test_oracle_nms.py that compare against the compiled nms.c, inputs + the reference's results, so that they run
+    where oracle/_ref/ cannot be built"""
+    assert O.have_ref(), "needs oracle/_ref/libnms_ref.so (make -C oracle ref, from the reference's sources)"
+    out = {}
+    for regime in ("distinct", "ties", "saturated", "allequal"):
+        for n in (1, 2, 7, 64, 65, 300, 1000):
+            sb = random_scored_boxes(np.random.default_rng(case_seed(regime, n)), n, regime, span=300.0 if n <= 65 else 1000.0)
+            out["%s_%d_in" % (regime, n)] = sb
+            for thr in (0.3, 0.5):
+                out["%s_%d_%g_keep" % (regime, n, thr)] = O.ref_nms(sb, thr)
+    tie = np.array([[0, 0, 10, 10, 0.5], [100, 100, 110, 110, 0.5], [200, 200, 210, 210, 0.9]], np.float32)
+    out["tie_in"], out["tie_keep"] = tie, O.ref_nms(tie, 0.3)
+    for regime in ("distinct", "ties"):
+        sb = random_scored_boxes(np.random.default_rng(11), 400, regime, span=400.0)
+        sb[:, 4] = np.maximum(sb[:, 4], 1e-3)
+        keep = O.ref_nms(sb, 0.3)
+        out["vote_%s_in" % regime], out["vote_%s_keep" % regime], out["vote_%s_out" % regime] = sb, keep, O.ref_bbox_vote(keep, sb, 0.5)
+    np.savez_compressed(os.path.join(HERE, "nms_ref_cases.npz"), **out)
+
+
 def main():
     if sys.argv[1:] == ["nms_dense"]:
         make_nms_dense()
         print("wrote nms_dense.npz")
         return
+    if sys.argv[1:] == ["nms_ref_cases"]:
+        make_nms_ref_cases()
+        print("wrote nms_ref_cases.npz")
+        return
     make_nms_dense()
+    make_nms_ref_cases()
     assert O.have_ref(), "needs oracle/_ref/libnms_ref.so (make -C oracle ref with /root/reference present)"
     out = {}
     rng = np.random.default_rng(20260923)

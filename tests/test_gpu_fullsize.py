@@ -485,6 +485,35 @@ def test_fullsize_pipelined_host_record_equals_serial(dev, full):
         assert torch.equal(d[: int(n.item())], ref[t % 3]), t
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_line_and_dumped_outputs(dev, full, tmp_path):
+    """`bench.py --steps 3 --warmup 2 --dump-outputs DIR`: the plain line carries the headline keys and none of the --full legs, and DIR
+    holds the record the LAST timed step handed back.  Step 5 of the run is rotation slot 0 = bench.synthetic_inputs(), so that record
+    must equal the serial mpn_frcnn_test_one on the same inputs and weights."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=540)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout.decode()[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["unit"] == "proposals/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["metric"] == "proposals/sec (1000 ROIs, 600x1000 img) VGG-16 Fast R-CNN"
+    assert out["value"] > 0 and abs(out["value"] - 1000 / (out["ms_per_step"] * 1e-3)) < 1e-3 * out["value"]
+    for k in ("value_inputs_resident", "sustained", "roofline", "kernels", "whole_path", "power_sensitivity", "fc_split3_aux", "cpu_baseline"):
+        assert k not in out, k
+    dets, n = np.load(str(tmp_path / "detections.npy")), np.load(str(tmp_path / "n_detections.npy"))
+    assert dets.dtype == np.float32 and n.dtype == np.float64 and n.shape == (1,)
+    d, k = full["net"].test_one_async(full["imd"], full["bd"])
+    torch.cuda.synchronize()
+    assert int(n[0]) == int(k.item()) > 0 and dets.shape == (min(int(n[0]), d.size(0)), 6)
+    assert np.array_equal(dets, d[: dets.shape[0]].cpu().numpy())
+
+
 def test_fullsize_properties(O, dev, full):
     net, imd, bd, boxes = full["net"], full["imd"], full["bd"], full["boxes"]
     N, C = boxes.shape[0], net.n_classes

@@ -162,7 +162,7 @@ def test_bench_two_ranks_on_one_gpu_share_mode(dev):
     WORLD_SIZE parsing, the gloo bootstrap group, the drift stream, the MAX-reduce of the elapsed time, rank-0-only printing.
     MPN_BENCH_SHARE_GPU=1 maps both ranks to device 0 and routes the record gather through gloo (RCCL refuses two ranks on one
     device); the line says so and is not a multi-GPU measurement."""
-    out = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"], {"MPN_BENCH_SHARE_GPU": "1"})
+    out = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline"], {"MPN_BENCH_SHARE_GPU": "1"})
     assert out["n_gpus"] == 2 and out["steps"] == 4 and out["warmup"] == 2 and out["scaling"] == "weak"
     assert "MPN_BENCH_SHARE_GPU=1" in out["config"]["parallelism"] and "NOT a multi-GPU measurement" in out["config"]["parallelism"]
     assert out["value"] > 0 and abs(out["value"] - 2 * 1000 * 4 / (out["ms_per_step"] * 4e-3)) < 1e-3 * out["value"]
@@ -178,7 +178,7 @@ def test_bench_two_ranks_fallback_group_branch(dev):
     all-reduce, the group is created, the gather runs through torch.distributed); on a one-GPU box the group is gloo (RCCL refuses two
     ranks on one device), on a multi-GPU node the same branch creates the RCCL group.  The line says which ran, carries the per-rank
     rates and rccl_ranks = 0."""
-    out = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--sustained-seconds", "0"],
+    out = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--sustained-seconds", "0"],
                      {"MPN_BENCH_SHARE_GPU": "1", "MPN_BENCH_FORCE_COMM_FAIL": "1"})
     par = out["config"]["parallelism"]
     assert "fallback group" in par and "MPN_BENCH_FORCE_COMM_FAIL=1" in par and "NOT a multi-GPU measurement" in par

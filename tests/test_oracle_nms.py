@@ -1,10 +1,18 @@
 """Pins the oracle's NMS family: (1) the reference's IoU known-answer vector (test.lua:40-52);
 (2) bit-for-bit agreement of the C restatement with the reference's OWN nms.c compiled unmodified
-(oracle/_ref/libnms_ref.so) over score regimes that exercise the tie-break history (nms.c:74-98)."""
+(oracle/_ref/libnms_ref.so) over score regimes that exercise the tie-break history (nms.c:74-98) — on its stored results
+(tests/golden/nms_ref_cases.npz) always, and on the library itself where oracle/_ref/ is built."""
+import os
+
 import numpy as np
 import pytest
 
 from conftest import case_seed, random_scored_boxes
+
+
+@pytest.fixture(scope="module")
+def ref_cases():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nms_ref_cases.npz"))
 
 
 def test_iou_known_answer(O):
@@ -26,15 +34,16 @@ def test_overlap_degenerate(O):
 @pytest.mark.parametrize("regime", ["distinct", "ties", "saturated", "allequal"])
 @pytest.mark.parametrize("n", [1, 2, 7, 64, 65, 300, 1000])
 @pytest.mark.parametrize("thr", [0.3, 0.5])
-def test_nms_matches_reference_c(O, regime, n, thr):
-    if not O.have_ref():
-        pytest.skip("oracle/_ref/libnms_ref.so not built (needs /root/reference)")
-    rng = np.random.default_rng(case_seed(regime, n))
-    sb = random_scored_boxes(rng, n, regime, span=300.0 if n <= 65 else 1000.0)
-    mine, idx = O.nms(sb, thr, return_index=True)
-    ref = O.ref_nms(sb, thr)
-    assert mine.shape == ref.shape and np.array_equal(mine, ref)
-    assert np.array_equal(sb[idx], mine)
+def test_nms_matches_reference_c(O, ref_cases, regime, n, thr):
+    cases = [(ref_cases["%s_%d_in" % (regime, n)], ref_cases["%s_%d_%g_keep" % (regime, n, thr)])]
+    if O.have_ref():
+        rng = np.random.default_rng(case_seed(regime, n))
+        sb = random_scored_boxes(rng, n, regime, span=300.0 if n <= 65 else 1000.0)
+        cases.append((sb, O.ref_nms(sb, thr)))
+    for sb, ref in cases:
+        mine, idx = O.nms(sb, thr, return_index=True)
+        assert mine.shape == ref.shape and np.array_equal(mine, ref)
+        assert np.array_equal(sb[idx], mine)
 
 
 def test_nms_empty_and_single(O):
@@ -45,30 +54,31 @@ def test_nms_empty_and_single(O):
     assert np.array_equal(O.nms(one, 0.3), one)
 
 
-def test_nms_tie_history_is_order_dependent(O):
+def test_nms_tie_history_is_order_dependent(O, ref_cases):
     """The property that forces the position-key emulation: with equal scores the winner is NOT simply
     'lowest index' once a swap has moved the old first element (nms.c:83-85)."""
-    if not O.have_ref():
-        pytest.skip("needs reference nms.c")
     sb = np.array([[0, 0, 10, 10, 0.5],       # A (first)
                    [100, 100, 110, 110, 0.5],  # B
                    [200, 200, 210, 210, 0.9],  # C best -> swapped with A, so A now sits after B
                    ], np.float32)
-    ref = O.ref_nms(sb, 0.3)
-    assert np.array_equal(ref[:, :4], sb[[2, 1, 0], :4])  # C, then B (now first), then A
-    assert np.array_equal(O.nms(sb, 0.3), ref)
+    assert np.array_equal(ref_cases["tie_in"], sb)
+    for ref in [ref_cases["tie_keep"]] + ([O.ref_nms(sb, 0.3)] if O.have_ref() else []):
+        assert np.array_equal(ref[:, :4], sb[[2, 1, 0], :4])  # C, then B (now first), then A
+        assert np.array_equal(O.nms(sb, 0.3), ref)
 
 
 @pytest.mark.parametrize("regime", ["distinct", "ties"])
-def test_bbox_vote_matches_reference_c(O, regime):
-    if not O.have_ref():
-        pytest.skip("needs reference nms.c")
-    rng = np.random.default_rng(11)
-    sb = random_scored_boxes(rng, 400, regime, span=400.0)
-    sb[:, 4] = np.maximum(sb[:, 4], 1e-3)
-    keep = O.nms(sb, 0.3)
-    a, b = O.bbox_vote(keep, sb, 0.5), O.ref_bbox_vote(keep, sb, 0.5)
-    assert np.array_equal(a, b)
+def test_bbox_vote_matches_reference_c(O, ref_cases, regime):
+    sb, keep = ref_cases["vote_%s_in" % regime], ref_cases["vote_%s_keep" % regime]
+    assert np.array_equal(O.nms(sb, 0.3), keep)
+    assert np.array_equal(O.bbox_vote(keep, sb, 0.5), ref_cases["vote_%s_out" % regime])
+    if O.have_ref():
+        rng = np.random.default_rng(11)
+        sb = random_scored_boxes(rng, 400, regime, span=400.0)
+        sb[:, 4] = np.maximum(sb[:, 4], 1e-3)
+        keep = O.nms(sb, 0.3)
+        a, b = O.bbox_vote(keep, sb, 0.5), O.ref_bbox_vote(keep, sb, 0.5)
+        assert np.array_equal(a, b)
 
 
 def test_decode_roundtrip_property(O):

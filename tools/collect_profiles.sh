@@ -5,22 +5,22 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err
-rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt --output-format csv -- python $R/bench.py --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/kt.err
+python $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err
+rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt --output-format csv -- python $R/bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/kt.err
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 for set in "sq:GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT" "fetch:FETCH_SIZE" "write:WRITE_SIZE"; do
   name=${set%%:*}; ctrs=${set#*:}
   rm -rf /tmp/pmc_$name
-  timeout 600 rocprofv3 --kernel-trace --pmc $ctrs -d /tmp/pmc_$name -o p --output-format csv -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > /tmp/pmc_$name.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $ctrs -d /tmp/pmc_$name -o p --output-format csv -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > /tmp/pmc_$name.log 2>&1
   D=$(dirname $(find /tmp/pmc_$name -name "*counter_collection.csv" | head -1))
   python $R/tools/pmc_summary.py $D > $OUT/${TAG}_pmc_$name.summary.txt 2>&1
 done
 ls -la $OUT
 # the other BASELINE configs as bench.py lines (own metric strings, never the headline)
 for c in c1 c3 c4 c5; do
-  timeout 600 python $R/bench.py --config $c --steps $([ $c = c1 ] && echo 50 || echo 6) --warmup 2 > $OUT/${TAG}_bench_$c.json 2> /tmp/bench_$c.err
+  timeout 600 python $R/bench.py --full --config $c --steps $([ $c = c1 ] && echo 50 || echo 6) --warmup 2 > $OUT/${TAG}_bench_$c.json 2> /tmp/bench_$c.err
 done
-timeout 600 python $R/bench.py --config c4 --dtype bf16 --steps 6 --warmup 2 > $OUT/${TAG}_bench_c4_bf16.json 2> /tmp/bench_c4b.err
+timeout 600 python $R/bench.py --full --config c4 --dtype bf16 --steps 6 --warmup 2 > $OUT/${TAG}_bench_c4_bf16.json 2> /tmp/bench_c4b.err
 # round 3: the ROI-sharded latency mode at N = 1 (+ the one-GPU projection of rank 0's share of an 8-rank world)
 timeout 600 python $R/bench.py --mode latency --steps 20 --warmup 5 > $OUT/${TAG}_bench_latency.json 2> /tmp/bench_lat.err
 timeout 600 python $R/bench.py --mode latency --config c3 --steps 6 --warmup 2 > $OUT/${TAG}_bench_latency_c3.json 2> /tmp/bench_lat3.err

@@ -2,8 +2,9 @@
 # Per-launch timeline of ONE image of a bench configuration (rocprofv3 --kernel-trace; serialised by the profiler, so the
 # durations are the kernels' own, the gaps are not the pipeline's).  usage: tools/kernel_timeline.sh c1 [extra bench args]
 cfg=${1:-c1}; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kt
-timeout 300 rocprofv3 --kernel-trace -d /tmp/kt -o kt --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --config $cfg --steps 3 --warmup 2 --no-cpu-baseline "$@" > /tmp/kt_bench.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace -d /tmp/kt -o kt --output-format csv -- python $R/bench.py --full --config $cfg --steps 3 --warmup 2 --no-cpu-baseline "$@" > /tmp/kt_bench.txt 2>&1
 python - <<PY
 import csv, glob
 f = glob.glob("/tmp/kt/**/*kernel_trace.csv", recursive=True)[0]
