@@ -479,6 +479,33 @@ int mpn_gather_dets(mpn_comm *c, const float *d_dets, const int *d_n_dets, int t
 int mpn_gather_rows(mpn_comm *c, const float *d_send, size_t n_floats, float *d_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * COCO box evaluation — testCoco/coco.lua:24-37 `Coco:evaluate` (pycocotools COCOeval, iouType 'bbox') on the device
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mpn_coco_eval mpn_coco_eval; /* opaque: one GT set + parameters, bound to one device */
+#define MPN_COCO_MAX_DETS 1024
+/* The GT arrays are in annotation-file order: h_gt_bbox [n_gt,4] {x,y,w,h} and h_gt_area as in the JSON, iscrowd / image id /
+ * category id / annotation id as int64.  h_img_ids [n_img]: the GT set's image ids (COCO.getImgIds()), strictly increasing; rows
+ * naming any other image are refused by _run (loadRes's assert), GTs of other images are never read.  h_eval_img_ids == NULL
+ * evaluates the images that have at least one row (coco.lua:28-30); otherwise params.imgIds = h_eval_img_ids [n_eval].
+ * h_cat_ids [n_cat] strictly increasing (params.catIds).  h_iou_thrs [n_iou], h_rec_thrs [n_rec], h_area_rng [n_area,2] (both ends
+ * closed), h_max_dets [n_max_dets] (each 1..MPN_COCO_MAX_DETS; the images are evaluated with the last one) are pycocotools' Params,
+ * passed as they are: n_iou * n_area <= 64, n_area <= 8.  Arguments are validated before the device is touched; device < 0 = the
+ * current device.  The handle allocates its GT tables here and its per-row buffers on the first _run of a larger n. */
+int mpn_coco_eval_create(int device, const double *h_gt_bbox, const double *h_gt_area, const int64_t *h_gt_iscrowd,
+                         const int64_t *h_gt_image_id, const int64_t *h_gt_category_id, const int64_t *h_gt_id, int n_gt,
+                         const int64_t *h_img_ids, int n_img, const int64_t *h_eval_img_ids, int n_eval, const int64_t *h_cat_ids,
+                         int n_cat, const double *h_iou_thrs, int n_iou, const double *h_rec_thrs, int n_rec, const double *h_area_rng,
+                         int n_area, const int *h_max_dets, int n_max_dets, mpn_coco_eval **out);
+/* evaluate + accumulate of d_rows [n,7] fp32 {image, x, y, w, h, score, category} (testCoco/init.lua:65-85's `boxt`) into
+ * d_precision / d_scores [T,R,K,A,M] and d_recall [T,K,A,M], float64, -1 where pycocotools leaves -1.
+ * Deterministic.  Unlike the module-level calls it synchronises `stream` once at the end: a row naming an image outside h_img_ids,
+ * or holding a NaN / inf, returns MPN_EINVAL (the outputs are then unspecified).  Drive one handle from one thread at a time, with
+ * its device current (MPN_ESTATE otherwise). */
+int mpn_coco_eval_run(mpn_coco_eval *h, const float *d_rows, int n, double *d_precision, double *d_recall, double *d_scores,
+                      void *stream);
+void mpn_coco_eval_destroy(mpn_coco_eval *h);
+
+/* ------------------------------------------------------------------------------------------------
  * Proposal (ROI) sharding of ONE image across the GPUs of a node — the latency mode (north_star "images+proposals
  * shard across the 8 GPUs").  Replaces ModelParallelTable.lua:195-242 (broadcast the input to every tower GPU, run, copy back,
  * concatenate) for a single image: every rank holds the full model and is handed the SAME image and the SAME proposal table;

@@ -7,6 +7,7 @@ in include/mpn.h).  It mirrors the reference's operator surface for the hot path
     utils   utils.nms / bbox_vote / boxoverlap / convertFrom / keep_top_k
     models  FastRCNN (models/vgg.lua graph) as one fused device pipeline
     detect  ImageDetect, Tester_FRCNN
+    cocoeval  COCOeval (bbox) on the device: load_coco_gt, COCOEvaluator, evaluate_boxes (testCoco.evaluate)
 
 No CPU fallback exists: importing works anywhere, running an op without the HIP library or a
 device raises MpnError.

@@ -1,0 +1,200 @@
+"""COCO box evaluation on the device: testCoco/coco.lua:24-37's `Coco:evaluate` (pycocotools COCOeval, iouType 'bbox') and
+testCoco/init.lua:35-87's `testCoco.evaluate`, reached from Tester:computeAP after run_test.lua's computeBBoxes.
+
+  load_coco_gt      COCO(annFile): the annotation JSON read with the standard library, annotation order kept
+  COCOEvaluator     loadRes + evaluate + accumulate in libmpn_hip.so (mpn_coco_eval_*), summarize on the host
+  evaluate_boxes    testCoco.evaluate: aboxes[class][image] -> [n,7] rows (formats.detections_to_coco's rules) -> the 12 stats
+
+The semantics (two pycocotools quirks included on purpose) are DESIGN.md section 10.
+"""
+import ctypes as C
+import json
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64)
+AREA_LBL = ["all", "small", "medium", "large"]
+MAX_DETS = [1, 10, 100]
+
+_i64p = C.POINTER(C.c_int64)
+_f64p = C.POINTER(C.c_double)
+
+
+def load_coco_gt(path_or_dict):
+    """An instances_*.json (path or parsed dict) -> dict of numpy arrays: img_ids, cat_ids (sorted, from the `images` /
+    `categories` lists, or from the annotations where a list is absent) and per annotation, in file order, bbox [G,4] f64,
+    area f64, iscrowd, image_id, category_id, id (int64)."""
+    if isinstance(path_or_dict, dict):
+        ds = path_or_dict
+    else:
+        with open(path_or_dict) as f:
+            ds = json.load(f)
+    anns = ds.get("annotations", [])
+    G = len(anns)
+    gt = {
+        "bbox": np.array([a["bbox"] for a in anns], np.float64).reshape(G, 4),
+        "area": np.array([a["area"] for a in anns], np.float64),
+        "iscrowd": np.array([int(a.get("iscrowd", 0)) for a in anns], np.int64),
+        "image_id": np.array([a["image_id"] for a in anns], np.int64),
+        "category_id": np.array([a["category_id"] for a in anns], np.int64),
+        "id": np.array([a["id"] for a in anns], np.int64),
+    }
+    imgs = [im["id"] for im in ds["images"]] if "images" in ds else gt["image_id"]
+    cats = [c["id"] for c in ds["categories"]] if "categories" in ds else gt["category_id"]
+    gt["img_ids"] = np.unique(np.asarray(imgs, np.int64))
+    gt["cat_ids"] = np.unique(np.asarray(cats, np.int64))
+    if np.any(gt["id"] == 0):
+        warnings.warn("annotation id 0 in the GT set: COCOeval counts every detection matched to it as a false positive "
+                      "(it tests the matched id for truthiness)")
+    return gt
+
+
+def _ptr(a, t):
+    return a.ctypes.data_as(t)
+
+
+class COCOEvaluator(object):
+    """COCOeval(cocoGt, cocoDt, 'bbox') with pycocotools' default Params.  img_ids None evaluates the images that have a detection
+    (what coco.lua:28-30 does); "all" evaluates every GT image (the usual COCO practice); a list sets params.imgIds."""
+
+    def __init__(self, gt, img_ids=None, device=None, iou_thrs=IOU_THRS, rec_thrs=REC_THRS, area_rng=AREA_RNG, max_dets=MAX_DETS):
+        _lib.require_gpu()
+        self.gt = gt if isinstance(gt, dict) and "img_ids" in gt else load_coco_gt(gt)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.iou_thrs = np.ascontiguousarray(iou_thrs, np.float64)
+        self.rec_thrs = np.ascontiguousarray(rec_thrs, np.float64)
+        self.area_rng = np.ascontiguousarray(area_rng, np.float64).reshape(-1, 2)
+        self.max_dets = [int(m) for m in max_dets]
+        g = self.gt
+        arr = {k: np.ascontiguousarray(g[k], np.int64) for k in ("iscrowd", "image_id", "category_id", "id", "img_ids", "cat_ids")}
+        bbox = np.ascontiguousarray(g["bbox"], np.float64).reshape(-1, 4)
+        area = np.ascontiguousarray(g["area"], np.float64)
+        if img_ids is None:
+            ev = None
+        elif isinstance(img_ids, str) and img_ids == "all":
+            ev = arr["img_ids"]
+        else:
+            ev = np.unique(np.asarray(img_ids, np.int64))
+        md = (C.c_int * len(self.max_dets))(*self.max_dets)
+        lib = _lib.load()
+        lib.mpn_coco_eval_destroy.restype = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib.mpn_coco_eval_create(
+                self.device.index if self.device.index is not None else -1, _ptr(bbox, _f64p), _ptr(area, _f64p),
+                _ptr(arr["iscrowd"], _i64p), _ptr(arr["image_id"], _i64p), _ptr(arr["category_id"], _i64p), _ptr(arr["id"], _i64p),
+                int(area.size), _ptr(arr["img_ids"], _i64p), int(arr["img_ids"].size),
+                _ptr(ev, _i64p) if ev is not None else None, int(ev.size) if ev is not None else 0,
+                _ptr(arr["cat_ids"], _i64p), int(arr["cat_ids"].size), _ptr(self.iou_thrs, _f64p), int(self.iou_thrs.size),
+                _ptr(self.rec_thrs, _f64p), int(self.rec_thrs.size), _ptr(self.area_rng, _f64p), int(self.area_rng.shape[0]),
+                md, len(self.max_dets), C.byref(h)), "mpn_coco_eval_create")
+        self._lib, self._h = lib, h
+        T, R, K, A, M = self.iou_thrs.size, self.rec_thrs.size, arr["cat_ids"].size, self.area_rng.shape[0], len(self.max_dets)
+        self._prec = torch.empty((T, R, K, A, M), dtype=torch.float64, device=self.device)
+        self._scores = torch.empty((T, R, K, A, M), dtype=torch.float64, device=self.device)
+        self._recall = torch.empty((T, K, A, M), dtype=torch.float64, device=self.device)
+        self.eval = None
+        self.stats = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.mpn_coco_eval_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, rows):
+        """evaluate + accumulate on the device only: the arrays stay in self.device_arrays (torch float64 on the device)."""
+        r = torch.as_tensor(rows).to(device=self.device, dtype=torch.float32).reshape(-1, 7).contiguous()
+        n = r.shape[0]
+        if n and not bool(torch.isfinite(r).all().item()):
+            raise ValueError("COCOEvaluator: the rows hold NaN or inf")
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            check(self._lib.mpn_coco_eval_run(self._h, C.cast(r.data_ptr(), _lib.f32p) if n else None, n,
+                                              C.cast(self._prec.data_ptr(), _f64p), C.cast(self._recall.data_ptr(), _f64p),
+                                              C.cast(self._scores.data_ptr(), _f64p), stream), "mpn_coco_eval_run")
+        return self.device_arrays
+
+    @property
+    def device_arrays(self):
+        return {"precision": self._prec, "recall": self._recall, "scores": self._scores}
+
+    def evaluate(self, rows):
+        """rows [n,7] {image, x, y, w, h, score, category} (numpy or torch; cast to float32 like loadRes's ndarray) ->
+        {"precision", "recall", "scores": numpy float64 in pycocotools' layout, "stats": the 12 summary numbers}."""
+        self.run(rows)
+        self.eval = {k: v.cpu().numpy() for k, v in self.device_arrays.items()}
+        self.stats = summarize_stats(self.eval["precision"], self.eval["recall"], self.iou_thrs, self.max_dets)
+        self.eval["stats"] = self.stats
+        return self.eval
+
+    def summarize(self):
+        """Prints COCOeval.summarize()'s 12 lines and returns the stats."""
+        if self.eval is None:
+            raise RuntimeError("Please run evaluate() first")
+        print(summary_text(self.stats, self.iou_thrs, self.max_dets))
+        return self.stats
+
+
+_SUMMARY = [(1, None, "all", 2), (1, .5, "all", 2), (1, .75, "all", 2), (1, None, "small", 2), (1, None, "medium", 2), (1, None, "large", 2),
+            (0, None, "all", 0), (0, None, "all", 1), (0, None, "all", 2), (0, None, "small", 2), (0, None, "medium", 2), (0, None, "large", 2)]
+
+
+def summarize_stats(precision, recall, iou_thrs=IOU_THRS, max_dets=MAX_DETS):
+    """cocoeval.py _summarizeDets: the mean of the entries > -1 of each slice, -1 when there are none."""
+    out = np.zeros(12)
+    for n, (ap, thr, area, mi) in enumerate(_SUMMARY):
+        aind = [i for i, lbl in enumerate(AREA_LBL) if lbl == area]
+        mind = [i for i, v in enumerate(max_dets) if v == max_dets[mi]] if n else [i for i, v in enumerate(max_dets) if v == 100]
+        s = precision if ap else recall
+        if thr is not None:
+            s = s[np.where(thr == np.asarray(iou_thrs))[0]]
+        s = s[:, :, :, aind, mind] if ap else s[:, :, aind, mind]
+        out[n] = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+    return out
+
+
+def summary_text(stats, iou_thrs=IOU_THRS, max_dets=MAX_DETS):
+    """The 12 lines COCOeval.summarize() prints."""
+    lines = []
+    i_str = " {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}"
+    for n, (ap, thr, area, mi) in enumerate(_SUMMARY):
+        iou = "{:0.2f}:{:0.2f}".format(iou_thrs[0], iou_thrs[-1]) if thr is None else "{:0.2f}".format(thr)
+        md = max_dets[mi] if n else 100
+        lines.append(i_str.format("Average Precision" if ap else "Average Recall", "(AP)" if ap else "(AR)", iou, area, md, stats[n]))
+    return "\n".join(lines)
+
+
+def evaluate_boxes(aboxes, gt, image_ids, category_ids, img_ids=None, device=None):
+    """testCoco.evaluate (testCoco/init.lua:35-87): aboxes[class][image] = [K,5] {x1,y1,x2,y2,score} (1-based pixels; tensors or
+    arrays, empty = none), image_ids[image] = the COCO image id of dataset image `image`, category_ids[class] = the COCO category
+    id of class `class`.  The [n,7] `boxt` rows are built class-major, then in image order, as the Lua loops build them, by
+    formats.detections_to_coco (mpn_dets_to_coco_rows: x1-1, y1-1, x2-x1, y2-y1 in fp32).  Prints the summary and returns
+    (the 12 stats, the COCOEvaluator, boxt)."""
+    from .formats import detections_to_coco
+    parts = []
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    for c, per_img in enumerate(aboxes):
+        for i, t in enumerate(per_img):
+            if t is None or len(t) == 0:
+                continue
+            b = torch.as_tensor(t).to(device=dev, dtype=torch.float32).reshape(-1, 5)
+            dets = torch.cat([b, torch.full((b.shape[0], 1), float(c + 1), dtype=torch.float32, device=dev)], 1).contiguous()
+            parts.append(detections_to_coco(dets, None, float(image_ids[i]), list(category_ids)))
+    boxt = torch.cat(parts) if parts else torch.zeros((0, 7), dtype=torch.float32, device=dev)
+    ev = COCOEvaluator(gt, img_ids=img_ids, device=dev)
+    ev.evaluate(boxt)
+    ev.summarize()
+    return ev.stats, ev, boxt

@@ -1,0 +1,650 @@
+// cocoeval.hip — COCOeval (iouType 'bbox') on the device: testCoco/coco.lua:24-37's Coco:evaluate, i.e. pycocotools 2.0's
+// loadRes + evaluate + accumulate over the [n,7] rows testCoco/init.lua:65-85 builds.  The contract is DESIGN.md section 10
+// (and tests/cocoeval_np.py, its numpy restatement, which every result here equals bit for bit).
+//
+// Stages (one stream, one host synchronisation at the end to report loadRes's assert):
+//   coco_bin      row -> cell (category k, image i) = k * I + i by binary search over the sorted id lists; histogram
+//   coco_scan     CSR offsets of the cells + the list of cells that hold detections (one workgroup)
+//   coco_scatter  row indices into their cell's range (atomic cursor: the order is undone by the stable rank below)
+//   coco_cells    one wave per detected cell: stable score rank inside the cell (score desc, row asc), cut to maxDets[-1],
+//                 then the greedy matching, one lane per (area, IoU threshold), IoU recomputed in fp64 in bbIou's order;
+//                 per kept detection one tp and one fp bit per (area, threshold)
+//   coco_rank     per category, the stable rank of every kept detection over the concatenation in image order
+//                 (key = score desc, slot asc): an LDS-tiled counting rank, deterministic
+//   coco_accum    one workgroup per (category, area, maxDet): per threshold a ballot scan of tp / fp, the precision of every
+//                 true positive, its suffix-max envelope and the 101 recall lookups
+// No atomic's order reaches a result: the histogram counts are order-free and the scatter order is erased by the rank.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "mpn_internal.h"
+
+namespace mpn {
+namespace {
+
+constexpr int kCellGtLds = 256;   // cells with up to this many GTs keep the per-lane matched bits in LDS, larger ones in HBM
+constexpr int kAccThreads = 256;
+constexpr int kRankThreads = 256;
+
+__device__ __forceinline__ int lower_bound_i64(const long long *a, int n, long long v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// float -> int64 as Python's int() does (truncation toward zero); false when the value has no int64 image
+__device__ __forceinline__ bool trunc_i64(float f, long long *out) {
+  if (!(f > -9.2e18f && f < 9.2e18f)) return false;
+  *out = (long long)f;
+  return true;
+}
+
+// ascending order of the key = descending score (-0.0 == 0.0), then ascending slot
+__device__ __forceinline__ unsigned long long score_key(float s, unsigned slot) {
+  if (s == 0.0f) s = 0.0f;
+  const unsigned u = __float_as_uint(s);
+  const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)(~o) << 32) | slot;
+}
+
+__global__ void coco_fill(double *p, size_t n, double v) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+// loadRes + _prepare: image / category ids by int() truncation; err bit 1 = an image that is not a GT image, 2 = a non-finite value
+__global__ __launch_bounds__(256) void coco_bin(const float *__restrict__ rows, int n, const long long *__restrict__ img_ids, int I,
+                                                const long long *__restrict__ cat_ids, int K, int explicit_eval,
+                                                unsigned char *__restrict__ img_eval, int *__restrict__ row_cell,
+                                                int *__restrict__ cell_cnt, int *__restrict__ err) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const float *x = rows + (size_t)r * 7;
+  row_cell[r] = -1;
+  for (int c = 0; c < 7; ++c)
+    if (!isfinite(x[c])) { atomicOr(err, 2); return; }
+  long long img = 0, cat = 0;
+  const int ii = trunc_i64(x[0], &img) ? lower_bound_i64(img_ids, I, img) : I;
+  if (ii >= I || img_ids[ii] != img) { atomicOr(err, 1); return; }
+  if (explicit_eval) {
+    if (!img_eval[ii]) return;                   // not in params.imgIds: dropped
+  } else {
+    img_eval[ii] = 1;                            // imgIds = sorted(images with a detection), whatever its category
+  }
+  if (!trunc_i64(x[6], &cat)) return;
+  const int kk = lower_bound_i64(cat_ids, K, cat);
+  if (kk >= K || cat_ids[kk] != cat) return;     // not in params.catIds: dropped
+  const int cell = kk * I + ii;
+  row_cell[r] = cell;
+  atomicAdd(&cell_cnt[cell], 1);
+}
+
+// exclusive scan of the cell counts (CSR offsets, cell_off[KI] = rows kept) + compaction of the cells that hold detections
+__global__ __launch_bounds__(1024) void coco_scan(const int *__restrict__ cell_cnt, int KI, int *__restrict__ cell_off,
+                                                  int *__restrict__ active, int *__restrict__ n_active) {
+  __shared__ int s_sum[1024], s_nz[1024];
+  const int tid = threadIdx.x, per = cdiv(KI, 1024);
+  const int b = min(tid * per, KI), e = min(b + per, KI);
+  int sum = 0, nz = 0;
+  for (int c = b; c < e; ++c) { sum += cell_cnt[c]; nz += cell_cnt[c] > 0; }
+  s_sum[tid] = sum; s_nz[tid] = nz;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {            // Hillis-Steele inclusive scan
+    const int a1 = tid >= d ? s_sum[tid - d] : 0, a2 = tid >= d ? s_nz[tid - d] : 0;
+    __syncthreads();
+    s_sum[tid] += a1; s_nz[tid] += a2;
+    __syncthreads();
+  }
+  int off = s_sum[tid] - sum, q = s_nz[tid] - nz;
+  for (int c = b; c < e; ++c) {
+    cell_off[c] = off;
+    if (cell_cnt[c] > 0) active[q++] = c;
+    off += cell_cnt[c];
+  }
+  if (tid == 1023) { cell_off[KI] = s_sum[1023]; *n_active = s_nz[1023]; }
+}
+
+__global__ __launch_bounds__(256) void coco_scatter(const int *__restrict__ row_cell, int n, const int *__restrict__ cell_off,
+                                                    int *__restrict__ cursor, int *__restrict__ cell_rows) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const int c = row_cell[r];
+  if (c >= 0) cell_rows[cell_off[c] + atomicAdd(&cursor[c], 1)] = r;
+}
+
+// maskApi.c bbIou for one (detection, GT) pair, in its operation order (-ffp-contract=off; IEEE fp64 division)
+__device__ __forceinline__ double bb_iou(double dx, double dy, double dw, double dh, const double *g, bool crowd) {
+  const double w = fmin(dw + dx, g[2] + g[0]) - fmax(dx, g[0]);
+  if (w <= 0) return 0.0;
+  const double h = fmin(dh + dy, g[3] + g[1]) - fmax(dy, g[1]);
+  if (h <= 0) return 0.0;
+  const double i = w * h, da = dw * dh;
+  const double u = crowd ? da : da + g[2] * g[3] - i;
+  return i / u;
+}
+
+struct CellArgs {
+  const float *rows;
+  const int *cell_off, *cell_rows, *active, *n_active, *gt_off;
+  const double *gt_box;              // [G,4] {x,y,w,h}, cell order (file order inside a cell)
+  const unsigned char *gt_crowd;     // iscrowd
+  const unsigned char *gt_igm;       // bit a: ignored in area range a (iscrowd or area outside the range)
+  const long long *gt_id;
+  const long long *gt_bitoff;        // per cell: word offset of its matched bits in gbits (cells above kCellGtLds GTs)
+  unsigned *gbits;
+  const double *thr, *arng;
+  int T, A, Dmax;
+  float *slot_score;
+  unsigned long long *tpm, *fpm, *key;
+  int *drank;
+};
+
+// evaluateImg for every area range at once, one wave per cell that holds detections
+__global__ __launch_bounds__(64) void coco_cells(CellArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double *s_box = reinterpret_cast<double *>(smem);                  // [Dmax][4]
+  float *s_area = reinterpret_cast<float *>(s_box + 4 * p.Dmax);      // [Dmax] fp32 w*h (loadRes's area)
+  float *s_score = s_area + p.Dmax;                                    // [Dmax]
+  int *s_row = reinterpret_cast<int *>(s_score + p.Dmax);              // [Dmax] rows in score order
+  unsigned *s_bits = reinterpret_cast<unsigned *>(s_row + p.Dmax);     // [kCellGtLds / 32][64] matched bits, one column per lane
+  const int lane = threadIdx.x;
+  const int AT = p.A * p.T;
+  const bool act = lane < AT;
+  const int a = act ? lane / p.T : 0, t = act ? lane % p.T : 0;
+  const double iou0 = act ? fmin(p.thr[t], 1 - 1e-10) : 0.0;
+  const double lo = p.arng[2 * a], hi = p.arng[2 * a + 1];
+  const int n_act = *p.n_active;
+  for (int q = blockIdx.x; q < n_act; q += gridDim.x) {
+    const int c = p.active[q];
+    const int off = p.cell_off[c], nc = p.cell_off[c + 1] - off;
+    const int gb = p.gt_off[c], G = p.gt_off[c + 1] - gb;
+    const int D = min(nc, p.Dmax);
+    // stable rank by score (np.argsort(-score, kind='mergesort')): #higher + #equal with a lower row number
+    for (int j = lane; j < nc; j += 64) {
+      const int rj = p.cell_rows[off + j];
+      const float sj = p.rows[(size_t)rj * 7 + 5];
+      int rank = 0;
+      for (int x = 0; x < nc; ++x) {
+        const int rx = p.cell_rows[off + x];
+        const float sx = p.rows[(size_t)rx * 7 + 5];
+        rank += (sx > sj) || (sx == sj && rx < rj);
+      }
+      if (rank < D) s_row[rank] = rj;
+      else p.key[off + rank] = ~0ull;             // beyond maxDets[-1]: never accumulated
+    }
+    __syncthreads();
+    for (int d = lane; d < D; d += 64) {
+      const float *x = p.rows + (size_t)s_row[d] * 7;
+      s_box[4 * d + 0] = x[1]; s_box[4 * d + 1] = x[2]; s_box[4 * d + 2] = x[3]; s_box[4 * d + 3] = x[4];
+      s_area[d] = x[3] * x[4];
+      s_score[d] = x[5];
+      p.slot_score[off + d] = x[5];
+      p.drank[off + d] = d;
+      p.key[off + d] = score_key(x[5], (unsigned)(off + d));
+    }
+    const int GW = cdiv(G, 32);
+    unsigned *bits = G <= kCellGtLds ? s_bits + lane : p.gbits + p.gt_bitoff[c] + lane;
+    for (int w = 0; w < GW; ++w) bits[w * 64] = 0u;
+    __syncthreads();
+    for (int d = 0; d < D; ++d) {
+      bool tp = false, fp = false;
+      if (act) {
+        const double dx = s_box[4 * d], dy = s_box[4 * d + 1], dw = s_box[4 * d + 2], dh = s_box[4 * d + 3];
+        double best = iou0;
+        int m = -1, m_ig = 0;
+        // GTs in _ignore-stable order: the non-ignored ones (pass 0), then the ignored ones (pass 1); once a non-ignored GT is
+        // held, the first ignored GT breaks the walk (cocoeval.py evaluateImg)
+        for (int pass = 0; pass < 2 && !(pass == 1 && m >= 0); ++pass) {
+          for (int g = 0; g < G; ++g) {
+            if (((p.gt_igm[gb + g] >> a) & 1) != pass) continue;
+            const bool crowd = p.gt_crowd[gb + g] != 0;
+            if (!crowd && ((bits[(g >> 5) * 64] >> (g & 31)) & 1u)) continue;
+            const double v = bb_iou(dx, dy, dw, dh, p.gt_box + 4 * (size_t)(gb + g), crowd);
+            if (v < best) continue;
+            best = v; m = g; m_ig = pass;
+          }
+        }
+        long long mid = 0;
+        if (m >= 0) {
+          mid = p.gt_id[gb + m];
+          bits[(m >> 5) * 64] |= 1u << (m & 31);
+        }
+        // dtIg = gtIg[m], or (dtm == 0 and area outside the range): a match to annotation id 0 is dtm == 0 (quirk kept)
+        const double ar = (double)s_area[d];
+        const bool ig = m_ig != 0 && m >= 0 ? true : (mid == 0 && (ar < lo || ar > hi));
+        tp = mid != 0 && !ig;
+        fp = mid == 0 && !ig;
+      }
+      const unsigned long long tb = __ballot(tp), fb = __ballot(fp);
+      if (lane == 0) { p.tpm[off + d] = tb; p.fpm[off + d] = fb; }
+    }
+    __syncthreads();
+  }
+}
+
+// per category: rank of every kept detection in (score desc, slot asc) order; slots of category k are [cell_off[k*I], cell_off[(k+1)*I])
+__global__ __launch_bounds__(kRankThreads) void coco_rank(const unsigned long long *__restrict__ key, const int *__restrict__ cell_off, int I,
+                                                          int K, int *__restrict__ sorted) {
+  __shared__ unsigned long long s_key[kRankThreads];
+  __shared__ int s_lo, s_hi;
+  const int total = cell_off[(size_t)K * I];
+  const int s0 = blockIdx.x * kRankThreads;
+  if (s0 >= total) return;                        // uniform over the block
+  const int s = s0 + threadIdx.x;
+  const bool valid = s < total;
+  int my_lo = 0, my_hi = 0;
+  unsigned long long mk = ~0ull;
+  if (valid) {
+    int lo = 0, hi = K;                           // the k with cell_off[k*I] <= s < cell_off[(k+1)*I]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (cell_off[(size_t)mid * I] <= s) lo = mid; else hi = mid;
+    }
+    my_lo = cell_off[(size_t)lo * I];
+    my_hi = cell_off[(size_t)(lo + 1) * I];
+    mk = key[s];
+  }
+  if (threadIdx.x == 0) s_lo = my_lo;
+  if (s == min(s0 + kRankThreads, total) - 1) s_hi = my_hi;
+  __syncthreads();
+  const int blo = s_lo, bhi = s_hi;
+  int cnt = 0;
+  for (int base = blo; base < bhi; base += kRankThreads) {
+    const int x = base + threadIdx.x;
+    s_key[threadIdx.x] = x < bhi ? key[x] : ~0ull;
+    __syncthreads();
+    const int xb = max(my_lo - base, 0), xe = min(my_hi - base, kRankThreads);
+    for (int j = xb; j < xe; ++j) cnt += s_key[j] < mk;
+    __syncthreads();
+  }
+  if (valid && mk != ~0ull) sorted[my_lo + cnt] = s;
+}
+
+struct AccArgs {
+  const int *cell_off, *sorted, *drank, *npig_static, *max_dets;
+  const unsigned char *img_eval;
+  const unsigned long long *tpm, *fpm;
+  const float *slot_score;
+  const double *rec;
+  const long long *scr_off;          // per category: first scratch entry of its (area, maxDet) blocks, G_k entries each
+  const int *gt_per_cat;
+  int *scr_j;
+  double *scr_pr;
+  int I, K, T, R, A, M, Dmax;
+  double *precision, *recall, *scores;
+};
+
+__device__ __forceinline__ int block_sum_i(int v, int *s_red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if (lane == 0) s_red[w] = v;
+  __syncthreads();
+  int t = 0;
+  for (int i = 0; i < kAccThreads / 64; ++i) t += s_red[i];
+  return t;
+}
+
+// accumulate for one (category k, area a, maxDet m), every threshold
+__global__ __launch_bounds__(kAccThreads) void coco_accum(AccArgs p) {
+  __shared__ int s_red[kAccThreads / 64];
+  __shared__ int s_wc[3][kAccThreads / 64];
+  __shared__ int s_first;
+  __shared__ double s_max[kAccThreads];
+  const int b = blockIdx.x, m = b % p.M, a = (b / p.M) % p.A, k = b / (p.M * p.A);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  int npig = 0, nvalid = 0;
+  for (int i = tid; i < p.I; i += kAccThreads) {
+    const int c = k * p.I + i;
+    if (p.img_eval[i]) npig += p.npig_static[((size_t)k * p.A + a) * p.I + i];
+    nvalid += min(p.cell_off[c + 1] - p.cell_off[c], p.Dmax);
+  }
+  npig = block_sum_i(npig, s_red);
+  nvalid = block_sum_i(nvalid, s_red);
+  if (npig == 0) return;                          // no non-ignored GT: the entries stay -1
+  const int cat0 = p.cell_off[(size_t)k * p.I];
+  const int md = p.max_dets[m];
+  const size_t sbase = (size_t)p.scr_off[k] + (size_t)(a * p.M + m) * p.gt_per_cat[k];
+  int *tj = p.scr_j + sbase;
+  double *tpr = p.scr_pr + sbase;
+  const unsigned long long below = (1ull << lane) - 1;
+  for (int t = 0; t < p.T; ++t) {
+    const int bit = a * p.T + t;
+    int nd = 0, ntp = 0, nfp = 0;                 // block-uniform running counts
+    if (tid == 0) s_first = -1;
+    for (int j0 = 0; j0 < nvalid; j0 += kAccThreads) {
+      const int j = j0 + tid;
+      bool inc = false, tp = false, fp = false;
+      if (j < nvalid) {
+        const int s = p.sorted[cat0 + j];
+        if (p.drank[s] < md) {
+          inc = true;
+          tp = (p.tpm[s] >> bit) & 1;
+          fp = (p.fpm[s] >> bit) & 1;
+        }
+      }
+      const unsigned long long bi = __ballot(inc), bt = __ballot(tp), bf = __ballot(fp);
+      __syncthreads();
+      if (lane == 0) { s_wc[0][w] = __popcll(bi); s_wc[1][w] = __popcll(bt); s_wc[2][w] = __popcll(bf); }
+      __syncthreads();
+      int pi = __popcll(bi & below), pt = __popcll(bt & below), pf = __popcll(bf & below);
+      int ti = 0, tt = 0, tf = 0;
+      for (int v = 0; v < kAccThreads / 64; ++v) {
+        if (v < w) { pi += s_wc[0][v]; pt += s_wc[1][v]; pf += s_wc[2][v]; }
+        ti += s_wc[0][v]; tt += s_wc[1][v]; tf += s_wc[2][v];
+      }
+      if (inc && nd + pi == 0) s_first = j;
+      if (tp) {
+        const int cnum = ntp + pt + 1;            // this is the cnum-th true positive; fp count so far = nfp + pf
+        if (cnum <= p.gt_per_cat[k]) {
+          tj[cnum - 1] = j;
+          tpr[cnum - 1] = (double)cnum / (((double)(nfp + pf) + (double)cnum) + 0x1p-52);  // tp / (fp + tp + np.spacing(1))
+        }
+      }
+      nd += ti; ntp += tt; nfp += tf;
+    }
+    __syncthreads();
+    const int C = min(ntp, p.gt_per_cat[k]);
+    // precision envelope: suffix max over the true positives' precisions (the other entries never exceed the last one before them)
+    double carry = 0.0;
+    for (int end = C; end > 0; end -= kAccThreads) {
+      const int idx = end - 1 - tid;              // tid 0 = the highest index: a prefix max in tid order
+      double v = idx >= 0 ? tpr[idx] : 0.0;
+      s_max[tid] = v;
+      __syncthreads();
+      for (int d = 1; d < kAccThreads; d <<= 1) {
+        const double o = tid >= d ? s_max[tid - d] : 0.0;
+        __syncthreads();
+        s_max[tid] = fmax(s_max[tid], o);
+        __syncthreads();
+      }
+      v = fmax(s_max[tid], carry);
+      if (idx >= 0) tpr[idx] = v;
+      carry = fmax(carry, s_max[kAccThreads - 1]);
+      __syncthreads();
+    }
+    __syncthreads();
+    const int first = s_first;
+    if (tid == 0) p.recall[(((size_t)t * p.K + k) * p.A + a) * p.M + m] = nd ? (double)ntp / (double)npig : 0.0;
+    for (int r = tid; r < p.R; r += kAccThreads) {
+      // searchsorted(rc, recThr, 'left') with rc = tp / npig: the first entry holding the c-th TP, c = min{c : c / npig >= recThr}
+      const double rt = p.rec[r];
+      int lo = 0, hi = npig + 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((double)mid / (double)npig >= rt) hi = mid; else lo = mid + 1;
+      }
+      double q = 0.0, sc = 0.0;
+      if (lo == 0) {
+        if (nd > 0) { q = C > 0 ? tpr[0] : 0.0; sc = (double)p.slot_score[p.sorted[cat0 + first]]; }
+      } else if (lo <= C) {
+        q = tpr[lo - 1];
+        sc = (double)p.slot_score[p.sorted[cat0 + tj[lo - 1]]];
+      }
+      const size_t o = ((((size_t)t * p.R + r) * p.K + k) * p.A + a) * p.M + m;
+      p.precision[o] = q;
+      p.scores[o] = sc;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+}  // namespace mpn
+
+struct mpn_coco_eval {
+  int device = -1;
+  int I = 0, K = 0, T = 0, R = 0, A = 0, M = 0, Dmax = 0, explicit_eval = 0;
+  size_t cap = 0;
+  long long *img_ids = nullptr, *cat_ids = nullptr, *gt_id = nullptr, *gt_bitoff = nullptr, *scr_off = nullptr;
+  unsigned char *img_eval_static = nullptr, *img_eval = nullptr, *gt_crowd = nullptr, *gt_igm = nullptr;
+  int *gt_off = nullptr, *npig = nullptr, *gt_per_cat = nullptr, *max_dets = nullptr;
+  double *gt_box = nullptr, *thr = nullptr, *rec = nullptr, *arng = nullptr, *scr_pr = nullptr;
+  int *scr_j = nullptr;
+  unsigned *gbits = nullptr;
+  int *cell_cnt = nullptr, *cell_off = nullptr, *cursor = nullptr, *active = nullptr, *n_active = nullptr, *err = nullptr;
+  int *h_err = nullptr;
+  // sized by the number of rows
+  int *row_cell = nullptr, *cell_rows = nullptr, *sorted = nullptr, *drank = nullptr;
+  float *slot_score = nullptr;
+  unsigned long long *tpm = nullptr, *fpm = nullptr, *key = nullptr;
+  std::vector<void *> owned;
+};
+
+namespace {
+
+void free_rows(mpn_coco_eval *h) {
+  void *p[] = {h->row_cell, h->cell_rows, h->sorted, h->drank, h->slot_score, h->tpm, h->fpm, h->key};
+  for (void *x : p) if (x) (void)hipFree(x);
+  h->row_cell = h->cell_rows = h->sorted = h->drank = nullptr;
+  h->slot_score = nullptr;
+  h->tpm = h->fpm = h->key = nullptr;
+  h->cap = 0;
+}
+
+void destroy(mpn_coco_eval *h) {
+  if (!h) return;
+  int cur = 0;
+  const bool have = hipGetDevice(&cur) == hipSuccess;
+  if (h->device >= 0) (void)hipSetDevice(h->device);
+  free_rows(h);
+  for (void *x : h->owned) if (x) (void)hipFree(x);
+  if (h->h_err) (void)hipHostFree(h->h_err);
+  if (have) (void)hipSetDevice(cur);
+  delete h;
+}
+
+template <class T>
+int dev_alloc(mpn_coco_eval *h, T **p, size_t n) {
+  MPN_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(p), sizeof(T) * (n ? n : 1)));
+  h->owned.push_back(*p);
+  return MPN_OK;
+}
+
+template <class T>
+int dev_upload(mpn_coco_eval *h, T **p, const T *src, size_t n) {
+  if (int rc = dev_alloc(h, p, n)) return rc;
+  if (n) MPN_CHECK_HIP(hipMemcpy(*p, src, sizeof(T) * n, hipMemcpyHostToDevice));
+  return MPN_OK;
+}
+
+bool strictly_increasing(const int64_t *v, int n) {
+  for (int i = 1; i < n; ++i)
+    if (!(v[i - 1] < v[i])) return false;
+  return true;
+}
+
+int create_impl(mpn_coco_eval *h, const double *gt_bbox, const double *gt_area, const int64_t *gt_iscrowd, const int64_t *gt_image_id,
+                const int64_t *gt_category_id, const int64_t *gt_id, int n_gt, const int64_t *img_ids, int n_img,
+                const int64_t *eval_img_ids, int n_eval, const int64_t *cat_ids, int n_cat, const double *iou_thrs,
+                const double *rec_thrs, const double *area_rng, const int *max_dets) {
+  const int I = h->I, K = h->K, A = h->A, KI = I * K;
+  auto find = [](const int64_t *v, int n, int64_t x) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) / 2; if (v[mid] < x) lo = mid + 1; else hi = mid; }
+    return lo < n && v[lo] == x ? lo : -1;
+  };
+  // _prepare's GT index: (image, category) cells, file order inside a cell; GTs outside the image / category lists are never read
+  std::vector<int> cell(n_gt), cnt(KI + 1, 0);
+  for (int g = 0; g < n_gt; ++g) {
+    const int ii = find(img_ids, n_img, gt_image_id[g]), kk = find(cat_ids, n_cat, gt_category_id[g]);
+    cell[g] = (ii < 0 || kk < 0) ? -1 : kk * I + ii;
+    if (cell[g] >= 0) cnt[cell[g] + 1]++;
+  }
+  for (int c = 0; c < KI; ++c) cnt[c + 1] += cnt[c];
+  const int G = cnt[KI];
+  std::vector<int> pos(cnt.begin(), cnt.end() - 1);
+  std::vector<double> box((size_t)G * 4 + 1);
+  std::vector<long long> id(G + 1), bitoff(KI, 0), scr_off(K + 1, 0);
+  std::vector<unsigned char> crowd(G + 1), igm(G + 1), evf(I, 0);
+  std::vector<int> npig((size_t)K * A * I, 0), per_cat(K, 0);
+  for (int g = 0; g < n_gt; ++g) {
+    if (cell[g] < 0) continue;
+    const int o = pos[cell[g]]++;
+    for (int j = 0; j < 4; ++j) box[(size_t)o * 4 + j] = gt_bbox[(size_t)g * 4 + j];
+    id[o] = gt_id[g];
+    crowd[o] = gt_iscrowd[g] != 0;             // _prepare: ignore = iscrowd
+    unsigned char bits = 0;
+    const int kk = cell[g] / I, ii = cell[g] % I;
+    for (int a = 0; a < A; ++a) {
+      const bool ig = crowd[o] || gt_area[g] < area_rng[2 * a] || gt_area[g] > area_rng[2 * a + 1];
+      bits |= (unsigned char)(ig ? 1u << a : 0u);
+      if (!ig) npig[((size_t)kk * A + a) * I + ii]++;
+    }
+    igm[o] = bits;
+    per_cat[kk]++;
+  }
+  long long words = 0;
+  for (int c = 0; c < KI; ++c) {
+    const int n = cnt[c + 1] - cnt[c];
+    if (n > mpn::kCellGtLds) { bitoff[c] = words; words += (long long)((n + 31) / 32) * 64; }
+  }
+  for (int k = 0; k < K; ++k) scr_off[k + 1] = scr_off[k] + (long long)per_cat[k] * A * h->M;
+  if (eval_img_ids) {
+    for (int e = 0; e < n_eval; ++e) {
+      const int ii = find(img_ids, n_img, eval_img_ids[e]);
+      if (ii >= 0) evf[ii] = 1;                  // an evaluated id that is no GT image has neither GT nor detections
+    }
+  }
+  std::vector<long long> iid(img_ids, img_ids + n_img), cid(cat_ids, cat_ids + n_cat);
+  int rc;
+  if ((rc = dev_upload(h, &h->img_ids, iid.data(), I)) || (rc = dev_upload(h, &h->cat_ids, cid.data(), K)) ||
+      (rc = dev_upload(h, &h->img_eval_static, evf.data(), I)) || (rc = dev_alloc(h, &h->img_eval, I)) ||
+      (rc = dev_upload(h, &h->gt_off, cnt.data(), KI + 1)) || (rc = dev_upload(h, &h->gt_box, box.data(), (size_t)G * 4)) ||
+      (rc = dev_upload(h, &h->gt_id, id.data(), G)) || (rc = dev_upload(h, &h->gt_crowd, crowd.data(), G)) ||
+      (rc = dev_upload(h, &h->gt_igm, igm.data(), G)) || (rc = dev_upload(h, &h->gt_bitoff, bitoff.data(), KI)) ||
+      (rc = dev_alloc(h, &h->gbits, (size_t)words)) || (rc = dev_upload(h, &h->npig, npig.data(), npig.size())) ||
+      (rc = dev_upload(h, &h->gt_per_cat, per_cat.data(), K)) || (rc = dev_upload(h, &h->scr_off, scr_off.data(), K + 1)) ||
+      (rc = dev_alloc(h, &h->scr_j, (size_t)scr_off[K])) || (rc = dev_alloc(h, &h->scr_pr, (size_t)scr_off[K])) ||
+      (rc = dev_upload(h, &h->thr, iou_thrs, h->T)) || (rc = dev_upload(h, &h->rec, rec_thrs, h->R)) ||
+      (rc = dev_upload(h, &h->arng, area_rng, (size_t)2 * A)) || (rc = dev_upload(h, &h->max_dets, max_dets, h->M)) ||
+      (rc = dev_alloc(h, &h->cell_cnt, KI)) || (rc = dev_alloc(h, &h->cell_off, KI + 1)) || (rc = dev_alloc(h, &h->cursor, KI)) ||
+      (rc = dev_alloc(h, &h->active, KI)) || (rc = dev_alloc(h, &h->n_active, 1)) || (rc = dev_alloc(h, &h->err, 1)))
+    return rc;
+  MPN_CHECK_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->h_err), sizeof(int), hipHostMallocDefault));
+  return MPN_OK;
+}
+
+}  // namespace
+
+extern "C" int mpn_coco_eval_create(int device, const double *h_gt_bbox, const double *h_gt_area, const int64_t *h_gt_iscrowd,
+                                    const int64_t *h_gt_image_id, const int64_t *h_gt_category_id, const int64_t *h_gt_id, int n_gt,
+                                    const int64_t *h_img_ids, int n_img, const int64_t *h_eval_img_ids, int n_eval,
+                                    const int64_t *h_cat_ids, int n_cat, const double *h_iou_thrs, int n_iou, const double *h_rec_thrs,
+                                    int n_rec, const double *h_area_rng, int n_area, const int *h_max_dets, int n_max_dets,
+                                    mpn_coco_eval **out) {
+  MPN_CHECK_ARG(out != nullptr);
+  *out = nullptr;
+  MPN_CHECK_ARG(n_gt >= 0 && (n_gt == 0 || (h_gt_bbox && h_gt_area && h_gt_iscrowd && h_gt_image_id && h_gt_category_id && h_gt_id)));
+  MPN_CHECK_ARG(n_img >= 1 && h_img_ids != nullptr && n_cat >= 1 && h_cat_ids != nullptr);
+  MPN_CHECK_ARG((long long)n_img * n_cat <= (1LL << 30));
+  MPN_CHECK_ARG(strictly_increasing(h_img_ids, n_img) && strictly_increasing(h_cat_ids, n_cat));
+  MPN_CHECK_ARG(n_eval >= 0 && (n_eval == 0 || h_eval_img_ids != nullptr));
+  MPN_CHECK_ARG(n_iou >= 1 && h_iou_thrs != nullptr && n_rec >= 1 && h_rec_thrs != nullptr);
+  MPN_CHECK_ARG(n_area >= 1 && n_area <= 8 && h_area_rng != nullptr && n_iou * n_area <= 64);
+  MPN_CHECK_ARG(n_max_dets >= 1 && h_max_dets != nullptr);
+  for (int i = 0; i < n_iou; ++i) MPN_CHECK_ARG(std::isfinite(h_iou_thrs[i]));
+  for (int i = 0; i < n_rec; ++i) MPN_CHECK_ARG(std::isfinite(h_rec_thrs[i]));
+  for (int i = 0; i < 2 * n_area; ++i) MPN_CHECK_ARG(!std::isnan(h_area_rng[i]));
+  for (int i = 0; i < n_max_dets; ++i) MPN_CHECK_ARG(h_max_dets[i] >= 1 && h_max_dets[i] <= MPN_COCO_MAX_DETS);
+  for (int g = 0; g < n_gt; ++g) {
+    for (int j = 0; j < 4; ++j) MPN_CHECK_ARG(std::isfinite(h_gt_bbox[(size_t)g * 4 + j]));
+    MPN_CHECK_ARG(!std::isnan(h_gt_area[g]));
+  }
+  int cur = 0;
+  MPN_CHECK_HIP(hipGetDevice(&cur));
+  const int dev = device < 0 ? cur : device;
+  MPN_CHECK_HIP(hipSetDevice(dev));
+  mpn_coco_eval *h = new mpn_coco_eval();
+  h->device = dev;
+  h->I = n_img; h->K = n_cat; h->T = n_iou; h->R = n_rec; h->A = n_area; h->M = n_max_dets;
+  h->Dmax = h_max_dets[n_max_dets - 1];        // evaluateImg runs with maxDets[-1]
+  h->explicit_eval = h_eval_img_ids != nullptr;
+  const int rc = create_impl(h, h_gt_bbox, h_gt_area, h_gt_iscrowd, h_gt_image_id, h_gt_category_id, h_gt_id, n_gt, h_img_ids, n_img,
+                             h_eval_img_ids, n_eval, h_cat_ids, n_cat, h_iou_thrs, h_rec_thrs, h_area_rng, h_max_dets);
+  (void)hipSetDevice(cur);
+  if (rc) { destroy(h); return rc; }
+  *out = h;
+  return MPN_OK;
+}
+
+extern "C" void mpn_coco_eval_destroy(mpn_coco_eval *h) { destroy(h); }
+
+extern "C" int mpn_coco_eval_run(mpn_coco_eval *h, const float *d_rows, int n, double *d_precision, double *d_recall, double *d_scores,
+                                 void *stream) {
+  using namespace mpn;
+  MPN_CHECK_ARG(h != nullptr);
+  MPN_CHECK_ARG(n >= 0 && (n == 0 || d_rows != nullptr));
+  MPN_CHECK_ARG(d_precision != nullptr && d_recall != nullptr && d_scores != nullptr);
+  int cur = 0;
+  MPN_CHECK_HIP(hipGetDevice(&cur));
+  if (cur != h->device) {
+    set_error("mpn_coco_eval_run: the handle lives on device %d, device %d is current", h->device, cur);
+    return MPN_ESTATE;
+  }
+  hipStream_t s = as_stream(stream);
+  const int I = h->I, K = h->K, KI = I * K;
+  if ((size_t)n > h->cap) {
+    MPN_CHECK_HIP(hipStreamSynchronize(s));
+    free_rows(h);
+    const size_t c = (size_t)n;
+    MPN_CHECK_HIP(hipMalloc(&h->row_cell, c * sizeof(int)));
+    MPN_CHECK_HIP(hipMalloc(&h->cell_rows, c * sizeof(int)));
+    MPN_CHECK_HIP(hipMalloc(&h->sorted, c * sizeof(int)));
+    MPN_CHECK_HIP(hipMalloc(&h->drank, c * sizeof(int)));
+    MPN_CHECK_HIP(hipMalloc(&h->slot_score, c * sizeof(float)));
+    MPN_CHECK_HIP(hipMalloc(&h->tpm, c * sizeof(unsigned long long)));
+    MPN_CHECK_HIP(hipMalloc(&h->fpm, c * sizeof(unsigned long long)));
+    MPN_CHECK_HIP(hipMalloc(&h->key, c * sizeof(unsigned long long)));
+    h->cap = c;
+  }
+  const size_t np = (size_t)h->T * h->R * K * h->A * h->M, nr = (size_t)h->T * K * h->A * h->M;
+  coco_fill<<<(unsigned)std::min<size_t>(cdiv_sz(np, 256), 4096), 256, 0, s>>>(d_precision, np, -1.0);
+  coco_fill<<<(unsigned)std::min<size_t>(cdiv_sz(np, 256), 4096), 256, 0, s>>>(d_scores, np, -1.0);
+  coco_fill<<<(unsigned)std::min<size_t>(cdiv_sz(nr, 256), 4096), 256, 0, s>>>(d_recall, nr, -1.0);
+  MPN_CHECK_LAUNCH();
+  MPN_CHECK_HIP(hipMemsetAsync(h->cell_cnt, 0, sizeof(int) * KI, s));
+  MPN_CHECK_HIP(hipMemsetAsync(h->cursor, 0, sizeof(int) * KI, s));
+  MPN_CHECK_HIP(hipMemsetAsync(h->err, 0, sizeof(int), s));
+  if (h->explicit_eval) MPN_CHECK_HIP(hipMemcpyAsync(h->img_eval, h->img_eval_static, I, hipMemcpyDeviceToDevice, s));
+  else MPN_CHECK_HIP(hipMemsetAsync(h->img_eval, 0, I, s));
+  if (n > 0) {
+    coco_bin<<<cdiv(n, 256), 256, 0, s>>>(d_rows, n, h->img_ids, I, h->cat_ids, K, h->explicit_eval, h->img_eval, h->row_cell,
+                                          h->cell_cnt, h->err);
+    MPN_CHECK_LAUNCH();
+  }
+  coco_scan<<<1, 1024, 0, s>>>(h->cell_cnt, KI, h->cell_off, h->active, h->n_active);
+  MPN_CHECK_LAUNCH();
+  if (n > 0) {
+    coco_scatter<<<cdiv(n, 256), 256, 0, s>>>(h->row_cell, n, h->cell_off, h->cursor, h->cell_rows);
+    MPN_CHECK_LAUNCH();
+    CellArgs ca{d_rows, h->cell_off, h->cell_rows, h->active, h->n_active, h->gt_off, h->gt_box, h->gt_crowd, h->gt_igm, h->gt_id,
+                h->gt_bitoff, h->gbits, h->thr, h->arng, h->T, h->A, h->Dmax, h->slot_score, h->tpm, h->fpm, h->key, h->drank};
+    const int lds = h->Dmax * (int)(4 * sizeof(double) + 2 * sizeof(float) + sizeof(int)) + (kCellGtLds / 32) * 64 * (int)sizeof(unsigned);
+    if (int rc = set_max_dyn_lds(reinterpret_cast<const void *>(&coco_cells), lds)) return rc;
+    coco_cells<<<min(n, 16384), 64, lds, s>>>(ca);
+    MPN_CHECK_LAUNCH();
+    coco_rank<<<cdiv(n, kRankThreads), kRankThreads, 0, s>>>(h->key, h->cell_off, I, K, h->sorted);
+    MPN_CHECK_LAUNCH();
+  }
+  // also without rows: evaluated images with GT only give recall 0 / precision 0 entries (cocoeval.py: nd == 0)
+  AccArgs aa{h->cell_off, h->sorted, h->drank, h->npig, h->max_dets, h->img_eval, h->tpm, h->fpm, h->slot_score, h->rec, h->scr_off,
+             h->gt_per_cat, h->scr_j, h->scr_pr, I, K, h->T, h->R, h->A, h->M, h->Dmax, d_precision, d_recall, d_scores};
+  coco_accum<<<K * h->A * h->M, kAccThreads, 0, s>>>(aa);
+  MPN_CHECK_LAUNCH();
+  MPN_CHECK_HIP(hipMemcpyAsync(h->h_err, h->err, sizeof(int), hipMemcpyDeviceToHost, s));
+  MPN_CHECK_HIP(hipStreamSynchronize(s));
+  if (*h->h_err & 1) {
+    set_error("mpn_coco_eval_run: a row names an image id that is not a GT image (loadRes: results do not correspond to the GT set)");
+    return MPN_EINVAL;
+  }
+  if (*h->h_err & 2) {
+    set_error("mpn_coco_eval_run: a row holds a NaN or infinite value");
+    return MPN_EINVAL;
+  }
+  return MPN_OK;
+}
