@@ -285,7 +285,12 @@ typedef struct mpn_frcnn_config {
   int fc_arith;            /* MPN_FC_FP32 (0, default): fc6 on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32).  MPN_FC_SPLIT3 (1; mpn_frcnn_create / mpn_mpnet_create): fc6 and fc7
                               on the bf16 pipe with fp32-level results — both operands split exactly into three bf16 planes (h + m + l = the fp32 value),
                               the six plane products of weight >= 2^-16 accumulated in fp32, the three <= 2^-24 ones (the size of an fp32 product's own
-                              rounding) dropped.  An AUXILIARY arithmetic: the headline and every parity claim are MPN_FC_FP32.  (MPN_VERSION 600) */
+                              rounding) dropped.  An AUXILIARY arithmetic: the headline and every parity claim are MPN_FC_FP32.  (MPN_VERSION 600)
+                              Edge values, both arithmetics: every output is NaN / +inf / -inf / finite exactly when the float64 sum is (inf x 0
+                              and inf - inf give NaN); the ReLU is t < 0 ? 0 : t, so NaN passes through it.  MPN_FC_SPLIT3 specifics: a finite
+                              |x| >= 3.3962e38 (where bf16 rounding overflows) keeps h = +-bf16's largest finite value and still splits exactly;
+                              a non-finite x is carried in h alone; an fp32 subnormal below bf16's 2^-133 grid is carried to within 2^-134
+                              absolutely (the only inexact split), and a weight with 0 < |w| < 2^-134 counts as zero against an infinite x. */
 } mpn_frcnn_config;
 #define MPN_FC_FP32 0
 #define MPN_FC_SPLIT3 1

@@ -108,6 +108,9 @@ struct SplitkSlotScope {
 // Always launched un-split (like row_invariant = 2, so a row's result does not depend on the row count); k_end = the K index (multiple of 32) at which segment i ends.
 // bin_rows > 0 (round 6): the rows are packed (bin, roi) pairs, bin_rows per bin, x_pitch rows between the operand's K chunks, and the output is
 // scattered into [N / 8][M / bin_rows][out_Mp][8] — the fc6 operand of the MultiPathNet towers (GemmArgs in dense.hip)
+// Contract: every scale[seg][r], r < rs_mod, is finite and non-zero — the in-place form (GemmArgs RSI, the default) multiplies the accumulator by
+// scale[seg] / scale[seg + 1] at each boundary.  Pad rows included: l2norm_scale_rows_kernel writes 1 there.  The kernel takes a scale outside the
+// contract as 1 (that row unscaled) rather than let 0 / 0 turn it into NaN.
 struct GemmRowScale { int n_seg; int k_end[2]; const float *scale[3]; int rs_mod; int bin_rows, out_Mp, x_pitch; };
 int linear_c8_rowscaled(const float *d_x_c8, int M, int K, const float *d_wpk, const float *d_bpk, int N, int relu, float *d_y_c8, hipStream_t s,
                         int Mp_override, const GemmRowScale &rs);

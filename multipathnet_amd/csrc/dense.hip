@@ -1168,10 +1168,13 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
       if (a.rs2) rsc[2][ni] = a.rs2[row];
     }
     if constexpr (RSI) {  // rsc[k] <- s_k / s_(k+1) for the interior boundaries, the last segment's scale stays: applied at the end
+      // Contract (GemmRowScale): every scale this launch reads is finite and non-zero.  One outside it (0 or non-finite) is taken as 1 here —
+      // that row comes out unscaled instead of as 0 / 0 = NaN times its accumulator
+      auto in_contract = [](float v) { return (v != 0.0f && __builtin_isfinite(v)) ? v : 1.0f; };
       const int nseg = a.nsb + 1;
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        const float s0 = rsc[0][ni], s1 = rsc[1][ni], s2 = rsc[2][ni];
+        const float s0 = in_contract(rsc[0][ni]), s1 = in_contract(rsc[1][ni]), s2 = in_contract(rsc[2][ni]);
         if (nseg == 2) { rsc[0][ni] = s0 / s1; rsc[2][ni] = s1; }
         else if (nseg == 3) { rsc[0][ni] = s0 / s1; rsc[1][ni] = s1 / s2; rsc[2][ni] = s2; }
         else rsc[2][ni] = s0;
@@ -1511,10 +1514,13 @@ static int linear_c8_impl(const float *d_x_c8, int M, int K, const float *d_wpk,
 // v_mfma_f32_32x32x16_bf16 — bf16 x bf16 is exact in fp32, the accumulation is the MFMA's fp32 — and the bf16 pipe runs 16x the fp32 MFMA rate:
 // six instructions of 32 cycles replace eight fp32 MFMAs of 64 (K = 16), 2.67x less matrix time for 1.5x the operand bytes.
 //
-// Kernel: block = 256 (N, weight rows) x 256 (M, ROI rows) x one k16 step per stage, four waves of 128 x 128 (16 accumulators = all 256 AGPRs, one
-// wave per SIMD); per stage 48 KiB of operands (3 planes x 2 chunks x 256 rows x 16 B, both sides) arrive by LDS-DMA into a two-slot ring (stage st + 2 goes
-// into stage st's slot as soon as stage st starts: its fragments are already in registers), the fragments of the next stage are read between
-// the 96 MFMAs of the current one (one LDS or DMA instruction per MFMA slot, no VALU in the loop), ONE barrier per stage.  15.6 B / clock / CU of DMA, 31 B / clock / CU of LDS reads.
+// Kernel: block = 256 (N, weight rows) x 128 (M, ROI rows) x one k16 step per stage, four waves of 128 weight rows x 64 ROI rows (8 accumulators
+// in AGPRs for the main sum, 8 in VGPRs for the corrections; one wave per SIMD); per stage 36 KiB of operands (3 planes x 2 chunks x (256 + 128)
+// rows x 16 B) arrive by LDS-DMA into a three-slot ring (108 KiB: stage st + 2 lands while st and st + 1 are being read), the fragments of the next
+// stage are read between the 48 MFMAs of the current one (one LDS or DMA instruction per MFMA slot, no VALU in the loop), ONE barrier per stage.
+// Edge values (mpn.h, fc_arith): a finite operand whose bf16 rounding would overflow keeps h = +-bf16's largest finite value, so the split stays
+// exact up to FLT_MAX; a non-finite operand is carried in h alone (m = l = 0), and the epilogue takes the main sum alone wherever the correction
+// sum is not finite (a non-finite h times a zero correction plane is NaN there), so a result has the class the fp32 path gives it.
 // Split-K over a FIXED number of K ranges (a function of K alone: a row's summation order does not depend on the rows it is batched with), partial
 // slabs reduced in split order by splitk_reduce_kernel, which also adds the bias and applies the ReLU.
 typedef __bf16 s3_bf16x8 __attribute__((ext_vector_type(8)));
@@ -1527,6 +1533,13 @@ __device__ __forceinline__ unsigned s3_pack2(float lo, float hi) {  // bits 0-15
 }
 __device__ __forceinline__ float s3_lo(unsigned pk) { return __uint_as_float(pk << 16); }
 __device__ __forceinline__ float s3_hi(unsigned pk) { return __uint_as_float(pk & 0xffff0000u); }
+// a finite value that rounds past bf16's largest finite magnitude (|x| >= 0x1.fep127 = 3.3962e38) gets h = +-0x7F7F instead of +-inf: x - h is then
+// exact (Sterbenz) and has at most 16 significant bits left, which m and l hold.  Values below that threshold keep their round-to-nearest h.
+__device__ __forceinline__ unsigned s3_no_overflow(unsigned pk, float lo, float hi) {
+  if ((pk & 0x7fffu) == 0x7f80u && __builtin_isfinite(lo)) pk -= 1u;                 // 0x7F80 -> 0x7F7F, sign bit kept
+  if ((pk & 0x7fff0000u) == 0x7f800000u && __builtin_isfinite(hi)) pk -= 0x10000u;
+  return pk;
+}
 
 // fp32 C8 matrix [Kc][rows_src][8] -> three bf16 planes [3][Kc][rows_dst][8] (rows beyond rows_valid are left untouched: the planes are
 // allocated zeroed).  One thread per 8-float record.
@@ -1541,8 +1554,9 @@ __global__ __launch_bounds__(256) void split3_planes_kernel(const float *__restr
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float x0 = v[2 * i], x1 = v[2 * i + 1];
-    h[i] = s3_pack2(x0, x1);
-    const float r0 = x0 - s3_lo(h[i]), r1 = x1 - s3_hi(h[i]);       // exact (Sterbenz-type cancellation: h is x rounded to 8 bits)
+    h[i] = s3_no_overflow(s3_pack2(x0, x1), x0, x1);
+    // exact (Sterbenz-type cancellation: h is x rounded to 8 bits); a non-finite x (h = x) leaves m = l = 0 instead of inf - inf = NaN
+    const float r0 = __builtin_isfinite(x0) ? x0 - s3_lo(h[i]) : 0.0f, r1 = __builtin_isfinite(x1) ? x1 - s3_hi(h[i]) : 0.0f;
     m[i] = s3_pack2(r0, r1);
     l[i] = s3_pack2(r0 - s3_lo(m[i]), r1 - s3_hi(m[i]));
   }
@@ -1716,8 +1730,14 @@ __global__ __launch_bounds__(256, 1) void gemm_c8_split3_kernel(Split3Args a) {
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int m = m0 + wm * 64 + ni * 32 + l31;
-        const f32x4 v = {acc[mi][ni][g * 4 + 0] + acc2[mi][ni][g * 4 + 0], acc[mi][ni][g * 4 + 1] + acc2[mi][ni][g * 4 + 1],
-                         acc[mi][ni][g * 4 + 2] + acc2[mi][ni][g * 4 + 2], acc[mi][ni][g * 4 + 3] + acc2[mi][ni][g * 4 + 3]};
+        // a non-finite correction sum only comes from a non-finite operand (h = x, m = l = 0: h times a zero correction plane is NaN), whose
+        // class the main sum already carries: it stands alone there.  Finite data: acc + acc2, as ever.
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float c = acc2[mi][ni][g * 4 + e];
+          v[e] = __builtin_isfinite(c) ? acc[mi][ni][g * 4 + e] + c : acc[mi][ni][g * 4 + e];
+        }
         if (n < a.part_np && m < a.part_mp) *reinterpret_cast<f32x4 *>(yb + ((size_t)(n / 8) * a.part_mp + m) * 8 + half * 4) = v;
       }
     }
@@ -2476,7 +2496,8 @@ __global__ __launch_bounds__(256) void roi_pool_pm_rmq_kernel(const float *__res
 }
 
 // pool (+ optionally nn.Normalize(2) x mul, or nn.MulConstant(mul)) one map into its channel range of the mix GEMM's operand
-// per-ROI scale mul / sqrt(sum + 1e-10) for n < N, 0 for the padding rows N .. Mp-1 (their pooled rows are zero)
+// per-ROI scale mul / sqrt(sum + 1e-10) for n < N, 1 for the padding rows N .. Mp-1 (their pooled rows are zero; the consumer's contract —
+// GemmRowScale in dense.h — is a finite non-zero scale on every row it reads: the in-place form divides by it)
 __global__ __launch_bounds__(256) void l2norm_scale_rows_kernel(const float *__restrict__ part, int G, int N, int Mp, float mul, float *__restrict__ scale) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= Mp) return;
@@ -2484,7 +2505,7 @@ __global__ __launch_bounds__(256) void l2norm_scale_rows_kernel(const float *__r
   if (n < N) for (int g = lane; g < G; g += 64) ss += part[(size_t)n * G + g];
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
-  if (lane == 0) scale[n] = n < N ? mul / sqrtf(ss + 1e-10f) : 0.0f;
+  if (lane == 0) scale[n] = n < N ? mul / sqrtf(ss + 1e-10f) : 1.0f;
 }
 
 int roi_pool_pm_rmq(Act feat, const float *d_tables_pm, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr, float *d_x_c8, hipStream_t s, int roi_stride, int Mp, int normalize, float mul, float *d_scale_out) {
@@ -2716,6 +2737,128 @@ extern "C" int mpn_debug_roi_pool_rmq_mismatches(const float *d_feat_nchw, int C
   }
   if (rc == MPN_OK) MPN_CHECK_HIP(hipMemcpy(n_mismatch, cnt, 4, hipMemcpyDeviceToHost));
   (void)hipFree(act); (void)hipFree(tab); (void)hipFree(o1); (void)hipFree(o2); (void)hipFree(cnt);
+  if (tabpm) (void)hipFree(tabpm);
+  return rc;
+}
+
+// test hook (tests/test_gpu_gemm_numerics.py): ONE launch form of the linear GEMM family on row-major device operands x[M,K], w[N,K], b[N]
+// (b may be null), with the C8 conversion and weight packing mpn_linear_forward does.  The hooks gemm_kch / gemm_split / gemm_rsi /
+// split3_ranges pick the variant inside a form.
+//   form 0: linear_c8 with row_invariant = ri (0, 1, 2) and C8 output (the direct form when un-split); res (optional, row-major [M,N]) is added
+//           before the ReLU.
+//   form 1: linear_c8_rowscaled over n_seg (1-3) K segments ending at k_end[0..n_seg-2] (host array, multiples of 32), scales [n_seg][rs_mod]
+//           (device); bin_rows > 0: packed (bin, roi) rows, M / bin_rows bins of bin_rows rows, the output scattered into out_Mp rows per bin.
+//   form 2: split3_planes of both operands, then linear_c8_split3.
+// y: row-major [rows_out, N] with rows_out = M, or (M / bin_rows) * out_Mp for the packed form (row bin * out_Mp + roi).  raw (optional,
+// raw_cap floats): a copy of the whole C8 output buffer [lin_np(N) / 8][pitch][8], pad rows included (pitch = lin_mp(M), or the packed
+// form's (M / bin_rows) * out_Mp; the buffer is NaN-filled before the launch, so a row no launch writes reads NaN).  Synchronous.
+__global__ void dbg_fill_kernel(float *p, size_t n, float v) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) p[t] = v;
+}
+extern "C" int mpn_debug_linear_form(const float *d_x, int M, int K, const float *d_w, const float *d_b, int N, int relu, int form, int ri,
+                                     const float *d_res, int n_seg, const int *k_end, const float *d_scales, int rs_mod, int bin_rows, int out_Mp,
+                                     float *d_y, float *d_raw, size_t raw_cap) {
+  MPN_CHECK_ARG(d_x && d_w && d_y && M > 0 && K > 0 && N > 0 && form >= 0 && form <= 2 && ri >= 0 && ri <= 2);
+  MPN_CHECK_ARG(form == 1 || bin_rows == 0);
+  MPN_CHECK_ARG(form != 1 || (n_seg >= 1 && n_seg <= 3 && d_scales && rs_mod > 0 && (n_seg == 1 || k_end)));
+  MPN_CHECK_ARG(bin_rows == 0 || (bin_rows > 0 && M % bin_rows == 0 && out_Mp >= bin_rows && out_Mp % 8 == 0));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  const int K64 = round_up(K, 64), NP = lin_np(N), Mp = lin_mp(M);
+  const int pitch = bin_rows > 0 ? (M / bin_rows) * out_Mp : Mp;   // output rows per channel block
+  const int x_pitch = bin_rows > 0 ? M : Mp;                        // operand rows per K chunk (packed: no padding between chunks)
+  const size_t xe = (size_t)(K64 / 8) * Mp * 8 + (size_t)Mp * 8;    // (+ one chunk of slack: a packed operand's last row tile reads past its rows)
+  const size_t we = lin_wpk_elems(K64, N), ye = (size_t)(NP / 8) * pitch * 8;
+  if (d_raw && raw_cap < ye) { set_error("mpn_debug_linear_form: raw needs %zu floats", ye); return MPN_EINVAL; }
+  float *x = nullptr, *w = nullptr, *b = nullptr, *y = nullptr, *res = nullptr;
+  unsigned short *x3 = nullptr, *w3 = nullptr;
+  MPN_CHECK_HIP(hipMalloc(&x, xe * 4)); MPN_CHECK_HIP(hipMalloc(&w, we * 4)); MPN_CHECK_HIP(hipMalloc(&b, (size_t)NP * 4));
+  MPN_CHECK_HIP(hipMalloc(&y, ye * 4));
+  MPN_CHECK_HIP(hipMemset(x, 0, xe * 4));
+  hipLaunchKernelGGL(dbg_fill_kernel, dim3((unsigned)cdiv_sz(ye, 256)), dim3(256), 0, nullptr, y, ye, __builtin_nanf(""));
+  MPN_CHECK_LAUNCH();
+  {
+    const size_t total = (size_t)((K + 7) / 8) * M;
+    hipLaunchKernelGGL(rowmajor_to_c8_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, d_x, M, K, x_pitch, x);
+    MPN_CHECK_LAUNCH();
+  }
+  int rc = pack_linear_weights(d_w, d_b, K, N, 1, w, b, nullptr);
+  if (rc == MPN_OK && d_res) {
+    MPN_CHECK_HIP(hipMalloc(&res, ye * 4)); MPN_CHECK_HIP(hipMemset(res, 0, ye * 4));
+    rc = rowmajor_to_c8(d_res, M, N, res, nullptr);
+  }
+  if (rc == MPN_OK && form == 0) rc = linear_c8(x, M, K, w, b, N, relu, y, nullptr, nullptr, 0, res, ri);
+  if (rc == MPN_OK && form == 1) {
+    GemmRowScale g{};
+    g.n_seg = n_seg; g.rs_mod = rs_mod;
+    for (int i = 0; i + 1 < n_seg; ++i) g.k_end[i] = k_end[i];
+    for (int i = 0; i < n_seg; ++i) g.scale[i] = d_scales + (size_t)i * rs_mod;
+    if (bin_rows > 0) { g.bin_rows = bin_rows; g.out_Mp = out_Mp; g.x_pitch = M; }
+    rc = linear_c8_rowscaled(x, M, K, w, b, N, relu, y, nullptr, bin_rows > 0 ? round_up(M, 128) : 0, g);
+  }
+  if (rc == MPN_OK && form == 2) {
+    const size_t x3e = split3_plane_elems(K, Mp), w3e = split3_plane_elems(K, NP);
+    MPN_CHECK_HIP(hipMalloc(&x3, x3e * 2)); MPN_CHECK_HIP(hipMalloc(&w3, w3e * 2));
+    MPN_CHECK_HIP(hipMemset(x3, 0, x3e * 2)); MPN_CHECK_HIP(hipMemset(w3, 0, w3e * 2));
+    rc = split3_planes(x, K, Mp, Mp, x3, nullptr);
+    if (rc == MPN_OK) rc = split3_planes(w, K, NP, NP, w3, nullptr);
+    if (rc == MPN_OK) rc = linear_c8_split3(x3, M, K, w3, b, N, relu, y, nullptr);
+  }
+  if (rc == MPN_OK) {
+    const int rows_out = bin_rows > 0 ? pitch : M;
+    const size_t total = (size_t)rows_out * N;
+    hipLaunchKernelGGL(c8_to_rowmajor_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, y, rows_out, N, pitch, d_y);
+    MPN_CHECK_LAUNCH();
+  }
+  if (rc == MPN_OK && d_raw) MPN_CHECK_HIP(hipMemcpy(d_raw, y, ye * 4, hipMemcpyDeviceToDevice));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  (void)hipFree(x); (void)hipFree(w); (void)hipFree(b); (void)hipFree(y);
+  if (res) (void)hipFree(res);
+  if (x3) (void)hipFree(x3);
+  if (w3) (void)hipFree(w3);
+  return rc;
+}
+
+// test hook: the three bf16 planes split3_planes_kernel writes for the fp32 values x[n] (n % 8 == 0): planes[3][n] (h, m, l) as bf16 bit patterns
+extern "C" int mpn_debug_split3_planes(const float *d_x, int n, unsigned short *d_planes) {
+  MPN_CHECK_ARG(d_x && d_planes && n > 0 && n % 8 == 0);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  const int rows = n / 8;   // the vector as a C8 matrix of ONE chunk (K = 8): record r = x[8 r .. 8 r + 7]
+  const size_t e = split3_plane_elems(8, rows), plane = e / 3;
+  unsigned short *p = nullptr;
+  MPN_CHECK_HIP(hipMalloc(&p, e * 2));
+  MPN_CHECK_HIP(hipMemset(p, 0, e * 2));
+  int rc = split3_planes(d_x, 8, rows, rows, p, nullptr);
+  for (int i = 0; i < 3 && rc == MPN_OK; ++i) MPN_CHECK_HIP(hipMemcpy(d_planes + (size_t)i * n, p + i * plane, (size_t)n * 2, hipMemcpyDeviceToDevice));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  (void)hipFree(p);
+  return rc;
+}
+
+// test hook: the per-ROI scale vector the normalising pixel-major range-max pooling writes for its consumer GEMM (roi_pool_pm_rmq with
+// d_scale_out; nn.Normalize(2) x mul): scale_out[Mp] — rows N .. Mp - 1 are the pad rows.  The scale array is NaN-filled first.
+extern "C" int mpn_debug_l2norm_row_scales(const float *d_feat_nchw, int C, int H, int W, const float *d_rois, int roi_stride, int N, int PH, int PW,
+                                           float scale, int Mp, float mul, float *d_scale_out) {
+  MPN_CHECK_ARG(d_feat_nchw && d_rois && d_scale_out && C > 0 && H > 0 && W > 0 && N > 0 && Mp >= N);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  const RoiRule rr{1.0f, 0, g_dbg_roi_bins};
+  float *act = nullptr, *tabpm = nullptr, *o = nullptr;
+  const size_t ab = act_bytes(C, H, W);
+  const int L = vmax_levels_for(H);
+  const size_t oe = (size_t)((C + 7) / 8) * PH * PW * round_up(Mp, 128) * 8;
+  MPN_CHECK_HIP(hipMalloc(&act, ab)); MPN_CHECK_HIP(hipMalloc(&o, oe * 4));
+  MPN_CHECK_HIP(hipMemset(act, 0, ab)); MPN_CHECK_HIP(hipMemset(o, 0, oe * 4));
+  hipLaunchKernelGGL(dbg_fill_kernel, dim3((unsigned)cdiv(Mp, 256)), dim3(256), 0, nullptr, d_scale_out, (size_t)Mp, __builtin_nanf(""));
+  MPN_CHECK_LAUNCH();
+  Act a = make_act(act, C, H, W);
+  int rc = nchw_to_c8p(d_feat_nchw, C, H, W, a, nullptr);
+  if (rc == MPN_OK) {
+    MPN_CHECK_HIP(hipMalloc(&tabpm, pixel_major_elems(a) * sizeof(float) * (L + 1)));
+    rc = build_vmax_tables_pm(a, tabpm, nullptr);
+  }
+  if (rc == MPN_OK) rc = roi_pool_pm_rmq(a, tabpm, d_rois, N, PH, PW, scale, rr, o, nullptr, roi_stride, Mp, 1, mul, d_scale_out);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  (void)hipFree(act); (void)hipFree(o);
   if (tabpm) (void)hipFree(tabpm);
   return rc;
 }
