@@ -133,6 +133,15 @@ double mpn_pick_scale(int H, int W, double target, double max_size);
 /* project_im_rois (ImageDetect.lua:66-70): rois = {1, (boxes-1)*s+1}.  d_boxes [n,4] -> d_rois [n,5]. */
 int mpn_project_im_rois(const float *d_boxes, int n, double scale, float *d_rois, void *stream);
 
+/* project_im_rois' multi-scale branch (ImageDetect.lua:57-65), completed as Fast R-CNN's _project_im_rois does.
+ * In fp32, each operation rounded: w = x2 - x1 + 1, h = y2 - y1 + 1, area = w*h, d_l = |area * (s_l*s_l) - 224*224| with
+ * s_l = (float)h_scales[l]; level = the FIRST l with minimal d_l under TH's min (a NaN difference stops the scan where it stands, so
+ * boxes whose differences are all equal or all NaN land on level 0).  d_rois [n,5] = {level + 1, (x1-1)*s_level+1, ...}: column 0
+ * is inn.ROIPooling's 1-based batch index into the [S,C,h,w] stack of level maps.  1 <= n_scales <= MPN_MAX_SCALES, every scale
+ * finite and > 0.  n_scales == 1 is mpn_project_im_rois bit for bit. */
+#define MPN_MAX_SCALES 8
+int mpn_project_im_rois_levels(const float *d_boxes, int n, int n_scales, const double *h_scales, float *d_rois, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * nn.Module:updateOutput mirrors
  * ---------------------------------------------------------------------------------------------- */
@@ -537,6 +546,25 @@ int mpn_frcnn_shard_finish(mpn_frcnn *p, const float *d_class_all, int N, int wo
                            void *stream);
 int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const float *d_image, int H, int W, const float *d_boxes, int N,
                                float *d_dets, int top_cap, int *d_n_dets, void *stream);
+
+/* Multi-scale testing (Fast R-CNN's image pyramid; getImages + project_im_rois with a scale TABLE, ImageDetect.lua:22-73; DESIGN.md
+ * section 11).  h_targets [n_scales] are getImages' targets t_l; cfg.scale_max stays the cap.
+ *   n_scales == 0 restores the creation-time cfg.scale_target (single scale); n_scales == 1 sets scale_target = t_0 (single scale,
+ *   today's path bit for bit); 2 <= n_scales <= MPN_MAX_SCALES sets the pyramid.  Targets must be finite and > 0.  Arguments are
+ *   checked before the device is touched; the call synchronises the device, drops every captured launch graph of the handle and
+ *   the cached trunk output (the next detect must pass an image), and allocates the per-level map slots on first use.
+ * With a pyramid, for an image [3,H0,W0]: s_l = mpn_pick_scale(H0, W0, t_l, scale_max), level size (H_l, W_l) = ((int)(H0*s_l),
+ * (int)(W0*s_l)), each level resampled and transformed as the single-scale image is and placed top-left in a zero canvas
+ * (max H_l) x (max W_l) (0 in the transformed domain); the whole trunk runs on every canvas; every ROI is levelled and projected
+ * as mpn_project_im_rois_levels does and pools from its level's map; heads, softmax, decode on the ORIGINAL boxes, clamp to the
+ * ORIGINAL image, NMS, voting and top-k are unchanged.  Levels with a scale equal to an earlier level's are computed once (no ROI
+ * can pick them).  The canvas must fit max_h x max_w (MPN_EINVAL otherwise).  Supported by mpn_frcnn_detect (cached features
+ * included) and mpn_frcnn_test_one (iterative localisation re-levels the refined boxes on the cached maps); the pipelined,
+ * host-fed and sharded forms return MPN_EINVAL while a pyramid is set.  Only mpn_frcnn_create handles take a pyramid:
+ * mpn_mpnet_create / mpn_resnet_create / mpn_graph_create handles return MPN_EINVAL for n_scales > 1.
+ * Debug tensors (mpn_frcnn_debug_tensor) with a pyramid: "conv5.<l>" (level l's final map, NCHW at the canvas geometry) and
+ * "rois" ([N,5], the projected table of the last head pass; also kept without a pyramid). */
+int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_targets);
 
 /* Captured launch graphs.  The kernel chains of the per-image path — the head (transform .. decode) and the tail (per-class NMS,
  * voting, top-k) of mpn_frcnn_test_one / _pipelined / _pipelined_host, and the bodies of mpn_frcnn_shard_head / _shard_nms /

@@ -2,6 +2,8 @@
 // ROI projection, Foveal / ContextRegion / BBoxNorm / SelectBoxes modules, softmax, bbox decode,
 // clamp, per-class scored-box selection and the global top-k.  Each kernel cites the reference
 // lines it mirrors; fp32 arithmetic follows the reference's operation order (no FMA contraction).
+#include <cmath>
+
 #include "mpn_internal.h"
 
 namespace mpn {
@@ -714,7 +716,72 @@ int project_im_rois_copy(const float *d_boxes, int n, double scale, float *d_roi
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
+
+struct ScaleTable { int n; float s[MPN_MAX_SCALES], sq[MPN_MAX_SCALES]; };
+
+// ImageDetect.lua:57-65 completed (include/mpn.h mpn_project_im_rois_levels): the level is the first l minimising |w*h*s_l^2 - 224^2|
+// under THTensor_(min) — start from the first value, take a value when !(value >= min), stop once a NaN is taken — then :66-70's
+// projection with that level's scale.  The table is walked with constant indices (no runtime-indexed kernel-argument array).
+__global__ void project_rois_levels_kernel(const float *__restrict__ boxes, int n, ScaleTable t, float *__restrict__ rois) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float *b = boxes + 4 * (size_t)i;
+  const float bx[4] = {b[0], b[1], b[2], b[3]};
+  float w = bx[2] - bx[0];
+  w = w + 1.0f;
+  float h = bx[3] - bx[1];
+  h = h + 1.0f;
+  const float area = w * h;
+  int lvl = 0;
+  float sl = t.s[0], best = fabsf(area * t.sq[0] - 50176.0f);
+#pragma unroll
+  for (int l = 0; l < MPN_MAX_SCALES; ++l) {
+    if (l >= t.n) break;
+    const float d = fabsf(area * t.sq[l] - 50176.0f);
+    if (!(d >= best)) {
+      best = d; lvl = l; sl = t.s[l];
+      if (d != d) break;
+    }
+  }
+  float *r = rois + 5 * (size_t)i;
+  r[0] = (float)(lvl + 1);
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    float v = bx[f];
+    v = v + (-1.0f);
+    v = v * sl;
+    v = v + 1.0f;
+    r[1 + f] = v;
+  }
+}
+
+int project_im_rois_levels(const float *d_boxes, int n, int n_scales, const double *scales, float *d_rois, hipStream_t s) {
+  if (n_scales < 1 || n_scales > MPN_MAX_SCALES || !scales) {
+    set_error("mpn_project_im_rois_levels: n_scales %d outside 1..MPN_MAX_SCALES (%d)", n_scales, MPN_MAX_SCALES);
+    return MPN_EINVAL;
+  }
+  ScaleTable t{};
+  t.n = n_scales;
+  for (int l = 0; l < n_scales; ++l) {
+    t.s[l] = (float)scales[l];
+    if (!(std::isfinite(scales[l]) && scales[l] > 0.0 && std::isfinite(t.s[l]) && t.s[l] > 0.0f)) {
+      set_error("mpn_project_im_rois_levels: scale %d is %g (must be finite and > 0)", l, scales[l]);
+      return MPN_EINVAL;
+    }
+    t.sq[l] = t.s[l] * t.s[l];
+  }
+  MPN_CHECK_ARG(n >= 0);
+  if (n == 0) return MPN_OK;
+  MPN_CHECK_ARG(d_boxes && d_rois);
+  hipLaunchKernelGGL(project_rois_levels_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, d_boxes, n, t, d_rois);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
 }  // namespace mpn
+
+extern "C" int mpn_project_im_rois_levels(const float *d_boxes, int n, int n_scales, const double *h_scales, float *d_rois, void *stream) {
+  return project_im_rois_levels(d_boxes, n, n_scales, h_scales, d_rois, as_stream(stream));
+}
 
 extern "C" int mpn_foveal_forward(const float *d_rois, int N, float *d_out, void *stream) {
   MPN_CHECK_ARG(N >= 0);

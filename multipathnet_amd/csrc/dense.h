@@ -59,6 +59,10 @@ int c8_to_rowmajor(const float *d_c8, int M, int N, float *d_y, hipStream_t s);
 // image transformer fused with the NCHW->C8P conversion (channels 3..7 zero)
 int image_transform_c8p(const float *d_in, int H, int W, const int *swap, double scale, const double *mean,
                         const double *std, int has_std, Act out, hipStream_t s);
+// the same for one level of an image pyramid: the H x W image top-left in the out.H x out.W canvas, every other interior pixel 0
+// (getImages' zero-padded batch, ImageDetect.lua:44-49)
+int image_transform_canvas_c8p(const float *d_in, int H, int W, const int *swap, double scale, const double *mean,
+                               const double *std, int has_std, Act out, hipStream_t s);
 
 // --- compute ------------------------------------------------------------------------------------
 // out = relu?(conv3x3(in) + b); optional fused ceil-mode 2x2 max-pool writes `pooled` as well
@@ -118,18 +122,21 @@ int linear_c8_rowscaled(const float *d_x_c8, int M, int K, const float *d_wpk, c
 size_t split3_plane_elems(int K, int rows);
 int split3_planes(const float *d_c8, int K, int rows_src, int rows_valid, unsigned short *d_planes, hipStream_t s);
 int linear_c8_split3(const unsigned short *d_x3, int M, int K, const unsigned short *d_w3, const float *d_bpk, int N, int relu, float *d_y_c8, hipStream_t s);
+// A stack of n equal-geometry maps `stride` floats apart (the levels of an image pyramid): a ROI pools from map (column 0) - 1,
+// inn.ROIPooling's 1-based batch index.  n == 0: one map, column 0 not read (the single-scale instantiations).
+struct LevelStack { size_t stride; int n; };
 // ROI max-pool reading a C8P feature map and writing the C8 matrix the fc6 GEMM consumes:
 // chunk q = cb*PH*PW + bin, row = roi.  argmax (optional) [N,C,PH,PW] int32 as the NCHW kernel.
 // roi_stride: floats between consecutive rois (5; 20 selects one Foveal region out of the [4N,5] table);
 // Mp: row pitch of the output matrix (0 = lin_mp(N)).
 int roi_pool_c8(Act feat, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr,
-                float *d_x_c8, int32_t *d_argmax, hipStream_t s, int roi_stride = 5, int Mp = 0);
+                float *d_x_c8, int32_t *d_argmax, hipStream_t s, int roi_stride = 5, int Mp = 0, LevelStack lv = LevelStack{0, 0});
 // The same pooling from a pixel-major copy [y][x][Cb*8] of the map (one contiguous 1 KiB per pixel and 256 channels; bit-identical
 // output, no argmax): c8p_to_pixel_major once per image, then roi_pool_pm.
 size_t pixel_major_elems(Act feat);
 int c8p_to_pixel_major(Act feat, float *d_pm, hipStream_t s);
 int roi_pool_pm(Act feat, const float *d_pm, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr,
-                float *d_x_c8, hipStream_t s, int roi_stride = 5, int Mp = 0);
+                float *d_x_c8, hipStream_t s, int roi_stride = 5, int Mp = 0, LevelStack lv = LevelStack{0, 0});
 // vertical range-max tables of a C8P map (levels 1..vmax_levels_for(H), each feat.elems() floats) and the ROI max-pool that
 // reads them: identical output to roi_pool_c8 (no argmax), cost 2 x bin-width reads per bin instead of bin-height x bin-width
 int vmax_levels_for(int H);

@@ -1980,6 +1980,39 @@ int image_transform_c8p(const float *d_in, int H, int W, const int *swap, double
   return MPN_OK;
 }
 
+// One level of getImages' padded batch (ImageDetect.lua:44-49: images:zero(), then the level's image copied top-left): the whole
+// Hc x Wc canvas interior is written, the level's H x W pixels exactly as image_transform_c8p_kernel writes them, the rest 0.
+__global__ void image_transform_canvas_c8p_kernel(const float *__restrict__ in, int H, int W, int Hc, int Wc, int s0, int s1, int s2,
+                                                  double scale, double m0, double m1, double m2, double d0, double d1, double d2,
+                                                  int has_std, float *__restrict__ out, int Hp, int Wp) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)Hc * Wc) return;
+  const int x = (int)(t % Wc), y = (int)(t / Wc);
+  f32x4 lo = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  if (y < H && x < W) {
+    const size_t plane = (size_t)H * W, i = (size_t)y * W + x;
+    double v0 = (double)in[(size_t)s0 * plane + i], v1 = (double)in[(size_t)s1 * plane + i], v2 = (double)in[(size_t)s2 * plane + i];
+    if (scale != 1.0) { v0 = v0 * scale; v1 = v1 * scale; v2 = v2 * scale; }
+    v0 = v0 + (-m0); v1 = v1 + (-m1); v2 = v2 + (-m2);
+    if (has_std) { v0 = v0 / d0; v1 = v1 / d1; v2 = v2 / d2; }
+    lo = f32x4{(float)v0, (float)v1, (float)v2, 0.0f};
+  }
+  float *o = out + (((size_t)y + 1) * Wp + x + 1) * 8;
+  *reinterpret_cast<f32x4 *>(o) = lo;
+  *reinterpret_cast<f32x4 *>(o + 4) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+int image_transform_canvas_c8p(const float *d_in, int H, int W, const int *swap, double scale, const double *mean, const double *std,
+                               int has_std, Act out, hipStream_t s) {
+  MPN_CHECK_ARG(d_in && out.p && H > 0 && W > 0 && H <= out.H && W <= out.W && out.C <= 8);
+  const size_t plane = (size_t)out.H * out.W;
+  hipLaunchKernelGGL(image_transform_canvas_c8p_kernel, dim3((unsigned)cdiv_sz(plane, 256)), dim3(256), 0, s, d_in, H, W, out.H, out.W,
+                     swap[0], swap[1], swap[2], scale, mean[0], mean[1], mean[2], has_std ? std[0] : 1.0, has_std ? std[1] : 1.0,
+                     has_std ? std[2] : 1.0, has_std, out.p, out.Hp, out.Wp);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
 // Re-lays the zero halo of up to kHaloMax C8P activations for a new image size in ONE launch: every record of a plane that is not one of the
 // H x W interior pixels (row 0, rows H + 1 .. Hp - 1, column 0, columns W + 1 .. Wp - 1).  The interior is rewritten by the producing layer
 // before anything reads it; the halo is what the 3x3 padding and the ragged tile edges read.  (Round 5: this replaces one hipMemsetAsync of
@@ -2082,12 +2115,18 @@ __global__ void maxpool2x2_nchw_kernel(const float *__restrict__ in, size_t BC, 
   out[t] = m;
 }
 
+// the map of a ROI inside a LevelStack: column 0 is the 1-based level; a value outside 1..n (NaN included) reads level 0
+__device__ __forceinline__ size_t roi_level_offset(float b, LevelStack lv) {
+  return (b >= 1.0f && b <= (float)lv.n) ? (size_t)((int)b - 1) * lv.stride : 0;
+}
+
 // ROI max-pool: C8P feature map -> C8 matrix [cb*PH*PW + bin][Mp][8].  One thread per
-// (cb, bin, roi) half-record; roi fastest so a wave writes 1 KiB contiguous.
+// (cb, bin, roi) half-record; roi fastest so a wave writes 1 KiB contiguous.  LEVELS: the map is one of a LevelStack's (pyramid).
+template <bool LEVELS>
 __global__ __launch_bounds__(256) void roi_pool_c8_kernel(const float *__restrict__ feat, int C, int H, int W, int Hp, int Wp,
                                                           const float *__restrict__ rois, int roi_stride, int N, int PH, int PW,
                                                           float scale, RoiRule rr, float *__restrict__ xc8,
-                                                          int Mp, int32_t *__restrict__ argmax) {
+                                                          int Mp, int32_t *__restrict__ argmax, LevelStack lv) {
   const int Cb = (C + 7) / 8, PP = PH * PW;
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t total = (size_t)Cb * PP * N * 2;
@@ -2103,6 +2142,7 @@ __global__ __launch_bounds__(256) void roi_pool_c8_kernel(const float *__restric
   f32x4 m = empty ? f32x4{0, 0, 0, 0} : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   int mi[4] = {-1, -1, -1, -1};
   const float *fp = feat + (size_t)cb * Hp * Wp * 8 + h * 4;
+  if constexpr (LEVELS) fp += roi_level_offset(ro[0], lv);
   for (int y = hs; y < he; ++y)
     for (int x = ws; x < we; ++x) {
       f32x4 v = *reinterpret_cast<const f32x4 *>(fp + ((size_t)(y + 1) * Wp + x + 1) * 8);
@@ -2312,9 +2352,11 @@ __global__ void c8p_to_pixel_major_kernel(const float *__restrict__ in, int Cb, 
       *reinterpret_cast<const f32x4 *>(in + (size_t)cb * Hp * Wp * 8 + ((size_t)(y + 1) * Wp + x + 1) * 8 + h * 4);
 }
 
-template <int ABL>  // ABL: timing experiments (debug flavour): 1 no feature loads, 2 no stores, 4 no ROI decode (fixed 3x3 bin)
+// ABL: timing experiments (debug flavour): 1 no feature loads, 2 no stores, 4 no ROI decode (fixed 3x3 bin); LEVELS: as roi_pool_c8_kernel
+template <int ABL, bool LEVELS = false>
 __global__ __launch_bounds__(256) void roi_pool_pm_kernel(const float *__restrict__ pm, int Cb, int H, int W, const float *__restrict__ rois,
-                                                          int roi_stride, int N, int PH, int PW, float scale, RoiRule rr, float *__restrict__ xc8, int Mp) {
+                                                          int roi_stride, int N, int PH, int PW, float scale, RoiRule rr, float *__restrict__ xc8, int Mp,
+                                                          LevelStack lv) {
   __shared__ f32x4 stage[4][64];   // [roi of the quad][lane] = 4 channels
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2332,10 +2374,12 @@ __global__ __launch_bounds__(256) void roi_pool_pm_kernel(const float *__restric
     if constexpr ((ABL & 4) != 0) { hs = (n * 7 + ph) % (H - 3); he = hs + 3; ws = (n * 13 + pw) % (W - 3); we = ws + 3; }
     if constexpr ((ABL & 1) != 0) { he = hs; }
     const int ch = cq * 256 + lane * 4;
+    const float *map = pm;
+    if constexpr (LEVELS) map += roi_level_offset(ro[0], lv);
     if (he > hs && we > ws && ch < C) {
       m = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
       for (int y = hs; y < he; ++y) {
-        const float *row = pm + ((size_t)y * W + ws) * C + ch;
+        const float *row = map + ((size_t)y * W + ws) * C + ch;
         for (int x = ws; x < we; ++x, row += C) {
           const f32x4 v = *reinterpret_cast<const f32x4 *>(row);
 #pragma unroll
@@ -2367,11 +2411,11 @@ int c8p_to_pixel_major(Act feat, float *d_pm, hipStream_t s) {
 }
 
 int roi_pool_pm(Act feat, const float *d_pm, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr,
-                float *d_x_c8, hipStream_t s, int roi_stride, int Mp) {
-  MPN_CHECK_ARG(d_pm && d_rois && d_x_c8 && N > 0 && PH > 0 && PW > 0);
-  auto kern = roi_pool_pm_kernel<0>;
+                float *d_x_c8, hipStream_t s, int roi_stride, int Mp, LevelStack lv) {
+  MPN_CHECK_ARG(d_pm && d_rois && d_x_c8 && N > 0 && PH > 0 && PW > 0 && lv.n >= 0);
+  auto kern = lv.n > 0 ? roi_pool_pm_kernel<0, true> : roi_pool_pm_kernel<0>;
 #ifdef MPN_DEBUG_HOOKS
-  switch (g_gemm_ablate & 7) {
+  switch (lv.n > 0 ? 0 : g_gemm_ablate & 7) {
     case 1: kern = roi_pool_pm_kernel<1>; break;
     case 2: kern = roi_pool_pm_kernel<2>; break;
     case 3: kern = roi_pool_pm_kernel<3>; break;
@@ -2381,7 +2425,7 @@ int roi_pool_pm(Act feat, const float *d_pm, const float *d_rois, int N, int PH,
   }
 #endif
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(N, 4), (unsigned)(PH * PW), (unsigned)cdiv(feat.Cb(), 32)), dim3(256), 0, s, d_pm,
-                     feat.Cb(), feat.H, feat.W, d_rois, roi_stride, N, PH, PW, scale, rr, d_x_c8, Mp > 0 ? Mp : lin_mp(N));
+                     feat.Cb(), feat.H, feat.W, d_rois, roi_stride, N, PH, PW, scale, rr, d_x_c8, Mp > 0 ? Mp : lin_mp(N), lv);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
@@ -2540,11 +2584,12 @@ int roi_pool_pm_rmq(Act feat, const float *d_tables_pm, const float *d_rois, int
 
 
 int roi_pool_c8(Act feat, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr,
-                float *d_x_c8, int32_t *d_argmax, hipStream_t s, int roi_stride, int Mp) {
-  MPN_CHECK_ARG(feat.p && d_rois && d_x_c8 && N > 0 && PH > 0 && PW > 0);
+                float *d_x_c8, int32_t *d_argmax, hipStream_t s, int roi_stride, int Mp, LevelStack lv) {
+  MPN_CHECK_ARG(feat.p && d_rois && d_x_c8 && N > 0 && PH > 0 && PW > 0 && lv.n >= 0);
   size_t total = (size_t)feat.Cb() * PH * PW * N * 2;
-  hipLaunchKernelGGL(roi_pool_c8_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, feat.p, feat.C, feat.H, feat.W, feat.Hp,
-                     feat.Wp, d_rois, roi_stride, N, PH, PW, scale, rr, d_x_c8, Mp > 0 ? Mp : lin_mp(N), d_argmax);
+  hipLaunchKernelGGL(lv.n > 0 ? roi_pool_c8_kernel<true> : roi_pool_c8_kernel<false>, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s,
+                     feat.p, feat.C, feat.H, feat.W, feat.Hp, feat.Wp, d_rois, roi_stride, N, PH, PW, scale, rr, d_x_c8, Mp > 0 ? Mp : lin_mp(N),
+                     d_argmax, lv);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }

@@ -67,6 +67,7 @@ void bump_alloc_generation();
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): function attributes are per device.
 int set_max_dyn_lds(const void *fn, int bytes);
 int project_im_rois_copy(const float *d_boxes, int n, double scale, float *d_rois, float *d_boxes_copy, hipStream_t s);  // boxes.hip
+int project_im_rois_levels(const float *d_boxes, int n, int n_scales, const double *scales, float *d_rois, hipStream_t s);  // boxes.hip
 // mpn_nms_batched for a call that runs on a side stream UNDER other work (the pipelined forms' tail under the next image's trunk): keeps the
 // launch chain for tables whose fused-kernel blocks (150 KB of LDS each) would displace that work (nms.hip: nms_batched_core)
 int nms_batched_under_trunk(const float *d_scored, const int *d_counts, int n_cls, int m_stride, float thr, float *d_keep, int *d_keep_idx,

@@ -8,6 +8,7 @@
 // allocated at create time.  The reference's 500-ROI chunking (ImageDetect.lua:116-124) is not
 // needed: all ROIs go through each GEMM at once (rows are independent, results identical), so the
 // fc weights stream from HBM once per image instead of twice.
+#include <cmath>
 #include <cstdlib>
 #include <iterator>
 #include <algorithm>
@@ -344,6 +345,16 @@ struct mpn_frcnn {
   hipStream_t cap_stream = nullptr;  // capture happens here (the caller's stream may be the legacy NULL stream, which cannot capture)
   int seg_shape[4][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};  // shape of the last execution per segment kind
   long graph_replays = 0, graph_captures = 0;
+  // ---- multi-scale testing (mpn_frcnn_set_scales): the image pyramid of the plain Fast R-CNN head
+  int n_scales = 0;                             // >= 2: a pyramid of scale_targets; otherwise the single scale cfg.scale_target
+  double scale_targets[MPN_MAX_SCALES] = {};
+  double create_scale_target = 0.0;             // cfg.scale_target at creation (set_scales(0) restores it)
+  float *ms_feat = nullptr, *ms_pm = nullptr;   // per-level final maps (C8P, canvas geometry) and their pixel-major copies
+  size_t ms_slot = 0, ms_pm_slot = 0;           // floats between levels (sized for the max_h x max_w canvas)
+  int ms_cap = 0;                               // levels allocated
+  double ms_scales[MPN_MAX_SCALES] = {};        // s_l of the cached maps
+  int ms_src[MPN_MAX_SCALES] = {};              // the level whose map level l uses (an earlier level with the same scale, or l)
+  int ms_h0 = -1, ms_w0 = -1;                   // original image size of the cached maps (-1: none)
   // optional per-kernel-group timing with HIP events recorded on the launch stream
   bool prof = false;
   std::vector<hipEvent_t> ev_pool;
@@ -444,6 +455,8 @@ extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   resnet_free(p->rn);
   if (p->scaled) (void)hipFree(p->scaled);
   if (p->scale_tmp) (void)hipFree(p->scale_tmp);
+  if (p->ms_feat) (void)hipFree(p->ms_feat);
+  if (p->ms_pm) (void)hipFree(p->ms_pm);
   if (p->dbg) (void)hipFree(p->dbg);
   for (int i = 0; i < 4; ++i) if (p->sh_buf[i]) (void)hipFree(p->sh_buf[i]);
   delete p;
@@ -463,6 +476,7 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
   MPN_CHECK_ARG(cfg->top_k > 0);
   mpn_frcnn *p = new mpn_frcnn();
   p->cfg = *cfg;
+  p->create_scale_target = cfg->scale_target;
   {  // captured launch graphs: OFF unless asked for (MPN_GRAPHS=1 in the environment, or mpn_frcnn_set_graphs per handle).  Measured on
      // MI355X (profiles/r04_launch_graphs.txt): the host's enqueue time per AlexNet image drops 484 -> 74 us, but the device-side timeline
      // does not change (the gaps between dependent kernels are the command processor's, not the host's) and the throughput lines read
@@ -747,15 +761,20 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
   return MPN_OK;
 }
 
-static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream_t s, Act *feat_out) {
+// Hc > 0: the H x W image is one level of an image pyramid, placed top-left in a zero Hc x Wc canvas on which the whole trunk runs
+// (getImages' padded batch, ImageDetect.lua:44-49); final_out (optional) receives the final map instead of the last layer's own buffer.
+static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream_t s, Act *feat_out, int Hc = 0, int Wc = 0,
+                     float *final_out = nullptr) {
   const mpn_frcnn_config &c = p->cfg;
-  if (H != p->last_h || W != p->last_w) {  // halo positions move with the image size: re-lay the zero halo of every activation, once
+  const bool canvas = Hc > 0;
+  if (!canvas) { Hc = H; Wc = W; }
+  if (Hc != p->last_h || Wc != p->last_w) {  // halo positions move with the image size: re-lay the zero halo of every activation, once
     if (g_halo_memset) {
       for (auto &b : p->act_bufs) MPN_CHECK_HIP(hipMemsetAsync(b.first, 0, b.second, s));
     } else {
       std::vector<Act> acts;
-      acts.push_back(make_act(p->img_c8p, 3, H, W));
-      int hh = H, ww = W;
+      acts.push_back(make_act(p->img_c8p, 3, Hc, Wc));
+      int hh = Hc, ww = Wc;
       for (auto &L : p->conv) {
         if (L.out) acts.push_back(make_act(L.out, L.Cout, hh, ww));
         if (L.pool) { hh = (hh + 1) / 2; ww = (ww + 1) / 2; if (L.pooled) acts.push_back(make_act(L.pooled, L.Cout, hh, ww)); }
@@ -763,25 +782,27 @@ static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream
       int rc_h = c8p_zero_halos(acts.data(), (int)acts.size(), s);
       if (rc_h) return rc_h;
     }
-    p->last_h = H; p->last_w = W;
+    p->last_h = Hc; p->last_w = Wc;
   }
-  Act cur = make_act(p->img_c8p, 3, H, W);
+  Act cur = make_act(p->img_c8p, 3, Hc, Wc);
   p->vmax_built[0] = p->vmax_built[1] = p->vmax_built[2] = false;
   p->feat_pm_valid = false;
   int rc;
   { ProfScope ps(p, MPN_PROF_TRANSFORM, s);
-    rc = image_transform_c8p(d_image, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, cur, s); }
+    rc = canvas ? image_transform_canvas_c8p(d_image, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, cur, s)
+                : image_transform_c8p(d_image, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, cur, s); }
   if (rc) return rc;
-  int h = H, w = W;
+  int h = Hc, w = Wc;
   int li = 0;
   for (auto &L : p->conv) {
-    Act out = make_act(L.out, L.Cout, h, w);
+    float *const final_here = (final_out && &L == &p->conv.back()) ? final_out : nullptr;
+    Act out = make_act(final_here && !L.pool ? final_here : L.out, L.Cout, h, w);
     const int ctag = conv3x3_variant_for(L.Cout, L.wino != nullptr) == 7 ? MPN_PROF_CONV_WINO : MPN_PROF_CONV_DIRECT;
     const bool is_tap = p->is_mpnet && (li == p->tap3 || li == p->tap4);
     if (is_tap) p->tap_act[li == p->tap4 ? 1 : 2] = out;
     ++li;
     if (L.pool) {
-      Act pooled = make_act(L.pooled, L.Cout, (h + 1) / 2, (w + 1) / 2);
+      Act pooled = make_act(final_here ? final_here : L.pooled, L.Cout, (h + 1) / 2, (w + 1) / 2);
       if (g_fuse_pool) {
         ProfScope ps(p, ctag, s);
         rc = conv3x3_c8p(cur, L.wpk, L.bpk, L.Cout, 1, is_tap ? out : Act{}, pooled, s, L.wino);  // tap layers keep the pre-pool map too
@@ -1021,6 +1042,70 @@ static int run_integral_heads(mpn_frcnn *p, const float *d_boxes, int N, int H, 
   return MPN_OK;
 }
 
+// getImages' rescaled image buffers (ImageDetect.lua:34-43), grown to hold `need` / `need_t` bytes
+static int grow_scaled(mpn_frcnn *p, size_t need, size_t need_t, hipStream_t s) {
+  if (need > p->scaled_bytes || need_t > p->scale_tmp_bytes) {
+    MPN_CHECK_HIP(hipStreamSynchronize(s));
+    bump_alloc_generation();  // BEFORE the frees: a hipMalloc that fails below must not leave captured graphs holding a freed pointer
+    if (need > p->scaled_bytes) { if (p->scaled) (void)hipFree(p->scaled); p->scaled = nullptr; p->scaled_bytes = 0; MPN_CHECK_HIP(hipMalloc(&p->scaled, need)); p->scaled_bytes = need; }
+    if (need_t > p->scale_tmp_bytes) { if (p->scale_tmp) (void)hipFree(p->scale_tmp); p->scale_tmp = nullptr; p->scale_tmp_bytes = 0; MPN_CHECK_HIP(hipMalloc(&p->scale_tmp, need_t)); p->scale_tmp_bytes = need_t; }
+  }
+  return MPN_OK;
+}
+
+// getImages with a scale table (ImageDetect.lua:22-52; include/mpn.h mpn_frcnn_set_scales): level l's image, resampled and transformed as
+// the single-scale image is, top-left in a zero canvas of the largest level's size -> the whole trunk -> its final map into slot l.
+// A level whose scale repeats an earlier one's is not recomputed (no ROI can pick it).  *feat: slot 0's view (every slot has its
+// geometry).  d_image == nullptr: the maps of the last image are reused (iterative localisation).
+static int run_pyramid_trunk(mpn_frcnn *p, const float *d_image, int H0, int W0, hipStream_t s, Act *feat) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int S = p->n_scales;
+  double sc[MPN_MAX_SCALES];
+  int hl[MPN_MAX_SCALES], wl[MPN_MAX_SCALES], Hc = 0, Wc = 0;
+  for (int l = 0; l < S; ++l) {
+    sc[l] = mpn_pick_scale(H0, W0, p->scale_targets[l], c.scale_max > 0.0 ? c.scale_max : 1e30);
+    hl[l] = H0; wl[l] = W0;
+    if (sc[l] != 1.0) { hl[l] = (int)((double)H0 * sc[l]); wl[l] = (int)((double)W0 * sc[l]); }
+    if (hl[l] <= 0 || wl[l] <= 0) { set_error("run_detect: level %d of a %dx%d image is %dx%d", l, H0, W0, hl[l], wl[l]); return MPN_EINVAL; }
+    Hc = std::max(Hc, hl[l]); Wc = std::max(Wc, wl[l]);
+  }
+  if (Hc > c.max_h || Wc > c.max_w) {
+    set_error("run_detect: the %d-level pyramid of a %dx%d image needs a %dx%d canvas; the pipeline holds %dx%d", S, H0, W0, Hc, Wc, c.max_h, c.max_w);
+    return MPN_EINVAL;
+  }
+  int fh = Hc, fw = Wc;
+  for (auto &L : p->conv) if (L.pool) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+  *feat = make_act(p->ms_feat, p->feat_c, fh, fw);
+  if (!d_image) {
+    if (p->ms_h0 != H0 || p->ms_w0 != W0 || p->last_h != Hc || p->last_w != Wc) { set_error("run_detect: no cached pyramid for a %dx%d image", H0, W0); return MPN_ESTATE; }
+    return MPN_OK;
+  }
+  p->ms_h0 = p->ms_w0 = -1;
+  size_t need = 0, need_t = 0;
+  for (int l = 0; l < S; ++l)
+    if (sc[l] != 1.0) { need = std::max(need, (size_t)3 * hl[l] * wl[l] * sizeof(float)); need_t = std::max(need_t, (size_t)3 * H0 * wl[l] * sizeof(float)); }
+  int rc = grow_scaled(p, need, need_t, s);
+  if (rc) return rc;
+  for (int l = 0; l < S; ++l) {
+    int src = l;
+    for (int k = 0; k < l && src == l; ++k) if (sc[k] == sc[l]) src = k;
+    p->ms_src[l] = src;
+    p->ms_scales[l] = sc[l];
+    if (src != l) continue;
+    const float *img = d_image;
+    if (sc[l] != 1.0) {
+      rc = mpn_image_scale(d_image, 3, H0, W0, hl[l], wl[l], p->scale_tmp, p->scaled, s);
+      if (rc) return rc;
+      img = p->scaled;
+    }
+    Act f;
+    rc = run_trunk(p, img, hl[l], wl[l], s, &f, Hc, Wc, p->ms_feat + (size_t)l * p->ms_slot);
+    if (rc) return rc;
+  }
+  p->ms_h0 = H0; p->ms_w0 = W0;
+  return MPN_OK;
+}
+
 // d_image == nullptr: recompute_features = false (ImageDetect.lua:107-111) — reuse the trunk output of the last
 // call on this handle (iterative localisation, Tester_FRCNN.lua:82-89) and run only the ROI head on new boxes.
 static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp = 1) {
@@ -1032,26 +1117,24 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
   // resampled to (long)(H*s) x (long)(W*s).  scale_target == 0 keeps the image as it is (s = 1).
   double sc = 1.0;
   int H = H0, W = W0;
-  if (c.scale_target > 0.0) {
+  const bool pyr = p->n_scales > 1;  // an image pyramid (mpn_frcnn_set_scales): run_pyramid_trunk does getImages per level
+  if (!pyr && c.scale_target > 0.0) {
     sc = mpn_pick_scale(H0, W0, c.scale_target, c.scale_max > 0.0 ? c.scale_max : 1e30);
     if (sc != 1.0) { H = (int)((double)H0 * sc); W = (int)((double)W0 * sc); }
   }
-  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
+  if (H <= 0 || W <= 0 || (!pyr && (H > c.max_h || W > c.max_w))) {
     set_error("run_detect: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
     return MPN_EINVAL;
   }
   Act feat;
   int rc = MPN_OK;
-  if (d_image) {
+  if (pyr) {
+    rc = run_pyramid_trunk(p, d_image, H0, W0, s, &feat);
+  } else if (d_image) {
     const float *img = d_image;
     if (sc != 1.0) {
-      const size_t need = (size_t)3 * H * W * sizeof(float), need_t = (size_t)3 * H0 * W * sizeof(float);
-      if (need > p->scaled_bytes || need_t > p->scale_tmp_bytes) {
-        MPN_CHECK_HIP(hipStreamSynchronize(s));
-        bump_alloc_generation();  // BEFORE the frees: a hipMalloc that fails below must not leave captured graphs holding a freed pointer
-        if (need > p->scaled_bytes) { if (p->scaled) (void)hipFree(p->scaled); p->scaled = nullptr; p->scaled_bytes = 0; MPN_CHECK_HIP(hipMalloc(&p->scaled, need)); p->scaled_bytes = need; }
-        if (need_t > p->scale_tmp_bytes) { if (p->scale_tmp) (void)hipFree(p->scale_tmp); p->scale_tmp = nullptr; p->scale_tmp_bytes = 0; MPN_CHECK_HIP(hipMalloc(&p->scale_tmp, need_t)); p->scale_tmp_bytes = need_t; }
-      }
+      rc = grow_scaled(p, (size_t)3 * H * W * sizeof(float), (size_t)3 * H0 * W * sizeof(float), s);
+      if (rc) return rc;
       rc = mpn_image_scale(d_image, 3, H0, W0, H, W, p->scale_tmp, p->scaled, s);
       if (rc) return rc;
       img = p->scaled;
@@ -1070,7 +1153,8 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
   }
   if (rc) return rc;
   const bool defer_heads = p->defer_stream && !p->rn && !p->is_mpnet;  // the pipelined forms of the plain VGG head (pipelined_impl)
-  rc = defer_heads ? project_im_rois_copy(d_boxes, N, sc, p->rois, p->boxes_b[p->defer_set], s) : mpn_project_im_rois(d_boxes, N, sc, p->rois, s);
+  rc = pyr ? project_im_rois_levels(d_boxes, N, p->n_scales, p->ms_scales, p->rois, s)
+           : defer_heads ? project_im_rois_copy(d_boxes, N, sc, p->rois, p->boxes_b[p->defer_set], s) : mpn_project_im_rois(d_boxes, N, sc, p->rois, s);
   if (rc) return rc;
   // decode uses the ORIGINAL boxes and clamps to the ORIGINAL image (ImageDetect.lua:183-185, Tester_FRCNN.lua:75-78)
   H = H0; W = W0;
@@ -1125,7 +1209,17 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
     if (rc) return rc;
   } else {
   { ProfScope ps(p, MPN_PROF_ROIPOOL, s);
-    if (p->feat_pm && g_roi_pool_pm) {
+    if (pyr && p->feat_pm && g_roi_pool_pm) {  // one pixel-major copy per computed level (once per image), the level read from column 0
+      for (int l = 0; l < p->n_scales && !p->feat_pm_valid && rc == MPN_OK; ++l)
+        if (p->ms_src[l] == l) rc = c8p_to_pixel_major(make_act(p->ms_feat + (size_t)l * p->ms_slot, feat.C, feat.H, feat.W), p->ms_pm + (size_t)l * p->ms_pm_slot, s);
+      if (rc) return rc;
+      p->feat_pm_valid = true;
+      rc = roi_pool_pm(feat, p->ms_pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, s, 5, 0,
+                       LevelStack{p->ms_pm_slot, p->n_scales});
+    } else if (pyr) {
+      rc = roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, nullptr, s, 5, 0,
+                       LevelStack{p->ms_slot, p->n_scales});
+    } else if (p->feat_pm && g_roi_pool_pm) {
       if (!p->feat_pm_valid) { rc = c8p_to_pixel_major(feat, p->feat_pm, s); if (rc) return rc; p->feat_pm_valid = true; }  // once per trunk run
       rc = roi_pool_pm(feat, p->feat_pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, s);
     } else {
@@ -1399,6 +1493,7 @@ extern "C" int mpn_frcnn_test_one(mpn_frcnn *p, const float *d_image, int H, int
 // The three steps take caller-provided records so that the exchange between them can be any transport; mpn_frcnn_test_one_sharded
 // chains them over an mpn_comm (RCCL all-gather, comm.hip).
 static int shard_passes(const mpn_frcnn_config &c) { return c.num_iter > 1 ? (c.use_rbox_scores ? c.num_iter - 1 : c.num_iter) : 1; }
+static int refuse_pyramid(const mpn_frcnn *p, const char *form);
 
 extern "C" int mpn_shard_range(int n, int world, int rank, int *lo, int *hi) {
   MPN_CHECK_ARG(n >= 0 && world >= 1 && rank >= 0 && rank < world && lo && hi);
@@ -1421,6 +1516,7 @@ extern "C" size_t mpn_frcnn_shard_class_floats(const mpn_frcnn *p, int N, int wo
 extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, int rank, int world,
                                     float *d_rows_rec, void *stream) {
   MPN_CHECK_ARG(p != nullptr && d_boxes && d_rows_rec && N > 0 && N <= p->cfg.max_rois && world >= 1 && rank >= 0 && rank < world);
+  if (int rp = refuse_pyramid(p, "mpn_frcnn_shard_head")) return rp;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   int rc = mpn_frcnn_flush(p, stream);
@@ -1524,6 +1620,7 @@ static int shard_buf(mpn_frcnn *p, int i, size_t floats, hipStream_t s) {
 extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const float *d_image, int H, int W, const float *d_boxes, int N,
                                           float *d_dets, int top_cap, int *d_n_dets, void *stream) {
   MPN_CHECK_ARG(p != nullptr && comm != nullptr && N > 0);
+  if (int rp = refuse_pyramid(p, "mpn_frcnn_test_one_sharded")) return rp;
   hipStream_t s = as_stream(stream);
   const int world = mpn_comm_world(comm), rank = mpn_comm_rank(comm);
   MPN_CHECK_ARG(world >= 1 && rank >= 0);
@@ -1545,9 +1642,17 @@ extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const fl
 // image i on `stream`; NMS + top-k of image i on the pipeline's side stream, overlapping image
 // i+1's MFMA kernels (they are latency-bound on ~20 CUs).  d_dets / d_n_dets of call i are ordered on `stream`
 // only after call i+1 returns or after mpn_frcnn_flush(); the caller alternates two output buffers.
+// the throughput and sharded forms run single-scale only (include/mpn.h mpn_frcnn_set_scales)
+static int refuse_pyramid(const mpn_frcnn *p, const char *form) {
+  if (p->n_scales <= 1) return MPN_OK;
+  set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales): use mpn_frcnn_test_one", form, p->n_scales);
+  return MPN_EINVAL;
+}
+
 static int pipelined_impl(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, float *d_dets, int top_cap, int *d_n_dets,
                           void *stream, bool stable_ptrs) {
   MPN_CHECK_ARG(p != nullptr && d_n_dets && (top_cap == 0 || d_dets) && top_cap >= 0);
+  if (int rp = refuse_pyramid(p, "mpn_frcnn_test_one_pipelined")) return rp;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   const int b = (int)(p->seq & 1);
@@ -1597,6 +1702,7 @@ extern "C" int mpn_frcnn_test_one_pipelined(mpn_frcnn *p, const float *d_image, 
 extern "C" int mpn_frcnn_test_one_pipelined_host(mpn_frcnn *p, const float *h_image, int H, int W, const float *h_boxes, int N,
                                                  float *d_dets, int top_cap, int *d_n_dets, void *stream) {
   MPN_CHECK_ARG(p != nullptr && h_image && h_boxes && H > 0 && W > 0 && N > 0 && N <= p->cfg.max_rois);
+  if (int rp = refuse_pyramid(p, "mpn_frcnn_test_one_pipelined_host")) return rp;
   hipStream_t s = as_stream(stream);
   const size_t img_n = (size_t)3 * H * W;
   if (!p->copy) {  // first use: copy stream, events, the two box staging buffers
@@ -1669,6 +1775,54 @@ extern "C" int mpn_graph_create(const mpn_frcnn_config *cfg, const mpn_graph_wei
 extern "C" int mpn_frcnn_set_graphs(mpn_frcnn *p, int enable) {
   MPN_CHECK_ARG(p != nullptr);
   p->graphs_on = enable ? 1 : 0;
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_targets) {
+  if (n_scales < 0 || n_scales > MPN_MAX_SCALES || (n_scales > 0 && !h_targets)) {
+    set_error("mpn_frcnn_set_scales: n_scales %d outside 0..MPN_MAX_SCALES (%d) or no targets", n_scales, MPN_MAX_SCALES);
+    return MPN_EINVAL;
+  }
+  for (int l = 0; l < n_scales; ++l)
+    if (!(std::isfinite(h_targets[l]) && h_targets[l] > 0.0)) { set_error("mpn_frcnn_set_scales: target %d is %g (must be finite and > 0)", l, h_targets[l]); return MPN_EINVAL; }
+  MPN_CHECK_ARG(p != nullptr);
+  if (n_scales > 1 && (p->is_mpnet || p->rn)) {
+    set_error("mpn_frcnn_set_scales: a %s handle has no image pyramid (only mpn_frcnn_create's VGG Fast R-CNN head pools from one)",
+              p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)");
+    return MPN_EINVAL;
+  }
+  MPN_CHECK_HIP(hipDeviceSynchronize());  // no replay or cached map of the old setting may still be in flight
+  for (auto &kv : p->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+  p->graphs.clear();
+  for (int k = 0; k < 4; ++k) {
+    p->unseen_next[k] = 0;
+    for (int q = 0; q < mpn_frcnn::kUnseen; ++q) p->unseen_valid[k][q] = false;
+    for (int j = 0; j < 4; ++j) p->seg_shape[k][j] = -1;
+  }
+  p->tap_act[0] = Act{};  // cached trunk output: gone (the next detect must pass an image)
+  p->ms_h0 = p->ms_w0 = -1;
+  p->feat_pm_valid = false;
+  if (n_scales <= 1) {
+    p->n_scales = 0;
+    p->cfg.scale_target = n_scales == 1 ? h_targets[0] : p->create_scale_target;
+    return MPN_OK;
+  }
+  if (n_scales > p->ms_cap) {  // per-level slots at the largest canvas geometry
+    int fh = p->cfg.max_h, fw = p->cfg.max_w;
+    for (auto &L : p->conv) if (L.pool) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+    const size_t slot = act_bytes(p->feat_c, fh, fw) / sizeof(float), pm_slot = pixel_major_elems(make_act(nullptr, p->feat_c, fh, fw));
+    bump_alloc_generation();
+    if (p->ms_feat) (void)hipFree(p->ms_feat);
+    if (p->ms_pm) (void)hipFree(p->ms_pm);
+    p->ms_feat = p->ms_pm = nullptr; p->ms_cap = 0; p->n_scales = 0;
+    MPN_CHECK_HIP(hipMalloc(&p->ms_feat, slot * n_scales * sizeof(float)));
+    MPN_CHECK_HIP(hipMalloc(&p->ms_pm, pm_slot * n_scales * sizeof(float)));
+    MPN_CHECK_HIP(hipMemset(p->ms_feat, 0, slot * n_scales * sizeof(float)));
+    MPN_CHECK_HIP(hipMemset(p->ms_pm, 0, pm_slot * n_scales * sizeof(float)));
+    p->ms_slot = slot; p->ms_pm_slot = pm_slot; p->ms_cap = n_scales;
+  }
+  p->n_scales = n_scales;
+  for (int l = 0; l < n_scales; ++l) p->scale_targets[l] = h_targets[l];
   return MPN_OK;
 }
 
@@ -1748,7 +1902,14 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   for (auto &L : p->conv) if (L.pool) { h = (h + 1) / 2; w = (w + 1) / 2; }
   std::string nm(name);
   size_t n = 0;
-  if (nm == "conv5") n = (size_t)p->feat_c * h * w;
+  int level = -1;  // "conv5.<l>": level l of the image pyramid
+  if (nm.compare(0, 6, "conv5.") == 0 && nm.size() == 7 && nm[6] >= '0' && nm[6] < '0' + MPN_MAX_SCALES) {
+    level = nm[6] - '0';
+    if (p->n_scales <= 1 || level >= p->n_scales) { set_error("mpn_frcnn_debug_tensor: '%s' needs an image pyramid of more than %d levels", name, level); return MPN_EINVAL; }
+    if (p->ms_h0 < 0) { set_error("mpn_frcnn_debug_tensor: no pyramid maps cached (run detect with an image first)"); return MPN_ESTATE; }
+    n = (size_t)p->feat_c * h * w;
+  } else if (nm == "conv5") n = (size_t)p->feat_c * h * w;
+  else if (nm == "rois") n = (size_t)N * 5;
   else if (nm == "pooled") n = (size_t)N * p->feat_c * PP;
   else if (nm == "fc7") n = (size_t)N * F;
   else if (nm == "cls") n = (size_t)N * C;
@@ -1768,9 +1929,14 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
     p->dbg_bytes = n * sizeof(float);
   }
   int rc = MPN_OK;
-  if (nm == "conv5") {
+  if (level >= 0 || (nm == "conv5" && p->n_scales > 1)) {
+    const int l = p->ms_src[level >= 0 ? level : 0];
+    rc = c8p_to_nchw(make_act(p->ms_feat + (size_t)l * p->ms_slot, p->feat_c, h, w), p->dbg, nullptr);
+  } else if (nm == "conv5") {
     const ConvLayer &L = p->conv.back();
     rc = c8p_to_nchw(make_act(L.pool ? L.pooled : L.out, p->feat_c, h, w), p->dbg, nullptr);
+  } else if (nm == "rois") {
+    MPN_CHECK_HIP(hipMemcpy(p->dbg, p->rois, n * sizeof(float), hipMemcpyDeviceToDevice));
   } else if (nm == "pooled") {
     hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, p->x6, N, p->feat_c, PP, lin_mp(N), p->dbg);
     MPN_CHECK_LAUNCH();

@@ -19,17 +19,21 @@ class ImageDetect(object):
         assert model is not None, "must provide model!"
         self.model = model
         self.image_transformer = transformer  # the pipeline applies it on the device (cfg.tf_*)
-        self.scale = scale or [600]
+        self.scale = list(scale) if isinstance(scale, (list, tuple)) else ([scale] if scale is not None else [600])
         self.max_size = max_size or 1000
-        # getImages' rescaling (ImageDetect.lua:34-43) runs inside the device pipeline with the MODEL's scale / max_size: an
-        # ImageDetect asked for another configuration would silently skip or change the resize — refuse instead.
-        m_scale, m_max = getattr(model, "scale", None), getattr(model, "max_size", None)
+        # getImages (ImageDetect.lua:22-52) runs inside the device pipeline with the MODEL's scale table / max_size: an ImageDetect asked
+        # for another configuration would silently skip or change the resize, or run one entry of a pyramid alone — refuse instead.
+        m_scales, m_max = getattr(model, "scales", None), getattr(model, "max_size", None)
+        if m_scales is None:
+            m_scales = [model.scale] if getattr(model, "scale", None) else []
+        m_scales = [float(t) for t in m_scales]
         if scale is not None or max_size is not None:
-            want = (float(self.scale[0]), float(self.max_size))
-            have = (float(m_scale), float(m_max or 0)) if m_scale else None
+            want = ([float(t) for t in self.scale], float(self.max_size))
+            have = (m_scales, float(m_max or 0)) if m_scales else None
             if have != want:
-                raise ValueError("ImageDetect(scale=%r, max_size=%r): the model's device pipeline was built with scale=%r, max_size=%r; "
-                                 "build models.FastRCNN(..., scale=%r, max_size=%r)" % (scale, max_size, m_scale, m_max, self.scale[0], self.max_size))
+                raise ValueError("ImageDetect(scale=%r, max_size=%r): the model's device pipeline runs the scales %r, max_size=%r; "
+                                 "build models.FastRCNN(..., scale=%r, max_size=%r) or call its set_scales()"
+                                 % (scale, max_size, m_scales, m_max, self.scale, self.max_size))
 
     def detect(self, im, boxes, min_images=None, recompute_features=True):
         """ImageDetect.lua:156-193: (softmax scores [N,C], decoded boxes [N,4C]) — NOT clamped to the image, as in the

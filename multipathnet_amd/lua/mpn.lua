@@ -136,7 +136,16 @@ local function common_config(cfg, opt, tf, bnorm)
    cfg.use_rbox_scores = opt.test_use_rbox_scores and 1 or 0
    cfg.roi_bin_rule = opt.roi_bin_rule or 0                        -- 1: inn.ROIPooling's CPU-branch bins (MPN_ROI_BINS_ADAPTIVE)
    cfg.fc_arith = opt.fc_arith or 0                                -- 1: fc6 as the three-plane bf16 split (MPN_FC_SPLIT3; auxiliary arithmetic)
-   cfg.scale_target, cfg.scale_max = opt.scale or 600, opt.max_size or 1000   -- getImages (ImageDetect.lua:34-43) on the device
+   local sc = type(opt.scale) == 'table' and opt.scale[1] or opt.scale   -- ImageDetect's scale TABLE: its first entry, or the pyramid below
+   cfg.scale_target, cfg.scale_max = sc or 600, opt.max_size or 1000   -- getImages (ImageDetect.lua:34-43) on the device
+end
+-- a scale table of more than one entry (ImageDetect.lua:22-52) = multi-scale testing: the image pyramid on the device (VGG Fast R-CNN handles)
+local function set_pyramid(self, opt)
+   if type(opt.scale) == 'table' and #opt.scale > 1 then
+      local t = ffi.new('double[?]', #opt.scale)
+      for i = 1, #opt.scale do t[i - 1] = opt.scale[i] end
+      check(C.mpn_frcnn_set_scales(self.handle, #opt.scale, t), 'mpn_frcnn_set_scales')
+   end
 end
 -- classAndBBoxLinear (model_utils.lua:105-119) [+ utils.integral's K classifier clones, model_utils.lua:275-317] -> (cls weight, cls bias,
 -- bbox Linear, BBoxNorm or nil, K); the K clones are stacked into one [K*C, in] matrix, which is what the C ABI takes
@@ -179,6 +188,7 @@ function FastRCNN:__init(model, opt)
    check(C.mpn_frcnn_create(cfg, wp, bp, lin[1].weight:data(), lin[1].bias:data(), lin[2].weight:data(), lin[2].bias:data(),
                             cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_frcnn_create')
    finish(self, h, cfg, {cout, pl, cls_w, cls_b})
+   set_pyramid(self, opt)
 end
 
 -- models/multipathnet.lua:30-120 — the namesake model.  model = nn.Sequential{
@@ -232,6 +242,7 @@ function mpn.MultiPathNet(model, opt)
    local h = ffi.new('mpn_frcnn *[1]')
    check(C.mpn_mpnet_create(cfg, wp, bp, mw, cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_mpnet_create')
    finish(self, h, cfg, keep)
+   set_pyramid(self, opt)
    return self
 end
 
@@ -303,6 +314,7 @@ function mpn.ResNet(model, opt)
    check(C.mpn_resnet_create(cfg, rw, cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_resnet_create')
    keep[#keep + 1] = {wp, bp, a_cin, a_co, a_ks, a_st, a_pd, a_bn, a_bs}
    finish(self, h, cfg, keep)
+   set_pyramid(self, opt)
    return self
 end
 
@@ -412,6 +424,7 @@ function mpn.Graph(model, opt)
    local h = ffi.new('mpn_frcnn *[1]')
    check(C.mpn_graph_create(cfg, gw, cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_graph_create')
    finish(self, h, cfg, keep)
+   set_pyramid(self, opt)
    return self
 end
 mpn.ROSS, mpn.IMAGENET = ROSS, IMAGENET

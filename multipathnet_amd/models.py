@@ -492,7 +492,9 @@ class FastRCNN(object):
     def __init__(self, params, cfg=VGG16_CFG, pooled=7, spatial_scale=1.0 / 16, transformer=None, max_h=600, max_w=1000,
                  max_rois=1000, nms_thresh=0.3, score_thresh=-1.5, top_k=100, num_iter=1, bbox_voting=False, bbox_vote_thresh=0.5,
                  bbox_vote_score_pow=1.0, scale=None, max_size=None, bf16=False, use_rbox_scores=False, roi_bin_rule=0, fc_arith=None):
-        """scale / max_size: getImages' rescaling (ImageDetect.lua:34-43) on the device; None feeds images as they are.
+        """scale / max_size: getImages' rescaling (ImageDetect.lua:34-43) on the device; None feeds images as they are.  `scale` may be
+        the reference's scale TABLE: a one-entry list is the scalar, more entries are the image pyramid of multi-scale testing
+        (set_scales; plain VGG Fast R-CNN only, include/mpn.h mpn_frcnn_set_scales).
         roi_bin_rule: 0 = inn.ROIPooling's CUDA-branch bins, 1 = its CPU branch (crop + SpatialAdaptiveMaxPooling), include/mpn.h MPN_ROI_BINS_*.
         num_iter / bbox_voting / use_rbox_scores: opt.test_num_iterative_loc / test_bbox_voting / test_use_rbox_scores
         (Tester_FRCNN.lua:82-99,118-124) inside the fused test_one."""
@@ -533,7 +535,8 @@ class FastRCNN(object):
         c.nms_thresh, c.score_thresh, c.top_k = nms_thresh, score_thresh, top_k
         c.num_iter, c.bbox_voting, c.bbox_vote_thresh, c.bbox_vote_score_pow = num_iter, int(bbox_voting), bbox_vote_thresh, bbox_vote_score_pow
         self.num_iter = num_iter
-        c.scale_target, c.scale_max = float(scale or 0.0), float(max_size or 0.0)
+        scales = [float(t) for t in scale] if isinstance(scale, (list, tuple)) else ([float(scale)] if scale else [])
+        c.scale_target, c.scale_max = (scales[0] if scales else 0.0), float(max_size or 0.0)
         c.use_rbox_scores = int(bool(use_rbox_scores))
         c.roi_bin_rule = int(roi_bin_rule)
         # fc_arith: 0 = fc6 on the fp32 matrix pipe (default), 1 / "split3" = the three-plane bf16 split with fp32 accumulation (include/mpn.h
@@ -545,6 +548,7 @@ class FastRCNN(object):
         c.fc_arith = 0 if (self.is_resnet or self.is_graph) else fc_arith   # the VGG pipelines (Fast R-CNN, MultiPathNet towers) have fc6 / fc7
         self.fc_arith = c.fc_arith
         self.scale, self.max_size = scale, max_size
+        self.scales, self._create_scales = scales, scales[:1]  # the scale table the device runs; the creation-time single scale
         self._cfg = c
         dev = torch.device("cuda", torch.cuda.current_device())
         d = lambda t: t.to(dev, torch.float32).contiguous()
@@ -656,6 +660,16 @@ class FastRCNN(object):
         self._dets2 = [torch.zeros_like(self._dets) for _ in range(2)]
         self._n_dets2 = [torch.zeros_like(self._n_dets) for _ in range(2)]
         self._pipe_seq = 0
+        if len(self.scales) > 1:
+            self.set_scales(self.scales)
+
+    def set_scales(self, targets):
+        """getImages' scale table (ImageDetect.lua:22-52) on the device (mpn_frcnn_set_scales): [] restores the creation-time single scale,
+        one entry is a single scale, 2..8 entries the image pyramid of multi-scale testing; max_size stays the cap.  Drops the handle's
+        captured graphs and cached features."""
+        t = [float(x) for x in targets]
+        check(self._lib.mpn_frcnn_set_scales(self._h, len(t), (C.c_double * max(1, len(t)))(*t)), "mpn_frcnn_set_scales")
+        self.scales = t if t else list(self._create_scales)
 
     def close(self):
         """mpn_frcnn_destroy now (streams, events, buffers) instead of at garbage collection: a process holds a few HIP hardware queues, and
