@@ -381,7 +381,11 @@ int mpn_resnet_create(const mpn_frcnn_config *cfg, const mpn_resnet_weights *rw,
  * `dst_c_off` — an Inception module's DepthConcat is its branches writing side by side into one tensor (offsets and widths
  * must be multiples of 8; of 16 with bf16).  BatchNorm folded into w / b by the caller (utils.BNtoFixed, inceptionv3.lua:23).
  * The `.t7` (Moodstocks' conversion of Google's Inception-v3) is not in the tree: PARITY UNPINNED, structure from the public
- * definition. */
+ * definition.
+ * Convolution edge values: without ReLU (relu = 0, or the channels a fused sibling keeps linear) every output is NaN / +inf / -inf /
+ * finite exactly when the float64 sum is (inf x 0 and inf - inf give NaN), except on the fp32 Winograd forms (3x3 / stride 1: the trunk's
+ * layers and the per-ROI mosaic), whose transforms spread a non-finite input over its 4x4 input tile.  ReLU(NaN): 0 on bf16 graphs and
+ * on the fp32 Winograd forms (as Torch's Threshold), NaN on the other fp32 forms (t < 0 ? 0 : t, like the fully-connected GEMM). */
 typedef struct mpn_graph_op {
   int kind;               /* 0 = convolution (+ bias, ReLU if relu), 1 = max-pool (padded cells never win; floor mode unless ceil_mode),
                              2 = average pool, count_include_pad (nn.SpatialAveragePooling's default: always / (kh*kw)),

@@ -8,6 +8,7 @@
 // staged through registers into double-buffered LDS; every MFMA operand fetch is then the same conflict-free ds_read_b128
 // as in dense.hip's kernels.  16 KiB of LDS per block lets several blocks share a CU, which hides the gather latency.
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -367,9 +368,9 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {  // bits 0
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hwbf16x2));
 }
 __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf16x2(f, 0.0f) & 0xffffu); }
-// ReLU switched by a wave-uniform flag, one v_med3_f32: clamp(v, lo, +inf) with lo = 0 (ReLU) or -inf (none)
-__device__ __forceinline__ float relu_lo(bool on) { return on ? 0.0f : -__builtin_inff(); }
-__device__ __forceinline__ float clamp_lo(float v, float lo) { return __builtin_amdgcn_fmed3f(v, lo, __builtin_inff()); }
+// The ReLU of every bf16 convolution epilogue, switched by a wave-uniform flag: one v_med3_f32 (v, 0, +inf), which maps NaN to 0 (as
+// Torch's Threshold does; include/mpn.h).  Off, the value passes untouched: a med3 against -inf would turn NaN into -inf.
+__device__ __forceinline__ float relu_bf(float v, bool on) { return on ? __builtin_amdgcn_fmed3f(v, 0.0f, __builtin_inff()) : v; }
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
 
 // packed bf16 weights: [tap][nch2][CoutP][8], nch2 = Cin chunks rounded up to even
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(256) void conv2d_c8i_bf16_kernel(GConvArgsB a) {
         u16x4 o;
         const bool rl = a.relu && !(cb >= a.norelu_cb0 && cb < a.norelu_cb1);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2bf((rl && v[e] < 0.0f) ? 0.0f : v[e]);
+        for (int e = 0; e < 4; ++e) o[e] = f2bf(relu_bf(v[e], rl));
         *reinterpret_cast<u16x4 *>(a.out + off) = o;
       }
   }
@@ -562,7 +563,7 @@ __global__ void conv_splitk_finalize_bf16_kernel(const float *__restrict__ part,
   u16x4 o;
   const bool rl = relu && !(cb >= norelu_cb0 && cb < norelu_cb1);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = f2bf((rl && v[e] < 0.0f) ? 0.0f : v[e]);
+  for (int e = 0; e < 4; ++e) o[e] = f2bf(relu_bf(v[e], rl));
   *reinterpret_cast<u16x4 *>(out + off) = o;
 }
 
@@ -880,9 +881,8 @@ __global__ __launch_bounds__(128 * WN, ((MI == 4 && NI == 4) || NCH == 8 || WN =
         {
           const int cba = cb0 + mi * 4 + gp * 2;  // va: block cba, vb: block cba + 1
           const bool rla = a.relu && !(cba >= a.norelu_cb0 && cba < a.norelu_cb1), rlb = a.relu && !(cba + 1 >= a.norelu_cb0 && cba + 1 < a.norelu_cb1);
-          const float loa = relu_lo(rla), lob = relu_lo(rlb);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] = clamp_lo(va[e], loa); vb[e] = clamp_lo(vb[e], lob); }
+          for (int e = 0; e < 4; ++e) { va[e] = relu_bf(va[e], rla); vb[e] = relu_bf(vb[e], rlb); }
         }
         unsigned ax = pack_bf16x2(va[0], va[1]), ay = pack_bf16x2(va[2], va[3]);
         unsigned bx = pack_bf16x2(vb[0], vb[1]), by = pack_bf16x2(vb[2], vb[3]);
@@ -1235,9 +1235,8 @@ __device__ __forceinline__ void bdir_body(const GConvArgsB &a, u32x4 (*lds_a)[4 
         {
           const int cba = cb0 + mi * 4 + gp * 2;
           const bool rla = a.relu && !(cba >= a.norelu_cb0 && cba < a.norelu_cb1), rlb = a.relu && !(cba + 1 >= a.norelu_cb0 && cba + 1 < a.norelu_cb1);
-          const float loa = relu_lo(rla), lob = relu_lo(rlb);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] = clamp_lo(va[e], loa); vb[e] = clamp_lo(vb[e], lob); }
+          for (int e = 0; e < 4; ++e) { va[e] = relu_bf(va[e], rla); vb[e] = relu_bf(vb[e], rlb); }
         }
         unsigned ax = pack_bf16x2(va[0], va[1]), ay = pack_bf16x2(va[2], va[3]);
         unsigned bx = pack_bf16x2(vb[0], vb[1]), by = pack_bf16x2(vb[2], vb[3]);
@@ -1493,9 +1492,8 @@ __device__ __forceinline__ void bdir8_body(const GConvArgsB &a, u32x4 (*lds_a)[4
       {
         const int cba = cb0 + mi * 4 + gp * 2;
         const bool rla = a.relu && !(cba >= a.norelu_cb0 && cba < a.norelu_cb1), rlb = a.relu && !(cba + 1 >= a.norelu_cb0 && cba + 1 < a.norelu_cb1);
-        const float loa = relu_lo(rla), lob = relu_lo(rlb);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { va[e] = clamp_lo(va[e], loa); vb[e] = clamp_lo(vb[e], lob); }
+        for (int e = 0; e < 4; ++e) { va[e] = relu_bf(va[e], rla); vb[e] = relu_bf(vb[e], rlb); }
       }
       unsigned ax = pack_bf16x2(va[0], va[1]), ay = pack_bf16x2(va[2], va[3]);
       unsigned bx = pack_bf16x2(vb[0], vb[1]), by = pack_bf16x2(vb[2], vb[3]);
@@ -1741,9 +1739,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_c8i_bf16_bdir2_kernel(GConvArgs
         {
           const int cba = cb0 + mi * 4 + gp * 2;
           const bool rla = a.relu && !(cba >= a.norelu_cb0 && cba < a.norelu_cb1), rlb = a.relu && !(cba + 1 >= a.norelu_cb0 && cba + 1 < a.norelu_cb1);
-          const float loa = relu_lo(rla), lob = relu_lo(rlb);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { va[e] = clamp_lo(va[e], loa); vb[e] = clamp_lo(vb[e], lob); }
+          for (int e = 0; e < 4; ++e) { va[e] = relu_bf(va[e], rla); vb[e] = relu_bf(vb[e], rlb); }
         }
         unsigned ax = pack_bf16x2(va[0], va[1]), ay = pack_bf16x2(va[2], va[3]);
         unsigned bx = pack_bf16x2(vb[0], vb[1]), by = pack_bf16x2(vb[2], vb[3]);
@@ -2654,6 +2651,16 @@ static int g_tower_knock = 0;
 static int g_pool_exp = 0;   // mpn_debug_set_pool_exp: timing experiments of the bf16 ROI pooling launch (resnet_head_forward)
 static int g_knock_arm = 0;  // the next `g_knock_arm` rn_conv calls are first-layer convolutions (armed by the caller)
 #endif
+#ifdef MPN_DEBUG_HOOKS
+// mpn_debug_conv_last_form (tests/test_gpu_conv_numerics.py): which launch form rn_conv's last call took.  fp32: 1-4 conv2d_c8i_kernel<KC>,
+// 5 conv2d_c8i_pf_kernel, 10 the Winograd mosaic, 11 im2col + GEMM, 12 the GEMM's split-K form on 1x1 maps, 13 / 14 the pointwise GEMM
+// (direct / row-invariant); bf16: 20 conv2d_c8i_bf16_bdir_kernel (32 / 33 / 38 / 39: bdir_ver 2 / 3 / 8 / 9), 21 / 22 / 23 the LDS-DMA kernel
+// at 256 x 128 / 128 x 256 / 256 x 256 (28: 64-channel stages, 29: the 8-wave shape), 26 / 27 conv2d_c8i_bf16_kernel<1 / 2>; + 0x100: split K
+static int g_dbg_conv_form = 0;
+#define RN_FORM(v) (g_dbg_conv_form = (v))
+#else
+#define RN_FORM(v) ((void)0)
+#endif
 MPN_KNOB(int, g_roi_invariant, 1);  // mpn_debug_set_roi_invariant: 0 = per-ROI layers pick kernel / split by batch size as round 3 did (tests, timing)
 // per_roi: the batch axis counts ROIs (the head of a graph model).  A ROI's result must not depend on which other ROIs share the
 // launch (memoryEfficientForward's chunked == full, ImageDetect.lua:126-133; the ROI-sharded mode == the unsharded one), so for
@@ -2702,6 +2709,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
         return MPN_OK;
       }
       if (g_bf16_bdir_ver == 9) {
+        RN_FORM(39);
         const int nxq = (nx + 7) / 8;
         const dim3 gridp((unsigned)(8 * ((nxq * ny + 1) / 2)));
         hipLaunchKernelGGL((conv2d_c8i_bf16_bdpp_kernel<3>), gridp, dim3(512), 0, s, b, nx, ny);
@@ -2709,6 +2717,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
         return MPN_OK;
       }
       if (g_bf16_bdir_ver == 8) {
+        RN_FORM(38);
         const int ny8 = (b.CoutP + 255) / 256;
         const dim3 grid8((unsigned)(((nx + 7) / 8) * 8 * ny8));
 #ifdef MPN_BF16_ABLATE
@@ -2724,7 +2733,9 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
         return MPN_OK;
       }
 #endif
+      RN_FORM(20);
 #ifdef MPN_DEBUG_HOOKS
+      if (g_bf16_bdir_ver == 2 || g_bf16_bdir_ver == 3) RN_FORM(30 + g_bf16_bdir_ver);
       if (g_bf16_bdir_ver == 2) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir2_kernel<3>), gridd, dim3(256), 0, s, b, nx, ny);
       else if (g_bf16_bdir_ver == 3) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir2_kernel<4>), gridd, dim3(256), 0, s, b, nx, ny);
       else
@@ -2786,6 +2797,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
         b.trace = (g_bf16_trace && b.KH == g_bf16_trace_kh) ? g_bf16_trace : nullptr;
         b.exp = g_bf16_exp;
         const dim3 gridd((unsigned)(((nx + 7) / 8) * 8 * ny));
+        RN_FORM(nch8 ? 28 : w8 ? 29 : tm == 128 ? 22 : tn == 128 ? 21 : 23);
 #ifdef MPN_DEBUG_HOOKS
         if (nch8 && tm == 256 && tn == 128) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<4, 2, 8>), gridd, dim3(256), LDS, s, b, nx, ny);
         else if (nch8 && tm == 128) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<2, 4, 8>), gridd, dim3(256), LDS, s, b, nx, ny);
@@ -2818,6 +2830,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
         const int splits = (nstages + b.stages_per_split - 1) / b.stages_per_split;
         b.part = c.ws;
         grid.z = (unsigned)splits;
+        RN_FORM(0x100 | (kp == 2 ? 27 : 26));
         if (kp == 2) hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<2>), grid, dim3(256), 0, s, b);
         else hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<1>), grid, dim3(256), 0, s, b);
         MPN_CHECK_LAUNCH();
@@ -2830,6 +2843,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
     }
     // 32-channel stages (32 KiB of LDS, 4-5 blocks per CU) measured 3 % faster than 64-channel ones on ResNet-50; either way this
     // kernel is bound by its operand loads (64 FLOP per loaded byte at a 128 x 128 tile), not by the bf16 matrix pipe
+    RN_FORM(b.nch2 % 4 == 0 ? 27 : 26);
     if (b.nch2 % 4 == 0) hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<2>), grid, dim3(256), 0, s, b);
     else hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<1>), grid, dim3(256), 0, s, b);
     MPN_CHECK_LAUNCH();
@@ -2855,6 +2869,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
       ((in.B + c.mos_mx - 1) / c.mos_mx) * (in.H + 1) <= c.mos_rows) {
     // per-ROI 3x3 / stride-1 convolution (layer4's conv2 of blocks 2, 3): the batch as a mosaic image on the Winograd kernel
     const int rows = ((in.B + c.mos_mx - 1) / c.mos_mx) * (in.H + 1);
+    RN_FORM(10);
     const int Hp = act_hp(c.mos_rows), Wp = act_wp(c.mos_cols);
     const size_t recs = (size_t)in.B * in.H * in.W;
     hipLaunchKernelGGL(c8i_to_mosaic_kernel, dim3((unsigned)cdiv_sz(recs * in.Cb() * 2, 256)), dim3(256), 0, s, in.p, in.Cb(), in.B, in.H, in.W, in.pitch(), c.mos_mx, Hp, Wp,
@@ -2870,6 +2885,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
   }
   if (allow_gemm && c.col_w && in.planar && in.B == 1 && in.C == 3 && !res && c.norelu_c1 == c.norelu_c0 && (g_graph_fuse & 16)) {
     const int Kc = c.KH * c.KW * 3, nkb = round_up(Kc, 64) / 8;
+    RN_FORM(11);
     const size_t need = (size_t)nkb * o->pitch() * 8 * sizeof(float);
     void *col = nullptr;
     { int rc_ws = scratch_get(SCR_IM2COL, need, s, &col); if (rc_ws) return rc_ws; }
@@ -2881,10 +2897,14 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
   // a pointwise convolution on 1x1 maps is a fully-connected layer (AlexNet's fc7): few row tiles, so the GEMM's split-K form
   // with its row-invariant segments rather than a 128-pixel-tile convolution (the un-split form folds at the same segments)
   if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && !res && in.H == 1 && in.W == 1 && (g_graph_fuse & 8) &&
-      (inv || !linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch())))
+      (inv || !linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch()))) {
+    RN_FORM(12);
     return linear_c8(in.p, (int)in.rows(), c.Cin, c.lin_w, c.lin_b, c.Cout, relu, out, nullptr, s, (int)in.pitch(), nullptr, 1);
-  if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && (inv || linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch())))  // same rows in and out: the tuned GEMM, residual + ReLU fused
+  }
+  if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && (inv || linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch()))) {  // same rows in and out: the tuned GEMM, residual + ReLU fused
+    RN_FORM(inv ? 14 : 13);
     return linear_c8(in.p, (int)in.rows(), c.Cin, c.lin_w, c.lin_b, c.Cout, relu, out, nullptr, s, (int)in.pitch(), res, inv ? 2 : 0);
+  }
   dim3 grid((unsigned)(((a.P + 127) / 128 + 7) / 8 * 8 * (a.CoutP / 128)));  // pixel tiles rounded up to the 8 XCDs x cout tiles (see the kernel)
   // 32-channel stages: the LDS-DMA / hand-pipelined kernel (32-bit gather offsets: the input batch must stay under 4 GiB)
   constexpr size_t PF_LDS = (size_t)2 * 2 * 4 * 128 * 8 * sizeof(float);
@@ -2902,6 +2922,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
       const int splits = (nstages + a.stages_per_split - 1) / a.stages_per_split;
       a.part = c.ws;
       grid.z = (unsigned)splits;
+      RN_FORM(0x100 | (kc == 4 && pf_ok ? 5 : kc));
       if (kc == 4 && pf_ok) hipLaunchKernelGGL(conv2d_c8i_pf_kernel, grid, dim3(256), PF_LDS, s, a);
       else if (kc == 4) hipLaunchKernelGGL((conv2d_c8i_kernel<4>), grid, dim3(256), 0, s, a);
       else if (kc == 3) hipLaunchKernelGGL((conv2d_c8i_kernel<3>), grid, dim3(256), 0, s, a);
@@ -2915,6 +2936,7 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
       return MPN_OK;
     }
   }
+  RN_FORM(a.nch % 4 == 0 && pf_ok ? 5 : a.nch % 4 == 0 ? 4 : a.nch % 3 == 0 ? 3 : a.nch % 2 == 0 ? 2 : 1);
   if (a.nch % 4 == 0 && pf_ok) hipLaunchKernelGGL(conv2d_c8i_pf_kernel, grid, dim3(256), PF_LDS, s, a);
   else if (a.nch % 4 == 0) hipLaunchKernelGGL((conv2d_c8i_kernel<4>), grid, dim3(256), 0, s, a);
   else if (a.nch % 3 == 0) hipLaunchKernelGGL((conv2d_c8i_kernel<3>), grid, dim3(256), 0, s, a);
@@ -3774,6 +3796,124 @@ extern "C" int mpn_debug_bench_conv_bf16(int Cin, int Cout, int KH, int KW, int 
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
+  resnet_free(g);
+  return rc;
+}
+// Test hook (tests/test_gpu_conv_numerics.py): ONE convolution through rn_conv, on NCHW fp32 device operands x [B, Cin, H, W], w [Cout, Cin,
+// KH, KW], b [Cout] (optional), res [B, Cout, OH, OW] (optional), packed by rn_pack into a scratch graph as graph building packs them
+// (lin_w / col_w; with `mosaic`, fp32 3x3 / stride-1 / pad-1 layers also get the Winograd weights and mosaic images for max_rois maps, as
+// mpn_resnet_create sets them up).  bf16: x, res and the weights round to bf16 (RNE), as the graph stores them.  The C8I input's pad channel
+// planes and its rows from B*H*W up to the pitch hold the finite pattern pad_fill * (+-1 .. 5); so do the residual's.  The output goes to
+// channels [out_c_off, out_c_off + Cout) of an out_c-channel C8I tensor (out_c_off: a multiple of 8) whose every element first holds the
+// sentinel NaN 0x7fa5a5a5 (bf16: 0x7fa5).  The rn_conv call is repeated for the batch sizes n_b[0 .. n_rep - 1] (each the first maps of x;
+// a fresh layout per run, one graph: the mosaic images carry over); y [n_b[n_rep - 1], Cout, OH, OW] fp32 is the last run's output.  raw
+// (optional, raw_cap bytes): the last run's whole output buffer, raw_bytes (optional) its size.  form_out: mpn_debug_conv_last_form().
+namespace mpn {
+__global__ void dbg_nchw_to_c8i_kernel(const float *__restrict__ x, int B, int C, int H, int W, size_t pitch, size_t total, float pad_fill, int bf16,
+                                       void *__restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int j = (int)(t & 7);
+  const size_t r = (t >> 3) % pitch;
+  const int c = (int)((t >> 3) / pitch) * 8 + j;
+  const size_t HW = (size_t)H * W;
+  float v = pad_fill * (float)(1 + (int)(t % 5)) * ((t & 8) ? -1.0f : 1.0f);
+  if (c < C && r < (size_t)B * HW) v = x[((r / HW) * C + c) * HW + r % HW];
+  if (bf16) static_cast<bf16_t *>(out)[t] = f2bf(v);
+  else static_cast<float *>(out)[t] = v;
+}
+__global__ void dbg_c8i_to_nchw_kernel(const void *__restrict__ in, int B, int C, int H, int W, size_t pitch, int cb0, int bf16, float *__restrict__ y) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t HW = (size_t)H * W;
+  if (t >= (size_t)B * C * HW) return;
+  const size_t b = t / ((size_t)C * HW), rem = t % ((size_t)C * HW);
+  const int c = (int)(rem / HW);
+  const size_t off = ((size_t)(cb0 + c / 8) * pitch + b * HW + rem % HW) * 8 + c % 8;
+  y[t] = bf16 ? bf2f(static_cast<const bf16_t *>(in)[off]) : static_cast<const float *>(in)[off];
+}
+__global__ void dbg_fill_u32_kernel(unsigned *p, size_t n, unsigned v) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) p[t] = v;
+}
+}  // namespace mpn
+extern "C" int mpn_debug_conv_last_form(void) { return mpn::g_dbg_conv_form; }
+extern "C" int mpn_debug_conv_form(const float *d_x, int Cin, int H, int W, const float *d_w, int Cout, int KH, int KW, int sh, int sw, int ph, int pw,
+                                   const float *d_b, const float *d_res, int relu, int norelu_c0, int norelu_c1, int bf16, int per_roi, int allow_gemm,
+                                   int mosaic, int max_rois, int n_rep, const int *n_b, int out_c, int out_c_off, float pad_fill, float *d_y, void *d_raw,
+                                   size_t raw_cap, size_t *raw_bytes, int *form_out) {
+  using namespace mpn;
+  MPN_CHECK_ARG(d_x && d_w && d_y && Cin > 0 && H > 0 && W > 0 && Cout > 0 && KH > 0 && KW > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0);
+  MPN_CHECK_ARG(n_rep >= 1 && n_b && out_c_off >= 0 && out_c_off % 8 == 0 && out_c >= out_c_off + Cout && norelu_c0 % 8 == 0 && norelu_c1 % 8 == 0);
+  for (int i = 0; i < n_rep; ++i) MPN_CHECK_ARG(n_b[i] > 0);
+  const int OH = (H + 2 * ph - KH) / sh + 1, OW = (W + 2 * pw - KW) / sw + 1;
+  MPN_CHECK_ARG(OH > 0 && OW > 0 && std::isfinite(pad_fill));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  ResNetGraph *g = new ResNetGraph();
+  g->bf16 = bf16 != 0;
+  const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
+  RnConv c;
+  c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.sh = sh; c.sw = sw; c.ph = ph; c.pw = pw; c.K = KH; c.stride = sh; c.pad = ph;
+  c.norelu_c0 = norelu_c0; c.norelu_c1 = norelu_c1;
+  int rc = rn_pack(g, c, d_w, d_b);
+  if (rc == MPN_OK && mosaic && !g->bf16 && (g_graph_fuse & 128) && KH == 3 && KW == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && Cin % 8 == 0 &&
+      Cout % 8 == 0 && Cin >= 16 && max_rois > 0) {  // as mpn_resnet_create: the Winograd weights and the two zeroed mosaic images
+    rc = rn_alloc(g, &c.wino, conv_wino_elems(Cin, Cout) * sizeof(float));
+    if (rc == MPN_OK) rc = pack_conv_weights_wino(d_w, Cin, Cout, c.wino, nullptr);
+    const int mx = std::max(1, 32 / (W + 1)), rows = ((max_rois + mx - 1) / mx) * (H + 1), cols = mx * (W + 1);
+    if (rc == MPN_OK) rc = rn_alloc(g, &c.mos_in, act_bytes(Cin, rows, cols));
+    if (rc == MPN_OK) rc = rn_alloc(g, &c.mos_out, act_bytes(Cout, rows, cols));
+    if (rc == MPN_OK && (hipMemset(c.mos_in, 0, act_bytes(Cin, rows, cols)) != hipSuccess || hipMemset(c.mos_out, 0, act_bytes(Cout, rows, cols)) != hipSuccess))
+      rc = MPN_EHIP;
+    c.mos_h = H; c.mos_w = W; c.mos_mx = mx; c.mos_rows = rows; c.mos_cols = cols;
+  }
+  // the output's channel blocks: the wider tensor's, and room for a form that writes whole 128-channel panels from out_c_off on
+  const int ob_all = std::max(round_up(out_c, 128), out_c_off + round_up(Cout, 128)) / 8;
+  float *in = nullptr, *out = nullptr, *res = nullptr;
+  for (int i = 0; i < n_rep && rc == MPN_OK; ++i) {
+    const int B = n_b[i];
+    if (in) { (void)hipFree(in); in = nullptr; }
+    if (out) { (void)hipFree(out); out = nullptr; }
+    if (res) { (void)hipFree(res); res = nullptr; }
+    const size_t ie = c8i_elems(B, Cin, H, W), pitch_o = ((size_t)B * OH * OW + 127) / 128 * 128, oe = (size_t)ob_all * pitch_o * 8;
+    const size_t re = c8i_elems(B, Cout, OH, OW);
+    if (hipMalloc(&in, ie * esz) != hipSuccess || hipMalloc(&out, oe * esz) != hipSuccess || (d_res && hipMalloc(&res, re * esz) != hipSuccess)) {
+      rc = MPN_EHIP;
+      break;
+    }
+    const ActI ai0{in, B, Cin, H, W};
+    hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(ie, 256)), dim3(256), 0, nullptr, d_x, B, Cin, H, W, ai0.pitch(), ie, pad_fill, bf16, in);
+    MPN_CHECK_LAUNCH();
+    if (res) {
+      hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(re, 256)), dim3(256), 0, nullptr, d_res, B, Cout, OH, OW, pitch_o, re, pad_fill, bf16, res);
+      MPN_CHECK_LAUNCH();
+    }
+    if (g->bf16) {
+      hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe / 2, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(out), oe / 2, 0x7fa57fa5u);
+    } else {
+      hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(out), oe, 0x7fa5a5a5u);
+    }
+    MPN_CHECK_LAUNCH();
+    ActI ai{in, B, Cin, H, W};
+    if (Cin == 3 && B == 1) ai.planar = d_x;  // the image layer: the graph keeps the same pixels as [3][H][W] planes
+    ActI o;
+    g_dbg_conv_form = 0;
+    rc = rn_conv(c, ai, reinterpret_cast<float *>(reinterpret_cast<char *>(out) + (size_t)(out_c_off / 8) * pitch_o * 8 * esz), res, relu, nullptr, &o,
+                 allow_gemm != 0, per_roi != 0);
+    if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
+    if (rc == MPN_OK && i + 1 == n_rep) {
+      const size_t total = (size_t)B * Cout * OH * OW;
+      hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, out, B, Cout, OH, OW, pitch_o, out_c_off / 8, bf16, d_y);
+      MPN_CHECK_LAUNCH();
+      if (raw_bytes) *raw_bytes = oe * esz;
+      if (d_raw && raw_cap < oe * esz) { set_error("mpn_debug_conv_form: raw needs %zu bytes", oe * esz); rc = MPN_EINVAL; }
+      else if (d_raw) MPN_CHECK_HIP(hipMemcpy(d_raw, out, oe * esz, hipMemcpyDeviceToDevice));
+    }
+  }
+  if (form_out) *form_out = g_dbg_conv_form;
+  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
+  if (in) (void)hipFree(in);
+  if (out) (void)hipFree(out);
+  if (res) (void)hipFree(res);
   resnet_free(g);
   return rc;
 }
