@@ -385,7 +385,10 @@ int mpn_resnet_create(const mpn_frcnn_config *cfg, const mpn_resnet_weights *rw,
  * Convolution edge values: without ReLU (relu = 0, or the channels a fused sibling keeps linear) every output is NaN / +inf / -inf /
  * finite exactly when the float64 sum is (inf x 0 and inf - inf give NaN), except on the fp32 Winograd forms (3x3 / stride 1: the trunk's
  * layers and the per-ROI mosaic), whose transforms spread a non-finite input over its 4x4 input tile.  ReLU(NaN): 0 on bf16 graphs and
- * on the fp32 Winograd forms (as Torch's Threshold), NaN on the other fp32 forms (t < 0 ? 0 : t, like the fully-connected GEMM). */
+ * on the fp32 Winograd forms (as Torch's Threshold), NaN on the other fp32 forms (t < 0 ? 0 : t, like the fully-connected GEMM).  A Winograd
+ * layer follows its rule in every launch: the tiles a split-K or tail-split launch finishes in the reduce kernel give 0 as well.
+ * The trunk's ceil-mode 2x2 max-pool, fused into a convolution or on its own: the NaNs of a window are ignored, a window holding only
+ * NaN gives -inf (v > m from -inf, the CPU oracle's rule) in every kernel that pools. */
 typedef struct mpn_graph_op {
   int kind;               /* 0 = convolution (+ bias, ReLU if relu), 1 = max-pool (padded cells never win; floor mode unless ceil_mode),
                              2 = average pool, count_include_pad (nn.SpatialAveragePooling's default: always / (kh*kw)),

@@ -68,6 +68,12 @@ int image_transform_canvas_c8p(const float *d_in, int H, int W, const int *swap,
 // out = relu?(conv3x3(in) + b); optional fused ceil-mode 2x2 max-pool writes `pooled` as well
 // (out.p may be null when only the pooled map is needed).
 // d_wino (optional): Winograd-transformed weights; used when the variant selector picks the Winograd kernel.
+// Edge values (include/mpn.h, convolution edge values; tests/test_gpu_trunk_conv_numerics.py): ReLU(NaN) is NaN on the direct kernels and
+// the first-layer kernel (t < 0 ? 0 : t) and 0 on EVERY Winograd launch (max(t, 0)), the tiles conv_splitk_reduce_kernel finishes for a
+// split-K or tail-split launch included.  The 2x2 max-pool — fused in the direct kernel, fused in the Winograd kernel, in the reduce
+// kernel, or maxpool2x2_c8p — ignores the NaNs of a window and gives -inf for a window holding only NaN (v > m from -inf).
+// Layout: a launch stores only inside the H x W interior of the planes of its ceil(Cout / 8) channel blocks (never the halo or the
+// pitch padding, which run_trunk zeroes once per image size) and writes +0.0 into the pad lanes of the last block for finite inputs.
 // batch_invariant (Winograd only): the launch plan must not depend on the map's height — no split-K, no tail split, the 8 x 32-px block
 // geometry — so that a cell of a mosaic of per-ROI maps (resnet.hip) gets the same bits whatever the number of maps in the mosaic.
 int conv3x3_c8p(Act in, const float *d_wpk, const float *d_bpk, int Cout, int relu, Act out, Act pooled, hipStream_t s,

@@ -261,7 +261,8 @@ __global__ __launch_bounds__(256) void conv3x3_c8p_kernel(ConvArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               float t = fmaxf(v[2 * q][e], v[2 * q + 1][e]);
-              m[e] = fmaxf(t, __shfl_xor(t, 1));
+              t = fmaxf(t, __shfl_xor(t, 1));
+              m[e] = t > -INFINITY ? t : -INFINITY;  // a window of NaNs pools to -inf, as v > m from -inf does (dense.h)
             }
             const int py = ((y0 + rbase) >> 1) + q, px = x >> 1;
             if (!(l31 & 1) && py < a.pool_H && px < a.pool_W)
@@ -837,6 +838,8 @@ static int launch_conv_wino(const ConvArgs &a, int tiles_y, hipStream_t s) {
 
 // split-K finish: sums S partial slabs in split order (deterministic), + bias, ReLU; writes the C8P
 // output and/or its ceil-mode 2x2 max-pool.  One thread per (channel block, pooled-or-full pixel, half).
+// relu: 1 = the direct kernels' t < 0 ? 0 : t (NaN stays NaN), 2 = the Winograd epilogue's max(t, 0) (NaN -> 0): a layer finishes
+// under ONE rule whether a tile was finished by its own block or here (dense.h, convolution edge values).
 __global__ void conv_splitk_reduce_kernel(const float *__restrict__ part, size_t slab, int S, size_t plane, int Wp, int H, int W,
                                           int out_cb, const float *__restrict__ bpk, int relu, float *__restrict__ out,
                                           float *__restrict__ pool, size_t pool_plane, int pool_Wp, int pool_H, int pool_W,
@@ -869,7 +872,7 @@ __global__ void conv_splitk_reduce_kernel(const float *__restrict__ part, size_t
       v += b4;
       if (relu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.0f ? 0.0f : v[e];
+        for (int e = 0; e < 4; ++e) v[e] = relu == 2 ? fmaxf(v[e], 0.0f) : (v[e] < 0.0f ? 0.0f : v[e]);
       }
       if (out) *reinterpret_cast<f32x4 *>(out + off) = v;
 #pragma unroll
@@ -965,6 +968,18 @@ MPN_KNOB(int, g_wino_tc, 0);  // test hook: force the Winograd block geometry (8
 MPN_KNOB(int, g_conv_variant, 0);  // 0 = auto; test/bench hook: 1 = 128x4 tile / 9 taps per stage, 2 = 64x8 / 9, 3 = 128x4 / 3, 4 = 64x8 / 3,
                                  // 5 = 128 couts x 8 rows (64x128 per wave, 8 accumulators), 6 = 64 couts x 16 rows
 
+#ifdef MPN_DEBUG_HOOKS
+// mpn_debug_conv3x3_last_plan: what the last conv3x3_c8p launched, written where the plan is final (after every clamp)
+static int g_conv_last_plan[8];
+static void record_conv_plan(int variant, const ConvArgs &a, bool reduce) {
+  const int v[8] = {variant, a.wino_tc, a.splits, a.chunks_per_split, a.tail_first, a.tail_splits, a.tail_cps, reduce ? 1 : 0};
+  for (int i = 0; i < 8; ++i) g_conv_last_plan[i] = v[i];
+}
+#define MPN_RECORD_CONV_PLAN(variant, a, reduce) record_conv_plan(variant, a, reduce)
+#else
+#define MPN_RECORD_CONV_PLAN(variant, a, reduce) ((void)0)
+#endif
+
 int conv3x3_variant_for(int Cout, bool has_wino) {
   int variant = g_conv_variant & 15;
   // measured on MI355X (tools/bench_layers.py): Winograd F(2x2,3x3) beats the direct kernels on every VGG layer with
@@ -1017,6 +1032,7 @@ int conv3x3_c8p(Act in, const float *d_wpk, const float *d_bpk, int Cout, int re
       { int rc_ws = scratch_get(SCR_CONV_SPLITK, need, s, &ws); if (rc_ws) return rc_ws; }
       a.part = static_cast<float *>(ws);
     }
+    MPN_RECORD_CONV_PLAN(7, a, n_slabs > 1);
     int rc = launch_conv_wino(a, tiles_y, s);
     if (rc != MPN_OK || n_slabs == 1) return rc;
     const int GH = pooled.p ? pooled.H : in.H, GW = pooled.p ? pooled.W : in.W;
@@ -1028,7 +1044,7 @@ int conv3x3_c8p(Act in, const float *d_wpk, const float *d_bpk, int Cout, int re
     }
     const size_t total = (size_t)a.out_cb * (GH - g_start) * GW * 2;
     hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, a.part, a.part_slab, n_slabs, geo.plane(),
-                       geo.Wp, in.H, in.W, a.out_cb, d_bpk, relu, out.p, pooled.p, a.pool_plane, a.pool_Wp, a.pool_H, a.pool_W, tile_first,
+                       geo.Wp, in.H, in.W, a.out_cb, d_bpk, relu ? 2 : 0, out.p, pooled.p, a.pool_plane, a.pool_Wp, a.pool_H, a.pool_W, tile_first,
                        a.tiles_x, g_start, a.wino_tc == 16 ? 3 : 4, a.wino_tc == 16 ? 5 : 4);
     MPN_CHECK_LAUNCH();
     return MPN_OK;
@@ -1051,6 +1067,7 @@ int conv3x3_c8p(Act in, const float *d_wpk, const float *d_bpk, int Cout, int re
     { int rc_ws = scratch_get(SCR_CONV_SPLITK, need, s, &ws); if (rc_ws) return rc_ws; }
     a.part = static_cast<float *>(ws);
   }
+  MPN_RECORD_CONV_PLAN(variant, a, a.splits > 1);
   int rc;
   switch (variant) {
     case 1: rc = launch_conv<128, 4, 2, 2, 9>(a, tiles_y, s); break;
@@ -1064,7 +1081,7 @@ int conv3x3_c8p(Act in, const float *d_wpk, const float *d_bpk, int Cout, int re
   const int GH = pooled.p ? pooled.H : in.H, GW = pooled.p ? pooled.W : in.W;
   const size_t total = (size_t)a.out_cb * GH * GW * 2;
   hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, a.part, a.part_slab, a.splits, geo.plane(),
-                     geo.Wp, in.H, in.W, a.out_cb, d_bpk, relu, out.p, pooled.p, a.pool_plane, a.pool_Wp, a.pool_H, a.pool_W, 0, 0, 0, 4, 4);
+                     geo.Wp, in.H, in.W, a.out_cb, d_bpk, relu ? 1 : 0, out.p, pooled.p, a.pool_plane, a.pool_Wp, a.pool_H, a.pool_W, 0, 0, 0, 4, 4);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
@@ -2905,6 +2922,64 @@ extern "C" int mpn_debug_l2norm_row_scales(const float *d_feat_nchw, int C, int 
   MPN_CHECK_HIP(hipDeviceSynchronize());
   (void)hipFree(act); (void)hipFree(o);
   if (tabpm) (void)hipFree(tabpm);
+  return rc;
+}
+
+// test hook (tests/test_gpu_trunk_conv_numerics.py): ONE call of conv3x3_c8p (kind 0), conv3x3_first_c8p (kind 1) or maxpool2x2_c8p
+// (kind 2) on raw C8P buffers the caller owns.  d_x [Cin,H,W] NCHW is laid out by nchw_to_c8p into a zeroed buffer (the zero halo is
+// the input contract), the weights go through the real packers (use_wino: pass the Winograd packing beside the direct one, as the trunk
+// does for layers with >= 16 input channels).  d_full / d_pool: raw C8P buffers of mpn_debug_act_elems(Cout, H, W) /
+// (Cout, ceil(H/2), ceil(W/2)) floats; which of them is non-null is the output mode (full map, pooled only, both = a tap layer).  The
+// entry writes neither itself, so whatever the caller filled them with survives wherever the kernels do not store.  kind 2 pools d_x
+// (Cout = Cin) into d_pool.  Variant / split / block geometry come from mpn_debug_set_conv_variant / _conv_split / _wino_tc.  Synchronous.
+extern "C" size_t mpn_debug_act_elems(int C, int H, int W, int *Hp, int *Wp) {
+  if (Hp) *Hp = act_hp(H);
+  if (Wp) *Wp = act_wp(W);
+  return act_bytes(C, H, W) / sizeof(float);
+}
+extern "C" void mpn_debug_conv3x3_last_plan(int *plan8) {
+  for (int i = 0; i < 8; ++i) plan8[i] = g_conv_last_plan[i];
+}
+extern "C" int mpn_debug_conv3x3_form(const float *d_x, int Cin, int H, int W, const float *d_w, const float *d_b, int Cout, int relu, int kind,
+                                      int use_wino, int batch_invariant, float *d_full, float *d_pool) {
+  MPN_CHECK_ARG(d_x && Cin > 0 && H > 0 && W > 0 && Cout > 0 && kind >= 0 && kind <= 2 && (d_full || d_pool));
+  MPN_CHECK_ARG(kind == 2 ? (Cout == Cin && d_pool && !d_full) : d_w != nullptr);
+  MPN_CHECK_ARG(kind != 1 || (Cin <= 4 && d_full && !d_pool));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  for (int i = 0; i < 8; ++i) g_conv_last_plan[i] = 0;
+  float *act = nullptr, *wpk = nullptr, *bpk = nullptr, *wx = nullptr;
+  const size_t ab = act_bytes(Cin, H, W);
+  MPN_CHECK_HIP(hipMalloc(&act, ab));
+  MPN_CHECK_HIP(hipMemset(act, 0, ab));
+  Act ain = make_act(act, Cin, H, W);
+  Act full = d_full ? make_act(d_full, Cout, H, W) : Act{};
+  Act pool = d_pool ? make_act(d_pool, Cout, (H + 1) / 2, (W + 1) / 2) : Act{};
+  int rc = nchw_to_c8p(d_x, Cin, H, W, ain, nullptr);
+  if (rc == MPN_OK && kind == 2) {
+    rc = maxpool2x2_c8p(ain, pool, nullptr);
+    g_conv_last_plan[0] = -1;
+  } else if (rc == MPN_OK) {
+    MPN_CHECK_HIP(hipMalloc(&wpk, conv_wpk_elems(Cin, Cout) * sizeof(float)));
+    MPN_CHECK_HIP(hipMalloc(&bpk, (size_t)conv_coutp(Cout) * sizeof(float)));
+    rc = pack_conv_weights(d_w, d_b, Cin, Cout, wpk, bpk, nullptr);
+    if (rc == MPN_OK && kind == 1) {
+      MPN_CHECK_HIP(hipMalloc(&wx, conv_first_elems(Cout) * sizeof(float)));
+      rc = pack_conv_weights_first(d_w, Cin, Cout, wx, nullptr);
+      if (rc == MPN_OK) rc = conv3x3_first_c8p(ain, wx, bpk, Cout, relu, full, nullptr);
+      g_conv_last_plan[0] = 36; g_conv_last_plan[2] = g_conv_last_plan[3] = 1;
+    } else if (rc == MPN_OK) {
+      if (use_wino) {
+        MPN_CHECK_HIP(hipMalloc(&wx, conv_wino_elems(Cin, Cout) * sizeof(float)));
+        rc = pack_conv_weights_wino(d_w, Cin, Cout, wx, nullptr);
+      }
+      if (rc == MPN_OK) rc = conv3x3_c8p(ain, wpk, bpk, Cout, relu, full, pool, nullptr, wx, batch_invariant != 0);
+    }
+  }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  (void)hipFree(act);
+  if (wpk) (void)hipFree(wpk);
+  if (bpk) (void)hipFree(bpk);
+  if (wx) (void)hipFree(wx);
   return rc;
 }
 
