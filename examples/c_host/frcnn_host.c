@@ -2,7 +2,10 @@
  * (utils.lua:15-39 for libnms; INTEGRATION.md §3 for the whole path), minus Lua, which this image does not have.
  * No torch, no Python, no C++: device memory comes from the HIP runtime's C API, exactly as a cutorch tensor's would.
  *
- *   frcnn_host <model+inputs blob> <out file>
+ *   frcnn_host [--augment] <model+inputs blob> <out file>
+ *
+ * --augment: opt.test_augment — horizontal-flip test-time augmentation (mpn_frcnn_set_augment) around Tester:testOne.  The loop form
+ * has no augmented variant: the program checks that it is refused with MPN_EINVAL and a message, and that the handle still works.
  *
  * blob (little-endian, written by tests/test_c_host.py with numpy):
  *   int32  magic 0x4d504e31, n_conv, conv_cout[n_conv], pool_after[n_conv], fc_dim, n_classes, pooled, H, W, N
@@ -35,7 +38,9 @@ static int upload(size_t n, float **d) {
 }
 
 int main(int argc, char **argv) {
-  if (argc != 3) { fprintf(stderr, "usage: %s <blob> <out>\n", argv[0]); return 1; }
+  int augment = 0;
+  if (argc == 4 && strcmp(argv[1], "--augment") == 0) { augment = 1; ++argv; --argc; }
+  if (argc != 3) { fprintf(stderr, "usage: %s [--augment] <blob> <out>\n", argv[0]); return 1; }
   FILE *f = fopen(argv[1], "rb");
   if (!f) { perror(argv[1]); return 1; }
   fseek(f, 0, SEEK_END);
@@ -101,10 +106,18 @@ int main(int argc, char **argv) {
     CHECK_HIP(hipMalloc((void **)&d_dets[i], (size_t)cap * 6 * sizeof(float)));
     CHECK_HIP(hipMalloc((void **)&d_n[i], sizeof(int)));
   }
+  if (augment) CHECK_MPN(mpn_frcnn_set_augment(net, 1));
   /* Tester:testOne on device-resident inputs */
   CHECK_MPN(mpn_frcnn_test_one(net, d_im, H, W, d_boxes, N, d_dets[0], cap, d_n[0], NULL));
-  /* Tester:test's loop form fed from HOST buffers: three images (the same one), the tail of each overlapping the next trunk */
-  for (int it = 0; it < 3; ++it) CHECK_MPN(mpn_frcnn_test_one_pipelined_host(net, h_im, H, W, h_boxes, N, d_dets[1], cap, d_n[1], NULL));
+  if (augment) {
+    /* the loop form runs one trunk pass per image: refused while augmentation is on, and the handle stays usable */
+    const int rc = mpn_frcnn_test_one_pipelined_host(net, h_im, H, W, h_boxes, N, d_dets[1], cap, d_n[1], NULL);
+    if (rc != MPN_EINVAL || !mpn_last_error()[0]) { fprintf(stderr, "the pipelined form under augmentation returned %d, not MPN_EINVAL with a message\n", rc); return 4; }
+    CHECK_MPN(mpn_frcnn_test_one(net, d_im, H, W, d_boxes, N, d_dets[1], cap, d_n[1], NULL));
+  } else {
+    /* Tester:test's loop form fed from HOST buffers: three images (the same one), the tail of each overlapping the next trunk */
+    for (int it = 0; it < 3; ++it) CHECK_MPN(mpn_frcnn_test_one_pipelined_host(net, h_im, H, W, h_boxes, N, d_dets[1], cap, d_n[1], NULL));
+  }
   CHECK_MPN(mpn_frcnn_flush(net, NULL));
   CHECK_HIP(hipDeviceSynchronize());
 
@@ -120,7 +133,7 @@ int main(int argc, char **argv) {
     CHECK_HIP(hipMemcpy(h_dets[i], d_dets[i], (size_t)n[i] * 6 * sizeof(float), hipMemcpyDeviceToHost));
   }
   if (n[0] != n[1] || memcmp(h_dets[0], h_dets[1], (size_t)n[0] * 6 * sizeof(float)) != 0) {
-    fprintf(stderr, "test_one and the pipelined host-fed loop disagree (%d vs %d detections)\n", n[0], n[1]);
+    fprintf(stderr, "test_one and %s disagree (%d vs %d detections)\n", augment ? "its repetition" : "the pipelined host-fed loop", n[0], n[1]);
     return 4;
   }
   printf("%d detections; first: [%.2f %.2f %.2f %.2f] score %.6f class %d\n", n[0], n[0] ? h_dets[0][0] : 0.f, n[0] ? h_dets[0][1] : 0.f,

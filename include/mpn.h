@@ -142,6 +142,14 @@ int mpn_project_im_rois(const float *d_boxes, int n, double scale, float *d_rois
 #define MPN_MAX_SCALES 8
 int mpn_project_im_rois_levels(const float *d_boxes, int n, int n_scales, const double *h_scales, float *d_rois, void *stream);
 
+/* image.hflip (BatchProviderBase.lua:22): d_out[c,y,x] = d_in[c,y,W-1-x].  d_in, d_out [C,H,W], d_in != d_out. */
+int mpn_image_hflip(const float *d_in, int C, int H, int W, float *d_out, void *stream);
+
+/* utils.flipBoxes (utils.lua:151-155): x1' = ((-x2) + image_width) + 1, x2' = ((-x1) + image_width) + 1 in fp32, each operation
+ * rounded on its own (no FMA), y unchanged.  d_boxes, d_out [n,4]; d_out may be d_boxes.  An involution on integer-valued
+ * coordinates below 2^24; not on others. */
+int mpn_flip_boxes(const float *d_boxes, int n, int image_width, float *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * nn.Module:updateOutput mirrors
  * ---------------------------------------------------------------------------------------------- */
@@ -572,6 +580,27 @@ int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const float *d_imag
  * Debug tensors (mpn_frcnn_debug_tensor) with a pyramid: "conv5.<l>" (level l's final map, NCHW at the canvas geometry) and
  * "rois" ([N,5], the projected table of the last head pass; also kept without a pyramid). */
 int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_targets);
+
+/* Horizontal-flip test-time augmentation (opt.test_augment, run_test.lua:39 — declared in the reference, read by nothing there;
+ * completed the standard way).  With enable != 0, for an image im [3,H0,W0] and boxes b [N,4], all in fp32,
+ * every operation rounded on its own:
+ *   im_f = mpn_image_hflip(im) (the ORIGINAL image, before getImages and the transformer);  b_f = mpn_flip_boxes(b, W0);
+ *   (sA, bA) = detect(im, b), (sB, bB) = detect(im_f, b_f): ImageDetect:detect as it is without augmentation, unclamped, scores
+ *   after the softmax (after the integral mean for noSoftMax models), bB decoded against b_f in the mirrored frame;
+ *   scores = (sA + sB) * 0.5f;  bbox[:, 4c:4c+4] = (bA_c + flipBoxes(bB_c, W0)) * 0.5f for every class c;
+ *   then the clamp to [1,W0] x [1,H0] where the caller asked for it (mpn_frcnn_detect's clamp, the first pass of test_one).
+ * Select, NMS, voting and top-k see the merged tables only.  Iterative localisation: pass i+1 takes SelectBoxes of the merged
+ * tables of pass i and runs both halves on cached trunk maps — the upright map with the new boxes, the mirrored map with their
+ * flip; use_rbox_scores pairs the merged tables.  enable == 0: every output of every entry point is what it was before the call.
+ * The call synchronises the device, drops every captured launch graph of the handle and the cached trunk output (the next detect
+ * must pass an image) and allocates the second half's buffers on first use; any N <= max_rois keeps working.
+ * mpn_frcnn_create handles (plain Fast R-CNN heads) keep BOTH trunk maps cached: mpn_frcnn_detect with cached features and every
+ * num_iter work.  mpn_mpnet_create / mpn_resnet_create / mpn_graph_create handles run the two halves as two whole passes and keep
+ * one map: enabling returns MPN_EINVAL when the handle was created with num_iter > 1, and a cached-features detect returns
+ * MPN_EINVAL while augmentation is on.  The pipelined, host-fed and sharded forms return MPN_EINVAL while augmentation is on.
+ * Augmentation and an image pyramid (mpn_frcnn_set_scales with more than one target) exclude each other: the setter called second
+ * returns MPN_EINVAL.  A refused call changes nothing. */
+int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
 
 /* Captured launch graphs.  The kernel chains of the per-image path — the head (transform .. decode) and the tail (per-class NMS,
  * voting, top-k) of mpn_frcnn_test_one / _pipelined / _pipelined_host, and the bodies of mpn_frcnn_shard_head / _shard_nms /

@@ -641,9 +641,46 @@ __global__ void proposals_permute_filter_kernel(const float *__restrict__ in, in
   if (keep) keep[i] = (min_area == 0.0f || s > min_area) ? 1 : 0;
 }
 
+// image.hflip (BatchProviderBase.lua:22): out[r][x] = in[r][W-1-x] over the C*H rows; consecutive threads write consecutive floats
+__global__ void image_hflip_kernel(const float *__restrict__ in, size_t rows, int W, float *__restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= rows * (size_t)W) return;
+  const size_t r = t / W;
+  const int x = (int)(t - r * W);
+  out[t] = in[r * W + (W - 1 - x)];
+}
+
+// utils.flipBoxes (utils.lua:151-155) in its operation order, each step rounded to fp32: x1' = ((-x2) + W) + 1, x2' = ((-x1) + W) + 1
+__device__ __forceinline__ float flip_x(float x, float im_w) { return __fadd_rn(__fadd_rn(-x, im_w), 1.0f); }
+
+__global__ void flip_boxes_kernel(const float *__restrict__ boxes, int n, float im_w, float *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float x1 = boxes[4 * (size_t)i], y1 = boxes[4 * (size_t)i + 1], x2 = boxes[4 * (size_t)i + 2], y2 = boxes[4 * (size_t)i + 3];
+  float *o = out + 4 * (size_t)i;
+  o[0] = flip_x(x2, im_w); o[1] = y1; o[2] = flip_x(x1, im_w); o[3] = y2;
+}
+
 }  // namespace mpn
 
 using namespace mpn;
+
+extern "C" int mpn_image_hflip(const float *d_in, int C, int H, int W, float *d_out, void *stream) {
+  MPN_CHECK_ARG(d_in && d_out && d_in != d_out && C > 0 && H > 0 && W > 0);
+  const size_t rows = (size_t)C * H;
+  hipLaunchKernelGGL(image_hflip_kernel, dim3((unsigned)cdiv_sz(rows * W, 256)), dim3(256), 0, as_stream(stream), d_in, rows, W, d_out);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+extern "C" int mpn_flip_boxes(const float *d_boxes, int n, int image_width, float *d_out, void *stream) {
+  MPN_CHECK_ARG(n >= 0 && image_width > 0);
+  if (n == 0) return MPN_OK;
+  MPN_CHECK_ARG(d_boxes && d_out);
+  hipLaunchKernelGGL(flip_boxes_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), d_boxes, n, (float)image_width, d_out);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
 
 extern "C" int mpn_image_scale(const float *d_in, int C, int H, int W, int H2, int W2, float *d_tmp, float *d_out, void *stream) {
   MPN_CHECK_ARG(d_in && d_tmp && d_out && C > 0 && H > 0 && W > 0 && H2 > 0 && W2 > 0);

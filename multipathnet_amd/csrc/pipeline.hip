@@ -77,6 +77,29 @@ __global__ void head_decode_kernel(const float *__restrict__ head, int ld, int c
   o[0] = o0; o[1] = o1; o[2] = o2; o[3] = o3;
 }
 
+// Horizontal-flip test-time augmentation, the merge (include/mpn.h mpn_frcnn_set_augment): one thread per (roi, class).
+// sA / bA: the upright half's tables; s_io / b_io: the mirrored half's on entry, the merged ones on return.  The mirrored boxes are
+// flipped back as utils.flipBoxes does ((-x) + W) + 1, then (a + b) * 0.5f, then head_decode_kernel's clamp; every step rounded on its own.
+__global__ void augment_merge_kernel(const float *__restrict__ sA, const float *__restrict__ bA, float *__restrict__ s_io,
+                                     float *__restrict__ b_io, int M, int C, int clamp, float im_w, float im_h) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)M * C) return;
+  s_io[t] = __fmul_rn(__fadd_rn(sA[t], s_io[t]), 0.5f);
+  const float *a = bA + 4 * t;
+  float *b = b_io + 4 * t;
+  const float b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+  const float f0 = __fadd_rn(__fadd_rn(-b2, im_w), 1.0f), f2 = __fadd_rn(__fadd_rn(-b0, im_w), 1.0f);
+  float o0 = __fmul_rn(__fadd_rn(a[0], f0), 0.5f), o1 = __fmul_rn(__fadd_rn(a[1], b1), 0.5f);
+  float o2 = __fmul_rn(__fadd_rn(a[2], f2), 0.5f), o3 = __fmul_rn(__fadd_rn(a[3], b3), 0.5f);
+  if (clamp) {
+    o0 = o0 < 1.0f ? 1.0f : (o0 > im_w ? im_w : o0);
+    o2 = o2 < 1.0f ? 1.0f : (o2 > im_w ? im_w : o2);
+    o1 = o1 < 1.0f ? 1.0f : (o1 > im_h ? im_h : o1);
+    o3 = o3 < 1.0f ? 1.0f : (o3 > im_h ? im_h : o3);
+  }
+  b[0] = o0; b[1] = o1; b[2] = o2; b[3] = o3;
+}
+
 // integral eval head (model_utils.lua:296-313): K classifiers -> softmax each -> mean over K.
 // logits [M, K*C] row-major; one wave per row; sum over k in k order, then * (1/K) like nn.Mean.
 __global__ __launch_bounds__(256) void integral_softmax_mean_kernel(const float *__restrict__ logits, int M, int K, int C,
@@ -355,6 +378,15 @@ struct mpn_frcnn {
   double ms_scales[MPN_MAX_SCALES] = {};        // s_l of the cached maps
   int ms_src[MPN_MAX_SCALES] = {};              // the level whose map level l uses (an earlier level with the same scale, or l)
   int ms_h0 = -1, ms_w0 = -1;                   // original image size of the cached maps (-1: none)
+  // ---- horizontal-flip test-time augmentation (mpn_frcnn_set_augment)
+  int augment = 0;
+  float *aug_img = nullptr;                     // the mirrored ORIGINAL image (grown on demand: an image that getImages scales down may exceed max_h x max_w)
+  size_t aug_img_bytes = 0;
+  float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
+  float *aug_feat = nullptr, *aug_pm = nullptr; // plain Fast R-CNN handles: the mirrored image's final map (C8P) and its pixel-major copy, cached beside the upright one
+  Act aug_act = Act{};
+  int aug_h = -1, aug_w = -1;                   // network-input size of the cached mirrored map (-1: none)
+  bool aug_pm_valid = false;
   // optional per-kernel-group timing with HIP events recorded on the launch stream
   bool prof = false;
   std::vector<hipEvent_t> ev_pool;
@@ -457,6 +489,7 @@ extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   if (p->scale_tmp) (void)hipFree(p->scale_tmp);
   if (p->ms_feat) (void)hipFree(p->ms_feat);
   if (p->ms_pm) (void)hipFree(p->ms_pm);
+  for (float *q : {p->aug_img, p->aug_boxes, p->aug_scores, p->aug_bbox, p->aug_feat, p->aug_pm}) if (q) (void)hipFree(q);
   if (p->dbg) (void)hipFree(p->dbg);
   for (int i = 0; i < 4; ++i) if (p->sh_buf[i]) (void)hipFree(p->sh_buf[i]);
   delete p;
@@ -1108,7 +1141,10 @@ static int run_pyramid_trunk(mpn_frcnn *p, const float *d_image, int H0, int W0,
 
 // d_image == nullptr: recompute_features = false (ImageDetect.lua:107-111) — reuse the trunk output of the last
 // call on this handle (iterative localisation, Tester_FRCNN.lua:82-89) and run only the ROI head on new boxes.
-static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp = 1) {
+// mirrored: the second half of an augmented detect on a plain Fast R-CNN handle (run_detect_aug) — the trunk's final map goes to
+// p->aug_feat and is cached there, the upright map and its pixel-major copy stay as they are.
+static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp = 1,
+                      bool mirrored = false) {
   const mpn_frcnn_config &c = p->cfg;
   MPN_CHECK_ARG(p && d_boxes);
   p->seg_shape[0][0] = -1;  // SEG_HEAD: the host-side state a captured head graph relies on is being rewritten (run_segment re-stamps it after its body)
@@ -1142,11 +1178,22 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
     if (p->rn) {
       ProfScope ps(p, MPN_PROF_CONV_DIRECT, s);
       rc = resnet_trunk_forward(p->rn, img, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, s);
+    } else if (mirrored) {
+      const Act upright = p->tap_act[0];
+      const bool upright_pm = p->feat_pm_valid;
+      p->aug_h = p->aug_w = -1;
+      rc = run_trunk(p, img, H, W, s, &feat, 0, 0, p->aug_feat);
+      p->tap_act[0] = upright; p->feat_pm_valid = upright_pm;
+      if (rc == MPN_OK) { p->aug_act = feat; p->aug_h = H; p->aug_w = W; p->aug_pm_valid = false; }
     } else {
+      p->aug_h = p->aug_w = -1;  // a new upright map: the mirrored one of the last image no longer goes with it
       rc = run_trunk(p, img, H, W, s, &feat);
     }
   } else if (p->rn) {
     if (!resnet_has_features(p->rn, H, W)) { set_error("run_detect: no cached features for a %dx%d image", H0, W0); return MPN_ESTATE; }
+  } else if (mirrored) {
+    if (p->aug_h != H || p->aug_w != W || p->last_h != H || p->last_w != W) { set_error("run_detect: no cached mirrored features for a %dx%d image", H0, W0); return MPN_ESTATE; }
+    feat = p->aug_act;
   } else {
     if (p->last_h != H || p->last_w != W || !p->tap_act[0].p) { set_error("run_detect: no cached features for a %dx%d image", H0, W0); return MPN_ESTATE; }
     feat = p->tap_act[0];
@@ -1220,8 +1267,10 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
       rc = roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, nullptr, s, 5, 0,
                        LevelStack{p->ms_slot, p->n_scales});
     } else if (p->feat_pm && g_roi_pool_pm) {
-      if (!p->feat_pm_valid) { rc = c8p_to_pixel_major(feat, p->feat_pm, s); if (rc) return rc; p->feat_pm_valid = true; }  // once per trunk run
-      rc = roi_pool_pm(feat, p->feat_pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, s);
+      float *const pm = mirrored ? p->aug_pm : p->feat_pm;
+      bool &pm_valid = mirrored ? p->aug_pm_valid : p->feat_pm_valid;
+      if (!pm_valid) { rc = c8p_to_pixel_major(feat, pm, s); if (rc) return rc; pm_valid = true; }  // once per trunk run
+      rc = roi_pool_pm(feat, pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, s);
     } else {
       rc = roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, nullptr, s);
     } }
@@ -1265,13 +1314,59 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
   return MPN_OK;
 }
 
+// Horizontal-flip test-time augmentation around run_detect (include/mpn.h mpn_frcnn_set_augment): the upright
+// half unclamped with its tables kept aside, the mirrored half (the ORIGINAL image mirrored in front of getImages, flipBoxes of the
+// boxes) unclamped, then one merge launch that leaves the merged tables where every later stage reads them (p->scores / p->bbox).
+// Plain Fast R-CNN handles keep both final maps cached, so d_image == nullptr runs both heads on them; the other handle kinds run
+// two whole passes and keep the mirrored map only.  All of it is stream work on library-owned buffers: it captures into a head graph.
+static int run_detect_aug(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp) {
+  if (!p->augment) return run_detect(p, d_image, H0, W0, d_boxes, N, s, clamp);
+  const int C = p->cfg.n_classes;
+  const bool two_maps = p->aug_feat != nullptr;
+  if (!d_image && !two_maps) {
+    set_error("run_detect: augmentation on a %s handle keeps one trunk map, so a detect on cached features has no upright map to read: pass the image",
+              p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)");
+    return MPN_EINVAL;
+  }
+  MPN_CHECK_ARG(d_boxes && H0 > 0 && W0 > 0 && N > 0 && N <= p->cfg.max_rois);
+  if (d_image) {
+    const size_t need = (size_t)3 * H0 * W0 * sizeof(float);
+    if (need > p->aug_img_bytes) {
+      MPN_CHECK_HIP(hipStreamSynchronize(s));
+      bump_alloc_generation();  // BEFORE the free (grow_scaled)
+      if (p->aug_img) (void)hipFree(p->aug_img);
+      p->aug_img = nullptr; p->aug_img_bytes = 0;
+      MPN_CHECK_HIP(hipMalloc(&p->aug_img, need));
+      p->aug_img_bytes = need;
+    }
+  }
+  int rc = run_detect(p, d_image, H0, W0, d_boxes, N, s, 0);
+  if (rc) return rc;
+  MPN_CHECK_HIP(hipMemcpyAsync(p->aug_scores, p->scores, (size_t)N * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(p->aug_bbox, p->bbox, (size_t)N * 4 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (d_image) {
+    ProfScope ps(p, MPN_PROF_TRANSFORM, s);
+    rc = mpn_image_hflip(d_image, 3, H0, W0, p->aug_img, s);
+    if (rc) return rc;
+  }
+  rc = mpn_flip_boxes(d_boxes, N, W0, p->aug_boxes, s);
+  if (rc) return rc;
+  rc = run_detect(p, d_image ? p->aug_img : nullptr, H0, W0, p->aug_boxes, N, s, 0, two_maps);
+  if (rc) return rc;
+  ProfScope ps(p, MPN_PROF_POST, s);
+  hipLaunchKernelGGL(augment_merge_kernel, dim3((unsigned)cdiv_sz((size_t)N * C, 256)), dim3(256), 0, s, p->aug_scores, p->aug_bbox, p->scores,
+                     p->bbox, N, C, clamp, (float)W0, (float)H0);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
 extern "C" int mpn_frcnn_detect(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N,
                                 float *d_scores, float *d_bbox, int clamp, void *stream) {
   MPN_CHECK_ARG(p != nullptr);
   ScratchScope scratch_scope(&p->scratch);
   { int rcf = mpn_frcnn_flush(p, stream); if (rcf) return rcf; }  // a pipelined predecessor's side-stream work may still use the head buffers
   hipStream_t s = as_stream(stream);
-  int rc = run_detect(p, d_image, H, W, d_boxes, N, s, clamp ? 1 : 0);
+  int rc = run_detect_aug(p, d_image, H, W, d_boxes, N, s, clamp ? 1 : 0);
   if (rc) return rc;
   const int C = p->cfg.n_classes;
   if (d_scores) MPN_CHECK_HIP(hipMemcpyAsync(d_scores, p->scores, (size_t)N * C * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1410,7 +1505,7 @@ static int run_tail(mpn_frcnn *p, int N, float *d_dets, int top_cap, int *d_n_de
 // boxes with recompute_features = false (NOT clamped: only the first bbox_pred is); the rows of all passes are concatenated
 // before the per-class NMS.  opt.test_use_rbox_scores (:91-97): the scores of pass i+1 go with the boxes of pass i.
 static int run_detect_iter(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, hipStream_t s, int *n_rows) {
-  int rc = run_detect(p, d_image, H, W, d_boxes, N, s, 1);
+  int rc = run_detect_aug(p, d_image, H, W, d_boxes, N, s, 1);
   *n_rows = N;
   const mpn_frcnn_config &c = p->cfg;
   if (rc || c.num_iter <= 1) return rc;
@@ -1424,7 +1519,7 @@ static int run_detect_iter(mpn_frcnn *p, const float *d_image, int H, int W, con
     if (it == c.num_iter) break;
     rc = mpn_select_boxes_forward(p->scores, p->bbox, N, C, p->it_boxes, s);
     if (rc) return rc;
-    rc = run_detect(p, nullptr, H, W, p->it_boxes, N, s, 0);
+    rc = run_detect_aug(p, nullptr, H, W, p->it_boxes, N, s, 0);
     if (rc) return rc;
   }
   *n_rows = (rbox ? c.num_iter - 1 : c.num_iter) * N;
@@ -1493,7 +1588,7 @@ extern "C" int mpn_frcnn_test_one(mpn_frcnn *p, const float *d_image, int H, int
 // The three steps take caller-provided records so that the exchange between them can be any transport; mpn_frcnn_test_one_sharded
 // chains them over an mpn_comm (RCCL all-gather, comm.hip).
 static int shard_passes(const mpn_frcnn_config &c) { return c.num_iter > 1 ? (c.use_rbox_scores ? c.num_iter - 1 : c.num_iter) : 1; }
-static int refuse_pyramid(const mpn_frcnn *p, const char *form);
+static int refuse_multi_pass(const mpn_frcnn *p, const char *form);
 
 extern "C" int mpn_shard_range(int n, int world, int rank, int *lo, int *hi) {
   MPN_CHECK_ARG(n >= 0 && world >= 1 && rank >= 0 && rank < world && lo && hi);
@@ -1516,7 +1611,7 @@ extern "C" size_t mpn_frcnn_shard_class_floats(const mpn_frcnn *p, int N, int wo
 extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, int rank, int world,
                                     float *d_rows_rec, void *stream) {
   MPN_CHECK_ARG(p != nullptr && d_boxes && d_rows_rec && N > 0 && N <= p->cfg.max_rois && world >= 1 && rank >= 0 && rank < world);
-  if (int rp = refuse_pyramid(p, "mpn_frcnn_shard_head")) return rp;
+  if (int rp = refuse_multi_pass(p, "mpn_frcnn_shard_head")) return rp;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   int rc = mpn_frcnn_flush(p, stream);
@@ -1620,7 +1715,7 @@ static int shard_buf(mpn_frcnn *p, int i, size_t floats, hipStream_t s) {
 extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const float *d_image, int H, int W, const float *d_boxes, int N,
                                           float *d_dets, int top_cap, int *d_n_dets, void *stream) {
   MPN_CHECK_ARG(p != nullptr && comm != nullptr && N > 0);
-  if (int rp = refuse_pyramid(p, "mpn_frcnn_test_one_sharded")) return rp;
+  if (int rp = refuse_multi_pass(p, "mpn_frcnn_test_one_sharded")) return rp;
   hipStream_t s = as_stream(stream);
   const int world = mpn_comm_world(comm), rank = mpn_comm_rank(comm);
   MPN_CHECK_ARG(world >= 1 && rank >= 0);
@@ -1642,8 +1737,13 @@ extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const fl
 // image i on `stream`; NMS + top-k of image i on the pipeline's side stream, overlapping image
 // i+1's MFMA kernels (they are latency-bound on ~20 CUs).  d_dets / d_n_dets of call i are ordered on `stream`
 // only after call i+1 returns or after mpn_frcnn_flush(); the caller alternates two output buffers.
-// the throughput and sharded forms run single-scale only (include/mpn.h mpn_frcnn_set_scales)
-static int refuse_pyramid(const mpn_frcnn *p, const char *form) {
+// the throughput and sharded forms run one trunk pass per image only: single-scale (include/mpn.h mpn_frcnn_set_scales), no flip
+// augmentation (mpn_frcnn_set_augment)
+static int refuse_multi_pass(const mpn_frcnn *p, const char *form) {
+  if (p->augment) {
+    set_error("%s: not supported with horizontal-flip augmentation (mpn_frcnn_set_augment): use mpn_frcnn_test_one", form);
+    return MPN_EINVAL;
+  }
   if (p->n_scales <= 1) return MPN_OK;
   set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales): use mpn_frcnn_test_one", form, p->n_scales);
   return MPN_EINVAL;
@@ -1652,7 +1752,7 @@ static int refuse_pyramid(const mpn_frcnn *p, const char *form) {
 static int pipelined_impl(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, float *d_dets, int top_cap, int *d_n_dets,
                           void *stream, bool stable_ptrs) {
   MPN_CHECK_ARG(p != nullptr && d_n_dets && (top_cap == 0 || d_dets) && top_cap >= 0);
-  if (int rp = refuse_pyramid(p, "mpn_frcnn_test_one_pipelined")) return rp;
+  if (int rp = refuse_multi_pass(p, "mpn_frcnn_test_one_pipelined")) return rp;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   const int b = (int)(p->seq & 1);
@@ -1702,7 +1802,7 @@ extern "C" int mpn_frcnn_test_one_pipelined(mpn_frcnn *p, const float *d_image, 
 extern "C" int mpn_frcnn_test_one_pipelined_host(mpn_frcnn *p, const float *h_image, int H, int W, const float *h_boxes, int N,
                                                  float *d_dets, int top_cap, int *d_n_dets, void *stream) {
   MPN_CHECK_ARG(p != nullptr && h_image && h_boxes && H > 0 && W > 0 && N > 0 && N <= p->cfg.max_rois);
-  if (int rp = refuse_pyramid(p, "mpn_frcnn_test_one_pipelined_host")) return rp;
+  if (int rp = refuse_multi_pass(p, "mpn_frcnn_test_one_pipelined_host")) return rp;
   hipStream_t s = as_stream(stream);
   const size_t img_n = (size_t)3 * H * W;
   if (!p->copy) {  // first use: copy stream, events, the two box staging buffers
@@ -1778,6 +1878,24 @@ extern "C" int mpn_frcnn_set_graphs(mpn_frcnn *p, int enable) {
   return MPN_OK;
 }
 
+// a setter that changes what a detect computes: every captured launch graph and every cached trunk map of the handle goes
+static int drop_graphs_and_features(mpn_frcnn *p) {
+  MPN_CHECK_HIP(hipDeviceSynchronize());  // no replay or cached map of the old setting may still be in flight
+  for (auto &kv : p->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+  p->graphs.clear();
+  for (int k = 0; k < 4; ++k) {
+    p->unseen_next[k] = 0;
+    for (int q = 0; q < mpn_frcnn::kUnseen; ++q) p->unseen_valid[k][q] = false;
+    for (int j = 0; j < 4; ++j) p->seg_shape[k][j] = -1;
+  }
+  p->tap_act[0] = Act{};  // cached trunk output: gone (the next detect must pass an image)
+  p->ms_h0 = p->ms_w0 = -1;
+  p->feat_pm_valid = false;
+  p->aug_h = p->aug_w = -1;
+  p->aug_pm_valid = false;
+  return MPN_OK;
+}
+
 extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_targets) {
   if (n_scales < 0 || n_scales > MPN_MAX_SCALES || (n_scales > 0 && !h_targets)) {
     set_error("mpn_frcnn_set_scales: n_scales %d outside 0..MPN_MAX_SCALES (%d) or no targets", n_scales, MPN_MAX_SCALES);
@@ -1791,17 +1909,12 @@ extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_
               p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)");
     return MPN_EINVAL;
   }
-  MPN_CHECK_HIP(hipDeviceSynchronize());  // no replay or cached map of the old setting may still be in flight
-  for (auto &kv : p->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-  p->graphs.clear();
-  for (int k = 0; k < 4; ++k) {
-    p->unseen_next[k] = 0;
-    for (int q = 0; q < mpn_frcnn::kUnseen; ++q) p->unseen_valid[k][q] = false;
-    for (int j = 0; j < 4; ++j) p->seg_shape[k][j] = -1;
+  if (n_scales > 1 && p->augment) {
+    set_error("mpn_frcnn_set_scales: an image pyramid (%d scales) and horizontal-flip augmentation exclude each other: call mpn_frcnn_set_augment(p, 0) first", n_scales);
+    return MPN_EINVAL;
   }
-  p->tap_act[0] = Act{};  // cached trunk output: gone (the next detect must pass an image)
-  p->ms_h0 = p->ms_w0 = -1;
-  p->feat_pm_valid = false;
+  int rc_drop = drop_graphs_and_features(p);
+  if (rc_drop) return rc_drop;
   if (n_scales <= 1) {
     p->n_scales = 0;
     p->cfg.scale_target = n_scales == 1 ? h_targets[0] : p->create_scale_target;
@@ -1823,6 +1936,50 @@ extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_
   }
   p->n_scales = n_scales;
   for (int l = 0; l < n_scales; ++l) p->scale_targets[l] = h_targets[l];
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_set_augment(mpn_frcnn *p, int enable) {
+  MPN_CHECK_ARG(p != nullptr);
+  const bool plain = !p->is_mpnet && !p->rn;
+  const char *kind = p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)";
+  if (enable && p->n_scales > 1) {
+    set_error("mpn_frcnn_set_augment: horizontal-flip augmentation and an image pyramid (mpn_frcnn_set_scales, %d scales) exclude each other: "
+              "restore a single scale first", p->n_scales);
+    return MPN_EINVAL;
+  }
+  if (enable && !plain && p->cfg.num_iter > 1) {
+    set_error("mpn_frcnn_set_augment: a %s handle keeps one trunk map, and iterative localisation (num_iter %d) under augmentation needs the "
+              "upright and the mirrored one cached (only mpn_frcnn_create handles hold both): create the handle with num_iter 1", kind, p->cfg.num_iter);
+    return MPN_EINVAL;
+  }
+  int rc = drop_graphs_and_features(p);
+  if (rc) return rc;
+  if (p->rn) resnet_drop_features(p->rn);
+  p->augment = 0;
+  if (!enable) return MPN_OK;
+  if (!p->aug_scores) {  // first use: the second half's buffers, sized for max_rois rows and the max_h x max_w geometry
+    const size_t M = (size_t)p->cfg.max_rois, C = (size_t)p->cfg.n_classes;
+    const size_t img_bytes = (size_t)3 * p->cfg.max_h * p->cfg.max_w * sizeof(float);
+    bump_alloc_generation();
+    for (float **q : {&p->aug_img, &p->aug_boxes, &p->aug_bbox, &p->aug_feat, &p->aug_pm}) if (*q) { (void)hipFree(*q); *q = nullptr; }  // (an earlier attempt that ran out of memory)
+    p->aug_img_bytes = 0;
+    MPN_CHECK_HIP(hipMalloc(&p->aug_img, img_bytes));
+    p->aug_img_bytes = img_bytes;
+    MPN_CHECK_HIP(hipMalloc(&p->aug_boxes, M * 4 * sizeof(float)));
+    MPN_CHECK_HIP(hipMalloc(&p->aug_bbox, M * 4 * C * sizeof(float)));
+    if (plain) {
+      int fh = p->cfg.max_h, fw = p->cfg.max_w;
+      for (auto &L : p->conv) if (L.pool) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+      const size_t feat_bytes = act_bytes(p->feat_c, fh, fw), pm_bytes = pixel_major_elems(make_act(nullptr, p->feat_c, fh, fw)) * sizeof(float);
+      MPN_CHECK_HIP(hipMalloc(&p->aug_feat, feat_bytes));
+      MPN_CHECK_HIP(hipMemset(p->aug_feat, 0, feat_bytes));
+      MPN_CHECK_HIP(hipMalloc(&p->aug_pm, pm_bytes));
+      MPN_CHECK_HIP(hipMemset(p->aug_pm, 0, pm_bytes));
+    }
+    MPN_CHECK_HIP(hipMalloc(&p->aug_scores, M * C * sizeof(float)));  // last: its presence says that all of them exist
+  }
+  p->augment = 1;
   return MPN_OK;
 }
 

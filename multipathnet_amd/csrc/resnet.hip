@@ -3109,6 +3109,7 @@ int resnet_feat_channels(const ResNetGraph *g) { return g->feat_c; }
 int resnet_out_channels(const ResNetGraph *g) { return g->out_c; }
 int resnet_n_heads(const ResNetGraph *g) { return (int)g->heads.size(); }
 bool resnet_has_features(const ResNetGraph *g, int H, int W) { return g->feat && g->last_h == H && g->last_w == W; }
+void resnet_drop_features(ResNetGraph *g) { g->last_h = g->last_w = -1; }
 
 // ---- op-list graphs ----------------------------------------------------------------------------------------------------
 static void gop_out_dims(const GOp &op, int h, int w, int &oh, int &ow) {

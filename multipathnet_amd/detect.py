@@ -56,6 +56,11 @@ class Tester_FRCNN(object):
         self.test_bbox_voting = opt.get("test_bbox_voting", False)
         self.test_bbox_voting_score_pow = opt.get("test_bbox_voting_score_pow", 1)
         self.test_use_rbox_scores = opt.get("test_use_rbox_scores", False)
+        # opt.test_augment (run_test.lua:39): horizontal-flip augmentation runs inside the module's device pipeline;
+        # detect() then returns the merged tables, which is all testOne needs
+        self.test_augment = bool(opt.get("test_augment", getattr(module, "augment", False)))
+        if self.test_augment != bool(getattr(module, "augment", False)):
+            module.set_augment(self.test_augment)
         self.num_classes = module.n_classes - 1
         self.thresh = -1.5  # Tester_FRCNN.lua:50
         self.boxselect = SelectBoxes()

@@ -147,6 +147,11 @@ local function set_pyramid(self, opt)
       check(C.mpn_frcnn_set_scales(self.handle, #opt.scale, t), 'mpn_frcnn_set_scales')
    end
 end
+-- opt.test_augment (run_test.lua:39): horizontal-flip test-time augmentation inside detect / testOne (DESIGN.md section 12).  After
+-- set_pyramid: the two exclude each other, and the setter called second says so
+local function set_augment(self, opt)
+   if opt.test_augment then check(C.mpn_frcnn_set_augment(self.handle, 1), 'mpn_frcnn_set_augment') end
+end
 -- classAndBBoxLinear (model_utils.lua:105-119) [+ utils.integral's K classifier clones, model_utils.lua:275-317] -> (cls weight, cls bias,
 -- bbox Linear, BBoxNorm or nil, K); the K clones are stacked into one [K*C, in] matrix, which is what the C ABI takes
 local function heads_of(heads)
@@ -189,6 +194,7 @@ function FastRCNN:__init(model, opt)
                             cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_frcnn_create')
    finish(self, h, cfg, {cout, pl, cls_w, cls_b})
    set_pyramid(self, opt)
+   set_augment(self, opt)
 end
 
 -- models/multipathnet.lua:30-120 — the namesake model.  model = nn.Sequential{
@@ -243,6 +249,7 @@ function mpn.MultiPathNet(model, opt)
    check(C.mpn_mpnet_create(cfg, wp, bp, mw, cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_mpnet_create')
    finish(self, h, cfg, keep)
    set_pyramid(self, opt)
+   set_augment(self, opt)
    return self
 end
 
@@ -315,6 +322,7 @@ function mpn.ResNet(model, opt)
    keep[#keep + 1] = {wp, bp, a_cin, a_co, a_ks, a_st, a_pd, a_bn, a_bs}
    finish(self, h, cfg, keep)
    set_pyramid(self, opt)
+   set_augment(self, opt)
    return self
 end
 
@@ -425,6 +433,7 @@ function mpn.Graph(model, opt)
    check(C.mpn_graph_create(cfg, gw, cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_graph_create')
    finish(self, h, cfg, keep)
    set_pyramid(self, opt)
+   set_augment(self, opt)
    return self
 end
 mpn.ROSS, mpn.IMAGENET = ROSS, IMAGENET

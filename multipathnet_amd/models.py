@@ -491,13 +491,14 @@ class FastRCNN(object):
 
     def __init__(self, params, cfg=VGG16_CFG, pooled=7, spatial_scale=1.0 / 16, transformer=None, max_h=600, max_w=1000,
                  max_rois=1000, nms_thresh=0.3, score_thresh=-1.5, top_k=100, num_iter=1, bbox_voting=False, bbox_vote_thresh=0.5,
-                 bbox_vote_score_pow=1.0, scale=None, max_size=None, bf16=False, use_rbox_scores=False, roi_bin_rule=0, fc_arith=None):
+                 bbox_vote_score_pow=1.0, scale=None, max_size=None, bf16=False, use_rbox_scores=False, roi_bin_rule=0, fc_arith=None, augment=False):
         """scale / max_size: getImages' rescaling (ImageDetect.lua:34-43) on the device; None feeds images as they are.  `scale` may be
         the reference's scale TABLE: a one-entry list is the scalar, more entries are the image pyramid of multi-scale testing
         (set_scales; plain VGG Fast R-CNN only, include/mpn.h mpn_frcnn_set_scales).
         roi_bin_rule: 0 = inn.ROIPooling's CUDA-branch bins, 1 = its CPU branch (crop + SpatialAdaptiveMaxPooling), include/mpn.h MPN_ROI_BINS_*.
         num_iter / bbox_voting / use_rbox_scores: opt.test_num_iterative_loc / test_bbox_voting / test_use_rbox_scores
-        (Tester_FRCNN.lua:82-99,118-124) inside the fused test_one."""
+        (Tester_FRCNN.lua:82-99,118-124) inside the fused test_one.
+        augment: opt.test_augment, horizontal-flip test-time augmentation inside detect / test_one (set_augment)."""
         _lib.require_gpu()
         lib = _lib.load()
         self.is_resnet = "trunk_blocks" in params
@@ -549,6 +550,7 @@ class FastRCNN(object):
         self.fc_arith = c.fc_arith
         self.scale, self.max_size = scale, max_size
         self.scales, self._create_scales = scales, scales[:1]  # the scale table the device runs; the creation-time single scale
+        self.augment, self._want_augment = False, bool(augment)
         self._cfg = c
         dev = torch.device("cuda", torch.cuda.current_device())
         d = lambda t: t.to(dev, torch.float32).contiguous()
@@ -662,6 +664,8 @@ class FastRCNN(object):
         self._pipe_seq = 0
         if len(self.scales) > 1:
             self.set_scales(self.scales)
+        if self._want_augment:
+            self.set_augment(True)
 
     def set_scales(self, targets):
         """getImages' scale table (ImageDetect.lua:22-52) on the device (mpn_frcnn_set_scales): [] restores the creation-time single scale,
@@ -670,6 +674,14 @@ class FastRCNN(object):
         t = [float(x) for x in targets]
         check(self._lib.mpn_frcnn_set_scales(self._h, len(t), (C.c_double * max(1, len(t)))(*t)), "mpn_frcnn_set_scales")
         self.scales = t if t else list(self._create_scales)
+
+    def set_augment(self, on):
+        """opt.test_augment on the device (mpn_frcnn_set_augment): detect / test_one run the image and its mirror and merge the two — mean
+        of the scores, mean of the boxes with the mirrored half flipped back.  Drops the handle's captured graphs
+        and cached features.  Not with an image pyramid, the pipelined / host-fed / sharded forms, or num_iter > 1 on the
+        MultiPathNet / ResNet / op-list handles."""
+        check(self._lib.mpn_frcnn_set_augment(self._h, int(bool(on))), "mpn_frcnn_set_augment")
+        self.augment = bool(on)
 
     def close(self):
         """mpn_frcnn_destroy now (streams, events, buffers) instead of at garbage collection: a process holds a few HIP hardware queues, and

@@ -15,6 +15,7 @@ Reference classes mirrored (file:line relative to /root/reference):
   nn.SoftMax / nn.Linear / cudnn.SpatialConvolution(3x3) / nn.SpatialMaxPooling(2,2,2,2):ceil() / nn.ReLU
                             — external nn/cudnn rocks, used by models/vgg.lua:14-31
   nn.ModeSwitch             — modules/ModeSwitch.lua (graph semantics only: evaluate -> branch 2)
+  image.hflip               — external `image` rock; call site BatchProviderBase.lua:22 (hflip)
 """
 import ctypes as C
 
@@ -41,6 +42,16 @@ def _i(t):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def hflip(image):
+    """image.hflip (BatchProviderBase.lua:22): image [C,H,W] (device) -> a new tensor with every row mirrored (mpn_image_hflip)."""
+    assert image.dim() == 3
+    out = torch.empty_like(image)
+    if image.numel():
+        Cc, H, W = image.shape
+        check(_lib.load().mpn_image_hflip(_f(image, "image"), Cc, H, W, _f(out), _stream()), "hflip")
+    return out
 
 
 class Module(object):

@@ -6,6 +6,7 @@
   utils.convertFrom             utils.lua:212-248
   utils.keep_top_k              utils.lua:75-96
   utils.joinTable               utils.lua:46-71
+  utils.flipBoxes               utils.lua:151-155
 """
 import ctypes as C
 
@@ -103,6 +104,18 @@ def decode_all_classes(boxes, deltas):
         check(_lib.load().mpn_bbox_decode(_f(boxes), _f(deltas), deltas.size(0), deltas.size(1) // 4, _f(res), _stream()),
               "convertFrom")
     return res
+
+
+def flipBoxes(boxes, image_width):
+    """utils.flipBoxes(boxes [N,4+], image_width) (utils.lua:151-155) -> a clone with x1 = -x2 + W + 1, x2 = -x1 + W + 1."""
+    flipped = boxes.clone()
+    if boxes.size(0):
+        b4 = boxes[:, :4].contiguous()
+        out = torch.empty_like(b4)
+        check(_lib.load().mpn_flip_boxes(_f(b4, "boxes"), b4.size(0), int(image_width), _f(out), _stream()), "flipBoxes")
+        flipped[:, 0] = out[:, 0]
+        flipped[:, 2] = out[:, 2]
+    return flipped
 
 
 def joinTable(input, dim=0):
