@@ -20,6 +20,18 @@ static std::atomic<unsigned long long> g_alloc_gen{1};
 unsigned long long alloc_generation() { return g_alloc_gen.load(std::memory_order_relaxed); }
 void bump_alloc_generation() { g_alloc_gen.fetch_add(1, std::memory_order_relaxed); }
 
+int grow_device_buffer(void **ptr, size_t *bytes, size_t need, hipStream_t s, bool zero) {
+  if (need <= *bytes) return MPN_OK;  // grows monotonically; steady state allocates nothing
+  MPN_CHECK_HIP(hipStreamSynchronize(s));
+  bump_alloc_generation();  // captured launch graphs hold the old pointer
+  if (*ptr) (void)hipFree(*ptr);
+  *ptr = nullptr; *bytes = 0;
+  MPN_CHECK_HIP(hipMalloc(ptr, need));
+  *bytes = need;
+  if (zero) MPN_CHECK_HIP(hipMemsetAsync(*ptr, 0, need, s));
+  return MPN_OK;
+}
+
 void Scratch::release() {
   for (int i = 0; i < SCR_NSLOTS; ++i) {
     if (buf[i]) (void)hipFree(buf[i]);
@@ -49,17 +61,9 @@ static int scratch_get_impl(ScratchSlot slot, size_t need, hipStream_t s, void *
     if (!e) { e = new Scratch(); e->device = dev; }
     sc = e;
   }
-  if (need > sc->bytes[slot]) {  // grows monotonically; steady state allocates nothing
-    MPN_CHECK_HIP(hipStreamSynchronize(s));
-    bump_alloc_generation();  // captured launch graphs hold the old pointer (bumped BEFORE the free: a failing hipMalloc must not leave them replayable)
-    if (sc->buf[slot]) (void)hipFree(sc->buf[slot]);
-    sc->buf[slot] = nullptr; sc->bytes[slot] = 0;
-    MPN_CHECK_HIP(hipMalloc(&sc->buf[slot], need));
-    sc->bytes[slot] = need;
-    if (zero) MPN_CHECK_HIP(hipMemsetAsync(sc->buf[slot], 0, need, s));
-  }
-  *out = sc->buf[slot];
-  return MPN_OK;
+  const int rc = grow_device_buffer(&sc->buf[slot], &sc->bytes[slot], need, s, zero);
+  if (rc == MPN_OK) *out = sc->buf[slot];
+  return rc;
 }
 
 int set_max_dyn_lds(const void *fn, int bytes) {

@@ -64,6 +64,10 @@ struct ScratchScope {
 // the generation it was captured under is still current.
 unsigned long long alloc_generation();
 void bump_alloc_generation();
+// THE grow-on-demand sequence of every library-owned device buffer.  need <= *bytes: nothing.  Otherwise, in this order: synchronise
+// `s` (the buffer's last user), bump the generation, free, null *ptr and *bytes, hipMalloc(need), set *bytes; `zero` clears the new
+// buffer on `s`.  The bump comes BEFORE the free: a hipMalloc that fails must not leave a captured graph able to replay a freed pointer.
+int grow_device_buffer(void **ptr, size_t *bytes, size_t need, hipStream_t s, bool zero = false);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): function attributes are per device.
 int set_max_dyn_lds(const void *fn, int bytes);
 int project_im_rois_copy(const float *d_boxes, int n, double scale, float *d_rois, float *d_boxes_copy, hipStream_t s);  // boxes.hip

@@ -251,16 +251,23 @@ struct mpn_frcnn {
   std::vector<int> cout, pool_after;
   std::vector<ConvLayer> conv;
   float *img_c8p = nullptr;
-  size_t act_total_bytes = 0;
   std::vector<std::pair<float *, size_t>> act_bufs;  // for re-zeroing when the image size changes
-  int last_h = -1, last_w = -1;
+  int last_h = -1, last_w = -1;                       // the (canvas) geometry the halos are laid for
   int feat_c = 0;
+  // One cached final trunk map (VGG trunks): what a detect on cached features pools from.  run_trunk fills the record it is handed and no other.
+  struct CachedMap {
+    Act act = Act{};           // the map
+    float *buf = nullptr;      // where the trunk writes it (nullptr: the last layer's own buffer)
+    float *pm = nullptr;       // its pixel-major copy (roi_pool_pm) ...
+    bool pm_valid = false;     // ... once the first pooling after a trunk run has built it
+    int h = -1, w = -1;        // network-input size of the image it was computed from (-1: none cached)
+    void invalidate() { act = Act{}; h = w = -1; pm_valid = false; }
+  };
+  CachedMap up, mir;           // of the upright image; of the mirrored one (plain Fast R-CNN handles under mpn_frcnn_set_augment: buf and pm exist)
   // head
   int K6 = 0, Mp = 0, n_head = 0;
   float *w6 = nullptr, *b6 = nullptr, *w7 = nullptr, *b7 = nullptr, *wh = nullptr, *bh = nullptr;
   float *rois = nullptr, *x6 = nullptr, *y6 = nullptr, *y7 = nullptr, *head = nullptr;
-  float *feat_pm = nullptr;   // pixel-major copy of the last trunk map (plain Fast R-CNN head: roi_pool_pm)
-  bool feat_pm_valid = false;
   float *scores = nullptr, *bbox = nullptr, *bbox_raw = nullptr;
   // NMS-stage buffers: two sets so that image i's NMS (side stream) overlaps image i+1's trunk
   float *scored_b[2] = {nullptr, nullptr}, *keep_b[2] = {nullptr, nullptr}, *thresh_b[2] = {nullptr, nullptr};
@@ -268,7 +275,6 @@ struct mpn_frcnn {
   float *it_scores = nullptr, *it_bbox = nullptr, *it_boxes = nullptr;  // iterative localisation: rows of both passes
   float *scaled = nullptr, *scale_tmp = nullptr;  // getImages' rescaled image (ImageDetect.lua:34-43), grown on demand
   size_t scaled_bytes = 0, scale_tmp_bytes = 0;
-  int net_h = 0, net_w = 0;                       // size of the image the trunk last saw
   int *counts_b[2] = {nullptr, nullptr}, *keep_idx_b[2] = {nullptr, nullptr}, *n_keep_b[2] = {nullptr, nullptr};
   float *scored = nullptr, *keep = nullptr, *thresh = nullptr;   // set of the most recent call
   int *counts = nullptr, *keep_idx = nullptr, *n_keep = nullptr;
@@ -287,7 +293,6 @@ struct mpn_frcnn {
   float *dbg = nullptr;
   size_t dbg_bytes = 0;
   int last_n = 0, last_rows = 0;
-  int fuse_pool = 1;
   // ---- MultiPathNet head (models/multipathnet.lua:64-120); empty for plain Fast R-CNN
   struct Tower { int region, use4, use3, total_feat; float *mix_w, *mix_b, *w6, *b6, *w7, *b7; unsigned short *w6_s3 = nullptr, *w7_s3 = nullptr; };
   bool is_mpnet = false;
@@ -298,7 +303,7 @@ struct mpn_frcnn {
   std::vector<Tower> towers;
   float *fov = nullptr, *tx = nullptr, *ty = nullptr, *tz6 = nullptr, *cat = nullptr, *cls_rm = nullptr, *bbox_rm = nullptr;
   float *wcls = nullptr, *bcls = nullptr, *wbbox = nullptr, *bbbox = nullptr;
-  Act tap_act[3];  // conv5, conv4, conv3 of the last trunk run
+  Act tap_act[3];  // [1], [2]: conv4, conv3 of the last trunk run ([0], conv5, is the upright record's map: up.act)
   float *vmax_tab[3] = {nullptr, nullptr, nullptr};  // vertical range-max tables of the three maps (MultiPathNet ROI pools)
   bool vmax_built[3] = {false, false, false};         // built for the current tap_act maps (per map: the pooling stream builds a map's tables where its first pooling is enqueued)
   bool vmax_pm = false;                               // ... in the pixel-major form
@@ -317,13 +322,13 @@ struct mpn_frcnn {
   hipStream_t pool_stream = nullptr;   // alias of `side` (never destroyed on its own); nullptr = no overlapped pooling (plain Fast R-CNN handles)
   bool pool_on_side = false;
   hipEvent_t ev_pool_done[3] = {nullptr, nullptr, nullptr}, ev_mix_done[3] = {nullptr, nullptr, nullptr}, ev_pool_go = nullptr;
+  unsigned short *w6_s3 = nullptr, *x6_s3 = nullptr;  // MPN_FC_SPLIT3: fc6's weights (packed once) and operand (per image) as three bf16 planes
+  unsigned short *w7_s3 = nullptr, *y6_s3 = nullptr;  // ... and fc7's
+  unsigned short *ty_s3[2] = {nullptr, nullptr}, *tz6_s3[2] = {nullptr, nullptr};  // MultiPathNet towers: the per-lane fc6 / fc7 operands as planes
   // two tower LANES (round 6): the towers of one image are independent until the concat (ModelParallelTable.lua:195-242 ran them on
   // different GPUs), so towers 1, 3 run on the handle's second tower stream with their own mix / fc6 buffers beside towers 0, 2, 4 on the
   // caller's stream: one lane's short-K mix GEMM (6.1 block rounds on 256 CUs, 40 stages per tile) and the prologue / epilogue of every
   // launch run under the other lane's fc6 / fc7 instead of leaving the matrix pipe idle.  Pure scheduling: bit-identical results.
-  unsigned short *w6_s3 = nullptr, *x6_s3 = nullptr;  // MPN_FC_SPLIT3: fc6's weights (packed once) and operand (per image) as three bf16 planes
-  unsigned short *w7_s3 = nullptr, *y6_s3 = nullptr;  // ... and fc7's
-  unsigned short *ty_s3[2] = {nullptr, nullptr}, *tz6_s3[2] = {nullptr, nullptr};  // MultiPathNet towers: the per-lane fc6 / fc7 operands as planes
   hipStream_t tower_stream = nullptr;
   hipEvent_t ev_lane_go = nullptr, ev_lane_done = nullptr;
   float *ty2 = nullptr, *tz6_2 = nullptr;
@@ -334,7 +339,7 @@ struct mpn_frcnn {
   hipStream_t copy = nullptr;
   static constexpr int kStage = 3;
   float *stage_img[kStage] = {}, *stage_boxes[kStage] = {};
-  size_t stage_cap[kStage] = {};
+  size_t stage_bytes[kStage] = {};
   hipEvent_t ev_up[kStage] = {}, ev_consumed[kStage] = {};
   bool used_pending[kStage] = {};
   unsigned long long up_seq = 0;
@@ -378,15 +383,12 @@ struct mpn_frcnn {
   double ms_scales[MPN_MAX_SCALES] = {};        // s_l of the cached maps
   int ms_src[MPN_MAX_SCALES] = {};              // the level whose map level l uses (an earlier level with the same scale, or l)
   int ms_h0 = -1, ms_w0 = -1;                   // original image size of the cached maps (-1: none)
+  bool ms_pm_valid = false;                     // the pixel-major copies go with the cached maps
   // ---- horizontal-flip test-time augmentation (mpn_frcnn_set_augment)
   int augment = 0;
   float *aug_img = nullptr;                     // the mirrored ORIGINAL image (grown on demand: an image that getImages scales down may exceed max_h x max_w)
   size_t aug_img_bytes = 0;
   float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
-  float *aug_feat = nullptr, *aug_pm = nullptr; // plain Fast R-CNN handles: the mirrored image's final map (C8P) and its pixel-major copy, cached beside the upright one
-  Act aug_act = Act{};
-  int aug_h = -1, aug_w = -1;                   // network-input size of the cached mirrored map (-1: none)
-  bool aug_pm_valid = false;
   // optional per-kernel-group timing with HIP events recorded on the launch stream
   bool prof = false;
   std::vector<hipEvent_t> ev_pool;
@@ -465,6 +467,29 @@ static int dev_alloc(mpn_frcnn *p, T **ptr, size_t bytes, bool zero) {
   return MPN_OK;
 }
 
+// the final trunk map's size for an h x w network input: halved (rounding up) at every pooling layer
+static void final_map_size(const mpn_frcnn *p, int *h, int *w) {
+  for (auto &L : p->conv) if (L.pool) { *h = (*h + 1) / 2; *w = (*w + 1) / 2; }
+}
+// getImages (ImageDetect.lua:34-43): s = target / min side, capped so that round(s * max side) <= cap (cap <= 0: none); the image is
+// resampled to (long)(H0 * s) x (long)(W0 * s), or kept as it is when s == 1.  Returns s.
+static double getimages_size(int H0, int W0, double target, double cap, int *H, int *W) {
+  const double sc = mpn_pick_scale(H0, W0, target, cap > 0.0 ? cap : 1e30);
+  *H = H0; *W = W0;
+  if (sc != 1.0) { *H = (int)((double)H0 * sc); *W = (int)((double)W0 * sc); }
+  return sc;
+}
+// localisation passes whose rows reach the NMS (Tester_FRCNN.lua:91-100: use_rbox_scores drops one)
+static int n_passes(const mpn_frcnn_config &c) { return c.num_iter > 1 ? (c.use_rbox_scores ? c.num_iter - 1 : c.num_iter) : 1; }
+// the score / box tables the tail reads: the joined rows of all passes (utils.joinTable, Tester_FRCNN.lua:99-100), or the single pass's
+static void joined_tables(const mpn_frcnn *p, float **scores, float **bbox) {
+  const bool joined = p->cfg.num_iter > 1;
+  *scores = joined ? p->it_scores : p->scores; *bbox = joined ? p->it_bbox : p->bbox;
+}
+static const char *handle_kind_name(const mpn_frcnn *p) {
+  return p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)";
+}
+
 extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   if (!p) return;
   (void)hipDeviceSynchronize();
@@ -485,12 +510,8 @@ extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   for (int i = 0; i < mpn_frcnn::kStage; ++i) if (p->stage_img[i]) (void)hipFree(p->stage_img[i]);
   for (void *q : p->allocs) (void)hipFree(q);
   resnet_free(p->rn);
-  if (p->scaled) (void)hipFree(p->scaled);
-  if (p->scale_tmp) (void)hipFree(p->scale_tmp);
-  if (p->ms_feat) (void)hipFree(p->ms_feat);
-  if (p->ms_pm) (void)hipFree(p->ms_pm);
-  for (float *q : {p->aug_img, p->aug_boxes, p->aug_scores, p->aug_bbox, p->aug_feat, p->aug_pm}) if (q) (void)hipFree(q);
-  if (p->dbg) (void)hipFree(p->dbg);
+  for (float *q : {p->scaled, p->scale_tmp, p->ms_feat, p->ms_pm, p->aug_img, p->aug_boxes, p->aug_scores, p->aug_bbox, p->mir.buf, p->mir.pm, p->dbg})
+    if (q) (void)hipFree(q);
   for (int i = 0; i < 4; ++i) if (p->sh_buf[i]) (void)hipFree(p->sh_buf[i]);
   delete p;
 }
@@ -608,12 +629,9 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
       TRY(dev_alloc(p, &T.b7, (size_t)lin_np(F) * sizeof(float), false));
       TRY(pack_linear_weights(mw->fc7_w[t], mw->fc7_b[t], F, F, 1, T.w7, T.b7, nullptr));
       if (cfg->fc_arith == MPN_FC_SPLIT3) {  // the towers' fc6 / fc7 weights as three bf16 planes (include/mpn.h)
-        float *tmp = nullptr;
-        TRY(dev_alloc(p, &tmp, split3_plane_elems(p->K6, lin_np(F)) * sizeof(unsigned short), true));
-        T.w6_s3 = reinterpret_cast<unsigned short *>(tmp);
+        TRY(dev_alloc(p, &T.w6_s3, split3_plane_elems(p->K6, lin_np(F)) * sizeof(unsigned short), true));
         TRY(split3_planes(T.w6, p->K6, lin_np(F), lin_np(F), T.w6_s3, nullptr));
-        TRY(dev_alloc(p, &tmp, split3_plane_elems(F, lin_np(F)) * sizeof(unsigned short), true));
-        T.w7_s3 = reinterpret_cast<unsigned short *>(tmp);
+        TRY(dev_alloc(p, &T.w7_s3, split3_plane_elems(F, lin_np(F)) * sizeof(unsigned short), true));
         TRY(split3_planes(T.w7, F, lin_np(F), lin_np(F), T.w7_s3, nullptr));
       }
       p->towers.push_back(T);
@@ -657,11 +675,8 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
     TRY(dev_alloc(p, &p->tz6, (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
     if (cfg->fc_arith == MPN_FC_SPLIT3)
       for (int ln = 0; ln < (mw->n_towers > 1 ? 2 : 1); ++ln) {
-        float *tmp = nullptr;
-        TRY(dev_alloc(p, &tmp, split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
-        p->ty_s3[ln] = reinterpret_cast<unsigned short *>(tmp);
-        TRY(dev_alloc(p, &tmp, split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
-        p->tz6_s3[ln] = reinterpret_cast<unsigned short *>(tmp);
+        TRY(dev_alloc(p, &p->ty_s3[ln], split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
+        TRY(dev_alloc(p, &p->tz6_s3[ln], split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
       }
     if (mw->n_towers > 1) {  // the second tower lane
       TRY(dev_alloc(p, &p->ty2, (size_t)(lin_np(c5) / 8) * rows * 8 * sizeof(float), true));
@@ -701,23 +716,17 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
   TRY(dev_alloc(p, &p->b6, (size_t)lin_np(F) * sizeof(float), false));
   TRY(pack_linear_weights(d_fc6_w, d_fc6_b, p->K6, F, PP, p->w6, p->b6, nullptr));
   if (cfg->fc_arith == MPN_FC_SPLIT3) {  // the packed fp32 weights [K/8][NP][8] split once into three bf16 planes [3][K/8][NP↑256][8]; the operand's planes per image
-    float *tmp = nullptr;
-    TRY(dev_alloc(p, &tmp, split3_plane_elems(p->K6, lin_np(F)) * sizeof(unsigned short), true));
-    p->w6_s3 = reinterpret_cast<unsigned short *>(tmp);
+    TRY(dev_alloc(p, &p->w6_s3, split3_plane_elems(p->K6, lin_np(F)) * sizeof(unsigned short), true));
     TRY(split3_planes(p->w6, p->K6, lin_np(F), lin_np(F), p->w6_s3, nullptr));
-    TRY(dev_alloc(p, &tmp, split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
-    p->x6_s3 = reinterpret_cast<unsigned short *>(tmp);
+    TRY(dev_alloc(p, &p->x6_s3, split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
   }
   TRY(dev_alloc(p, &p->w7, lin_wpk_elems(F32, F) * sizeof(float), false));
   TRY(dev_alloc(p, &p->b7, (size_t)lin_np(F) * sizeof(float), false));
   TRY(pack_linear_weights(d_fc7_w, d_fc7_b, F, F, 1, p->w7, p->b7, nullptr));
   if (cfg->fc_arith == MPN_FC_SPLIT3) {
-    float *tmp = nullptr;
-    TRY(dev_alloc(p, &tmp, split3_plane_elems(F, lin_np(F)) * sizeof(unsigned short), true));
-    p->w7_s3 = reinterpret_cast<unsigned short *>(tmp);
+    TRY(dev_alloc(p, &p->w7_s3, split3_plane_elems(F, lin_np(F)) * sizeof(unsigned short), true));
     TRY(split3_planes(p->w7, F, lin_np(F), lin_np(F), p->w7_s3, nullptr));
-    TRY(dev_alloc(p, &tmp, split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
-    p->y6_s3 = reinterpret_cast<unsigned short *>(tmp);
+    TRY(dev_alloc(p, &p->y6_s3, split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
   }
   }
   {  // cls and bbox heads share their input -> one [5C, F] GEMM (model_utils.lua:105-119 ConcatTable)
@@ -736,8 +745,8 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
   if (!graph_net) {
   {  // pixel-major copy of the final map at its largest size
     int fh = cfg->max_h, fw = cfg->max_w;
-    for (int l = 0; l < n_conv; ++l) if (p->pool_after[l]) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
-    TRY(dev_alloc(p, &p->feat_pm, (size_t)fh * fw * ((p->feat_c + 7) / 8) * 8 * sizeof(float), false));
+    final_map_size(p, &fh, &fw);
+    TRY(dev_alloc(p, &p->up.pm, (size_t)fh * fw * ((p->feat_c + 7) / 8) * 8 * sizeof(float), false));
   }
   TRY(dev_alloc(p, &p->x6, (size_t)(K6_32 / 8) * p->Mp * 8 * sizeof(float), true));
   TRY(dev_alloc(p, &p->y6, (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
@@ -794,11 +803,13 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
   return MPN_OK;
 }
 
-// Hc > 0: the H x W image is one level of an image pyramid, placed top-left in a zero Hc x Wc canvas on which the whole trunk runs
-// (getImages' padded batch, ImageDetect.lua:44-49); final_out (optional) receives the final map instead of the last layer's own buffer.
-static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream_t s, Act *feat_out, int Hc = 0, int Wc = 0,
-                     float *final_out = nullptr) {
+// The trunk on an H x W image into the record `m` (the map goes to m->buf if set) — the only record it touches: invalid from the
+// start, valid again where the last launch is enqueued.  Hc > 0: the image is one level of an image pyramid, placed top-left in a
+// zero Hc x Wc canvas on which the whole trunk runs (getImages' padded batch, ImageDetect.lua:44-49).
+static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream_t s, mpn_frcnn::CachedMap *m, int Hc = 0, int Wc = 0) {
   const mpn_frcnn_config &c = p->cfg;
+  float *const final_out = m->buf;
+  m->invalidate();
   const bool canvas = Hc > 0;
   if (!canvas) { Hc = H; Wc = W; }
   if (Hc != p->last_h || Wc != p->last_w) {  // halo positions move with the image size: re-lay the zero halo of every activation, once
@@ -819,7 +830,6 @@ static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream
   }
   Act cur = make_act(p->img_c8p, 3, Hc, Wc);
   p->vmax_built[0] = p->vmax_built[1] = p->vmax_built[2] = false;
-  p->feat_pm_valid = false;
   int rc;
   { ProfScope ps(p, MPN_PROF_TRANSFORM, s);
     rc = canvas ? image_transform_canvas_c8p(d_image, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, cur, s)
@@ -852,9 +862,18 @@ static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream
       cur = out;
     }
   }
-  *feat_out = cur;
-  p->tap_act[0] = cur;
+  m->act = cur; m->h = H; m->w = W;
   return MPN_OK;
+}
+
+// One fc6 / fc7 layer (Linear + ReLU) x[N, K] -> y[N, fc_dim] on C8 operands, timed under `tag`: the fp32 GEMM, or where the layer has
+// w_s3 (MPN_FC_SPLIT3) the operand split into three bf16 planes (x_s3), then six bf16 products per k-step with fp32 accumulation, fixed K ranges
+static int fc_relu(mpn_frcnn *p, int tag, const float *x, int N, int K, const float *w, const float *b, const unsigned short *w_s3,
+                   unsigned short *x_s3, float *y, hipStream_t s, int Mp_override) {
+  ProfScope ps(p, tag, s);
+  if (!w_s3) return linear_c8(x, N, K, w, b, p->cfg.fc_dim, 1, y, nullptr, s, Mp_override, nullptr, 1);
+  const int rc = split3_planes(x, K, lin_mp(N), lin_mp(N), x_s3, s);
+  return rc ? rc : linear_c8_split3(x_s3, N, K, w_s3, b, p->cfg.fc_dim, 1, y, s);
 }
 
 // models/multipathnet.lua:64-120 + model_utils.lua:209-251,296-313 on the C8 layouts: Foveal -> per tower
@@ -863,12 +882,12 @@ static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream
 // -> K integral classifiers (mean of softmaxes) + bbox regressor on the "het" tower.
 static int run_integral_heads(mpn_frcnn *p, const float *d_boxes, int N, int H, int W, int n_fov, hipStream_t s, int clamp);
 
-static int run_mpnet_head(mpn_frcnn *p, const float *d_boxes, int N, int H, int W, hipStream_t s, int clamp) {
+static int run_mpnet_head(mpn_frcnn *p, const Act &conv5, const float *d_boxes, int N, int H, int W, hipStream_t s, int clamp) {
   const mpn_frcnn_config &c = p->cfg;
   const int F = c.fc_dim, PP = c.pooled_h * c.pooled_w, Mp = lin_mp(N);
   int rc = mpn_foveal_forward(p->rois, N, p->fov, s);
   if (rc) return rc;
-  const Act maps[3] = {p->tap_act[0], p->tap_act[1], p->tap_act[2]};
+  const Act maps[3] = {conv5, p->tap_act[1], p->tap_act[2]};
   const float scales[3] = {c.spatial_scale, c.spatial_scale * 2.0f, c.spatial_scale * 4.0f};
   const float kConv345Factor[3] = {1.0f, (float)(1.0 / 30), (float)(1.0 / 200)};  // model_utils.lua:231-237 normFactor (Lua doubles -> float)
   const int Fcb = lin_np(F) / 8;
@@ -1030,19 +1049,9 @@ static int run_mpnet_head(mpn_frcnn *p, const float *d_boxes, int N, int H, int 
     if (rc) return rc;
     if (overlap) MPN_CHECK_HIP(hipEventRecord(p->ev_mix_done[b], ls));
     if (lanes && k + 2 < n_tow) { rc = pool_tower(order[k + 2]); if (rc) return rc; }  // waits for its buffer's last reader; runs under this lane's fc6 and the other lane's tower
-    { ProfScope ps(p, MPN_PROF_FC6, ls);
-      if (T.w6_s3) {  // MPN_FC_SPLIT3 (auxiliary arithmetic)
-        rc = split3_planes(lane_ty[ln], p->K6, Mp, Mp, p->ty_s3[ln], ls);
-        if (rc == MPN_OK) rc = linear_c8_split3(p->ty_s3[ln], N, p->K6, T.w6_s3, T.b6, F, 1, lane_tz6[ln], ls);
-      } else
-        rc = linear_c8(lane_ty[ln], N, p->K6, T.w6, T.b6, F, 1, lane_tz6[ln], nullptr, ls, Mp, nullptr, 1); }
+    rc = fc_relu(p, MPN_PROF_FC6, lane_ty[ln], N, p->K6, T.w6, T.b6, T.w6_s3, p->ty_s3[ln], lane_tz6[ln], ls, Mp);
     if (rc) return rc;
-    { ProfScope ps(p, MPN_PROF_FC7, ls);
-      if (T.w7_s3) {
-        rc = split3_planes(lane_tz6[ln], F, Mp, Mp, p->tz6_s3[ln], ls);
-        if (rc == MPN_OK) rc = linear_c8_split3(p->tz6_s3[ln], N, F, T.w7_s3, T.b7, F, 1, p->cat + (size_t)ti * Fcb * Mp * 8, ls);
-      } else
-        rc = linear_c8(lane_tz6[ln], N, F, T.w7, T.b7, F, 1, p->cat + (size_t)ti * Fcb * Mp * 8, nullptr, ls, Mp, nullptr, 1); }
+    rc = fc_relu(p, MPN_PROF_FC7, lane_tz6[ln], N, F, T.w7, T.b7, T.w7_s3, p->tz6_s3[ln], p->cat + (size_t)ti * Fcb * Mp * 8, ls, Mp);
     if (rc) return rc;
     if (!overlap && k + 1 < n_tow) { rc = pool_tower(order[k + 1]); if (rc) return rc; }
   }
@@ -1077,13 +1086,8 @@ static int run_integral_heads(mpn_frcnn *p, const float *d_boxes, int N, int H, 
 
 // getImages' rescaled image buffers (ImageDetect.lua:34-43), grown to hold `need` / `need_t` bytes
 static int grow_scaled(mpn_frcnn *p, size_t need, size_t need_t, hipStream_t s) {
-  if (need > p->scaled_bytes || need_t > p->scale_tmp_bytes) {
-    MPN_CHECK_HIP(hipStreamSynchronize(s));
-    bump_alloc_generation();  // BEFORE the frees: a hipMalloc that fails below must not leave captured graphs holding a freed pointer
-    if (need > p->scaled_bytes) { if (p->scaled) (void)hipFree(p->scaled); p->scaled = nullptr; p->scaled_bytes = 0; MPN_CHECK_HIP(hipMalloc(&p->scaled, need)); p->scaled_bytes = need; }
-    if (need_t > p->scale_tmp_bytes) { if (p->scale_tmp) (void)hipFree(p->scale_tmp); p->scale_tmp = nullptr; p->scale_tmp_bytes = 0; MPN_CHECK_HIP(hipMalloc(&p->scale_tmp, need_t)); p->scale_tmp_bytes = need_t; }
-  }
-  return MPN_OK;
+  const int rc = grow_device_buffer((void **)&p->scaled, &p->scaled_bytes, need, s);
+  return rc ? rc : grow_device_buffer((void **)&p->scale_tmp, &p->scale_tmp_bytes, need_t, s);
 }
 
 // getImages with a scale table (ImageDetect.lua:22-52; include/mpn.h mpn_frcnn_set_scales): level l's image, resampled and transformed as
@@ -1096,9 +1100,7 @@ static int run_pyramid_trunk(mpn_frcnn *p, const float *d_image, int H0, int W0,
   double sc[MPN_MAX_SCALES];
   int hl[MPN_MAX_SCALES], wl[MPN_MAX_SCALES], Hc = 0, Wc = 0;
   for (int l = 0; l < S; ++l) {
-    sc[l] = mpn_pick_scale(H0, W0, p->scale_targets[l], c.scale_max > 0.0 ? c.scale_max : 1e30);
-    hl[l] = H0; wl[l] = W0;
-    if (sc[l] != 1.0) { hl[l] = (int)((double)H0 * sc[l]); wl[l] = (int)((double)W0 * sc[l]); }
+    sc[l] = getimages_size(H0, W0, p->scale_targets[l], c.scale_max, &hl[l], &wl[l]);
     if (hl[l] <= 0 || wl[l] <= 0) { set_error("run_detect: level %d of a %dx%d image is %dx%d", l, H0, W0, hl[l], wl[l]); return MPN_EINVAL; }
     Hc = std::max(Hc, hl[l]); Wc = std::max(Wc, wl[l]);
   }
@@ -1107,13 +1109,15 @@ static int run_pyramid_trunk(mpn_frcnn *p, const float *d_image, int H0, int W0,
     return MPN_EINVAL;
   }
   int fh = Hc, fw = Wc;
-  for (auto &L : p->conv) if (L.pool) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+  final_map_size(p, &fh, &fw);
   *feat = make_act(p->ms_feat, p->feat_c, fh, fw);
   if (!d_image) {
     if (p->ms_h0 != H0 || p->ms_w0 != W0 || p->last_h != Hc || p->last_w != Wc) { set_error("run_detect: no cached pyramid for a %dx%d image", H0, W0); return MPN_ESTATE; }
     return MPN_OK;
   }
   p->ms_h0 = p->ms_w0 = -1;
+  p->ms_pm_valid = false;
+  p->up.invalidate();  // the levels run through the upright trunk's buffers
   size_t need = 0, need_t = 0;
   for (int l = 0; l < S; ++l)
     if (sc[l] != 1.0) { need = std::max(need, (size_t)3 * hl[l] * wl[l] * sizeof(float)); need_t = std::max(need_t, (size_t)3 * H0 * wl[l] * sizeof(float)); }
@@ -1131,173 +1135,93 @@ static int run_pyramid_trunk(mpn_frcnn *p, const float *d_image, int H0, int W0,
       if (rc) return rc;
       img = p->scaled;
     }
-    Act f;
-    rc = run_trunk(p, img, hl[l], wl[l], s, &f, Hc, Wc, p->ms_feat + (size_t)l * p->ms_slot);
+    mpn_frcnn::CachedMap level;  // (the pyramid keeps its own record of what is cached: ms_h0 / ms_w0)
+    level.buf = p->ms_feat + (size_t)l * p->ms_slot;
+    rc = run_trunk(p, img, hl[l], wl[l], s, &level, Hc, Wc);
     if (rc) return rc;
   }
   p->ms_h0 = H0; p->ms_w0 = W0;
   return MPN_OK;
 }
 
-// d_image == nullptr: recompute_features = false (ImageDetect.lua:107-111) — reuse the trunk output of the last
-// call on this handle (iterative localisation, Tester_FRCNN.lua:82-89) and run only the ROI head on new boxes.
-// mirrored: the second half of an augmented detect on a plain Fast R-CNN handle (run_detect_aug) — the trunk's final map goes to
-// p->aug_feat and is cached there, the upright map and its pixel-major copy stay as they are.
-static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp = 1,
-                      bool mirrored = false) {
+// The features of a detect: *feat = the final map to pool from (ResNet / op-list handles keep theirs inside the graph object).  H x W: the
+// network-input size of the H0 x W0 image at getImages' scale sc.  d_image == nullptr: recompute_features = false (ImageDetect.lua:107-111)
+// — the last call's map is reused (iterative localisation, Tester_FRCNN.lua:82-89).  `m`: the VGG trunk's record to fill or to read.
+static int obtain_features(mpn_frcnn *p, const float *d_image, int H0, int W0, int H, int W, double sc, mpn_frcnn::CachedMap *m, hipStream_t s, Act *feat) {
   const mpn_frcnn_config &c = p->cfg;
-  MPN_CHECK_ARG(p && d_boxes);
-  p->seg_shape[0][0] = -1;  // SEG_HEAD: the host-side state a captured head graph relies on is being rewritten (run_segment re-stamps it after its body)
-  MPN_CHECK_ARG(H0 > 0 && W0 > 0 && N > 0 && N <= c.max_rois);
-  // getImages (ImageDetect.lua:34-43): s = target/min side, capped so that round(s*max side) <= max_size; the image is
-  // resampled to (long)(H*s) x (long)(W*s).  scale_target == 0 keeps the image as it is (s = 1).
-  double sc = 1.0;
-  int H = H0, W = W0;
-  const bool pyr = p->n_scales > 1;  // an image pyramid (mpn_frcnn_set_scales): run_pyramid_trunk does getImages per level
-  if (!pyr && c.scale_target > 0.0) {
-    sc = mpn_pick_scale(H0, W0, c.scale_target, c.scale_max > 0.0 ? c.scale_max : 1e30);
-    if (sc != 1.0) { H = (int)((double)H0 * sc); W = (int)((double)W0 * sc); }
+  if (p->n_scales > 1) return run_pyramid_trunk(p, d_image, H0, W0, s, feat);  // getImages per level
+  const float *img = d_image;
+  if (d_image && sc != 1.0) {
+    int rc = grow_scaled(p, (size_t)3 * H * W * sizeof(float), (size_t)3 * H0 * W * sizeof(float), s);
+    if (rc) return rc;
+    rc = mpn_image_scale(d_image, 3, H0, W0, H, W, p->scale_tmp, p->scaled, s);
+    if (rc) return rc;
+    img = p->scaled;
   }
-  if (H <= 0 || W <= 0 || (!pyr && (H > c.max_h || W > c.max_w))) {
-    set_error("run_detect: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
-    return MPN_EINVAL;
+  if (p->rn) {
+    if (!d_image) {
+      if (!resnet_has_features(p->rn, H, W)) { set_error("run_detect: no cached features for a %dx%d image", H0, W0); return MPN_ESTATE; }
+      return MPN_OK;
+    }
+    ProfScope ps(p, MPN_PROF_CONV_DIRECT, s);
+    return resnet_trunk_forward(p->rn, img, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, s);
   }
-  Act feat;
-  int rc = MPN_OK;
-  if (pyr) {
-    rc = run_pyramid_trunk(p, d_image, H0, W0, s, &feat);
-  } else if (d_image) {
-    const float *img = d_image;
-    if (sc != 1.0) {
-      rc = grow_scaled(p, (size_t)3 * H * W * sizeof(float), (size_t)3 * H0 * W * sizeof(float), s);
-      if (rc) return rc;
-      rc = mpn_image_scale(d_image, 3, H0, W0, H, W, p->scale_tmp, p->scaled, s);
-      if (rc) return rc;
-      img = p->scaled;
+  if (!d_image) {
+    if (m->h != H || m->w != W || p->last_h != H || p->last_w != W) {
+      set_error("run_detect: no cached %sfeatures for a %dx%d image", m == &p->mir ? "mirrored " : "", H0, W0);
+      return MPN_ESTATE;
     }
-    if (p->rn) {
-      ProfScope ps(p, MPN_PROF_CONV_DIRECT, s);
-      rc = resnet_trunk_forward(p->rn, img, H, W, c.tf_swap, c.tf_scale, c.tf_mean, c.tf_std, c.tf_std[0] != 0.0, s);
-    } else if (mirrored) {
-      const Act upright = p->tap_act[0];
-      const bool upright_pm = p->feat_pm_valid;
-      p->aug_h = p->aug_w = -1;
-      rc = run_trunk(p, img, H, W, s, &feat, 0, 0, p->aug_feat);
-      p->tap_act[0] = upright; p->feat_pm_valid = upright_pm;
-      if (rc == MPN_OK) { p->aug_act = feat; p->aug_h = H; p->aug_w = W; p->aug_pm_valid = false; }
-    } else {
-      p->aug_h = p->aug_w = -1;  // a new upright map: the mirrored one of the last image no longer goes with it
-      rc = run_trunk(p, img, H, W, s, &feat);
-    }
-  } else if (p->rn) {
-    if (!resnet_has_features(p->rn, H, W)) { set_error("run_detect: no cached features for a %dx%d image", H0, W0); return MPN_ESTATE; }
-  } else if (mirrored) {
-    if (p->aug_h != H || p->aug_w != W || p->last_h != H || p->last_w != W) { set_error("run_detect: no cached mirrored features for a %dx%d image", H0, W0); return MPN_ESTATE; }
-    feat = p->aug_act;
   } else {
-    if (p->last_h != H || p->last_w != W || !p->tap_act[0].p) { set_error("run_detect: no cached features for a %dx%d image", H0, W0); return MPN_ESTATE; }
-    feat = p->tap_act[0];
+    if (m == &p->up) p->mir.invalidate();  // a new upright map: the mirrored one of the last image no longer goes with it
+    const int rc = run_trunk(p, img, H, W, s, m);
+    if (rc) return rc;
   }
+  *feat = m->act;
+  return MPN_OK;
+}
+
+// ResNet towers: Foveal region t -> ROI pool -> layer4 copy t -> average pool -> its slice of `cat`; then the integral heads
+static int run_resnet_towers_head(mpn_frcnn *p, const float *d_boxes, int N, int H, int W, hipStream_t s, int clamp) {
+  const mpn_frcnn_config &c = p->cfg;
+  int rc = mpn_foveal_forward(p->rois, N, p->fov, s);
   if (rc) return rc;
-  const bool defer_heads = p->defer_stream && !p->rn && !p->is_mpnet;  // the pipelined forms of the plain VGG head (pipelined_impl)
-  rc = pyr ? project_im_rois_levels(d_boxes, N, p->n_scales, p->ms_scales, p->rois, s)
-           : defer_heads ? project_im_rois_copy(d_boxes, N, sc, p->rois, p->boxes_b[p->defer_set], s) : mpn_project_im_rois(d_boxes, N, sc, p->rois, s);
-  if (rc) return rc;
-  // decode uses the ORIGINAL boxes and clamps to the ORIGINAL image (ImageDetect.lua:183-185, Tester_FRCNN.lua:75-78)
-  H = H0; W = W0;
-  if (p->is_mpnet) {
-    rc = run_mpnet_head(p, d_boxes, N, H, W, s, clamp);
-    p->last_n = N;
-    return rc;
+  const int Fcb = lin_np(c.fc_dim) / 8, Mp = lin_mp(N);
+  // Two tower lanes (see mpn_frcnn::tower_stream): tower t on lane t & 1 — its own stream and activation buffers; the sorted / range-max
+  // images of the feature map every tower pools from are built before the fork.  Tower t + 1's ROI pooling (a store-bound launch with no
+  // matrix work), the ragged last block round and the launch gaps of each of a tower's ~20-80 convolutions then run under the other
+  // lane's convolutions.  Pure scheduling: bit-identical results (the towers meet only in `cat`, each writing its own slice).
+  // MEASURED (profiles/r06_tower_lanes_ab.txt): 10.86 -> 10.87 ms on configs[3] bf16, 23.61 -> 23.69 ms on configs[4] — nothing: two
+  // towers' convolutions contend for the same vector-memory path that bounds each of them alone (the VGG towers' matrix-bound GEMMs are
+  // a different story: 13.71 -> 13.43 ms, run_mpnet_head).  The graph lanes therefore exist in the debug flavour only (tower_lanes = 2).
+  const bool lanes = p->tower_stream && resnet_has_second_lane(p->rn) && g_tower_lanes == 2 && p->rn_region.size() > 1 && !p->prof;
+  if (lanes) {
+    rc = resnet_heads_prepare(p->rn, s);
+    if (rc) return rc;
+    MPN_CHECK_HIP(hipEventRecord(p->ev_lane_go, s));
+    MPN_CHECK_HIP(hipStreamWaitEvent(p->tower_stream, p->ev_lane_go, 0));
   }
+  for (size_t t = 0; t < p->rn_region.size(); ++t) {
+    const int ln = lanes ? (int)(t & 1) : 0;
+    hipStream_t ls = ln ? p->tower_stream : s;
+    SplitkSlotScope lane_slabs(ln ? SCR_GEMM_SPLITK_LANE : SCR_GEMM_SPLITK);  // (fp32 graphs: a pointwise layer of few tiles on the split-K GEMM)
+    ProfScope ps(p, MPN_PROF_FC6, ls);
+    rc = resnet_head_forward(p->rn, (int)t, p->fov + 5 * p->rn_region[t], 20, N, c.spatial_scale, p->cat + t * (size_t)Fcb * Mp * 8, Mp, ls, ln);
+    if (rc) return rc;
+  }
+  if (lanes) {
+    MPN_CHECK_HIP(hipEventRecord(p->ev_lane_done, p->tower_stream));
+    MPN_CHECK_HIP(hipStreamWaitEvent(s, p->ev_lane_done, 0));
+  }
+  p->last_n = N;
+  return run_integral_heads(p, d_boxes, N, H, W, (int)p->rn_region.size() - 1, s, clamp);
+}
+
+// The plain Fast R-CNN heads on fc7's output (VGG) / the pooled vector (ResNet, op-list), on stream hs: cls and bbox as one GEMM
+// (model_utils.lua:105-119), softmax, decode (+ clamp).  `s`: the launch stream (hs != s: the side stream took the heads over).
+static int run_plain_heads(mpn_frcnn *p, const float *y7, const float *dec_boxes, int N, int H, int W, hipStream_t hs, hipStream_t s, int clamp) {
+  const mpn_frcnn_config &c = p->cfg;
   const int C = c.n_classes, F = c.fc_dim;
-  if (p->rn && !p->rn_region.empty()) {  // ResNet towers: Foveal region t -> ROI pool -> layer4 copy t -> average pool -> its slice of `cat`
-    rc = mpn_foveal_forward(p->rois, N, p->fov, s);
-    if (rc) return rc;
-    const int Fcb = lin_np(F) / 8, Mp = lin_mp(N);
-    // Two tower lanes (see mpn_frcnn::tower_stream): tower t on lane t & 1 — its own stream and activation buffers; the sorted / range-max
-    // images of the feature map every tower pools from are built before the fork.  Tower t + 1's ROI pooling (a store-bound launch with no
-    // matrix work), the ragged last block round and the launch gaps of each of a tower's ~20-80 convolutions then run under the other
-    // lane's convolutions.  Pure scheduling: bit-identical results (the towers meet only in `cat`, each writing its own slice).
-    // MEASURED (profiles/r06_tower_lanes_ab.txt): 10.86 -> 10.87 ms on configs[3] bf16, 23.61 -> 23.69 ms on configs[4] — nothing: two
-    // towers' convolutions contend for the same vector-memory path that bounds each of them alone (the VGG towers' matrix-bound GEMMs are
-    // a different story: 13.71 -> 13.43 ms, run_mpnet_head).  The graph lanes therefore exist in the debug flavour only (tower_lanes = 2).
-    const bool lanes = p->tower_stream && resnet_has_second_lane(p->rn) && g_tower_lanes == 2 && p->rn_region.size() > 1 && !p->prof;
-    if (lanes) {
-      rc = resnet_heads_prepare(p->rn, s);
-      if (rc) return rc;
-      MPN_CHECK_HIP(hipEventRecord(p->ev_lane_go, s));
-      MPN_CHECK_HIP(hipStreamWaitEvent(p->tower_stream, p->ev_lane_go, 0));
-    }
-    for (size_t t = 0; t < p->rn_region.size(); ++t) {
-      const int ln = lanes ? (int)(t & 1) : 0;
-      hipStream_t ls = ln ? p->tower_stream : s;
-      SplitkSlotScope lane_slabs(ln ? SCR_GEMM_SPLITK_LANE : SCR_GEMM_SPLITK);  // (fp32 graphs: a pointwise layer of few tiles on the split-K GEMM)
-      ProfScope ps(p, MPN_PROF_FC6, ls);
-      rc = resnet_head_forward(p->rn, (int)t, p->fov + 5 * p->rn_region[t], 20, N, c.spatial_scale, p->cat + t * (size_t)Fcb * Mp * 8, Mp, ls, ln);
-      if (rc) return rc;
-    }
-    if (lanes) {
-      MPN_CHECK_HIP(hipEventRecord(p->ev_lane_done, p->tower_stream));
-      MPN_CHECK_HIP(hipStreamWaitEvent(s, p->ev_lane_done, 0));
-    }
-    rc = run_integral_heads(p, d_boxes, N, H, W, (int)p->rn_region.size() - 1, s, clamp);
-    p->last_n = N;
-    return rc;
-  }
-  // the pipelined forms of the plain VGG head hand the heads over to the side stream after fc7 (mpn_frcnn::defer_stream)
-  hipStream_t hs = defer_heads ? p->defer_stream : s;
-  float *y7 = hs != s ? p->y7_b[p->defer_set] : p->y7;
-  p->y7_last = y7;
-  const float *dec_boxes = d_boxes;
-  if (p->rn) {  // resnet.lua:40-48: ROIPooling(14,14) -> layer4 -> average pool -> View; lands in y7 as the heads' operand
-    ProfScope ps(p, MPN_PROF_FC6, s);
-    rc = resnet_head_forward(p->rn, 0, p->rois, 5, N, c.spatial_scale, p->y7, lin_mp(N), s);
-    if (rc) return rc;
-  } else {
-  { ProfScope ps(p, MPN_PROF_ROIPOOL, s);
-    if (pyr && p->feat_pm && g_roi_pool_pm) {  // one pixel-major copy per computed level (once per image), the level read from column 0
-      for (int l = 0; l < p->n_scales && !p->feat_pm_valid && rc == MPN_OK; ++l)
-        if (p->ms_src[l] == l) rc = c8p_to_pixel_major(make_act(p->ms_feat + (size_t)l * p->ms_slot, feat.C, feat.H, feat.W), p->ms_pm + (size_t)l * p->ms_pm_slot, s);
-      if (rc) return rc;
-      p->feat_pm_valid = true;
-      rc = roi_pool_pm(feat, p->ms_pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, s, 5, 0,
-                       LevelStack{p->ms_pm_slot, p->n_scales});
-    } else if (pyr) {
-      rc = roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, nullptr, s, 5, 0,
-                       LevelStack{p->ms_slot, p->n_scales});
-    } else if (p->feat_pm && g_roi_pool_pm) {
-      float *const pm = mirrored ? p->aug_pm : p->feat_pm;
-      bool &pm_valid = mirrored ? p->aug_pm_valid : p->feat_pm_valid;
-      if (!pm_valid) { rc = c8p_to_pixel_major(feat, pm, s); if (rc) return rc; pm_valid = true; }  // once per trunk run
-      rc = roi_pool_pm(feat, pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, s);
-    } else {
-      rc = roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, p->x6, nullptr, s);
-    } }
-  if (rc) return rc;
-  { ProfScope ps(p, MPN_PROF_FC6, s);
-    if (p->w6_s3) {  // MPN_FC_SPLIT3: the pooled operand -> three bf16 planes, six bf16 products per k-step with fp32 accumulation, fixed K ranges
-      rc = split3_planes(p->x6, p->K6, lin_mp(N), lin_mp(N), p->x6_s3, s);
-      if (rc == MPN_OK) rc = linear_c8_split3(p->x6_s3, N, p->K6, p->w6_s3, p->b6, F, 1, p->y6, s);
-    } else
-      rc = linear_c8(p->x6, N, p->K6, p->w6, p->b6, F, 1, p->y6, nullptr, s, 0, nullptr, 1); }
-  if (rc) return rc;
-  { ProfScope ps(p, MPN_PROF_FC7, s);
-    if (p->w7_s3) {
-      rc = split3_planes(p->y6, F, lin_mp(N), lin_mp(N), p->y6_s3, s);
-      if (rc == MPN_OK) rc = linear_c8_split3(p->y6_s3, N, F, p->w7_s3, p->b7, F, 1, y7, s);
-    } else
-      rc = linear_c8(p->y6, N, F, p->w7, p->b7, F, 1, y7, nullptr, s, 0, nullptr, 1); }
-  if (rc) return rc;
-  }
-  if (hs != s) {  // hand over: the side stream continues from here (its work on this buffer set is ordered by ev_tail[set])
-    MPN_CHECK_HIP(hipEventRecord(p->ev_fc7, s));
-    MPN_CHECK_HIP(hipStreamWaitEvent(hs, p->ev_fc7, 0));
-    dec_boxes = p->boxes_b[p->defer_set];
-#ifdef MPN_DEBUG_HOOKS
-    if (g_defer_heads == 2) hipLaunchKernelGGL(side_stream_delay_kernel, dim3(1), dim3(64), 0, hs, 100000ll);
-#endif
-  }
+  int rc;
   { ProfScope ps(p, MPN_PROF_HEADS, hs);
     SplitkSlotScope sk(hs != s ? SCR_GEMM_SPLITK_SIDE : SCR_GEMM_SPLITK);  // its partial sums must not share a buffer with fc6 / fc7 of the next image
     rc = linear_c8(y7, N, F, p->wh, p->bh, 5 * C, 0, nullptr, p->head, hs, 0, nullptr, 1); }
@@ -1314,33 +1238,106 @@ static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const 
   return MPN_OK;
 }
 
+// resnet.lua:40-48: ROIPooling(14,14) -> layer4 -> average pool -> View; lands in y7 as the heads' operand
+static int run_resnet_head(mpn_frcnn *p, const float *d_boxes, int N, int H, int W, hipStream_t s, int clamp) {
+  p->y7_last = p->y7;
+  int rc;
+  { ProfScope ps(p, MPN_PROF_FC6, s); rc = resnet_head_forward(p->rn, 0, p->rois, 5, N, p->cfg.spatial_scale, p->y7, lin_mp(N), s); }
+  return rc ? rc : run_plain_heads(p, p->y7, d_boxes, N, H, W, s, s, clamp);
+}
+
+// The VGG head's ROI pooling of the projected ROIs into fc6's operand, by one of four routes: from the pyramid's level stack or from
+// the one map `feat` of record `m`, each from the pixel-major copy (built once per trunk run) or straight from the C8P map
+static int vgg_roi_pool(mpn_frcnn *p, const Act &feat, mpn_frcnn::CachedMap *m, int N, hipStream_t s) {
+  const mpn_frcnn_config &c = p->cfg;
+  const RoiRule rule{1.0f, 0, c.roi_bin_rule};
+  const bool pyr = p->n_scales > 1;
+  int rc = MPN_OK;
+  ProfScope ps(p, MPN_PROF_ROIPOOL, s);
+  if (pyr && p->ms_pm && g_roi_pool_pm) {  // one pixel-major copy per computed level (once per image), the level read from column 0
+    for (int l = 0; l < p->n_scales && !p->ms_pm_valid && rc == MPN_OK; ++l)
+      if (p->ms_src[l] == l) rc = c8p_to_pixel_major(make_act(p->ms_feat + (size_t)l * p->ms_slot, feat.C, feat.H, feat.W), p->ms_pm + (size_t)l * p->ms_pm_slot, s);
+    if (rc) return rc;
+    p->ms_pm_valid = true;
+    return roi_pool_pm(feat, p->ms_pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, rule, p->x6, s, 5, 0, LevelStack{p->ms_pm_slot, p->n_scales});
+  }
+  if (pyr) return roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, rule, p->x6, nullptr, s, 5, 0, LevelStack{p->ms_slot, p->n_scales});
+  if (m->pm && g_roi_pool_pm) {
+    if (!m->pm_valid) { rc = c8p_to_pixel_major(feat, m->pm, s); if (rc) return rc; m->pm_valid = true; }  // once per trunk run
+    return roi_pool_pm(feat, m->pm, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, rule, p->x6, s);
+  }
+  return roi_pool_c8(feat, p->rois, N, c.pooled_h, c.pooled_w, c.spatial_scale, rule, p->x6, nullptr, s);
+}
+
+// models/vgg.lua:23-31 behind the trunk: ROI pool -> fc6 -> fc7 -> heads.  The pipelined forms hand the heads over to the side stream
+// after fc7 (mpn_frcnn::defer_stream): fc7 then writes buffer set defer_set's y7, and decode reads that set's copy of the boxes.
+static int run_vgg_head(mpn_frcnn *p, const Act &feat, mpn_frcnn::CachedMap *m, const float *d_boxes, int N, int H, int W, hipStream_t s, int clamp) {
+  const int F = p->cfg.fc_dim;
+  hipStream_t hs = p->defer_stream ? p->defer_stream : s;
+  float *y7 = hs != s ? p->y7_b[p->defer_set] : p->y7;
+  p->y7_last = y7;
+  const float *dec_boxes = d_boxes;
+  int rc = vgg_roi_pool(p, feat, m, N, s);
+  if (rc == MPN_OK) rc = fc_relu(p, MPN_PROF_FC6, p->x6, N, p->K6, p->w6, p->b6, p->w6_s3, p->x6_s3, p->y6, s, 0);
+  if (rc == MPN_OK) rc = fc_relu(p, MPN_PROF_FC7, p->y6, N, F, p->w7, p->b7, p->w7_s3, p->y6_s3, y7, s, 0);
+  if (rc) return rc;
+  if (hs != s) {  // hand over: the side stream continues from here (its work on this buffer set is ordered by ev_tail[set])
+    MPN_CHECK_HIP(hipEventRecord(p->ev_fc7, s));
+    MPN_CHECK_HIP(hipStreamWaitEvent(hs, p->ev_fc7, 0));
+    dec_boxes = p->boxes_b[p->defer_set];
+#ifdef MPN_DEBUG_HOOKS
+    if (g_defer_heads == 2) hipLaunchKernelGGL(side_stream_delay_kernel, dim3(1), dim3(64), 0, hs, 100000ll);
+#endif
+  }
+  return run_plain_heads(p, y7, dec_boxes, N, H, W, hs, s, clamp);
+}
+
+// One ImageDetect:detect (ImageDetect.lua:100-193) on record `m` (see obtain_features): getImages' size, the features, the ROI
+// projection, then the head of the handle's kind.
+static int run_detect(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp, mpn_frcnn::CachedMap *m) {
+  const mpn_frcnn_config &c = p->cfg;
+  MPN_CHECK_ARG(p && d_boxes);
+  p->seg_shape[0][0] = -1;  // SEG_HEAD: the host-side state a captured head graph relies on is being rewritten (run_segment re-stamps it after its body)
+  MPN_CHECK_ARG(H0 > 0 && W0 > 0 && N > 0 && N <= c.max_rois);
+  double sc = 1.0;  // scale_target == 0 keeps the image as it is (s = 1)
+  int H = H0, W = W0;
+  const bool pyr = p->n_scales > 1;  // an image pyramid (mpn_frcnn_set_scales): its levels' sizes are run_pyramid_trunk's
+  if (!pyr && c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
+  if (H <= 0 || W <= 0 || (!pyr && (H > c.max_h || W > c.max_w))) {
+    set_error("run_detect: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
+    return MPN_EINVAL;
+  }
+  Act feat;
+  int rc = obtain_features(p, d_image, H0, W0, H, W, sc, m, s, &feat);
+  if (rc) return rc;
+  const bool vgg = !p->rn && !p->is_mpnet;
+  rc = pyr ? project_im_rois_levels(d_boxes, N, p->n_scales, p->ms_scales, p->rois, s)
+           : (vgg && p->defer_stream) ? project_im_rois_copy(d_boxes, N, sc, p->rois, p->boxes_b[p->defer_set], s) : mpn_project_im_rois(d_boxes, N, sc, p->rois, s);
+  if (rc) return rc;
+  // decode uses the ORIGINAL boxes and clamps to the ORIGINAL image (ImageDetect.lua:183-185, Tester_FRCNN.lua:75-78)
+  if (p->is_mpnet) { p->last_n = N; return run_mpnet_head(p, feat, d_boxes, N, H0, W0, s, clamp); }
+  if (p->rn) return p->rn_region.empty() ? run_resnet_head(p, d_boxes, N, H0, W0, s, clamp) : run_resnet_towers_head(p, d_boxes, N, H0, W0, s, clamp);
+  return run_vgg_head(p, feat, m, d_boxes, N, H0, W0, s, clamp);
+}
+
 // Horizontal-flip test-time augmentation around run_detect (include/mpn.h mpn_frcnn_set_augment): the upright
 // half unclamped with its tables kept aside, the mirrored half (the ORIGINAL image mirrored in front of getImages, flipBoxes of the
 // boxes) unclamped, then one merge launch that leaves the merged tables where every later stage reads them (p->scores / p->bbox).
 // Plain Fast R-CNN handles keep both final maps cached, so d_image == nullptr runs both heads on them; the other handle kinds run
-// two whole passes and keep the mirrored map only.  All of it is stream work on library-owned buffers: it captures into a head graph.
+// two whole passes through the one (upright) record and keep the mirrored map only.  All of it is stream work on library-owned buffers: it captures into a head graph.
 static int run_detect_aug(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_boxes, int N, hipStream_t s, int clamp) {
-  if (!p->augment) return run_detect(p, d_image, H0, W0, d_boxes, N, s, clamp);
+  if (!p->augment) return run_detect(p, d_image, H0, W0, d_boxes, N, s, clamp, &p->up);
   const int C = p->cfg.n_classes;
-  const bool two_maps = p->aug_feat != nullptr;
+  const bool two_maps = p->mir.buf != nullptr;
   if (!d_image && !two_maps) {
     set_error("run_detect: augmentation on a %s handle keeps one trunk map, so a detect on cached features has no upright map to read: pass the image",
-              p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)");
+              handle_kind_name(p));
     return MPN_EINVAL;
   }
   MPN_CHECK_ARG(d_boxes && H0 > 0 && W0 > 0 && N > 0 && N <= p->cfg.max_rois);
-  if (d_image) {
-    const size_t need = (size_t)3 * H0 * W0 * sizeof(float);
-    if (need > p->aug_img_bytes) {
-      MPN_CHECK_HIP(hipStreamSynchronize(s));
-      bump_alloc_generation();  // BEFORE the free (grow_scaled)
-      if (p->aug_img) (void)hipFree(p->aug_img);
-      p->aug_img = nullptr; p->aug_img_bytes = 0;
-      MPN_CHECK_HIP(hipMalloc(&p->aug_img, need));
-      p->aug_img_bytes = need;
-    }
-  }
-  int rc = run_detect(p, d_image, H0, W0, d_boxes, N, s, 0);
+  int rc = d_image ? grow_device_buffer((void **)&p->aug_img, &p->aug_img_bytes, (size_t)3 * H0 * W0 * sizeof(float), s) : MPN_OK;
+  if (rc) return rc;
+  rc = run_detect(p, d_image, H0, W0, d_boxes, N, s, 0, &p->up);
   if (rc) return rc;
   MPN_CHECK_HIP(hipMemcpyAsync(p->aug_scores, p->scores, (size_t)N * C * sizeof(float), hipMemcpyDeviceToDevice, s));
   MPN_CHECK_HIP(hipMemcpyAsync(p->aug_bbox, p->bbox, (size_t)N * 4 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1351,7 +1348,7 @@ static int run_detect_aug(mpn_frcnn *p, const float *d_image, int H0, int W0, co
   }
   rc = mpn_flip_boxes(d_boxes, N, W0, p->aug_boxes, s);
   if (rc) return rc;
-  rc = run_detect(p, d_image ? p->aug_img : nullptr, H0, W0, p->aug_boxes, N, s, 0, two_maps);
+  rc = run_detect(p, d_image ? p->aug_img : nullptr, H0, W0, p->aug_boxes, N, s, 0, two_maps ? &p->mir : &p->up);
   if (rc) return rc;
   ProfScope ps(p, MPN_PROF_POST, s);
   hipLaunchKernelGGL(augment_merge_kernel, dim3((unsigned)cdiv_sz((size_t)N * C, 256)), dim3(256), 0, s, p->aug_scores, p->aug_bbox, p->scores,
@@ -1466,14 +1463,28 @@ static int run_segment(mpn_frcnn *p, int kind, const mpn_frcnn::GraphKey &key, c
   return direct();
 }
 
+// Tester_FRCNN.lua:111-124 for the classes [c0, c1) (0-based, background left out) of the current buffer set: per-class NMS of the
+// selected boxes (`rows` per class at most), then bbox voting if configured.  under_trunk: the pipelined tail's NMS form (mpn_internal.h)
+static int nms_and_vote(mpn_frcnn *p, int c0, int c1, int rows, hipStream_t q, bool under_trunk) {
+  const mpn_frcnn_config &c = p->cfg;
+  const size_t off = (size_t)c0 * rows;
+  int r;
+  { ProfScope ps(p, MPN_PROF_NMS, q);
+    r = under_trunk ? nms_batched_under_trunk(p->scored + off * 5, p->counts + c0, c1 - c0, rows, c.nms_thresh, p->keep + off * 5, p->keep_idx + off, p->n_keep + c0, q)
+                    : mpn_nms_batched(p->scored + off * 5, p->counts + c0, c1 - c0, rows, c.nms_thresh, p->keep + off * 5, p->keep_idx + off, p->n_keep + c0, q); }
+  if (r || !c.bbox_voting) return r;
+  return mpn_bbox_vote_batched(p->keep + off * 5, p->n_keep + c0, p->scored + off * 5, p->counts + c0, c1 - c0, rows, c.bbox_vote_thresh,
+                               c.bbox_vote_score_pow != 0.0f ? c.bbox_vote_score_pow : 1.0f, p->voted + off * 5, q);
+}
+
 // Tester_FRCNN.lua:106-125 + keep_top_k: per class j=1..C-1 select (score > thresh) -> NMS -> top-k, on stream `t`
 static int run_tail(mpn_frcnn *p, int N, float *d_dets, int top_cap, int *d_n_dets, hipStream_t sel_stream, hipStream_t t,
                     hipEvent_t after_select) {
   const mpn_frcnn_config &c = p->cfg;
   const int C = c.n_classes;
   int rc;
-  const float *sc = p->scores, *bb = p->bbox;
-  if (c.num_iter > 1) { sc = p->it_scores; bb = p->it_bbox; }  // rows of both localisation passes (utils.joinTable, Tester_FRCNN.lua:99-100)
+  float *sc, *bb;
+  joined_tables(p, &sc, &bb);
   { ProfScope ps(p, MPN_PROF_SELECT, sel_stream);
     rc = mpn_select_scored(sc, bb, N, C, 1, c.score_thresh, p->scored, p->counts, nullptr, sel_stream); }
   if (rc) return rc;
@@ -1484,20 +1495,10 @@ static int run_tail(mpn_frcnn *p, int N, float *d_dets, int top_cap, int *d_n_de
   const mpn_frcnn::GraphKey key{SEG_TAIL, d_dets, d_n_dets, p->scored, nullptr, N, top_cap, 0, 0};  // p->scored names the buffer set
   const int shape[4] = {N, top_cap, c.bbox_voting ? 1 : 0, 0};
   return run_segment(p, SEG_TAIL, key, shape, false, t, [&](hipStream_t q) -> int {
-    int r;
-    { ProfScope ps(p, MPN_PROF_NMS, q);
-      r = after_select ? nms_batched_under_trunk(p->scored, p->counts, C - 1, N, c.nms_thresh, p->keep, p->keep_idx, p->n_keep, q)
-                       : mpn_nms_batched(p->scored, p->counts, C - 1, N, c.nms_thresh, p->keep, p->keep_idx, p->n_keep, q); }
+    const int r = nms_and_vote(p, 0, C - 1, N, q, after_select != nullptr);
     if (r) return r;
-    const float *final_tables = p->keep;
-    if (c.bbox_voting) {  // Tester_FRCNN.lua:118-124
-      r = mpn_bbox_vote_batched(p->keep, p->n_keep, p->scored, p->counts, C - 1, N, c.bbox_vote_thresh,
-                                c.bbox_vote_score_pow != 0.0f ? c.bbox_vote_score_pow : 1.0f, p->voted, q);
-      if (r) return r;
-      final_tables = p->voted;
-    }
     ProfScope ps(p, MPN_PROF_TOPK, q);
-    return mpn_keep_top_k_sorted(final_tables, p->n_keep, C - 1, N, c.top_k, p->thresh, d_dets, top_cap, d_n_dets, q);  // NMS / voted tables: scores non-increasing per class
+    return mpn_keep_top_k_sorted(c.bbox_voting ? p->voted : p->keep, p->n_keep, C - 1, N, c.top_k, p->thresh, d_dets, top_cap, d_n_dets, q);  // NMS / voted tables: scores non-increasing per class
   });
 }
 
@@ -1522,7 +1523,7 @@ static int run_detect_iter(mpn_frcnn *p, const float *d_image, int H, int W, con
     rc = run_detect_aug(p, nullptr, H, W, p->it_boxes, N, s, 0);
     if (rc) return rc;
   }
-  *n_rows = (rbox ? c.num_iter - 1 : c.num_iter) * N;
+  *n_rows = n_passes(c) * N;
   return MPN_OK;
 }
 
@@ -1534,8 +1535,7 @@ static int run_head(mpn_frcnn *p, const float *d_image, int H, int W, const floa
     p->seg_shape[SEG_HEAD][0] = -1;
     return rc;
   }
-  const mpn_frcnn_config &c = p->cfg;
-  *n_rows = c.num_iter > 1 ? (c.use_rbox_scores ? c.num_iter - 1 : c.num_iter) * N : N;
+  *n_rows = n_passes(p->cfg) * N;
   const mpn_frcnn::GraphKey key{SEG_HEAD, d_image, d_boxes, nullptr, nullptr, H, W, N, 0};
   const int shape[4] = {H, W, N, 1};
   const int rc = run_segment(p, SEG_HEAD, key, shape, stable_ptrs, s, [&](hipStream_t q) -> int {
@@ -1587,7 +1587,6 @@ extern "C" int mpn_frcnn_test_one(mpn_frcnn *p, const float *d_image, int H, int
 // classes are independent (Tester_FRCNN.lua:106-125's loop), so the result is the unsharded mpn_frcnn_test_one's bit for bit.
 // The three steps take caller-provided records so that the exchange between them can be any transport; mpn_frcnn_test_one_sharded
 // chains them over an mpn_comm (RCCL all-gather, comm.hip).
-static int shard_passes(const mpn_frcnn_config &c) { return c.num_iter > 1 ? (c.use_rbox_scores ? c.num_iter - 1 : c.num_iter) : 1; }
 static int refuse_multi_pass(const mpn_frcnn *p, const char *form);
 
 extern "C" int mpn_shard_range(int n, int world, int rank, int *lo, int *hi) {
@@ -1599,13 +1598,13 @@ extern "C" int mpn_shard_range(int n, int world, int rank, int *lo, int *hi) {
 extern "C" size_t mpn_frcnn_shard_rows_floats(const mpn_frcnn *p, int N, int world) {
   if (!p || N <= 0 || world < 1) return 0;
   const int chunk = (N + world - 1) / world;
-  return (size_t)shard_passes(p->cfg) * chunk * 5 * p->cfg.n_classes;
+  return (size_t)n_passes(p->cfg) * chunk * 5 * p->cfg.n_classes;
 }
 
 extern "C" size_t mpn_frcnn_shard_class_floats(const mpn_frcnn *p, int N, int world) {
   if (!p || N <= 0 || world < 1) return 0;
   const int n_cls = p->cfg.n_classes - 1, cmax = (n_cls + world - 1) / world;
-  return shard_class_rec_floats(cmax, shard_passes(p->cfg) * N, p->cfg.bbox_voting);
+  return shard_class_rec_floats(cmax, n_passes(p->cfg) * N, p->cfg.bbox_voting);
 }
 
 extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, int rank, int world,
@@ -1617,7 +1616,7 @@ extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, i
   int rc = mpn_frcnn_flush(p, stream);
   if (rc) return rc;
   const mpn_frcnn_config &c = p->cfg;
-  const int C = c.n_classes, P = shard_passes(c), chunk = (N + world - 1) / world;
+  const int C = c.n_classes, P = n_passes(c), chunk = (N + world - 1) / world;
   int lo, hi;
   shard_bounds(N, world, rank, &lo, &hi);
   const int n_local = hi - lo;
@@ -1629,7 +1628,8 @@ extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, i
   int rows = n_local;
   rc = run_head(p, d_image, H, W, d_boxes + 4 * (size_t)lo, n_local, s, &rows, false);
   if (rc) return rc;
-  const float *sc = c.num_iter > 1 ? p->it_scores : p->scores, *bb = c.num_iter > 1 ? p->it_bbox : p->bbox;
+  float *sc, *bb;
+  joined_tables(p, &sc, &bb);
   hipLaunchKernelGGL(shard_pack_rows_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, sc, bb, n_local, P, C, chunk, d_rows_rec);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
@@ -1642,9 +1642,10 @@ extern "C" int mpn_frcnn_shard_nms(mpn_frcnn *p, const float *d_rows_all, int N,
   int rc = mpn_frcnn_flush(p, stream);
   if (rc) return rc;
   const mpn_frcnn_config &c = p->cfg;
-  const int C = c.n_classes, P = shard_passes(c), chunk = (N + world - 1) / world, rows = P * N;
+  const int C = c.n_classes, P = n_passes(c), chunk = (N + world - 1) / world, rows = P * N;
   // the whole image's joined tables, in the unsharded row order, where run_tail reads them
-  float *sc = c.num_iter > 1 ? p->it_scores : p->scores, *bb = c.num_iter > 1 ? p->it_bbox : p->bbox;
+  float *sc, *bb;
+  joined_tables(p, &sc, &bb);
   const size_t rec_floats = (size_t)P * chunk * 5 * C, total = (size_t)rows * 5 * C;
   select_set(p, 0);
   p->last_rows = rows;
@@ -1661,17 +1662,7 @@ extern "C" int mpn_frcnn_shard_nms(mpn_frcnn *p, const float *d_rows_all, int N,
     { ProfScope ps(p, MPN_PROF_SELECT, q);
       r = mpn_select_scored(sc, bb, rows, C, 1, c.score_thresh, p->scored, p->counts, nullptr, q); }
     if (r) return r;
-    if (c1 > c0) {
-      const size_t off = (size_t)c0 * rows;
-      { ProfScope ps(p, MPN_PROF_NMS, q);
-        r = mpn_nms_batched(p->scored + off * 5, p->counts + c0, c1 - c0, rows, c.nms_thresh, p->keep + off * 5, p->keep_idx + off, p->n_keep + c0, q); }
-      if (r) return r;
-      if (c.bbox_voting) {
-        r = mpn_bbox_vote_batched(p->keep + off * 5, p->n_keep + c0, p->scored + off * 5, p->counts + c0, c1 - c0, rows, c.bbox_vote_thresh,
-                                  c.bbox_vote_score_pow != 0.0f ? c.bbox_vote_score_pow : 1.0f, p->voted + off * 5, q);
-        if (r) return r;
-      }
-    }
+    if (c1 > c0 && (r = nms_and_vote(p, c0, c1, rows, q, false)) != MPN_OK) return r;
     hipLaunchKernelGGL(shard_pack_classes_kernel, dim3(cdiv(rows, 256), cmax), dim3(256), 0, q, p->keep, p->keep_idx, p->n_keep,
                        c.bbox_voting ? p->voted : nullptr, c0, c1, rows, cmax, d_class_rec);
     MPN_CHECK_LAUNCH();
@@ -1686,7 +1677,7 @@ extern "C" int mpn_frcnn_shard_finish(mpn_frcnn *p, const float *d_class_all, in
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   const mpn_frcnn_config &c = p->cfg;
-  const int n_cls = c.n_classes - 1, cmax = (n_cls + world - 1) / world, rows = shard_passes(c) * N;
+  const int n_cls = c.n_classes - 1, cmax = (n_cls + world - 1) / world, rows = n_passes(c) * N;
   select_set(p, 0);
   p->last_rows = rows;
   const mpn_frcnn::GraphKey key{SEG_SHARD_FIN, d_class_all, d_dets, d_n_dets, nullptr, N, world, top_cap, 0};
@@ -1700,18 +1691,6 @@ extern "C" int mpn_frcnn_shard_finish(mpn_frcnn *p, const float *d_class_all, in
   });
 }
 
-static int shard_buf(mpn_frcnn *p, int i, size_t floats, hipStream_t s) {
-  const size_t need = floats * sizeof(float);
-  if (need <= p->sh_bytes[i]) return MPN_OK;
-  MPN_CHECK_HIP(hipStreamSynchronize(s));
-  bump_alloc_generation();  // before the free: see run_detect's regrow
-  if (p->sh_buf[i]) (void)hipFree(p->sh_buf[i]);
-  p->sh_buf[i] = nullptr; p->sh_bytes[i] = 0;
-  MPN_CHECK_HIP(hipMalloc(&p->sh_buf[i], need));
-  p->sh_bytes[i] = need;
-  return MPN_OK;
-}
-
 extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const float *d_image, int H, int W, const float *d_boxes, int N,
                                           float *d_dets, int top_cap, int *d_n_dets, void *stream) {
   MPN_CHECK_ARG(p != nullptr && comm != nullptr && N > 0);
@@ -1720,8 +1699,10 @@ extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const fl
   const int world = mpn_comm_world(comm), rank = mpn_comm_rank(comm);
   MPN_CHECK_ARG(world >= 1 && rank >= 0);
   const size_t rr = mpn_frcnn_shard_rows_floats(p, N, world), cr = mpn_frcnn_shard_class_floats(p, N, world);
+  const size_t floats[4] = {rr, rr * world, cr, cr * world};
   int rc;
-  if ((rc = shard_buf(p, 0, rr, s)) || (rc = shard_buf(p, 1, rr * world, s)) || (rc = shard_buf(p, 2, cr, s)) || (rc = shard_buf(p, 3, cr * world, s))) return rc;
+  for (int i = 0; i < 4; ++i)
+    if ((rc = grow_device_buffer((void **)&p->sh_buf[i], &p->sh_bytes[i], floats[i] * sizeof(float), s)) != MPN_OK) return rc;
   rc = mpn_frcnn_shard_head(p, d_image, H, W, d_boxes, N, rank, world, p->sh_buf[0], stream);
   if (rc) return rc;
   rc = mpn_gather_rows(comm, p->sh_buf[0], rr, p->sh_buf[1], stream);
@@ -1804,7 +1785,7 @@ extern "C" int mpn_frcnn_test_one_pipelined_host(mpn_frcnn *p, const float *h_im
   MPN_CHECK_ARG(p != nullptr && h_image && h_boxes && H > 0 && W > 0 && N > 0 && N <= p->cfg.max_rois);
   if (int rp = refuse_multi_pass(p, "mpn_frcnn_test_one_pipelined_host")) return rp;
   hipStream_t s = as_stream(stream);
-  const size_t img_n = (size_t)3 * H * W;
+  const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
   if (!p->copy) {  // first use: copy stream, events, the two box staging buffers
     MPN_CHECK_HIP(hipStreamCreateWithFlags(&p->copy, hipStreamNonBlocking));
     for (int i = 0; i < mpn_frcnn::kStage; ++i) {
@@ -1815,23 +1796,17 @@ extern "C" int mpn_frcnn_test_one_pipelined_host(mpn_frcnn *p, const float *h_im
     }
   }
   const int b = (int)(p->up_seq % mpn_frcnn::kStage);
-  if (img_n > p->stage_cap[b]) {  // image staging grows on demand (getImages may be handed images larger than max_h x max_w)
-    MPN_CHECK_HIP(hipStreamSynchronize(p->copy));
-    MPN_CHECK_HIP(hipStreamSynchronize(s));
-    bump_alloc_generation();  // before the free: see run_detect's regrow
-    if (p->stage_img[b]) (void)hipFree(p->stage_img[b]);
-    p->stage_img[b] = nullptr; p->stage_cap[b] = 0;
-    size_t cap = (size_t)3 * p->cfg.max_h * p->cfg.max_w;
-    if (cap < img_n) cap = img_n;
-    MPN_CHECK_HIP(hipMalloc(&p->stage_img[b], cap * sizeof(float)));
-    p->stage_cap[b] = cap;
+  if (img_bytes > p->stage_bytes[b]) {  // image staging grows on demand (getImages may be handed images larger than max_h x max_w)
+    MPN_CHECK_HIP(hipStreamSynchronize(p->copy));  // the set's last upload (grow_device_buffer waits for `s`)
+    const int rcg = grow_device_buffer((void **)&p->stage_img[b], &p->stage_bytes[b], std::max(img_bytes, (size_t)3 * p->cfg.max_h * p->cfg.max_w * sizeof(float)), s);
+    if (rcg) return rcg;
   }
   // The staging set is free once the image that used it (three calls ago) has been consumed.  Waited for on the HOST, not with
   // hipStreamWaitEvent on the copy stream: a copy that depends on a compute-queue event leaves the SDMA path (measured on AlexNet,
   // tools/host_enqueue_probe.py: 0.99 ms / image with the stream wait, 0.86 resident), and this bounds the host's run-ahead to
   // three images, as a queue should.
   if (p->used_pending[b]) { MPN_CHECK_HIP(hipEventSynchronize(p->ev_consumed[b])); p->used_pending[b] = false; }
-  MPN_CHECK_HIP(hipMemcpyAsync(p->stage_img[b], h_image, img_n * sizeof(float), hipMemcpyHostToDevice, p->copy));
+  MPN_CHECK_HIP(hipMemcpyAsync(p->stage_img[b], h_image, img_bytes, hipMemcpyHostToDevice, p->copy));
   // (Round 5 tried the proposal table's copy on the launch stream instead — small copies are shader blits, i.e. a kernel on the copy stream's
   // hardware queue — and took it back: a 32-KB table there stalls the launch stream for 0.25 ms per image, 5.40 -> 5.65 ms at 2000 proposals.)
   MPN_CHECK_HIP(hipMemcpyAsync(p->stage_boxes[b], h_boxes, (size_t)N * 4 * sizeof(float), hipMemcpyHostToDevice, p->copy));
@@ -1888,11 +1863,9 @@ static int drop_graphs_and_features(mpn_frcnn *p) {
     for (int q = 0; q < mpn_frcnn::kUnseen; ++q) p->unseen_valid[k][q] = false;
     for (int j = 0; j < 4; ++j) p->seg_shape[k][j] = -1;
   }
-  p->tap_act[0] = Act{};  // cached trunk output: gone (the next detect must pass an image)
+  p->up.invalidate();  // cached trunk outputs: gone (the next detect must pass an image)
+  p->mir.invalidate();
   p->ms_h0 = p->ms_w0 = -1;
-  p->feat_pm_valid = false;
-  p->aug_h = p->aug_w = -1;
-  p->aug_pm_valid = false;
   return MPN_OK;
 }
 
@@ -1906,7 +1879,7 @@ extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_
   MPN_CHECK_ARG(p != nullptr);
   if (n_scales > 1 && (p->is_mpnet || p->rn)) {
     set_error("mpn_frcnn_set_scales: a %s handle has no image pyramid (only mpn_frcnn_create's VGG Fast R-CNN head pools from one)",
-              p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)");
+              handle_kind_name(p));
     return MPN_EINVAL;
   }
   if (n_scales > 1 && p->augment) {
@@ -1922,9 +1895,9 @@ extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_
   }
   if (n_scales > p->ms_cap) {  // per-level slots at the largest canvas geometry
     int fh = p->cfg.max_h, fw = p->cfg.max_w;
-    for (auto &L : p->conv) if (L.pool) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+    final_map_size(p, &fh, &fw);
     const size_t slot = act_bytes(p->feat_c, fh, fw) / sizeof(float), pm_slot = pixel_major_elems(make_act(nullptr, p->feat_c, fh, fw));
-    bump_alloc_generation();
+    bump_alloc_generation();  // (behind drop_graphs_and_features' device synchronise; both buffers go, then both come back cleared)
     if (p->ms_feat) (void)hipFree(p->ms_feat);
     if (p->ms_pm) (void)hipFree(p->ms_pm);
     p->ms_feat = p->ms_pm = nullptr; p->ms_cap = 0; p->n_scales = 0;
@@ -1942,7 +1915,6 @@ extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_
 extern "C" int mpn_frcnn_set_augment(mpn_frcnn *p, int enable) {
   MPN_CHECK_ARG(p != nullptr);
   const bool plain = !p->is_mpnet && !p->rn;
-  const char *kind = p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)";
   if (enable && p->n_scales > 1) {
     set_error("mpn_frcnn_set_augment: horizontal-flip augmentation and an image pyramid (mpn_frcnn_set_scales, %d scales) exclude each other: "
               "restore a single scale first", p->n_scales);
@@ -1950,7 +1922,7 @@ extern "C" int mpn_frcnn_set_augment(mpn_frcnn *p, int enable) {
   }
   if (enable && !plain && p->cfg.num_iter > 1) {
     set_error("mpn_frcnn_set_augment: a %s handle keeps one trunk map, and iterative localisation (num_iter %d) under augmentation needs the "
-              "upright and the mirrored one cached (only mpn_frcnn_create handles hold both): create the handle with num_iter 1", kind, p->cfg.num_iter);
+              "upright and the mirrored one cached (only mpn_frcnn_create handles hold both): create the handle with num_iter 1", handle_kind_name(p), p->cfg.num_iter);
     return MPN_EINVAL;
   }
   int rc = drop_graphs_and_features(p);
@@ -1962,7 +1934,7 @@ extern "C" int mpn_frcnn_set_augment(mpn_frcnn *p, int enable) {
     const size_t M = (size_t)p->cfg.max_rois, C = (size_t)p->cfg.n_classes;
     const size_t img_bytes = (size_t)3 * p->cfg.max_h * p->cfg.max_w * sizeof(float);
     bump_alloc_generation();
-    for (float **q : {&p->aug_img, &p->aug_boxes, &p->aug_bbox, &p->aug_feat, &p->aug_pm}) if (*q) { (void)hipFree(*q); *q = nullptr; }  // (an earlier attempt that ran out of memory)
+    for (float **q : {&p->aug_img, &p->aug_boxes, &p->aug_bbox, &p->mir.buf, &p->mir.pm}) if (*q) { (void)hipFree(*q); *q = nullptr; }  // (an earlier attempt that ran out of memory)
     p->aug_img_bytes = 0;
     MPN_CHECK_HIP(hipMalloc(&p->aug_img, img_bytes));
     p->aug_img_bytes = img_bytes;
@@ -1970,12 +1942,12 @@ extern "C" int mpn_frcnn_set_augment(mpn_frcnn *p, int enable) {
     MPN_CHECK_HIP(hipMalloc(&p->aug_bbox, M * 4 * C * sizeof(float)));
     if (plain) {
       int fh = p->cfg.max_h, fw = p->cfg.max_w;
-      for (auto &L : p->conv) if (L.pool) { fh = (fh + 1) / 2; fw = (fw + 1) / 2; }
+      final_map_size(p, &fh, &fw);
       const size_t feat_bytes = act_bytes(p->feat_c, fh, fw), pm_bytes = pixel_major_elems(make_act(nullptr, p->feat_c, fh, fw)) * sizeof(float);
-      MPN_CHECK_HIP(hipMalloc(&p->aug_feat, feat_bytes));
-      MPN_CHECK_HIP(hipMemset(p->aug_feat, 0, feat_bytes));
-      MPN_CHECK_HIP(hipMalloc(&p->aug_pm, pm_bytes));
-      MPN_CHECK_HIP(hipMemset(p->aug_pm, 0, pm_bytes));
+      MPN_CHECK_HIP(hipMalloc(&p->mir.buf, feat_bytes));
+      MPN_CHECK_HIP(hipMemset(p->mir.buf, 0, feat_bytes));
+      MPN_CHECK_HIP(hipMalloc(&p->mir.pm, pm_bytes));
+      MPN_CHECK_HIP(hipMemset(p->mir.pm, 0, pm_bytes));
     }
     MPN_CHECK_HIP(hipMalloc(&p->aug_scores, M * C * sizeof(float)));  // last: its presence says that all of them exist
   }
@@ -2056,7 +2028,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   const mpn_frcnn_config &c = p->cfg;
   const int N = p->last_n, C = c.n_classes, F = c.fc_dim, PP = c.pooled_h * c.pooled_w;
   int h = p->last_h, w = p->last_w;
-  for (auto &L : p->conv) if (L.pool) { h = (h + 1) / 2; w = (w + 1) / 2; }
+  final_map_size(p, &h, &w);
   std::string nm(name);
   size_t n = 0;
   int level = -1;  // "conv5.<l>": level l of the image pyramid
@@ -2079,7 +2051,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   if (p->is_mpnet && nm != "conv5" && nm != "bbox_raw" && nm != "cls_k" && nm != "cat") { set_error("mpn_frcnn_debug_tensor: '%s' is not kept by the MultiPathNet head", name); return MPN_EINVAL; }
   if (p->rn && nm != "bbox_raw" && nm != "cls_k" && nm != "cat" && !((nm == "cls" || nm == "fc7") && p->rn_region.empty())) { set_error("mpn_frcnn_debug_tensor: '%s' is not kept by the op-list / ResNet pipelines", name); return MPN_EINVAL; }
   MPN_CHECK_HIP(hipDeviceSynchronize());
-  if (n * sizeof(float) > p->dbg_bytes) {
+  if (n * sizeof(float) > p->dbg_bytes) {  // not grow_device_buffer: no kernel of a captured graph reads dbg, and a bump here would cost the caller its graphs
     if (p->dbg) (void)hipFree(p->dbg);
     p->dbg = nullptr; p->dbg_bytes = 0;
     MPN_CHECK_HIP(hipMalloc(&p->dbg, n * sizeof(float)));

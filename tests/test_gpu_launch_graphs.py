@@ -161,6 +161,25 @@ def test_fresh_buffers_every_call_never_capture(dev):
     assert cap2 > cap and rep2 >= rep0 + 3
 
 
+def test_regrow_between_capture_and_replay_recaptures(dev):
+    """a library buffer that grows between a capture and a replay (getImages' resampled image: B's is larger than A's) drops the captured
+    graphs: A is captured again, never replayed on the freed pointer.  Sizes of test_getimages_rescale_on_device (short side -> 150, long
+    side capped at 250): A 200x320 -> 150x240, B 60x100 -> 150x250."""
+    sizes = [(200, 320), (60, 100)]
+    ims = [torch.from_numpy(np.random.default_rng(20 + i).random((3, h, w), dtype=np.float32)).to(dev) for i, (h, w) in enumerate(sizes)]
+    bxs = [torch.from_numpy(_boxes(np.random.default_rng(30 + i), 60, w, h, lo=6)).to(dev) for i, (h, w) in enumerate(sizes)]
+    ref_net, net = _net(scale=150, max_size=250), _on(_net(scale=150, max_size=250))
+    ref_net.set_graphs(False)
+    stats = []                                            # (captures, replays) in front of every call
+    for step, i in enumerate([0, 0, 0, 1, 0, 0, 0]):    # fixed caller buffers per image: the pointers repeat
+        stats.append(net.graph_stats())
+        want, got = _run(ref_net, ims[i], bxs[i]), _run(net, ims[i], bxs[i])
+        assert want.shape[0] > 0 and torch.equal(got, want), step
+    assert ref_net.graph_stats() == (0, 0)
+    assert stats[3][1] >= 1                      # A was replayed before B
+    assert net.graph_stats()[0] > stats[3][0]    # ... and captured again after B's regrow
+
+
 def test_pipelined_host_fed_form_replays(dev):
     """what bench.py times (mpn_frcnn_test_one_pipelined_host: uploads on the copy stream into three staging sets, the NMS / top-k tail on
     the side stream) with the head of every staging set and the tail of both buffer sets replayed as graphs: 16 steps over three
