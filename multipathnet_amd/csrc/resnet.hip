@@ -2641,8 +2641,6 @@ MPN_KNOB(int, g_bf16_bdir, 1);  // mpn_debug_set_bf16_bdir: 1 = conv2d_c8i_bf16_
 #ifdef MPN_DEBUG_HOOKS
 MPN_KNOB(int, g_bf16_bdir_abl, 0);  // mpn_debug_set_bf16_bdir_abl: the B-direct kernel's ABL knock-outs (only in -DMPN_BF16_ABLATE builds)
 MPN_KNOB(int, g_bf16_bdir_ver, 1);  // mpn_debug_set_bf16_bdir_ver: 1 = compiler-counted form <3>, 2 / 3 = hand-counted form <3> / <4> (debug flavour only)
-#endif
-#ifdef MPN_DEBUG_HOOKS
 // mpn_debug_set_tower_knock (tools/tower_knockout.py; timing only, garbage results): the CEILING of a first per-ROI layer that never reads a
 // materialised pooled tensor (VERDICT r5 task 1, step 1).  bit 0: the ROI pooling launch of the bf16 heads is skipped; bit 1: the convolutions
 // that read the pooled tensor (Mixed_7a's fused 1x1 768 -> 384; layer4 block 1's conv1 and shortcut) run the B-direct kernel with every pixel
@@ -2650,208 +2648,33 @@ MPN_KNOB(int, g_bf16_bdir_ver, 1);  // mpn_debug_set_bf16_bdir_ver: 1 = compiler
 static int g_tower_knock = 0;
 static int g_pool_exp = 0;   // mpn_debug_set_pool_exp: timing experiments of the bf16 ROI pooling launch (resnet_head_forward)
 static int g_knock_arm = 0;  // the next `g_knock_arm` rn_conv calls are first-layer convolutions (armed by the caller)
+static bool knock_first() { return g_knock_arm > 0 && (g_tower_knock & 2); }
+#else
+constexpr bool knock_first() { return false; }
 #endif
+// Which launch rn_conv's call took (mpn_debug_conv_last_form: tests/test_gpu_conv_numerics.py asserts it per case)
+enum ConvForm : int {
+  CF_KC1 = 1, CF_KC2 = 2, CF_KC3 = 3, CF_KC4 = 4, CF_PF = 5,  // fp32: conv2d_c8i_kernel<KC>, conv2d_c8i_pf_kernel
+  CF_MOSAIC = 10, CF_IM2COL = 11, CF_GEMM_FC = 12,            // the Winograd mosaic, im2col + GEMM, the GEMM's split-K form on 1x1 maps
+  CF_GEMM_DIRECT = 13, CF_GEMM_RI = 14,                       // the pointwise GEMM (direct / row-invariant)
+  CF_BDIR = 20,                                               // bf16: conv2d_c8i_bf16_bdir_kernel
+  CF_DMA_256x128 = 21, CF_DMA_128x256 = 22, CF_DMA_256x256 = 23,  // the LDS-DMA kernel, couts x pixels
+  CF_B_KP1 = 26, CF_B_KP2 = 27,                               // conv2d_c8i_bf16_kernel<KP>
+  CF_DMA_NCH8 = 28, CF_DMA_W8 = 29,                           // debug flavour: the LDS-DMA kernel with 64-channel stages / in the 8-wave shape
+  CF_BDIR2_DS3 = 32, CF_BDIR2_DS4 = 33, CF_BDIR8 = 38, CF_BDPP = 39,  // debug flavour: bdir_ver 2 / 3 / 8 / 9
+  CF_SPLIT = 0x100,                                           // or-ed in: split K (the generic fp32 / the 128 x 128 bf16 kernel + a finalize kernel)
+};
 #ifdef MPN_DEBUG_HOOKS
-// mpn_debug_conv_last_form (tests/test_gpu_conv_numerics.py): which launch form rn_conv's last call took.  fp32: 1-4 conv2d_c8i_kernel<KC>,
-// 5 conv2d_c8i_pf_kernel, 10 the Winograd mosaic, 11 im2col + GEMM, 12 the GEMM's split-K form on 1x1 maps, 13 / 14 the pointwise GEMM
-// (direct / row-invariant); bf16: 20 conv2d_c8i_bf16_bdir_kernel (32 / 33 / 38 / 39: bdir_ver 2 / 3 / 8 / 9), 21 / 22 / 23 the LDS-DMA kernel
-// at 256 x 128 / 128 x 256 / 256 x 256 (28: 64-channel stages, 29: the 8-wave shape), 26 / 27 conv2d_c8i_bf16_kernel<1 / 2>; + 0x100: split K
 static int g_dbg_conv_form = 0;
 #define RN_FORM(v) (g_dbg_conv_form = (v))
 #else
 #define RN_FORM(v) ((void)0)
 #endif
 MPN_KNOB(int, g_roi_invariant, 1);  // mpn_debug_set_roi_invariant: 0 = per-ROI layers pick kernel / split by batch size as round 3 did (tests, timing)
-// per_roi: the batch axis counts ROIs (the head of a graph model).  A ROI's result must not depend on which other ROIs share the
-// launch (memoryEfficientForward's chunked == full, ImageDetect.lua:126-133; the ROI-sharded mode == the unsharded one), so for
-// these layers everything that changes the summation ORDER is a function of the layer alone, never of in.B: no split-K (every
-// kernel family below accumulates K = (tap, channel chunk) in ONE chain per output, and the bf16 tile shapes / the small and the
-// LDS-DMA kernel share that chain bit for bit), pointwise convolutions always on the un-split GEMM, eligible 3x3 convolutions
-// always on the Winograd mosaic with a batch-independent launch plan.  Tile shapes may still follow the batch size.
-static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int relu, hipStream_t s, ActI *o, bool allow_gemm = true, bool per_roi = false) {
-  const bool inv = per_roi && g_roi_invariant;
-  if (c.wpk16) {  // bf16 graph
-    GConvArgsB b{};
-    b.in = reinterpret_cast<const bf16_t *>(in.p); b.wpk = c.wpk16; b.res = reinterpret_cast<const bf16_t *>(res); b.bpk = c.bpk;
-    b.out = reinterpret_cast<bf16_t *>(out);
-    b.B = in.B; b.H = in.H; b.W = in.W; b.nch2 = round_up((c.Cin + 7) / 8, 2);
-    b.CoutP = round_up(c.Cout, 128); b.Cb_out = (c.Cout + 7) / 8;
-    b.KH = c.KH; b.KW = c.KW; b.sh = c.sh; b.sw = c.sw; b.ph = c.ph; b.pw = c.pw;
-    b.OH = (in.H + 2 * c.ph - c.KH) / c.sh + 1; b.OW = (in.W + 2 * c.pw - c.KW) / c.sw + 1;
-    b.relu = relu; b.norelu_cb0 = c.norelu_c0 / 8; b.norelu_cb1 = c.norelu_c1 / 8;
-    MPN_CHECK_ARG(in.C == c.Cin && b.OH > 0 && b.OW > 0);
-    b.P = (long long)in.B * b.OH * b.OW;
-    *o = ActI{out, in.B, c.Cout, b.OH, b.OW};
-    b.pitch_in = in.pitch(); b.pitch_out = o->pitch();
-    // round 4: the B-direct kernel (128 couts x 256 pixels; pixels straight into registers), where both tensors fit a 2-GiB descriptor
-    // Where it measured faster, layer by layer against the LDS-DMA kernel on the per-ROI layers of configs[3] / [4] (tools/bench_conv_bf16.py,
-    // profiles/r04_bf16_conv_bdirect.txt): convolutions with spatial taps at stride 1 (every pixel record is re-read once per tap, from
-    // the CU's own cache: 1x3 / 3x1 -17 %, 3x3 -21 %, 1x7 / 7x1 -10 %), strided 3x3 with >= 512 input channels (-4 %), and pointwise
-    // layers with Cin >= 2 Cout (2048 -> 512: -9 %).  NOT on pointwise layers with many output channels (512 -> 2048 + residual: +9 %:
-    // its 128-cout tile re-reads the pixel tile twice as often as the 256-cout LDS-DMA shape), nor on strided pointwise layers
-    // (every second record of a row: half-used cache lines per fragment load, +26 %).  A rule of the layer alone, never of the batch.
-    const bool pointwise = b.KH == 1 && b.KW == 1, strided = b.sh > 1 || b.sw > 1;
-    const bool bdir_wins = pointwise ? (!strided && c.Cin >= 2 * c.Cout) : (!strided || c.Cin >= 512);
-#ifdef MPN_DEBUG_HOOKS
-    const bool knock_first = g_knock_arm > 0 && (g_tower_knock & 2);
-#else
-    constexpr bool knock_first = false;
-#endif
-    if (g_bf16_bdir && (g_bf16_bdir == 2 || bdir_wins || knock_first) && g_bf16_dma && b.nch2 % 4 == 0 && b.P >= (g_bf16_dma == 2 ? 1 : 256 * 128) &&
-        (size_t)b.nch2 * b.pitch_in * 16 < ((size_t)1 << 31) && (size_t)b.KH * b.KW * b.nch2 * b.CoutP * 16 < ((size_t)1 << 31)) {
-      const int nx = (int)((b.P + 255) / 256), ny = b.CoutP / 128;
-      const dim3 gridd((unsigned)(((nx + 7) / 8) * 8 * ny));
-#ifdef MPN_DEBUG_HOOKS
-      if (g_knock_arm > 0 && (g_tower_knock & 2)) {
-        --g_knock_arm;
-        hipLaunchKernelGGL((conv2d_c8i_bf16_bdir_kernel<3, 32 | 512>), gridd, dim3(256), 0, s, b, nx, ny);
-        MPN_CHECK_LAUNCH();
-        return MPN_OK;
-      }
-      if (g_bf16_bdir_ver == 9) {
-        RN_FORM(39);
-        const int nxq = (nx + 7) / 8;
-        const dim3 gridp((unsigned)(8 * ((nxq * ny + 1) / 2)));
-        hipLaunchKernelGGL((conv2d_c8i_bf16_bdpp_kernel<3>), gridp, dim3(512), 0, s, b, nx, ny);
-        MPN_CHECK_LAUNCH();
-        return MPN_OK;
-      }
-      if (g_bf16_bdir_ver == 8) {
-        RN_FORM(38);
-        const int ny8 = (b.CoutP + 255) / 256;
-        const dim3 grid8((unsigned)(((nx + 7) / 8) * 8 * ny8));
-#ifdef MPN_BF16_ABLATE
-#define MPN_BDIR8_ABL(v) if (g_bf16_bdir_abl == v) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<4, v>), grid8, dim3(512), 0, s, b, nx, ny8); else
-        MPN_BDIR8_ABL(1) MPN_BDIR8_ABL(2) MPN_BDIR8_ABL(8) MPN_BDIR8_ABL(16) MPN_BDIR8_ABL(32) MPN_BDIR8_ABL(7) MPN_BDIR8_ABL(23) MPN_BDIR8_ABL(24)
-#undef MPN_BDIR8_ABL
-#endif
-        if (g_bf16_bdir_abl == 1000) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<8>), grid8, dim3(512), 0, s, b, nx, ny8);
-        else if (g_bf16_bdir_abl == 1001) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<6>), grid8, dim3(512), 0, s, b, nx, ny8);
-        else
-        hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<4>), grid8, dim3(512), 0, s, b, nx, ny8);
-        MPN_CHECK_LAUNCH();
-        return MPN_OK;
-      }
-#endif
-      RN_FORM(20);
-#ifdef MPN_DEBUG_HOOKS
-      if (g_bf16_bdir_ver == 2 || g_bf16_bdir_ver == 3) RN_FORM(30 + g_bf16_bdir_ver);
-      if (g_bf16_bdir_ver == 2) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir2_kernel<3>), gridd, dim3(256), 0, s, b, nx, ny);
-      else if (g_bf16_bdir_ver == 3) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir2_kernel<4>), gridd, dim3(256), 0, s, b, nx, ny);
-      else
-#ifdef MPN_BF16_ABLATE
-#define MPN_BDIR_ABL(v) if (g_bf16_bdir_abl == v) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir_kernel<3, v>), gridd, dim3(256), 0, s, b, nx, ny); else
-      MPN_BDIR_ABL(1) MPN_BDIR_ABL(2) MPN_BDIR_ABL(4) MPN_BDIR_ABL(8) MPN_BDIR_ABL(16) MPN_BDIR_ABL(32) MPN_BDIR_ABL(7) MPN_BDIR_ABL(23) MPN_BDIR_ABL(6) MPN_BDIR_ABL(24) MPN_BDIR_ABL(36) MPN_BDIR_ABL(64) MPN_BDIR_ABL(192) MPN_BDIR_ABL(194) MPN_BDIR_ABL(198) MPN_BDIR_ABL(70) MPN_BDIR_ABL(256)
-#undef MPN_BDIR_ABL
-#endif
-#endif
-      hipLaunchKernelGGL((conv2d_c8i_bf16_bdir_kernel<3>), gridd, dim3(256), 0, s, b, nx, ny);
-      MPN_CHECK_LAUNCH();
-      return MPN_OK;
-    }
-    // large layers: the LDS-DMA kernel (32-channel stages, 32-bit record offsets); tile shape per layer
-    if (g_bf16_dma && b.nch2 % 4 == 0 && b.P >= (g_bf16_dma == 2 ? 1 : 256 * 128) && (size_t)in.B * in.H * in.W * 16 < ((size_t)1 << 32)) {
-      // cost of a shape = block-rounds over the 256 CUs x work per block (the two 3-ring shapes run two blocks per CU at half speed
-      // each: the same count); 256-cout tiles need whole 256-row weight tiles
-      struct Shape { int tm, tn; };
-      const Shape shapes[3] = {{256, 128}, {128, 256}, {256, 256}};  // ties go to the earlier entry
-#ifdef MPN_DEBUG_HOOKS
-      const bool w8 = g_bf16_dma_tn == 2256 && b.CoutP % 256 == 0;  // (hook) the 8-wave 256 x 256 shape: bit-identical, measured no faster than the per-layer pick (ResNet towers 1.95 vs 1.89 ms: 1.5 block rounds on 49 000 pixels), debug flavour only
-#else
-      constexpr bool w8 = false;
-#endif
-      int best = -1; long long best_cost = 0;
-      for (int i = 0; i < 3; ++i) {
-        const Shape &sh = shapes[i];
-        if (sh.tm == 256 && b.CoutP % 256 != 0) continue;
-        if (w8 && !(sh.tm == 256 && sh.tn == 256)) continue;
-        if (!w8 && g_bf16_dma_tn && !(sh.tn == g_bf16_dma_tn % 1000 && sh.tm == (g_bf16_dma_tn >= 1000 ? 128 : 256))) continue;
-        const long long nb = (b.P + sh.tn - 1) / sh.tn * (b.CoutP / sh.tm);
-        const long long cost = (nb + 255) / 256 * sh.tm * sh.tn;
-        if (best < 0 || cost < best_cost) { best = i; best_cost = cost; }
-      }
-      if (best >= 0) {
-        const int tm = shapes[best].tm, tn = shapes[best].tn;
-#ifdef MPN_DEBUG_HOOKS
-        const bool nch8 = g_bf16_nch == 8 && b.nch2 % 8 == 0;
-#else
-        constexpr bool nch8 = false;  // 64-channel stages measured 12 % SLOWER (one block per CU: tools/bench_conv_bf16.py, profiles/r04_bf16_conv_ablation.txt)
-#endif
-        const int ring = nch8 ? ((tm == 256 && tn == 256) ? 2 : 3) : ((tm == 256 && tn == 256) ? 4 : 3);
-        const size_t LDS = (size_t)ring * (nch8 ? 8 : 4) * (tm + tn) * 16;  // ring depth x stage bytes (as in the kernel)
-        {
-          int rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<4, 4>), 4 * 32768);
-#ifdef MPN_DEBUG_HOOKS
-          if (rc_attr == MPN_OK) rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<4, 2, 4, 4>), 4 * 32768);
-#endif
-          if (rc_attr == MPN_OK) rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<4, 2>), 3 * 24576);
-          if (rc_attr == MPN_OK) rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<2, 4>), 3 * 24576);
-#ifdef MPN_DEBUG_HOOKS
-          if (rc_attr == MPN_OK && nch8) rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<4, 4, 8>), 2 * 65536);
-          if (rc_attr == MPN_OK && nch8) rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<4, 2, 8>), 3 * 49152);
-          if (rc_attr == MPN_OK && nch8) rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_bf16_dma_kernel<2, 4, 8>), 3 * 49152);
-#endif
-          if (rc_attr) return rc_attr;
-        }
-        const int nx = (int)((b.P + tn - 1) / tn), ny = b.CoutP / tm;
-        b.trace = (g_bf16_trace && b.KH == g_bf16_trace_kh) ? g_bf16_trace : nullptr;
-        b.exp = g_bf16_exp;
-        const dim3 gridd((unsigned)(((nx + 7) / 8) * 8 * ny));
-        RN_FORM(nch8 ? 28 : w8 ? 29 : tm == 128 ? 22 : tn == 128 ? 21 : 23);
-#ifdef MPN_DEBUG_HOOKS
-        if (nch8 && tm == 256 && tn == 128) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<4, 2, 8>), gridd, dim3(256), LDS, s, b, nx, ny);
-        else if (nch8 && tm == 128) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<2, 4, 8>), gridd, dim3(256), LDS, s, b, nx, ny);
-        else if (nch8) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<4, 4, 8>), gridd, dim3(256), LDS, s, b, nx, ny);
-        else
-#endif
-#ifdef MPN_DEBUG_HOOKS
-        if (w8) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<4, 2, 4, 4>), gridd, dim3(512), LDS, s, b, nx, ny);
-        else
-#endif
-        if (tm == 256 && tn == 128) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<4, 2>), gridd, dim3(256), LDS, s, b, nx, ny);
-        else if (tm == 128) hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<2, 4>), gridd, dim3(256), LDS, s, b, nx, ny);
-        else hipLaunchKernelGGL((conv2d_c8i_bf16_dma_kernel<4, 4>), gridd, dim3(256), LDS, s, b, nx, ny);
-        MPN_CHECK_LAUNCH();
-        return MPN_OK;
-      }
-    }
-    dim3 grid((unsigned)(((b.P + 127) / 128 + 7) / 8 * 8 * (b.CoutP / 128)));  // pixel tiles rounded up to the 8 XCDs x cout tiles (see the kernel)
-    const long long n_tiles = (b.P + 127) / 128 * (b.CoutP / 128);
-    // small layers (layer2 / layer3 of the trunk: a few dozen tiles for 256 CUs): split K across blockIdx.z into fp32 slabs
-    {
-      const int kp = b.nch2 % 4 == 0 ? 2 : 1;
-      const int nstages = b.KH * b.KW * (b.nch2 / (2 * kp));
-      const long long nblocks = n_tiles;
-      const size_t slab = (size_t)b.CoutP * o->pitch() * sizeof(float);
-      int want = (int)std::min<long long>(nstages / 2, (g_bf16_split_target + nblocks - 1) / nblocks);
-      if (c.ws && slab) want = (int)std::min<size_t>((size_t)want, c.ws_bytes / slab); else want = 1;
-      if (g_bf16_split_target > 0 && !inv && nblocks < g_split_max_tiles && want >= 2) {
-        b.stages_per_split = (nstages + want - 1) / want;
-        const int splits = (nstages + b.stages_per_split - 1) / b.stages_per_split;
-        b.part = c.ws;
-        grid.z = (unsigned)splits;
-        RN_FORM(0x100 | (kp == 2 ? 27 : 26));
-        if (kp == 2) hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<2>), grid, dim3(256), 0, s, b);
-        else hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<1>), grid, dim3(256), 0, s, b);
-        MPN_CHECK_LAUNCH();
-        const size_t total = (size_t)b.Cb_out * (size_t)b.P * 2;
-        hipLaunchKernelGGL(conv_splitk_finalize_bf16_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, c.ws, splits, b.CoutP / 8, b.Cb_out, b.pitch_out,
-                           b.P, b.bpk, b.res, b.relu, b.out, b.norelu_cb0, b.norelu_cb1);
-        MPN_CHECK_LAUNCH();
-        return MPN_OK;
-      }
-    }
-    // 32-channel stages (32 KiB of LDS, 4-5 blocks per CU) measured 3 % faster than 64-channel ones on ResNet-50; either way this
-    // kernel is bound by its operand loads (64 FLOP per loaded byte at a 128 x 128 tile), not by the bf16 matrix pipe
-    RN_FORM(b.nch2 % 4 == 0 ? 27 : 26);
-    if (b.nch2 % 4 == 0) hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<2>), grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<1>), grid, dim3(256), 0, s, b);
-    MPN_CHECK_LAUNCH();
-    return MPN_OK;
-  }
-  GConvArgs a{};
-  a.in = in.p; a.wpk = c.wpk; a.bpk = c.bpk; a.res = res; a.out = out;
-  a.B = in.B; a.Cb_in = in.Cb(); a.H = in.H; a.W = in.W; a.nch = (c.Cin + 7) / 8;
+// the fields GConvArgs and GConvArgsB share, from the layer and its input; *o = the output batch
+template <class Args>
+static int conv_geometry(const RnConv &c, const ActI &in, float *out, int relu, Args &a, ActI *o) {
+  a.B = in.B; a.H = in.H; a.W = in.W;
   a.CoutP = round_up(c.Cout, 128); a.Cb_out = (c.Cout + 7) / 8;
   a.KH = c.KH; a.KW = c.KW; a.sh = c.sh; a.sw = c.sw; a.ph = c.ph; a.pw = c.pw;
   a.OH = (in.H + 2 * c.ph - c.KH) / c.sh + 1; a.OW = (in.W + 2 * c.pw - c.KW) / c.sw + 1;
@@ -2860,16 +2683,232 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
   a.P = (long long)in.B * a.OH * a.OW;
   *o = ActI{out, in.B, c.Cout, a.OH, a.OW};
   a.pitch_in = in.pitch(); a.pitch_out = o->pitch();
+  return MPN_OK;
+}
+
+// Split K across blockIdx.z into fp32 slabs of `slab` bytes in the layer's workspace, for small layers (layer2 / layer3 of the trunk: a few
+// dozen 128 x 128 tiles for 256 CUs).  splits == 1: no split (a split plan always has >= 2: want <= nstages / 2).
+struct SplitK { int splits, stages_per_split; };
+static SplitK plan_split_k(int nstages, long long n_tiles, size_t slab, const RnConv &c, bool inv) {
+  int want = (int)std::min<long long>(nstages / 2, (g_bf16_split_target + n_tiles - 1) / n_tiles);
+  if (c.ws && slab) want = (int)std::min<size_t>((size_t)want, c.ws_bytes / slab); else want = 1;
+  if (!(g_bf16_split_target > 0 && !inv && n_tiles < g_split_max_tiles && want >= 2)) return {1, 0};
+  const int stages_per_split = (nstages + want - 1) / want;
+  return {(nstages + stages_per_split - 1) / stages_per_split, stages_per_split};
+}
+
+// round 4: the B-direct kernel (128 couts x 256 pixels; pixels straight into registers), where both tensors fit a 2-GiB descriptor
+// Where it measured faster, layer by layer against the LDS-DMA kernel on the per-ROI layers of configs[3] / [4] (tools/bench_conv_bf16.py,
+// profiles/r04_bf16_conv_bdirect.txt): convolutions with spatial taps at stride 1 (every pixel record is re-read once per tap, from
+// the CU's own cache: 1x3 / 3x1 -17 %, 3x3 -21 %, 1x7 / 7x1 -10 %), strided 3x3 with >= 512 input channels (-4 %), and pointwise
+// layers with Cin >= 2 Cout (2048 -> 512: -9 %).  NOT on pointwise layers with many output channels (512 -> 2048 + residual: +9 %:
+// its 128-cout tile re-reads the pixel tile twice as often as the 256-cout LDS-DMA shape), nor on strided pointwise layers
+// (every second record of a row: half-used cache lines per fragment load, +26 %).  A rule of the layer alone, never of the batch.
+static bool bdir_eligible(const RnConv &c, const GConvArgsB &b) {
+  const bool pointwise = b.KH == 1 && b.KW == 1, strided = b.sh > 1 || b.sw > 1;
+  const bool bdir_wins = pointwise ? (!strided && c.Cin >= 2 * c.Cout) : (!strided || c.Cin >= 512);
+  return g_bf16_bdir && (g_bf16_bdir == 2 || bdir_wins || knock_first()) && (size_t)b.nch2 * b.pitch_in * 16 < ((size_t)1 << 31) &&
+         (size_t)b.KH * b.KW * b.nch2 * b.CoutP * 16 < ((size_t)1 << 31);
+}
+
+struct ConvTile { int tm, tn; ConvForm form; };  // a large-layer bf16 kernel's tile, couts x pixels
+static bool dma_w8(const GConvArgsB &b) { return g_bf16_dma_tn == 2256 && b.CoutP % 256 == 0; }  // (hook) the 8-wave 256 x 256 shape: bit-identical, measured no faster than the per-layer pick (ResNet towers 1.95 vs 1.89 ms: 1.5 block rounds on 49 000 pixels), debug flavour only
+// The LDS-DMA kernel's tile shape for a layer (nullptr: none fits, or none the dma_tn hook allows): cost of a shape = block-rounds over the
+// 256 CUs x work per block (the two 3-ring shapes run two blocks per CU at half speed each: the same count); 256-cout tiles need whole
+// 256-row weight tiles
+static const ConvTile *pick_dma_shape(const GConvArgsB &b) {
+  static const ConvTile shapes[3] = {{256, 128, CF_DMA_256x128}, {128, 256, CF_DMA_128x256}, {256, 256, CF_DMA_256x256}};  // ties go to the earlier entry
+  const bool w8 = dma_w8(b);
+  const ConvTile *best = nullptr;
+  long long best_cost = 0;
+  for (const ConvTile &sh : shapes) {
+    if (sh.tm == 256 && b.CoutP % 256 != 0) continue;
+    if (w8 && !(sh.tm == 256 && sh.tn == 256)) continue;
+    if (!w8 && g_bf16_dma_tn && !(sh.tn == g_bf16_dma_tn % 1000 && sh.tm == (g_bf16_dma_tn >= 1000 ? 128 : 256))) continue;
+    const long long nb = (b.P + sh.tn - 1) / sh.tn * (b.CoutP / sh.tm);
+    const long long cost = (nb + 255) / 256 * sh.tm * sh.tn;
+    if (!best || cost < best_cost) { best = &sh; best_cost = cost; }
+  }
+  return best;
+}
+// one LDS-DMA launch (the caller checks it); lds = ring depth x stage bytes (as in the kernel), also the instantiation's dynamic-LDS limit
+static int launch_dma(void (*kernel)(GConvArgsB, int, int), int threads, int lds, const GConvArgsB &b, int nx, int ny, hipStream_t s) {
+  { int rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(kernel), lds); if (rc_attr) return rc_attr; }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(((nx + 7) / 8) * 8 * ny)), dim3(threads), lds, s, b, nx, ny);
+  return MPN_OK;
+}
+
+#ifdef MPN_DEBUG_HOOKS
+// Debug flavour only: the experiments that can take a B-direct / an LDS-DMA launch over (timing tools, tests/test_gpu_resnet.py), given the
+// filled arguments, the tile and the grid numbers of the product launch (bf16_experiment).  *launched: it ran a kernel and set its form; else
+// the product launch follows.
+static int bdir_experiment(const GConvArgsB &b, int nx, int ny, hipStream_t s, bool *launched) {
+  const dim3 gridd((unsigned)(((nx + 7) / 8) * 8 * ny));
+  *launched = true;
+  if (g_knock_arm > 0 && (g_tower_knock & 2)) {
+    --g_knock_arm;
+    hipLaunchKernelGGL((conv2d_c8i_bf16_bdir_kernel<3, 32 | 512>), gridd, dim3(256), 0, s, b, nx, ny);
+  } else if (g_bf16_bdir_ver == 9) {
+    RN_FORM(CF_BDPP);
+    const int nxq = (nx + 7) / 8;
+    const dim3 gridp((unsigned)(8 * ((nxq * ny + 1) / 2)));
+    hipLaunchKernelGGL((conv2d_c8i_bf16_bdpp_kernel<3>), gridp, dim3(512), 0, s, b, nx, ny);
+  } else if (g_bf16_bdir_ver == 8) {
+    RN_FORM(CF_BDIR8);
+    const int ny8 = (b.CoutP + 255) / 256;
+    const dim3 grid8((unsigned)(((nx + 7) / 8) * 8 * ny8));
+    switch (g_bf16_bdir_abl) {
+#ifdef MPN_BF16_ABLATE
+#define MPN_BDIR8_ABL(v) case v: hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<4, v>), grid8, dim3(512), 0, s, b, nx, ny8); break;
+    MPN_BDIR8_ABL(1) MPN_BDIR8_ABL(2) MPN_BDIR8_ABL(8) MPN_BDIR8_ABL(16) MPN_BDIR8_ABL(32) MPN_BDIR8_ABL(7) MPN_BDIR8_ABL(23) MPN_BDIR8_ABL(24)
+#undef MPN_BDIR8_ABL
+#endif
+    case 1000: hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<8>), grid8, dim3(512), 0, s, b, nx, ny8); break;
+    case 1001: hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<6>), grid8, dim3(512), 0, s, b, nx, ny8); break;
+    default: hipLaunchKernelGGL((conv2d_c8i_bf16_bdir8_kernel<4>), grid8, dim3(512), 0, s, b, nx, ny8);
+    }
+  } else if (g_bf16_bdir_ver == 2 || g_bf16_bdir_ver == 3) {
+    RN_FORM(g_bf16_bdir_ver == 2 ? CF_BDIR2_DS3 : CF_BDIR2_DS4);
+    if (g_bf16_bdir_ver == 2) hipLaunchKernelGGL((conv2d_c8i_bf16_bdir2_kernel<3>), gridd, dim3(256), 0, s, b, nx, ny);
+    else hipLaunchKernelGGL((conv2d_c8i_bf16_bdir2_kernel<4>), gridd, dim3(256), 0, s, b, nx, ny);
+  } else {
+    RN_FORM(CF_BDIR);  // the product kernel with parts knocked out (-DMPN_BF16_ABLATE builds only)
+    switch (g_bf16_bdir_abl) {
+#ifdef MPN_BF16_ABLATE
+#define MPN_BDIR_ABL(v) case v: hipLaunchKernelGGL((conv2d_c8i_bf16_bdir_kernel<3, v>), gridd, dim3(256), 0, s, b, nx, ny); break;
+    MPN_BDIR_ABL(1) MPN_BDIR_ABL(2) MPN_BDIR_ABL(4) MPN_BDIR_ABL(8) MPN_BDIR_ABL(16) MPN_BDIR_ABL(32) MPN_BDIR_ABL(7) MPN_BDIR_ABL(23) MPN_BDIR_ABL(6) MPN_BDIR_ABL(24) MPN_BDIR_ABL(36) MPN_BDIR_ABL(64) MPN_BDIR_ABL(192) MPN_BDIR_ABL(194) MPN_BDIR_ABL(198) MPN_BDIR_ABL(70) MPN_BDIR_ABL(256)
+#undef MPN_BDIR_ABL
+#endif
+    default: *launched = false;
+    }
+  }
+  if (*launched) MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+static int dma_experiment(const GConvArgsB &b, const ConvTile &sh, int nx, int ny, hipStream_t s, bool *launched) {
+  int rc = MPN_OK;
+  *launched = true;
+  if (g_bf16_nch == 8 && b.nch2 % 8 == 0) {  // 64-channel stages measured 12 % SLOWER (one block per CU: tools/bench_conv_bf16.py, profiles/r04_bf16_conv_ablation.txt)
+    RN_FORM(CF_DMA_NCH8);
+    if (sh.tm == 256 && sh.tn == 128) rc = launch_dma(conv2d_c8i_bf16_dma_kernel<4, 2, 8>, 256, 3 * 49152, b, nx, ny, s);
+    else if (sh.tm == 128) rc = launch_dma(conv2d_c8i_bf16_dma_kernel<2, 4, 8>, 256, 3 * 49152, b, nx, ny, s);
+    else rc = launch_dma(conv2d_c8i_bf16_dma_kernel<4, 4, 8>, 256, 2 * 65536, b, nx, ny, s);
+  } else if (dma_w8(b)) {
+    RN_FORM(CF_DMA_W8);
+    rc = launch_dma(conv2d_c8i_bf16_dma_kernel<4, 2, 4, 4>, 512, 4 * 32768, b, nx, ny, s);
+  } else {
+    *launched = false;
+  }
+  if (rc == MPN_OK && *launched) MPN_CHECK_LAUNCH();
+  return rc;
+}
+static int bf16_experiment(const GConvArgsB &b, const ConvTile &tile, int nx, int ny, hipStream_t s, bool *launched) {
+  return tile.form == CF_BDIR ? bdir_experiment(b, nx, ny, s, launched) : dma_experiment(b, tile, nx, ny, s, launched);
+}
+#endif
+
+static int rn_conv_bf16(const RnConv &c, ActI in, float *out, const float *res, int relu, hipStream_t s, ActI *o, bool inv) {
+  GConvArgsB b{};
+  b.in = reinterpret_cast<const bf16_t *>(in.p); b.wpk = c.wpk16; b.res = reinterpret_cast<const bf16_t *>(res); b.bpk = c.bpk;
+  b.out = reinterpret_cast<bf16_t *>(out);
+  b.nch2 = round_up((c.Cin + 7) / 8, 2);
+  b.trace = (g_bf16_trace && c.KH == g_bf16_trace_kh) ? g_bf16_trace : nullptr; b.exp = g_bf16_exp;  // read by the LDS-DMA kernel only
+  { int rc = conv_geometry(c, in, out, relu, b, o); if (rc) return rc; }
+  // large layers with 32-channel stages: the B-direct kernel where it wins, else the LDS-DMA kernel (32-bit record offsets) at the tile
+  // shape picked per layer; every other layer: the 128 x 128 kernel
+  static const ConvTile bdir_tile = {128, 256, CF_BDIR};
+  const bool large = g_bf16_dma && b.nch2 % 4 == 0 && b.P >= (g_bf16_dma == 2 ? 1 : 256 * 128);
+  const ConvTile *tile = nullptr;
+  if (large && bdir_eligible(c, b)) tile = &bdir_tile;
+  else if (large && (size_t)in.B * in.H * in.W * 16 < ((size_t)1 << 32)) tile = pick_dma_shape(b);
+  int form = tile ? tile->form : b.nch2 % 4 == 0 ? CF_B_KP2 : CF_B_KP1;
+  if (tile) {
+    const int nx = (int)((b.P + tile->tn - 1) / tile->tn), ny = b.CoutP / tile->tm;
+#ifdef MPN_DEBUG_HOOKS
+    bool launched = false;
+    if (int rc = bf16_experiment(b, *tile, nx, ny, s, &launched); rc || launched) return rc;
+#endif
+    int rc = MPN_OK;  // LDS-DMA: a ring of four stages of 256 + 256 rows, or of three of 384
+    switch (form) {
+    case CF_BDIR: hipLaunchKernelGGL((conv2d_c8i_bf16_bdir_kernel<3>), dim3((unsigned)(((nx + 7) / 8) * 8 * ny)), dim3(256), 0, s, b, nx, ny); break;
+    case CF_DMA_256x256: rc = launch_dma(conv2d_c8i_bf16_dma_kernel<4, 4>, 256, 4 * 32768, b, nx, ny, s); break;
+    case CF_DMA_256x128: rc = launch_dma(conv2d_c8i_bf16_dma_kernel<4, 2>, 256, 3 * 24576, b, nx, ny, s); break;
+    default: rc = launch_dma(conv2d_c8i_bf16_dma_kernel<2, 4>, 256, 3 * 24576, b, nx, ny, s);  // CF_DMA_128x256
+    }
+    if (rc) return rc;
+  } else {
+    // 32-channel stages (32 KiB of LDS, 4-5 blocks per CU) measured 3 % faster than 64-channel ones on ResNet-50; either way this
+    // kernel is bound by its operand loads (64 FLOP per loaded byte at a 128 x 128 tile), not by the bf16 matrix pipe
+    const int kp = form == CF_B_KP2 ? 2 : 1;
+    dim3 grid((unsigned)(((b.P + 127) / 128 + 7) / 8 * 8 * (b.CoutP / 128)));  // pixel tiles rounded up to the 8 XCDs x cout tiles (see the kernel)
+    const SplitK sk = plan_split_k(b.KH * b.KW * (b.nch2 / (2 * kp)), (b.P + 127) / 128 * (b.CoutP / 128), (size_t)b.CoutP * o->pitch() * sizeof(float), c, inv);
+    if (sk.splits > 1) {
+      b.stages_per_split = sk.stages_per_split;
+      b.part = c.ws;
+      grid.z = (unsigned)sk.splits;
+      form |= CF_SPLIT;
+    }
+    if (kp == 2) hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<2>), grid, dim3(256), 0, s, b);
+    else hipLaunchKernelGGL((conv2d_c8i_bf16_kernel<1>), grid, dim3(256), 0, s, b);
+    if (sk.splits > 1) {
+      MPN_CHECK_LAUNCH();
+      const size_t total = (size_t)b.Cb_out * (size_t)b.P * 2;
+      hipLaunchKernelGGL(conv_splitk_finalize_bf16_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, c.ws, sk.splits, b.CoutP / 8, b.Cb_out,
+                         b.pitch_out, b.P, b.bpk, b.res, b.relu, b.out, b.norelu_cb0, b.norelu_cb1);
+    }
+  }
+  RN_FORM(form);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// the form of an fp32 layer: the mosaic, the GEMM forms where the layer is one (allow_gemm), else the generic kernel by channel count
+static ConvForm pick_fp32_form(const RnConv &c, const ActI &in, const float *res, bool allow_gemm, bool inv) {
   // Row invariance on the mosaic: the F(2x2,3x3) kernel's rounding depends on a pixel's position inside its 2x2 output tile, and ROI b
   // sits at ((b / mx) * (H + 1) + 1, (b % mx) * (W + 1) + 1) — the same tile phase for every b only when both cell pitches are EVEN
   // (7x7 maps: pitch 8).  Even map sizes (pooled 16 -> 8x8 maps, pitch 9) would make a row depend on its index in the batch: those take
   // the generic kernel whenever rows must not depend on the batch (inv).
   const bool mos_phase_ok = ((in.H + 1) % 2 == 0) && ((in.W + 1) % 2 == 0);
+  // per-ROI 3x3 / stride-1 convolution (layer4's conv2 of blocks 2, 3): the batch as a mosaic image on the Winograd kernel
   if (c.wino && c.mos_in && !res && (inv || in.B > 1) && (!inv || mos_phase_ok) && in.H == c.mos_h && in.W == c.mos_w && c.norelu_c1 == c.norelu_c0 && (g_graph_fuse & 128) &&
-      ((in.B + c.mos_mx - 1) / c.mos_mx) * (in.H + 1) <= c.mos_rows) {
-    // per-ROI 3x3 / stride-1 convolution (layer4's conv2 of blocks 2, 3): the batch as a mosaic image on the Winograd kernel
+      ((in.B + c.mos_mx - 1) / c.mos_mx) * (in.H + 1) <= c.mos_rows)
+    return CF_MOSAIC;
+  if (allow_gemm && c.col_w && in.planar && in.B == 1 && in.C == 3 && !res && c.norelu_c1 == c.norelu_c0 && (g_graph_fuse & 16)) return CF_IM2COL;
+  // a pointwise convolution on 1x1 maps is a fully-connected layer (AlexNet's fc7): few row tiles, so the GEMM's split-K form
+  // with its row-invariant segments rather than a 128-pixel-tile convolution (the un-split form folds at the same segments)
+  if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && !res && in.H == 1 && in.W == 1 && (g_graph_fuse & 8) &&
+      (inv || !linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch())))
+    return CF_GEMM_FC;
+  // same rows in and out: the tuned GEMM, residual + ReLU fused
+  if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && (inv || linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch()))) return inv ? CF_GEMM_RI : CF_GEMM_DIRECT;
+  // the generic kernel, 8-channel chunks per stage by what divides the channel count; 32-channel stages: the LDS-DMA / hand-pipelined
+  // kernel (32-bit gather offsets: the input batch must stay under 4 GiB)
+  const int nch = (c.Cin + 7) / 8;
+  const bool pf_ok = g_fp32_pf && (size_t)in.B * in.H * in.W * 32 < ((size_t)1 << 32);
+  return nch % 4 == 0 ? (pf_ok ? CF_PF : CF_KC4) : nch % 3 == 0 ? CF_KC3 : nch % 2 == 0 ? CF_KC2 : CF_KC1;
+}
+
+static int rn_conv_fp32(const RnConv &c, ActI in, float *out, const float *res, int relu, hipStream_t s, ActI *o, bool allow_gemm, bool inv) {
+  GConvArgs a{};
+  a.in = in.p; a.wpk = c.wpk; a.bpk = c.bpk; a.res = res; a.out = out;
+  a.Cb_in = in.Cb(); a.nch = (c.Cin + 7) / 8;
+  { int rc = conv_geometry(c, in, out, relu, a, o); if (rc) return rc; }
+  const ConvForm form = pick_fp32_form(c, in, res, allow_gemm, inv);
+  dim3 grid((unsigned)(((a.P + 127) / 128 + 7) / 8 * 8 * (a.CoutP / 128)));  // pixel tiles rounded up to the 8 XCDs x cout tiles (see the kernel)
+  SplitK sk{1, 0};
+  if (form <= CF_PF) {  // the generic kernel: small layers split K (as the bf16 graph does)
+    const int kc = form == CF_PF ? 4 : (int)form;  // 8-channel chunks per stage
+    sk = plan_split_k(a.KH * a.KW * (a.nch / kc), (a.P + 127) / 128 * (a.CoutP / 128), (size_t)a.CoutP * o->pitch() * sizeof(float), c, inv);
+    if (sk.splits > 1) {
+      a.stages_per_split = sk.stages_per_split;
+      a.part = c.ws;
+      grid.z = (unsigned)sk.splits;
+    }
+  }
+  RN_FORM(form | (sk.splits > 1 ? CF_SPLIT : 0));
+  switch (form) {
+  case CF_MOSAIC: {
     const int rows = ((in.B + c.mos_mx - 1) / c.mos_mx) * (in.H + 1);
-    RN_FORM(10);
     const int Hp = act_hp(c.mos_rows), Wp = act_wp(c.mos_cols);
     const size_t recs = (size_t)in.B * in.H * in.W;
     hipLaunchKernelGGL(c8i_to_mosaic_kernel, dim3((unsigned)cdiv_sz(recs * in.Cb() * 2, 256)), dim3(256), 0, s, in.p, in.Cb(), in.B, in.H, in.W, in.pitch(), c.mos_mx, Hp, Wp,
@@ -2883,9 +2922,8 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
     MPN_CHECK_LAUNCH();
     return MPN_OK;
   }
-  if (allow_gemm && c.col_w && in.planar && in.B == 1 && in.C == 3 && !res && c.norelu_c1 == c.norelu_c0 && (g_graph_fuse & 16)) {
+  case CF_IM2COL: {
     const int Kc = c.KH * c.KW * 3, nkb = round_up(Kc, 64) / 8;
-    RN_FORM(11);
     const size_t need = (size_t)nkb * o->pitch() * 8 * sizeof(float);
     void *col = nullptr;
     { int rc_ws = scratch_get(SCR_IM2COL, need, s, &col); if (rc_ws) return rc_ws; }
@@ -2894,56 +2932,41 @@ static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int r
     MPN_CHECK_LAUNCH();
     return linear_c8(static_cast<const float *>(col), (int)a.P, Kc, c.col_w, c.col_b, c.Cout, relu, out, nullptr, s, (int)o->pitch());
   }
-  // a pointwise convolution on 1x1 maps is a fully-connected layer (AlexNet's fc7): few row tiles, so the GEMM's split-K form
-  // with its row-invariant segments rather than a 128-pixel-tile convolution (the un-split form folds at the same segments)
-  if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && !res && in.H == 1 && in.W == 1 && (g_graph_fuse & 8) &&
-      (inv || !linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch()))) {
-    RN_FORM(12);
+  case CF_GEMM_FC:
     return linear_c8(in.p, (int)in.rows(), c.Cin, c.lin_w, c.lin_b, c.Cout, relu, out, nullptr, s, (int)in.pitch(), nullptr, 1);
-  }
-  if (allow_gemm && c.lin_w && c.norelu_c1 == c.norelu_c0 && (inv || linear_c8_is_direct((int)in.rows(), c.Cout, (int)in.pitch()))) {  // same rows in and out: the tuned GEMM, residual + ReLU fused
-    RN_FORM(inv ? 14 : 13);
+  case CF_GEMM_DIRECT: case CF_GEMM_RI:
     return linear_c8(in.p, (int)in.rows(), c.Cin, c.lin_w, c.lin_b, c.Cout, relu, out, nullptr, s, (int)in.pitch(), res, inv ? 2 : 0);
+  case CF_PF: {
+    constexpr size_t PF_LDS = (size_t)2 * 2 * 4 * 128 * 8 * sizeof(float);
+    { int rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_pf_kernel), (int)PF_LDS); if (rc_attr) return rc_attr; }
+    hipLaunchKernelGGL(conv2d_c8i_pf_kernel, grid, dim3(256), PF_LDS, s, a);
+    break;
   }
-  dim3 grid((unsigned)(((a.P + 127) / 128 + 7) / 8 * 8 * (a.CoutP / 128)));  // pixel tiles rounded up to the 8 XCDs x cout tiles (see the kernel)
-  // 32-channel stages: the LDS-DMA / hand-pipelined kernel (32-bit gather offsets: the input batch must stay under 4 GiB)
-  constexpr size_t PF_LDS = (size_t)2 * 2 * 4 * 128 * 8 * sizeof(float);
-  const bool pf_ok = g_fp32_pf && (size_t)in.B * in.H * in.W * 32 < ((size_t)1 << 32);
-  { int rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(conv2d_c8i_pf_kernel), (int)PF_LDS); if (rc_attr) return rc_attr; }
-  {  // small layers: split K across blockIdx.z into fp32 slabs (as the bf16 graph does)
-    const int kc = a.nch % 4 == 0 ? 4 : a.nch % 3 == 0 ? 3 : a.nch % 2 == 0 ? 2 : 1;  // 8-channel chunks per stage
-    const int nstages = a.KH * a.KW * (a.nch / kc);
-    const long long n_tiles = (a.P + 127) / 128 * (a.CoutP / 128);
-    const size_t slab = (size_t)a.CoutP * o->pitch() * sizeof(float);
-    int want = (int)std::min<long long>(nstages / 2, (g_bf16_split_target + n_tiles - 1) / n_tiles);
-    if (c.ws && slab) want = (int)std::min<size_t>((size_t)want, c.ws_bytes / slab); else want = 1;
-    if (g_bf16_split_target > 0 && !inv && n_tiles < g_split_max_tiles && want >= 2) {
-      a.stages_per_split = (nstages + want - 1) / want;
-      const int splits = (nstages + a.stages_per_split - 1) / a.stages_per_split;
-      a.part = c.ws;
-      grid.z = (unsigned)splits;
-      RN_FORM(0x100 | (kc == 4 && pf_ok ? 5 : kc));
-      if (kc == 4 && pf_ok) hipLaunchKernelGGL(conv2d_c8i_pf_kernel, grid, dim3(256), PF_LDS, s, a);
-      else if (kc == 4) hipLaunchKernelGGL((conv2d_c8i_kernel<4>), grid, dim3(256), 0, s, a);
-      else if (kc == 3) hipLaunchKernelGGL((conv2d_c8i_kernel<3>), grid, dim3(256), 0, s, a);
-      else if (kc == 2) hipLaunchKernelGGL((conv2d_c8i_kernel<2>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((conv2d_c8i_kernel<1>), grid, dim3(256), 0, s, a);
-      MPN_CHECK_LAUNCH();
-      const size_t total = (size_t)a.Cb_out * (size_t)a.P * 2;
-      hipLaunchKernelGGL(conv_splitk_finalize_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, c.ws, splits, a.CoutP / 8, a.Cb_out, a.pitch_out, a.P,
-                         a.bpk, a.res, a.relu, a.out, a.norelu_cb0, a.norelu_cb1);
-      MPN_CHECK_LAUNCH();
-      return MPN_OK;
-    }
+  case CF_KC4: hipLaunchKernelGGL((conv2d_c8i_kernel<4>), grid, dim3(256), 0, s, a); break;
+  case CF_KC3: hipLaunchKernelGGL((conv2d_c8i_kernel<3>), grid, dim3(256), 0, s, a); break;
+  case CF_KC2: hipLaunchKernelGGL((conv2d_c8i_kernel<2>), grid, dim3(256), 0, s, a); break;
+  default: hipLaunchKernelGGL((conv2d_c8i_kernel<1>), grid, dim3(256), 0, s, a);
   }
-  RN_FORM(a.nch % 4 == 0 && pf_ok ? 5 : a.nch % 4 == 0 ? 4 : a.nch % 3 == 0 ? 3 : a.nch % 2 == 0 ? 2 : 1);
-  if (a.nch % 4 == 0 && pf_ok) hipLaunchKernelGGL(conv2d_c8i_pf_kernel, grid, dim3(256), PF_LDS, s, a);
-  else if (a.nch % 4 == 0) hipLaunchKernelGGL((conv2d_c8i_kernel<4>), grid, dim3(256), 0, s, a);
-  else if (a.nch % 3 == 0) hipLaunchKernelGGL((conv2d_c8i_kernel<3>), grid, dim3(256), 0, s, a);
-  else if (a.nch % 2 == 0) hipLaunchKernelGGL((conv2d_c8i_kernel<2>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((conv2d_c8i_kernel<1>), grid, dim3(256), 0, s, a);
   MPN_CHECK_LAUNCH();
+  if (sk.splits > 1) {
+    const size_t total = (size_t)a.Cb_out * (size_t)a.P * 2;
+    hipLaunchKernelGGL(conv_splitk_finalize_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, c.ws, sk.splits, a.CoutP / 8, a.Cb_out, a.pitch_out, a.P,
+                       a.bpk, a.res, a.relu, a.out, a.norelu_cb0, a.norelu_cb1);
+    MPN_CHECK_LAUNCH();
+  }
   return MPN_OK;
+}
+
+// per_roi: the batch axis counts ROIs (the head of a graph model).  A ROI's result must not depend on which other ROIs share the
+// launch (memoryEfficientForward's chunked == full, ImageDetect.lua:126-133; the ROI-sharded mode == the unsharded one), so for
+// these layers everything that changes the summation ORDER is a function of the layer alone, never of in.B: no split-K (every
+// kernel family below accumulates K = (tap, channel chunk) in ONE chain per output, and the bf16 tile shapes / the small and the
+// LDS-DMA kernel share that chain bit for bit), pointwise convolutions always on the un-split GEMM, eligible 3x3 convolutions
+// always on the Winograd mosaic with a batch-independent launch plan.  Tile shapes may still follow the batch size.
+static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int relu, hipStream_t s, ActI *o, bool allow_gemm = true, bool per_roi = false) {
+  const bool inv = per_roi && g_roi_invariant;
+  if (c.wpk16) return rn_conv_bf16(c, in, out, res, relu, s, o, inv);  // bf16 graph
+  return rn_conv_fp32(c, in, out, res, relu, s, o, allow_gemm, inv);
 }
 
 // one residual block: y = relu(conv_n(... relu(conv_1(x))) + shortcut(x)); buffers b[0..3] rotate, x may live in any of them

@@ -28,14 +28,15 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-KNOB_DEFAULTS = dict(fp32_pf=1, bf16_dma=1, bf16_dma_tn=0, bf16_bdir=1, bf16_split_target=256, split_max_tiles=192, graph_fuse=511,
-                     roi_invariant=1)
+KNOB_DEFAULTS = dict(fp32_pf=1, bf16_dma=1, bf16_dma_tn=0, bf16_bdir=1, bf16_bdir_ver=1, bf16_split_target=256, split_max_tiles=192,
+                     graph_fuse=511, roi_invariant=1)
 SENT32, SENT16 = 0x7FA5A5A5, 0x7FA5
 NOSPLIT = dict(bf16_split_target=0)
 
-# form ids (mpn_debug_conv_last_form): rn_conv's comment in resnet.hip
+# form ids (mpn_debug_conv_last_form): enum ConvForm in resnet.hip
 KC1, KC2, KC3, KC4, PF, MOSAIC, IM2COL, GEMM_FC, GEMM_DIRECT, GEMM_RI = 1, 2, 3, 4, 5, 10, 11, 12, 13, 14
 BDIR, DMA_256x128, DMA_128x256, DMA_256x256, B_KP1, B_KP2 = 20, 21, 22, 23, 26, 27
+DMA_W8, BDIR8 = 29, 38  # debug-flavour experiments: the 8-wave LDS-DMA shape, the 256-cout B-direct kernel
 SPLIT = 0x100
 GEMM_FORMS = (IM2COL, GEMM_FC, GEMM_DIRECT, GEMM_RI)
 # what a form leaves in the rows from P up to the pitch of its output planes: every form, the GEMM ones included, stores only rows < P
@@ -43,7 +44,7 @@ GEMM_FORMS = (IM2COL, GEMM_FC, GEMM_DIRECT, GEMM_RI)
 PAD_ROWS = {}
 # ReLU(NaN) per form: the fp32 convolution kernels and the GEMM keep NaN (t < 0 ? 0 : t); the Winograd mosaic and every bf16 form give 0
 RELU_NAN = {MOSAIC: 0.0}
-for _f in (BDIR, DMA_256x128, DMA_128x256, DMA_256x256, B_KP1, B_KP2):
+for _f in (BDIR, DMA_256x128, DMA_128x256, DMA_256x256, B_KP1, B_KP2, DMA_W8, BDIR8):
     RELU_NAN[_f] = RELU_NAN[_f | SPLIT] = 0.0
 
 
@@ -103,6 +104,9 @@ CASES = {
     "b_dma_128x256": (DMA_128x256, 1, dict(bf16_dma=2, bf16_bdir=0, bf16_dma_tn=1256), _s(2, 32, 8, 8, 129)),
     "b_dma_256x256": (DMA_256x256, 1, dict(bf16_dma=2, bf16_bdir=0, bf16_dma_tn=256), _s(2, 2048, 7, 7, 512, 1)),
     "b_dma_256x256_7x7s2": (DMA_256x256, 1, dict(bf16_dma=2, bf16_bdir=0, bf16_dma_tn=256), _s(1, 64, 17, 17, 256, 7, sh=2, ph=3, pw=3)),
+    # debug-flavour experiments (bit-identical to the product forms): cout count a multiple of 256; ragged 256-cout and pixel tiles
+    "b_dma_w8": (DMA_W8, 1, dict(bf16_dma=2, bf16_bdir=0, bf16_dma_tn=2256), _s(2, 64, 8, 8, 256, 1)),
+    "b_bdir8_c257": (BDIR8, 1, dict(bf16_dma=2, bf16_bdir=2, bf16_bdir_ver=8), _s(2, 64, 7, 7, 257)),
     # the default dispatch across the 32 768-pixel threshold of a per-ROI layer (7x7 maps: B = 668 -> 32 732 px, B = 669 -> 32 781 px)
     "b_roi_668_small": (B_KP2, 1, {}, _s(668, 64, 7, 7, 192), dict(per_roi=1)),
     "b_roi_669_bdir": (BDIR, 1, {}, _s(669, 64, 7, 7, 192), dict(per_roi=1)),
@@ -429,7 +433,7 @@ def test_accuracy(name, kind, O):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 EDGE = ["kc1_cin5", "kc2_cin9_1x7", "kc3_cin24_3x3s2p0", "kc4_cin32_3x3p2", "pf_cin64", "split_pf", "split_kc1", "gemm_ri2_res",
         "gemm_fc_1x1maps", "im2col_7x7s2", "b_kp1_cin40", "b_kp2_cin64_5x5", "b_split_kp2", "b_split_kp1_5x5", "b_bdir_1x3_c200",
-        "b_bdir_3x1_c60", "b_dma_256x128", "b_dma_128x256", "b_dma_256x256_7x7s2"]
+        "b_bdir_3x1_c60", "b_dma_256x128", "b_dma_128x256", "b_dma_256x256_7x7s2", "b_dma_w8", "b_bdir8_c257"]
 
 
 def edge_operands(name, seed):
@@ -564,7 +568,7 @@ def test_roi_invariance_bf16_threshold(planted):
 
 
 RUN_TWICE = ["kc1_cin5", "kc3_cin65_7x1", "pf_cin64", "split_pf", "split_kc2_11x11s4", "split_kc4", "gemm_fc_1x1maps", "im2col_11x11s4",
-             "mosaic_8x8", "b_kp1_cin40", "b_split_kp2", "b_split_kp1_5x5", "b_bdir_c257", "b_dma_256x256_7x7s2", "b_dma_128x256"]
+             "mosaic_8x8", "b_kp1_cin40", "b_split_kp2", "b_split_kp1_5x5", "b_bdir_c257", "b_dma_256x256_7x7s2", "b_dma_128x256", "b_dma_w8", "b_bdir8_c257"]
 
 
 @pytest.mark.parametrize("name", RUN_TWICE)
