@@ -602,6 +602,51 @@ int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_targets);
  * returns MPN_EINVAL.  A refused call changes nothing. */
 int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fine-tuning the Fast R-CNN head on the device, trunk frozen (train.lua:154-158, BatchProviderROI.lua:125-131,
+ * BBoxRegressionCriterion.lua, engines/Optim.lua)
+ * ------------------------------------------------------------------------------------------------
+ * Only a plain VGG Fast R-CNN handle (mpn_frcnn_create, fc_arith == MPN_FC_FP32) trains: fc6, fc7 and the fused cls + bbox head.
+ * MultiPathNet, ResNet and op-list handles, MPN_FC_SPLIT3 handles, a handle with an image pyramid or augmentation on, and a handle
+ * whose pipelined tail is still pending (until mpn_frcnn_flush) answer MPN_ESTATE with a message naming what refused.
+ * What is built is the reference's opt.train_remove_dropouts = true configuration: NO dropout, so a step is deterministic — the
+ * same calls on the same inputs give the same bits (fixed summation orders, no atomics).
+ *
+ *   mpn_frcnn_train_begin  allocates one zeroed momentum buffer per trained tensor, in the packed layout of its weight (fc6's, as
+ *                          large as fc6's weights, only at depth MPN_TRAIN_FC6), and the gradient scratch.  A second begin without an
+ *                          end: MPN_ESTATE.
+ *   mpn_frcnn_train_add    appends one image's n rows to the pending minibatch (total rows <= max_rois, MPN_EINVAL beyond): getImages'
+ *                          rescale and the frozen trunk exactly as mpn_frcnn_detect runs them, the ROI projection, the ROI pooling of
+ *                          these rows into the minibatch's fc6 operand behind the rows already pending (a buffer of its own: a detect between two
+ *                          training calls disturbs nothing); d_rois / d_gt / d_labels are copied.  Boxes are
+ *                          in the ORIGINAL image's coordinates, as detect takes them; d_gt[i] is the ground-truth box row i regresses to
+ *                          (read only where d_labels[i] > 0).  Flip on the caller's side with mpn_image_hflip / mpn_flip_boxes.  The
+ *                          handle's cached trunk features are invalid afterwards: a detect with d_image == NULL returns MPN_ESTATE.
+ *   mpn_frcnn_train_step   head forward, loss, backward and SGD update on the B pending rows; clears the batch (MPN_ESTATE with none).
+ *                          z = class logits [B,C], t^ = raw box outputs [B,4C] (nn.BBoxNorm is the identity in training), y = labels:
+ *                            t_i = (utils.convertTo(roi_i, gt_i) - bbox_mean) / bbox_std for y_i > 0 (bbox_std[0] == 0: not normalised)
+ *                            d_loss[0] = (1/B) sum_i -log softmax(z_i)[y_i]                      (log-sum-exp)
+ *                            d_loss[1] = (bbox_weight/B) sum_{i: y_i > 0} sum_{j<4} smoothL1(t^_{i,4 y_i + j} - t_{i,j})   (B counts ALL rows)
+ *                          backward through heads -> fc7 -> fc6 as far as `depth` says, nothing below the pooled features;
+ *                          optim.sgd, dampening 0, no Nesterov: g += weight_decay * w (weights only, biases never decay), v = momentum * v + g,
+ *                          w -= lr * v.  The packed weights are updated IN PLACE, where detect's kernels and captured graphs read them:
+ *                          a detect after a step uses the new weights, with no re-pack and no re-capture.  d_loss may be NULL.
+ *   mpn_frcnn_train_end    frees the momentum buffers and the scratch; the weights stay as trained.
+ *   mpn_frcnn_get_head_weights  the current weights back in Torch layout ([out, in]; fc6's `in` index as at creation; cls and bbox split out
+ *                          of the fused head); any pointer may be NULL; with or without a train_begin; any mpn_frcnn_create handle.  The exact
+ *                          inverse of creation: unpack -> create -> unpack is bit-identical.
+ * Debug tensor "train_pooled": fc6's operand of the last step, [B, C, PH, PW] (valid until the next mpn_frcnn_train_add). */
+#define MPN_TRAIN_HEADS 0   /* cls + bbox linear only          */
+#define MPN_TRAIN_FC7   1   /* + fc7                           */
+#define MPN_TRAIN_FC6   2   /* + fc6 (the whole ROI head)      */
+int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight);
+int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_rois /*[n,4]*/,
+                        const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);
+int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss /*[2]: cls, bbox*/, void *stream);
+int mpn_frcnn_train_end(mpn_frcnn *p);
+int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b,
+                               float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
+
 /* Captured launch graphs.  The kernel chains of the per-image path — the head (transform .. decode) and the tail (per-class NMS,
  * voting, top-k) of mpn_frcnn_test_one / _pipelined / _pipelined_host, and the bodies of mpn_frcnn_shard_head / _shard_nms /
  * _shard_finish — are captured with hipStreamBeginCapture once per (buffer pointers, H, W, N) and replayed with hipGraphLaunch: one host

@@ -19,6 +19,7 @@
 
 #include "dense.h"
 #include "resnet.h"
+#include "train.h"
 
 namespace mpn {
 int launch_bbox_decode(const float *d_boxes, const float *d_deltas, int N, int C, float *d_out, int clamp, float im_w,
@@ -389,6 +390,20 @@ struct mpn_frcnn {
   float *aug_img = nullptr;                     // the mirrored ORIGINAL image (grown on demand: an image that getImages scales down may exceed max_h x max_w)
   size_t aug_img_bytes = 0;
   float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
+  // ---- training the head (mpn_frcnn_train_*): exists between train_begin and train_end
+  struct Train {
+    int depth = 0;                       // MPN_TRAIN_HEADS / _FC7 / _FC6
+    float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
+    float *vh = nullptr, *vbh = nullptr, *v7 = nullptr, *vb7 = nullptr, *v6 = nullptr, *vb6 = nullptr;  // momentum, in the layout of the weight it goes with
+    // the minibatch's own activations, C8 matrices at row pitch Mp (head: row-major [B, 5C]) — not detect's buffers, so a detect between
+    // two training calls disturbs nothing: fc6's operand (the ROI-pooled rows of the pending images), fc6's / fc7's outputs, the head's
+    float *x6 = nullptr, *y6 = nullptr, *y7 = nullptr, *head = nullptr;
+    float *gh = nullptr, *g7 = nullptr, *g6 = nullptr;       // gradients w.r.t. the head's output, fc7's and fc6's: C8 matrices at row pitch Mp
+    float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
+    int *labels = nullptr;
+    int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
+  };
+  Train *train = nullptr;
   // optional per-kernel-group timing with HIP events recorded on the launch stream
   bool prof = false;
   std::vector<hipEvent_t> ev_pool;
@@ -490,6 +505,15 @@ static const char *handle_kind_name(const mpn_frcnn *p) {
   return p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)";
 }
 
+static void free_train_state(mpn_frcnn *p) {
+  if (!p->train) return;
+  mpn_frcnn::Train *t = p->train;
+  for (float *q : {t->vh, t->vbh, t->v7, t->vb7, t->v6, t->vb6, t->x6, t->y6, t->y7, t->head, t->gh, t->g7, t->g6, t->rois, t->gt, t->loss}) if (q) (void)hipFree(q);
+  if (t->labels) (void)hipFree(t->labels);
+  delete t;
+  p->train = nullptr;
+}
+
 extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   if (!p) return;
   (void)hipDeviceSynchronize();
@@ -513,6 +537,7 @@ extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   for (float *q : {p->scaled, p->scale_tmp, p->ms_feat, p->ms_pm, p->aug_img, p->aug_boxes, p->aug_scores, p->aug_bbox, p->mir.buf, p->mir.pm, p->dbg})
     if (q) (void)hipFree(q);
   for (int i = 0; i < 4; ++i) if (p->sh_buf[i]) (void)hipFree(p->sh_buf[i]);
+  free_train_state(p);
   delete p;
 }
 
@@ -1996,7 +2021,202 @@ extern "C" int mpn_frcnn_nms_results(mpn_frcnn *p, const float **d_keep, const i
   return MPN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Training the head with the trunk frozen (include/mpn.h mpn_frcnn_train_*; kernels: train.hip)
+// ------------------------------------------------------------------------------------------------------------------------------
+// the handle kinds and states that cannot train, each named (as refuse_multi_pass does for the throughput forms)
+static int refuse_train(const mpn_frcnn *p, const char *fn) {
+  if (p->is_mpnet || p->rn) {
+    set_error("%s: a %s handle cannot be trained: only mpn_frcnn_create's VGG Fast R-CNN head (fc6, fc7, cls + bbox) has a backward pass", fn, handle_kind_name(p));
+    return MPN_ESTATE;
+  }
+  if (p->cfg.fc_arith != MPN_FC_FP32) {
+    set_error("%s: an MPN_FC_SPLIT3 handle cannot be trained (its bf16 weight planes would go stale): create it with MPN_FC_FP32", fn);
+    return MPN_ESTATE;
+  }
+  if (p->n_scales > 1) {
+    set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales): restore a single scale first", fn, p->n_scales);
+    return MPN_ESTATE;
+  }
+  if (p->augment) {
+    set_error("%s: not supported with horizontal-flip augmentation (mpn_frcnn_set_augment): switch it off; flip training images with mpn_image_hflip / mpn_flip_boxes", fn);
+    return MPN_ESTATE;
+  }
+  if (p->tail_pending[0] || p->tail_pending[1]) {
+    set_error("%s: a pipelined call's tail is still pending on this handle: call mpn_frcnn_flush first", fn);
+    return MPN_ESTATE;
+  }
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, "mpn_frcnn_train_begin");
+  if (rc) return rc;
+  if (p->train) { set_error("mpn_frcnn_train_begin: training has already begun on this handle (mpn_frcnn_train_end first)"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(depth >= MPN_TRAIN_HEADS && depth <= MPN_TRAIN_FC6);
+  MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  const mpn_frcnn_config &c = p->cfg;
+  const int F = c.fc_dim, C = c.n_classes;
+  const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
+  mpn_frcnn::Train *t = new mpn_frcnn::Train();
+  t->depth = depth; t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
+  p->train = t;
+  auto alloc0 = [&](float **q, size_t bytes) -> bool { return hipMalloc(q, bytes) == hipSuccess && hipMemset(*q, 0, bytes) == hipSuccess; };
+  bool ok = alloc0(&t->vh, lin_wpk_elems(round_up(F, 64), 5 * C) * sizeof(float)) && alloc0(&t->vbh, (size_t)lin_np(5 * C) * sizeof(float));
+  ok = ok && alloc0(&t->gh, (size_t)(lin_np(5 * C) / 8) * rec);
+  ok = ok && alloc0(&t->x6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->y6, (size_t)(lin_np(F) / 8) * rec) && alloc0(&t->y7, (size_t)(lin_np(F) / 8) * rec);
+  ok = ok && alloc0(&t->head, M * 5 * C * sizeof(float));
+  if (depth >= MPN_TRAIN_FC7) {
+    ok = ok && alloc0(&t->v7, lin_wpk_elems(round_up(F, 64), F) * sizeof(float)) && alloc0(&t->vb7, (size_t)lin_np(F) * sizeof(float));
+    ok = ok && alloc0(&t->g7, (size_t)(lin_np(F) / 8) * rec);
+  }
+  if (depth >= MPN_TRAIN_FC6) {
+    ok = ok && alloc0(&t->v6, lin_wpk_elems(round_up(p->K6, 64), F) * sizeof(float)) && alloc0(&t->vb6, (size_t)lin_np(F) * sizeof(float));
+    ok = ok && alloc0(&t->g6, (size_t)(lin_np(F) / 8) * rec);
+  }
+  ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
+  ok = ok && hipMalloc(&t->labels, M * sizeof(int)) == hipSuccess && hipMemset(t->labels, 0, M * sizeof(int)) == hipSuccess;
+  if (ok) ok = hipDeviceSynchronize() == hipSuccess;
+  if (!ok) {
+    set_error("mpn_frcnn_train_begin: allocating the momentum / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
+    free_train_state(p);
+    return MPN_ENOMEM;
+  }
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_end(mpn_frcnn *p) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (!p->train) { set_error("mpn_frcnn_train_end: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  free_train_state(p);
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
+                                   const int *d_labels, int n, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, "mpn_frcnn_train_add");
+  if (rc) return rc;
+  mpn_frcnn::Train *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_add: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
+  const mpn_frcnn_config &c = p->cfg;
+  if (t->pending + n > c.max_rois) {
+    set_error("mpn_frcnn_train_add: %d pending rows + %d exceed the handle's max_rois (%d)", t->pending, n, c.max_rois);
+    return MPN_EINVAL;
+  }
+  double sc = 1.0;
+  int H = H0, W = W0;
+  if (c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
+  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
+    set_error("mpn_frcnn_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
+    return MPN_EINVAL;
+  }
+  ScratchScope scratch_scope(&p->scratch);
+  hipStream_t s = as_stream(stream);
+  p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers and the ROI table are rewritten: the next head segment runs for real
+  Act feat;
+  rc = obtain_features(p, d_image, H0, W0, H, W, sc, &p->up, s, &feat);  // getImages' rescale + the frozen trunk, exactly as detect
+  // the map now belongs to a training image: nothing a detect on cached features may pool from
+  p->up.invalidate(); p->mir.invalidate();
+  if (rc) return rc;
+  rc = mpn_project_im_rois(d_rois, n, sc, p->rois, s);
+  if (rc) return rc;
+  // this image's rows behind the pending ones: a shifted base pointer with the buffer's row pitch
+  rc = roi_pool_c8(feat, p->rois, n, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, t->x6 + (size_t)t->pending * 8, nullptr, s, 5, p->Mp);
+  if (rc) return rc;
+  MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  t->pending += n;
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, "mpn_frcnn_train_step");
+  if (rc) return rc;
+  mpn_frcnn::Train *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_step: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  if (t->pending <= 0) { set_error("mpn_frcnn_train_step: no pending rows (mpn_frcnn_train_add first)"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(std::isfinite(lr));
+  const mpn_frcnn_config &c = p->cfg;
+  const int B = t->pending, F = c.fc_dim, C = c.n_classes, Mp = p->Mp, PP = c.pooled_h * c.pooled_w;
+  ScratchScope scratch_scope(&p->scratch);
+  hipStream_t s = as_stream(stream);
+  // forward: detect's GEMMs on the pending rows (row pitch Mp); no dropout (opt.train_remove_dropouts)
+  rc = linear_c8(t->x6, B, p->K6, p->w6, p->b6, F, 1, t->y6, nullptr, s, Mp, nullptr, 1);
+  if (rc == MPN_OK) rc = linear_c8(t->y6, B, F, p->w7, p->b7, F, 1, t->y7, nullptr, s, Mp, nullptr, 1);
+  if (rc == MPN_OK) rc = linear_c8(t->y7, B, F, p->wh, p->bh, 5 * C, 0, nullptr, t->head, s, Mp, nullptr, 1);
+  if (rc) return rc;
+  LossCfg lc{};
+  for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
+  lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
+  lc.bbox_weight = t->bbox_weight;
+  rc = train_loss(t->head, B, C, t->rois, t->gt, t->labels, lc, t->gh, Mp, d_loss ? d_loss : t->loss, s);
+  // backward: every input gradient before the update of the weights it was computed with
+  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC7) rc = linear_dgrad_c8(t->gh, Mp, B, 5 * C, p->wh, F, t->y7, t->g7, Mp, s);
+  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC6) rc = linear_dgrad_c8(t->g7, Mp, B, F, p->w7, F, t->y6, t->g6, Mp, s);
+  if (rc == MPN_OK) rc = sgd_wgrad_c8(t->gh, Mp, t->y7, Mp, B, 5 * C, F, 1, p->wh, t->vh, lr, t->momentum, t->weight_decay, s);
+  if (rc == MPN_OK) rc = sgd_bias_c8(t->gh, Mp, B, 5 * C, p->bh, t->vbh, lr, t->momentum, s);
+  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC7) {
+    rc = sgd_wgrad_c8(t->g7, Mp, t->y6, Mp, B, F, F, 1, p->w7, t->v7, lr, t->momentum, t->weight_decay, s);
+    if (rc == MPN_OK) rc = sgd_bias_c8(t->g7, Mp, B, F, p->b7, t->vb7, lr, t->momentum, s);
+  }
+  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC6) {
+    rc = sgd_wgrad_c8(t->g6, Mp, t->x6, Mp, B, F, p->K6, PP, p->w6, t->v6, lr, t->momentum, t->weight_decay, s);
+    if (rc == MPN_OK) rc = sgd_bias_c8(t->g6, Mp, B, F, p->b6, t->vb6, lr, t->momentum, s);
+  }
+  t->last_rows = B;
+  t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
+  return rc;
+}
+
+extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b, float *d_cls_w,
+                                          float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (p->is_mpnet || p->rn) {
+    set_error("mpn_frcnn_get_head_weights: a %s handle has no fc6 / fc7 / fused cls + bbox head to unpack", handle_kind_name(p));
+    return MPN_ESTATE;
+  }
+  const mpn_frcnn_config &c = p->cfg;
+  const int F = c.fc_dim, C = c.n_classes;
+  hipStream_t s = as_stream(stream);
+  int rc = unpack_linear_weights(p->w6, p->b6, p->K6, F, c.pooled_h * c.pooled_w, 0, F, d_fc6_w, d_fc6_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->w7, p->b7, F, F, 1, 0, F, d_fc7_w, d_fc7_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, 0, C, d_cls_w, d_cls_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, C, 5 * C, d_bbox_w, d_bbox_b, s);
+  return rc;
+}
+
 #ifdef MPN_DEBUG_HOOKS
+// tools/bench_train.py (debug flavour only): fc6's fused weight-gradient + SGD kernel issued `iters` times BACK TO BACK on the operands the
+// last mpn_frcnn_train_step left (depth MPN_TRAIN_FC6), with lr = momentum = wd = 0 — the weights keep their values, the momentum
+// buffer ends as the plain gradient; the traffic is the real step's: w and v read and written once.
+extern "C" int mpn_debug_bench_train_fc6(mpn_frcnn *p, int iters, float *ms_out) {
+  MPN_CHECK_ARG(p && iters > 0 && ms_out);
+  mpn_frcnn::Train *t = p->train;
+  if (!t || t->depth < MPN_TRAIN_FC6 || t->last_rows <= 0) { set_error("mpn_debug_bench_train_fc6: needs a mpn_frcnn_train_step at depth MPN_TRAIN_FC6"); return MPN_ESTATE; }
+  const int F = p->cfg.fc_dim, PP = p->cfg.pooled_h * p->cfg.pooled_w;
+  hipEvent_t e0, e1;
+  MPN_CHECK_HIP(hipEventCreate(&e0)); MPN_CHECK_HIP(hipEventCreate(&e1));
+  int rc = MPN_OK;
+  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  MPN_CHECK_HIP(hipEventRecord(e0, nullptr));
+  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr);
+  MPN_CHECK_HIP(hipEventRecord(e1, nullptr));
+  MPN_CHECK_HIP(hipEventSynchronize(e1));
+  float ms = 0.f;
+  MPN_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
+  *ms_out = ms / iters;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  return rc;
+}
+
 // bench.py's `power_sensitivity` leg (debug flavour only): fc6 of the VGG Fast R-CNN pipeline issued `iters` times BACK TO BACK on the
 // operand the last detect() left in HBM (the ROI-pooled, post-ReLU conv5 features and the handle's own fc6 weights) — the same GEMM that
 // mpn_debug_bench_linear times on dense random operands.  Inside the pipeline fc6 follows the trunk's phases and runs at a higher clock.
@@ -2024,6 +2244,23 @@ extern "C" int mpn_debug_bench_fc6(mpn_frcnn *p, int iters, float *ms_out) {
 
 extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems) {
   MPN_CHECK_ARG(p && name && d_ptr && n_elems);
+  if (!strcmp(name, "train_pooled")) {  // fc6's operand of the last mpn_frcnn_train_step, [rows, C, PH, PW]: rows at pitch Mp, valid until the next train_add
+    if (!p->train || p->train->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: 'train_pooled' needs a mpn_frcnn_train_step"); return MPN_ESTATE; }
+    const int PPt = p->cfg.pooled_h * p->cfg.pooled_w;
+    const size_t nt = (size_t)p->train->last_rows * p->feat_c * PPt;
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    if (nt * sizeof(float) > p->dbg_bytes) {
+      if (p->dbg) (void)hipFree(p->dbg);
+      p->dbg = nullptr; p->dbg_bytes = 0;
+      MPN_CHECK_HIP(hipMalloc(&p->dbg, nt * sizeof(float)));
+      p->dbg_bytes = nt * sizeof(float);
+    }
+    hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(nt, 256)), dim3(256), 0, nullptr, p->train->x6, p->train->last_rows, p->feat_c, PPt, p->Mp, p->dbg);
+    MPN_CHECK_LAUNCH();
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    *d_ptr = p->dbg; *n_elems = nt;
+    return MPN_OK;
+  }
   if (p->last_n <= 0 || (!p->rn && p->last_h <= 0)) { set_error("mpn_frcnn_debug_tensor: run detect first"); return MPN_ESTATE; }
   const mpn_frcnn_config &c = p->cfg;
   const int N = p->last_n, C = c.n_classes, F = c.fc_dim, PP = c.pooled_h * c.pooled_w;

@@ -799,6 +799,43 @@ class FastRCNN(object):
         hip.hipMemcpy(C.c_void_p(n.data_ptr()), np_, C.c_size_t(n.numel() * 4), 3)
         return keep, idx, n
 
+    # ---- fine-tuning the head on the device, trunk frozen (mpn_frcnn_train_*, include/mpn.h) ----
+    def train_begin(self, depth=2, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0):
+        """Start training: depth 0 = cls + bbox linear only, 1 = + fc7, 2 = + fc6 (the whole ROI head); optim.sgd's momentum and weight
+        decay (engines/Optim.lua; biases never decay), the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN handles in fp32
+        only; no dropout (the reference's opt.train_remove_dropouts configuration)."""
+        check(self._lib.mpn_frcnn_train_begin(self._h, int(depth), C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)),
+              "mpn_frcnn_train_begin")
+
+    def train_add(self, image, rois, gt_boxes, labels):
+        """Append one image's rows to the pending minibatch: image [3,H,W] fp32 in [0,1], rois / gt_boxes [n,4] in the image's own
+        coordinates (as detect takes boxes), labels [n] int32, 0 = background — all on the device.  The trunk runs frozen."""
+        H, W = image.shape[1:]
+        n = rois.size(0)
+        assert gt_boxes.shape == rois.shape and labels.numel() == n and labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
+        check(self._lib.mpn_frcnn_train_add(self._h, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream()),
+              "mpn_frcnn_train_add")
+
+    def train_step(self, lr):
+        """Head forward, loss, backward and the SGD update on the pending rows -> device tensor [2] = (cls loss, bbox loss)."""
+        loss = torch.empty(2, dtype=torch.float32, device=self.device)
+        check(self._lib.mpn_frcnn_train_step(self._h, C.c_float(lr), _f(loss), _stream()), "mpn_frcnn_train_step")
+        return loss
+
+    def train_end(self):
+        check(self._lib.mpn_frcnn_train_end(self._h), "mpn_frcnn_train_end")
+
+    def head_weights(self):
+        """The handle's current fc6 / fc7 / cls / bbox weights and biases in Torch layout, under synthetic_params' keys (device tensors):
+        update a parameter dict with it to build a new FastRCNN, or write it with t7.py."""
+        F, Cn = self.fc_dim, self.n_classes
+        k6 = self._cout[len(self._cout) - 1] * self._cfg.pooled_h * self._cfg.pooled_w if len(self._cout) else 0
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        P = {"fc6_w": z(F, k6), "fc6_b": z(F), "fc7_w": z(F, F), "fc7_b": z(F), "cls_w": z(Cn, F), "cls_b": z(Cn), "bbox_w": z(4 * Cn, F), "bbox_b": z(4 * Cn)}
+        check(self._lib.mpn_frcnn_get_head_weights(self._h, *[_f(P[k]) for k in ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")],
+                                                   _stream()), "mpn_frcnn_get_head_weights")
+        return P
+
     def set_graphs(self, on):
         """captured launch graphs (mpn_frcnn_set_graphs): replay the per-image kernel chains with hipGraphLaunch.
         Default OFF (opt-in: MPN_GRAPHS=1 in the environment or set_graphs(True); include/mpn.h)"""

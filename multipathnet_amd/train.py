@@ -1,0 +1,106 @@
+"""Host side of training the Fast R-CNN head (file:line relative to the reference tree): which ROIs enter a minibatch and the
+statistics of their regression targets.  numpy / torch on the host, not on the per-image path; the per-step work — frozen trunk, ROI
+pooling, head forward, loss, backward, SGD — is models.FastRCNN.train_add / train_step on the device.
+
+  attach_proposals        DataSetJSON.lua:280-390  (DataSetCOCO:attachProposals, without the crowd and the sample-around-GT branches)
+  RoiSampler              BatchProviderROI.lua:39-49 (setupOne), BatchProviderBase.lua:54-107 (takeSubset, selectBBoxesOne)
+  bbox_regression_stats   BatchProviderROI.lua:53-69 (setupData)
+"""
+import numpy as np
+import torch
+
+from . import utils
+
+
+def _boxoverlap_host(a, b):
+    """utils.boxoverlap (utils.lua:104-128) in fp32 on the host: IoU of a [N,4] with one box b, the +1 pixel convention, 0 where the
+    intersection's width or height is negative."""
+    a = np.asarray(a, np.float32).reshape(-1, 4)
+    b = np.asarray(b, np.float32).reshape(4)
+    x1, y1 = np.maximum(a[:, 0], b[0]), np.maximum(a[:, 1], b[1])
+    x2, y2 = np.minimum(a[:, 2], b[2]), np.minimum(a[:, 3], b[3])
+    w, h = x2 - x1 + np.float32(1), y2 - y1 + np.float32(1)
+    inter = w * h
+    aarea = (a[:, 2] - a[:, 0] + np.float32(1)) * (a[:, 3] - a[:, 1] + np.float32(1))
+    barea = (b[2] - b[0] + np.float32(1)) * (b[3] - b[1] + np.float32(1))
+    o = inter / (aarea + barea - inter)
+    o[(w < 0) | (h < 0)] = 0
+    return o.astype(np.float32)
+
+
+def attach_proposals(proposals, gt_boxes, gt_labels):
+    """DataSetCOCO:attachProposals for one image: the GT boxes FIRST, then the proposals (DataSetJSON.lua:291-299); per row the maximum IoU
+    with a GT box (`overlap`), the 1-based index of that GT box (`correspondance`, the reference's spelling; the first maximum, 0 where the
+    overlap is 0) and its class (`label`, 0 where there is none).  gt_labels are class ids >= 1.  Returns a dict of numpy arrays:
+    boxes [n,4] float32, gt [n] uint8 (1 on the GT rows), overlap [n] float32, correspondance [n] int64, label [n] int32."""
+    to_np = lambda t, dt: (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
+    prop = to_np(proposals, np.float32).reshape(-1, 4)
+    gtb = to_np(gt_boxes, np.float32).reshape(-1, 4)
+    gtl = to_np(gt_labels, np.int32).reshape(-1)
+    assert gtb.shape[0] == gtl.shape[0]
+    ng, n = gtb.shape[0], gtb.shape[0] + prop.shape[0]
+    boxes = np.concatenate([gtb, prop], 0)
+    rec = {"boxes": boxes, "gt": np.concatenate([np.ones(ng, np.uint8), np.zeros(prop.shape[0], np.uint8)])}
+    if ng:
+        ov = np.stack([_boxoverlap_host(boxes, gtb[j]) for j in range(ng)], 1) if n else np.zeros((0, ng), np.float32)
+        rec["overlap"] = ov.max(1) if n else np.zeros(0, np.float32)
+        corr = ov.argmax(1).astype(np.int64) + 1 if n else np.zeros(0, np.int64)   # first maximum, 1-based
+        corr[rec["overlap"] == 0] = 0
+    else:
+        rec["overlap"] = np.zeros(n, np.float32)
+        corr = np.zeros(n, np.int64)
+    rec["correspondance"] = corr
+    label = np.zeros(n, np.int32)
+    label[corr > 0] = gtl[corr[corr > 0] - 1]
+    rec["label"] = label
+    return rec
+
+
+class RoiSampler(object):
+    """BatchProviderROI's choice of ROIs for ONE image of a minibatch.  setupOne: foreground = overlap >= fg_threshold, background =
+    bg_threshold[0] <= overlap < bg_threshold[1].  selectBBoxesOne: min(num, n) draws WITH replacement from each set, num =
+    fg_fraction * batch_size foreground and the rest background PER IMAGE (BatchProviderROI.lua:116-117 — the reference's 128 / 0.25
+    are per image; with imgs_per_batch = 2 and 64 rows each pass batch_size = 64).  Background rows first, then foreground
+    (BatchProviderROI.lua:98-101).  Labels come out 0-based with 0 = background (the reference's are 1-based)."""
+
+    def __init__(self, batch_size=128, fg_fraction=0.25, fg_threshold=0.5, bg_threshold=(0.1, 0.5), rng=None):
+        self.batch_size, self.fg_fraction = int(batch_size), float(fg_fraction)
+        self.fg_threshold, self.bg_threshold = float(fg_threshold), (float(bg_threshold[0]), float(bg_threshold[1]))
+        self.rng = rng if rng is not None else np.random.default_rng()
+
+    def setup_one(self, rec):
+        """(background row indices, foreground row indices) of an attach_proposals record"""
+        ov = rec["overlap"]
+        fg = np.nonzero(ov >= np.float32(self.fg_threshold))[0]
+        bg = np.nonzero((ov >= np.float32(self.bg_threshold[0])) & (ov < np.float32(self.bg_threshold[1])))[0]
+        return bg, fg
+
+    def sample(self, rec):
+        """-> (rois [m,4] float32, gt_boxes [m,4] float32, labels [m] int32): background rows (gt box zeros, label 0) then foreground
+        rows (the GT box each corresponds to, its class)."""
+        bg, fg = self.setup_one(rec)
+        fg_num = int(self.fg_fraction * self.batch_size)
+        bg_num = self.batch_size - fg_num
+        pick_bg = bg[self.rng.integers(0, len(bg), min(bg_num, len(bg)))] if len(bg) else bg
+        pick_fg = fg[self.rng.integers(0, len(fg), min(fg_num, len(fg)))] if len(fg) else fg
+        boxes = rec["boxes"]
+        rois = np.concatenate([boxes[pick_bg], boxes[pick_fg]], 0).astype(np.float32)
+        gtb = np.concatenate([np.zeros((len(pick_bg), 4), np.float32), boxes[rec["correspondance"][pick_fg] - 1]], 0).astype(np.float32)
+        labels = np.concatenate([np.zeros(len(pick_bg), np.int32), rec["label"][pick_fg]]).astype(np.int32)
+        return rois, gtb, labels
+
+
+def bbox_regression_stats(records, fg_threshold=0.5):
+    """BatchProviderROI:setupData over attach_proposals records: mean and (unbiased, as torch's std) standard deviation of
+    utils.convertTo(roi, gt box) over every foreground row -> (mean [4], std [4]) float32 numpy, what FastRCNN takes as
+    params["bbox_mean"] / params["bbox_std"]."""
+    vals = []
+    for rec in records:
+        fg = np.nonzero(rec["overlap"] >= np.float32(fg_threshold))[0]
+        if len(fg):
+            rois = torch.from_numpy(rec["boxes"][fg])
+            gtb = torch.from_numpy(rec["boxes"][rec["correspondance"][fg] - 1])
+            vals.append(utils.convertTo(rois, gtb))
+    assert vals, "no foreground rows"
+    v = torch.cat(vals, 0)
+    return v.mean(0).numpy(), v.std(0).numpy()

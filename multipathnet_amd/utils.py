@@ -4,6 +4,7 @@
   utils.nms_dense               utils.lua:402-462 (index-returning NMS of demo.lua)
   utils.boxoverlap              utils.lua:104-128 (same formula as nms.c:14-41)
   utils.convertFrom             utils.lua:212-248
+  utils.convertTo               utils.lua:171-210 (host arithmetic: the training targets' statistics; the device computes its own in the loss kernel)
   utils.keep_top_k              utils.lua:75-96
   utils.joinTable               utils.lua:46-71
   utils.flipBoxes               utils.lua:151-155
@@ -95,6 +96,18 @@ def convertFrom(out, bbox, y):
               "convertFrom")
     out.copy_(res)
     return out
+
+
+def convertTo(bbox, tbox):
+    """utils.convertTo(bbox [N,4], tbox [N,4]) (utils.lua:171-210, the two-argument form) -> regression targets [N,4]:
+    ((xtc - xc) / w, (ytc - yc) / h, log(wt / w), log(ht / h)) with w = x2 - x1 (no +1), the inverse of convertFrom.  Plain tensor
+    arithmetic in the inputs' dtype and on their device — not on the per-image path (train.bbox_regression_stats)."""
+    assert bbox.shape == tbox.shape and bbox.size(-1) == 4
+    xc, yc = (bbox[..., 0] + bbox[..., 2]) * 0.5, (bbox[..., 1] + bbox[..., 3]) * 0.5
+    w, h = bbox[..., 2] - bbox[..., 0], bbox[..., 3] - bbox[..., 1]
+    xtc, ytc = (tbox[..., 0] + tbox[..., 2]) * 0.5, (tbox[..., 1] + tbox[..., 3]) * 0.5
+    wt, ht = tbox[..., 2] - tbox[..., 0], tbox[..., 3] - tbox[..., 1]
+    return torch.stack([(xtc - xc) / w, (ytc - yc) / h, torch.log(wt / w), torch.log(ht / h)], -1)
 
 
 def decode_all_classes(boxes, deltas):

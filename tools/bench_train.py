@@ -1,0 +1,80 @@
+"""Cost of one training step of the Fast R-CNN head on one GPU: VGG-16 at 600 x 1000, the reference's minibatch
+of 2 images x 64 ROIs (BatchProviderROI.lua:18-24 with 128 rows in all), frozen trunk.
+Per depth (0 = cls + bbox, 1 = + fc7, 2 = + fc6): ms of mpn_frcnn_train_step alone and of the whole iteration (two train_add — trunk,
+projection, ROI pooling each — plus the step), HIP events, median of --steps after --warmup.  Then fc6's fused weight-gradient + SGD
+kernel alone (debug flavour, mpn_debug_bench_train_fc6: back-to-back launches) and its GB/s against the bytes it must move — the packed
+weights and their momentum, each read and written once.  One JSON line per measurement.
+
+    python tools/bench_train.py [--steps 20] [--warmup 5]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W, ROWS, IMAGES = 600, 1000, 64, 2
+
+
+def batch(rng, n_classes):
+    im = rng.random((3, H, W), dtype=np.float32)
+    c = rng.uniform([40, 40], [W - 40, H - 40], (ROWS, 2))
+    wh = np.exp(rng.uniform(np.log(32), np.log(300), (ROWS, 2)))
+    rois = np.clip(np.concatenate([c - wh / 2, c + wh / 2], 1), 1, [W, H, W, H]).astype(np.float32)
+    gt = (rois + rng.normal(0, 2.0, (ROWS, 4))).astype(np.float32)
+    labels = rng.integers(1, n_classes, ROWS).astype(np.int32)
+    labels[: ROWS * 3 // 4] = 0   # fg_fraction 0.25, background rows first
+    return im, rois, gt, labels
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    import torch
+    from multipathnet_amd import _lib, models
+    assert torch.cuda.is_available(), "bench_train needs a HIP device"
+    P = models.synthetic_params(seed=557)
+    C_ = P["cls_w"].shape[0]
+    rng = np.random.default_rng(5)
+    dev_batches = [[torch.from_numpy(x).cuda() for x in batch(rng, C_)] for _ in range(IMAGES)]
+    name = torch.cuda.get_device_name(0)
+    with _lib.debug_hooks() as lib:
+        net = models.FastRCNN(P, max_h=H, max_w=W, max_rois=IMAGES * ROWS)
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        for depth in (0, 1, 2):
+            net.train_begin(depth=depth, momentum=0.9, weight_decay=5e-4)
+            step_ms, iter_ms = [], []
+            for i in range(a.warmup + a.steps):
+                e[0].record()
+                for b in dev_batches:
+                    net.train_add(*b)
+                e[1].record()
+                net.train_step(1e-6)   # a tiny step: the weights stay in their range over the run
+                e[2].record()
+                e[2].synchronize()
+                if i >= a.warmup:
+                    step_ms.append(e[1].elapsed_time(e[2]))
+                    iter_ms.append(e[0].elapsed_time(e[2]))
+            print(json.dumps({"what": "train_step", "depth": depth, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
+                              "ms_step_min": round(float(np.min(step_ms)), 3), "ms_iteration_median": round(float(np.median(iter_ms)), 3),
+                              "steps": a.steps, "device": name}), flush=True)
+            if depth == 2:
+                ms = C.c_float()
+                _lib.check(lib.mpn_debug_bench_train_fc6(net._h, 20, C.byref(ms)), "mpn_debug_bench_train_fc6")
+                k6, F = P["fc6_w"].shape[1], P["fc6_w"].shape[0]
+                gb = 4 * (k6 * F * 4) / 1e9   # w read + w write + v read + v write (pad lanes of the packing: none at 25088 x 4096)
+                print(json.dumps({"what": "fc6_wgrad_sgd_kernel", "ms": round(ms.value, 4), "gbytes_moved": round(gb, 3),
+                                  "gbytes_per_s": round(gb / (ms.value * 1e-3), 1), "floor_ms_at_6.3TBps": round(gb / 6.3e3 * 1e3, 3), "device": name}), flush=True)
+            net.train_end()
+        net.close()
+
+
+if __name__ == "__main__":
+    main()
