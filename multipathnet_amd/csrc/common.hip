@@ -1,4 +1,5 @@
 // common.hip — error reporting, version, device query.
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -30,6 +31,85 @@ int grow_device_buffer(void **ptr, size_t *bytes, size_t need, hipStream_t s, bo
   *bytes = need;
   if (zero) MPN_CHECK_HIP(hipMemsetAsync(*ptr, 0, need, s));
   return MPN_OK;
+}
+
+// what all DeviceOwners of the process hold: buffers, streams, events (debug flavour only; the product build has no counter)
+#ifdef MPN_DEBUG_HOOKS
+static std::atomic<long> g_live[3];
+#define MPN_LIVE(kind, d) g_live[kind].fetch_add(d, std::memory_order_relaxed)
+#else
+#define MPN_LIVE(kind, d) ((void)(d))
+#endif
+
+int DeviceOwner::alloc_block(void **q, size_t bytes, bool zero) {
+  const size_t n = bytes ? bytes : 16;
+  hipError_t e = hipMalloc(q, n);
+  if (e != hipSuccess) { *q = nullptr; set_error("DeviceOwner: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); return MPN_ENOMEM; }
+  MPN_LIVE(0, 1);
+  if (zero && (e = hipMemset(*q, 0, n)) != hipSuccess) {
+    set_error("DeviceOwner: hipMemset failed: %s", hipGetErrorString(e));
+    (void)hipFree(*q); *q = nullptr;
+    MPN_LIVE(0, -1);
+    return MPN_EHIP;
+  }
+  return MPN_OK;
+}
+void DeviceOwner::track(void **slot) {
+  if (std::find(slots_.begin(), slots_.end(), slot) == slots_.end()) slots_.push_back(slot);
+}
+int DeviceOwner::grow_slot(void **slot, size_t *bytes, size_t need, hipStream_t s, bool zero) {
+  if (need <= *bytes) return MPN_OK;
+  track(slot);
+  const bool had = *slot != nullptr;
+  const int rc = grow_device_buffer(slot, bytes, need, s, zero);
+  MPN_LIVE(0, (*slot != nullptr) - had);
+  return rc;
+}
+void DeviceOwner::free_block(void **ptr) {
+  if (!*ptr) return;
+  auto it = std::find(blocks_.begin(), blocks_.end(), *ptr);
+  if (it != blocks_.end()) blocks_.erase(it);  // (a slot stays tracked: it is empty until its next alloc_slot / grow)
+  (void)hipFree(*ptr);
+  *ptr = nullptr;
+  MPN_LIVE(0, -1);
+}
+int DeviceOwner::stream(hipStream_t *s) {
+  MPN_CHECK_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  streams_.push_back(*s);
+  MPN_LIVE(1, 1);
+  return MPN_OK;
+}
+int DeviceOwner::event(hipEvent_t *e, bool timing) {
+  MPN_CHECK_HIP(timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming));
+  events_.push_back(*e);
+  MPN_LIVE(2, 1);
+  return MPN_OK;
+}
+void DeviceOwner::drop(hipStream_t *s) {
+  auto it = std::find(streams_.begin(), streams_.end(), *s);
+  if (!*s || it == streams_.end()) return;
+  streams_.erase(it);
+  (void)hipStreamDestroy(*s);
+  *s = nullptr;
+  MPN_LIVE(1, -1);
+}
+void DeviceOwner::drop(hipEvent_t *e) {
+  auto it = std::find(events_.begin(), events_.end(), *e);
+  if (!*e || it == events_.end()) return;
+  events_.erase(it);
+  (void)hipEventDestroy(*e);
+  *e = nullptr;
+  MPN_LIVE(2, -1);
+}
+void DeviceOwner::release_streams() {
+  for (hipStream_t s : streams_) { (void)hipStreamDestroy(s); MPN_LIVE(1, -1); }
+  for (hipEvent_t e : events_) { (void)hipEventDestroy(e); MPN_LIVE(2, -1); }
+  streams_.clear(); events_.clear();
+}
+void DeviceOwner::release_buffers() {
+  for (void *q : blocks_) { (void)hipFree(q); MPN_LIVE(0, -1); }
+  for (void **slot : slots_) if (*slot) { (void)hipFree(*slot); *slot = nullptr; MPN_LIVE(0, -1); }
+  blocks_.clear(); slots_.clear();
 }
 
 void Scratch::release() {
@@ -116,6 +196,14 @@ extern "C" int mpn_release_all_scratch(void) {
   if (rc) mpn::set_error("mpn_release_all_scratch: a device could not be synchronised");
   return rc;
 }
+
+#ifdef MPN_DEBUG_HOOKS
+extern "C" void mpn_debug_live_resources(long *buffers, long *streams, long *events) {
+  if (buffers) *buffers = mpn::g_live[0].load(std::memory_order_relaxed);
+  if (streams) *streams = mpn::g_live[1].load(std::memory_order_relaxed);
+  if (events) *events = mpn::g_live[2].load(std::memory_order_relaxed);
+}
+#endif
 
 extern "C" int mpn_version(void) { return MPN_VERSION; }
 extern "C" const char *mpn_last_error(void) { return mpn::g_err; }

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/mpn.h"
 
@@ -68,6 +69,61 @@ void bump_alloc_generation();
 // `s` (the buffer's last user), bump the generation, free, null *ptr and *bytes, hipMalloc(need), set *bytes; `zero` clears the new
 // buffer on `s`.  The bump comes BEFORE the free: a hipMalloc that fails must not leave a captured graph able to replay a freed pointer.
 int grow_device_buffer(void **ptr, size_t *bytes, size_t need, hipStream_t s, bool zero = false);
+
+// ---- DeviceOwner: the ONE owner of a handle's device memory, streams and events ------------------------
+// A handle (mpn_frcnn, its training state, ResNetGraph) creates every device resource that lives as long as it does through its
+// DeviceOwner, and release() gives all of them back: nothing is freed through a list of member names, and adding a buffer is one call.
+//   alloc       a FIXED buffer (hipMalloc(bytes ? bytes : 16), `zero`: a synchronous hipMemset).  The owner records the block itself,
+//               so the pointer may sit in a struct that is copied around (ConvLayer, Tower, RnConv).
+//   alloc_slot  a buffer that is REPLACED later, held in a pointer MEMBER of the handle: the owner records the member's address
+//   grow        (handles are heap objects that never move) and frees whatever is there at release.  grow is grow_device_buffer on a
+//               slot; alloc_slot fills an empty slot.
+//   free_now    gives ONE buffer (of either kind) back early and nulls the pointer.  It never bumps the allocation generation: where a
+//               captured graph could hold the pointer the caller bumps FIRST — the order is always bump, free, null (see above).
+//   stream / event   hipStreamNonBlocking streams; hipEventDisableTiming events unless `timing`.  drop() destroys one early.
+// A creator of several resources that belong together (lazily built feature state) publishes the member its guard tests LAST, and on
+// a failure frees what it made, so that the next call starts from scratch ("its presence says that all of them exist").
+// release_streams() and release_buffers() are the two halves of release(), for a handle that frees its Scratch between them.
+// Errors: MPN_ENOMEM for a failed hipMalloc, MPN_EHIP otherwise.  The debug flavour counts what all owners hold (mpn_debug_live_resources).
+struct DeviceOwner {
+  DeviceOwner() = default;
+  DeviceOwner(const DeviceOwner &) = delete;
+  DeviceOwner &operator=(const DeviceOwner &) = delete;
+  ~DeviceOwner() { release(); }
+  template <typename T> int alloc(T **ptr, size_t bytes, bool zero = false) {
+    void *q = nullptr;
+    const int rc = alloc_block(&q, bytes, zero);
+    if (rc == MPN_OK) { blocks_.push_back(q); *ptr = static_cast<T *>(q); }
+    return rc;
+  }
+  template <typename T> int alloc_slot(T **slot, size_t bytes, bool zero = false) {
+    void *q = nullptr;
+    const int rc = alloc_block(&q, bytes, zero);
+    if (rc == MPN_OK) { track(reinterpret_cast<void **>(slot)); *slot = static_cast<T *>(q); }
+    return rc;
+  }
+  template <typename T> int grow(T **slot, size_t *bytes, size_t need, hipStream_t s, bool zero = false) {
+    return grow_slot(reinterpret_cast<void **>(slot), bytes, need, s, zero);
+  }
+  template <typename T> void free_now(T **ptr) { free_block(reinterpret_cast<void **>(ptr)); }
+  int stream(hipStream_t *s);
+  int event(hipEvent_t *e, bool timing = false);
+  void drop(hipStream_t *s);
+  void drop(hipEvent_t *e);
+  void release_streams();  // streams and events (the handle has synchronised the device)
+  void release_buffers();
+  void release() { release_streams(); release_buffers(); }
+
+ private:
+  int alloc_block(void **q, size_t bytes, bool zero);
+  int grow_slot(void **slot, size_t *bytes, size_t need, hipStream_t s, bool zero);
+  void free_block(void **ptr);
+  void track(void **slot);
+  std::vector<void *> blocks_;   // fixed buffers
+  std::vector<void **> slots_;   // addresses of the handle's replaceable-buffer members
+  std::vector<hipStream_t> streams_;
+  std::vector<hipEvent_t> events_;
+};
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): function attributes are per device.
 int set_max_dyn_lds(const void *fn, int bytes);
 int project_im_rois_copy(const float *d_boxes, int n, double scale, float *d_rois, float *d_boxes_copy, hipStream_t s);  // boxes.hip

@@ -13,6 +13,7 @@
 #include <iterator>
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -333,7 +334,7 @@ struct mpn_frcnn {
   hipStream_t tower_stream = nullptr;
   hipEvent_t ev_lane_go = nullptr, ev_lane_done = nullptr;
   float *ty2 = nullptr, *tz6_2 = nullptr;
-  std::vector<void *> allocs;
+  DeviceOwner own;  // every device buffer, stream and event below that lives as long as the handle (mpn_internal.h)
   Scratch scratch;  // split-K slabs, NMS masks, ... of THIS handle (bound to the calling thread by ScratchScope in every entry point)
   int device = 0;   // the handle lives on the device that was current at creation
   // host-fed throughput form (mpn_frcnn_test_one_pipelined_host): three staging sets filled by the copy stream
@@ -370,7 +371,7 @@ struct mpn_frcnn {
   GraphKey unseen[4][kUnseen] = {};
   bool unseen_valid[4][kUnseen] = {};
   int unseen_next[4] = {0, 0, 0, 0};
-  int graphs_on = 0;                 // mpn_frcnn_set_graphs / MPN_GRAPHS (opt-in: see create_impl)
+  int graphs_on = 0;                 // mpn_frcnn_set_graphs / MPN_GRAPHS (opt-in: see create_handle)
   hipStream_t cap_stream = nullptr;  // capture happens here (the caller's stream may be the legacy NULL stream, which cannot capture)
   int seg_shape[4][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};  // shape of the last execution per segment kind
   long graph_replays = 0, graph_captures = 0;
@@ -402,6 +403,7 @@ struct mpn_frcnn {
     float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
     int *labels = nullptr;
     int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
+    DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
   };
   Train *train = nullptr;
   // optional per-kernel-group timing with HIP events recorded on the launch stream
@@ -418,7 +420,7 @@ struct ProfScope {
   ProfScope(mpn_frcnn *p_, int tag, hipStream_t s_) : p(p_), s(s_), on(p_->prof) {
     if (!on) return;
     if (p->ev_used + 2 > p->ev_pool.size()) {
-      for (int i = 0; i < 64; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { on = false; return; } p->ev_pool.push_back(e); }
+      for (int i = 0; i < 64; ++i) { hipEvent_t e; if (p->own.event(&e, true) != MPN_OK) { on = false; return; } p->ev_pool.push_back(e); }
     }
     p->ev_tag.push_back(tag);
     (void)hipEventRecord(p->ev_pool[p->ev_used], s);
@@ -468,20 +470,6 @@ extern "C" void mpn_debug_set_halo_memset(int v) { g_halo_memset = v; }
 extern "C" void mpn_debug_set_defer_heads(int v) { g_defer_heads = v; }
 #endif
 
-template <typename T>
-static int dev_alloc(mpn_frcnn *p, T **ptr, size_t bytes, bool zero) {
-  void *q = nullptr;
-  hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-  if (e != hipSuccess) { set_error("mpn_frcnn_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); return MPN_ENOMEM; }
-  if (zero) {
-    e = hipMemset(q, 0, bytes ? bytes : 16);
-    if (e != hipSuccess) { set_error("mpn_frcnn_create: hipMemset failed: %s", hipGetErrorString(e)); return MPN_EHIP; }
-  }
-  p->allocs.push_back(q);
-  *ptr = static_cast<T *>(q);
-  return MPN_OK;
-}
-
 // the final trunk map's size for an h x w network input: halved (rounding up) at every pooling layer
 static void final_map_size(const mpn_frcnn *p, int *h, int *w) {
   for (auto &L : p->conv) if (L.pool) { *h = (*h + 1) / 2; *w = (*w + 1) / 2; }
@@ -506,54 +494,296 @@ static const char *handle_kind_name(const mpn_frcnn *p) {
 }
 
 static void free_train_state(mpn_frcnn *p) {
-  if (!p->train) return;
-  mpn_frcnn::Train *t = p->train;
-  for (float *q : {t->vh, t->vbh, t->v7, t->vb7, t->v6, t->vb6, t->x6, t->y6, t->y7, t->head, t->gh, t->g7, t->g6, t->rois, t->gt, t->loss}) if (q) (void)hipFree(q);
-  if (t->labels) (void)hipFree(t->labels);
-  delete t;
+  delete p->train;  // (its DeviceOwner gives the buffers back)
   p->train = nullptr;
 }
 
+// Everything the handle holds on the device goes back through its DeviceOwner (mpn_internal.h): no buffer, stream or event is named here.
 extern "C" void mpn_frcnn_destroy(mpn_frcnn *p) {
   if (!p) return;
   (void)hipDeviceSynchronize();
   for (auto &kv : p->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-  if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
-  for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
-  for (int i = 0; i < 2; ++i) { if (p->ev_head[i]) (void)hipEventDestroy(p->ev_head[i]); if (p->ev_tail[i]) (void)hipEventDestroy(p->ev_tail[i]); }
-  if (p->ev_fc7) (void)hipEventDestroy(p->ev_fc7);
-  if (p->side) (void)hipStreamDestroy(p->side);
-  for (int i = 0; i < 3; ++i) { if (p->ev_pool_done[i]) (void)hipEventDestroy(p->ev_pool_done[i]); if (p->ev_mix_done[i]) (void)hipEventDestroy(p->ev_mix_done[i]); }
-  if (p->ev_pool_go) (void)hipEventDestroy(p->ev_pool_go);
-  if (p->tower_stream) (void)hipStreamDestroy(p->tower_stream);
-  if (p->ev_lane_go) (void)hipEventDestroy(p->ev_lane_go);
-  if (p->ev_lane_done) (void)hipEventDestroy(p->ev_lane_done);
-  if (p->copy) (void)hipStreamDestroy(p->copy);
-  for (int i = 0; i < mpn_frcnn::kStage; ++i) { if (p->ev_up[i]) (void)hipEventDestroy(p->ev_up[i]); if (p->ev_consumed[i]) (void)hipEventDestroy(p->ev_consumed[i]); }
+  p->own.release_streams();
   p->scratch.release();
-  for (int i = 0; i < mpn_frcnn::kStage; ++i) if (p->stage_img[i]) (void)hipFree(p->stage_img[i]);
-  for (void *q : p->allocs) (void)hipFree(q);
+  p->own.release_buffers();
   resnet_free(p->rn);
-  for (float *q : {p->scaled, p->scale_tmp, p->ms_feat, p->ms_pm, p->aug_img, p->aug_boxes, p->aug_scores, p->aug_bbox, p->mir.buf, p->mir.pm, p->dbg})
-    if (q) (void)hipFree(q);
-  for (int i = 0; i < 4; ++i) if (p->sh_buf[i]) (void)hipFree(p->sh_buf[i]);
   free_train_state(p);
   delete p;
 }
 
-static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w, const float *const *d_conv_b,
-                       const float *d_fc6_w, const float *d_fc6_b, const float *d_fc7_w, const float *d_fc7_b,
-                       const float *d_cls_w, const float *d_cls_b, const float *d_bbox_w, const float *d_bbox_b,
-                       const mpn_mpnet_weights *mw, mpn_frcnn **out, const mpn_resnet_weights *rw = nullptr, const mpn_graph_weights *gw = nullptr) {
-  MPN_CHECK_ARG(cfg && d_cls_w && d_bbox_w && out);
-  const bool graph_net = rw || gw;  // the trunk / per-ROI stage live in a ResNetGraph object
-  MPN_CHECK_ARG(graph_net || (d_conv_w && d_conv_b));
-  MPN_CHECK_ARG(graph_net || mw || (d_fc6_w && d_fc7_w));
+// ---- create: config checks, then one builder per part of the handle.  The builders allocate in a fixed order (trunk, graph net, towers /
+// classifier or plain head, tail): placement in HBM is part of what the headline was measured with.
+#define TRY(x) do { const int rc_ = (x); if (rc_ != MPN_OK) return rc_; } while (0)
+
+struct CreateArgs {
+  const mpn_frcnn_config *cfg;
+  const float *const *conv_w, *const *conv_b;
+  const float *fc6_w, *fc6_b, *fc7_w, *fc7_b, *cls_w, *cls_b, *bbox_w, *bbox_b;
+  const mpn_mpnet_weights *mw; const mpn_resnet_weights *rw; const mpn_graph_weights *gw;  // at most one of them
+  bool graph_net() const { return rw || gw; }  // the trunk / per-ROI stage live in a ResNetGraph object
+  int tower_heads() const { return rw ? rw->n_heads : (gw ? gw->n_heads : 0); }  // > 1: MultiPathNet towers on a ResNet / op-list backbone
+};
+
+// packed weights and bias of one linear layer [N, K] (`inner`: see pack_linear_weights)
+static int pack_linear(mpn_frcnn *p, const float *w, const float *b, int K, int N, int inner, float **wpk, float **bpk) {
+  TRY(p->own.alloc(wpk, lin_wpk_elems(round_up(K, 64), N) * sizeof(float)));
+  TRY(p->own.alloc(bpk, (size_t)lin_np(N) * sizeof(float)));
+  return pack_linear_weights(w, b, K, N, inner, *wpk, *bpk, nullptr);
+}
+// MPN_FC_SPLIT3: the packed fp32 weights [K/8][NP][8] split once into three bf16 planes [3][K/8][NP↑256][8] (include/mpn.h)
+static int pack_split3(mpn_frcnn *p, const float *wpk, int K, int N, unsigned short **planes) {
+  TRY(p->own.alloc(planes, split3_plane_elems(K, lin_np(N)) * sizeof(unsigned short), true));
+  return split3_planes(wpk, K, lin_np(N), lin_np(N), *planes, nullptr);
+}
+
+// Everything that can be refused from the descriptors alone, before a handle or a byte of device memory exists.
+static int check_config(const CreateArgs &a) {
+  const mpn_frcnn_config *cfg = a.cfg;
+  MPN_CHECK_ARG(cfg && a.cls_w && a.bbox_w);
+  const bool graph_net = a.graph_net();
+  MPN_CHECK_ARG(graph_net || (a.conv_w && a.conv_b));
+  MPN_CHECK_ARG(graph_net || a.mw || (a.fc6_w && a.fc7_w));
   MPN_CHECK_ARG(graph_net || (cfg->n_conv > 0 && cfg->conv_cout && cfg->pool_after && cfg->fc_dim > 0));
   MPN_CHECK_ARG(cfg->pooled_h > 0 && cfg->pooled_w > 0 && cfg->n_classes > 1);
   MPN_CHECK_ARG(cfg->max_h > 0 && cfg->max_w > 0 && cfg->max_rois > 0 && cfg->max_rois <= MPN_NMS_MAX_BOXES);
   MPN_CHECK_ARG(cfg->top_k > 0);
-  mpn_frcnn *p = new mpn_frcnn();
+  if (!(cfg->fc_arith == MPN_FC_FP32 || (cfg->fc_arith == MPN_FC_SPLIT3 && !graph_net))) { set_error("mpn_frcnn_config.fc_arith: %d (MPN_FC_SPLIT3 is for mpn_frcnn_create / mpn_mpnet_create pipelines)", cfg->fc_arith); return MPN_EINVAL; }
+  if (cfg->roi_bin_rule != MPN_ROI_BINS_CAFFE && cfg->roi_bin_rule != MPN_ROI_BINS_ADAPTIVE) { set_error("mpn_frcnn_config.roi_bin_rule: %d is not an MPN_ROI_BINS_* value", cfg->roi_bin_rule); return MPN_EINVAL; }
+  for (int l = 0; !graph_net && l < cfg->n_conv; ++l) MPN_CHECK_ARG(a.conv_w[l] != nullptr);
+  const int C = cfg->n_classes;
+  if (const mpn_mpnet_weights *mw = a.mw) {
+    MPN_CHECK_ARG(mw->n_towers >= 2 && mw->n_towers <= 8 && mw->tap_conv3 >= 0 && mw->tap_conv4 > mw->tap_conv3 && mw->tap_conv4 < cfg->n_conv - 1);
+    MPN_CHECK_ARG(C <= 256 && cfg->fc_dim % 128 == 0);
+    MPN_CHECK_ARG(cfg->conv_cout[mw->tap_conv4] % 8 == 0 && cfg->conv_cout[mw->tap_conv3] % 8 == 0);
+    for (int t = 0; t < mw->n_towers; ++t)
+      MPN_CHECK_ARG(mw->region[t] >= 0 && mw->region[t] < 4 && mw->mix_w[t] && mw->fc6_w[t] && mw->fc7_w[t]);
+  } else if (a.tower_heads() > 1) {
+    const int *region = a.rw ? a.rw->head_region : a.gw->head_region;
+    MPN_CHECK_ARG(C <= 256 && a.tower_heads() <= 8);
+    for (int t = 0; t < a.tower_heads(); ++t) MPN_CHECK_ARG(region[t] >= 0 && region[t] < 4);
+  }
+  const int n_it = cfg->num_iter > 1 ? cfg->num_iter : 1;
+  MPN_CHECK_ARG((size_t)n_it * cfg->max_rois <= MPN_NMS_MAX_BOXES);
+  MPN_CHECK_ARG(!cfg->use_rbox_scores || n_it > 1);  // Tester_FRCNN.lua:92 assert(#all_output > 1)
+  return MPN_OK;
+}
+
+// the conv layers' packed / Winograd / K = 36 weights, one C8P buffer per layer output, the MultiPathNet maps' range-max tables
+static int build_vgg_trunk(mpn_frcnn *p, const CreateArgs &a) {
+  const mpn_mpnet_weights *mw = a.mw;
+  const int n_conv = p->cfg.n_conv;
+  int h = p->cfg.max_h, w = p->cfg.max_w, cin = 3;
+  size_t b = act_bytes(3, h, w);
+  TRY(p->own.alloc(&p->img_c8p, b, true));
+  p->act_bufs.push_back({p->img_c8p, b});
+  for (int l = 0; l < n_conv; ++l) {
+    ConvLayer L;
+    L.Cin = cin; L.Cout = p->cout[l]; L.pool = p->pool_after[l];
+    TRY(p->own.alloc(&L.wpk, conv_wpk_elems(L.Cin, L.Cout) * sizeof(float)));
+    TRY(p->own.alloc(&L.bpk, (size_t)conv_coutp(L.Cout) * sizeof(float)));
+    TRY(pack_conv_weights(a.conv_w[l], a.conv_b[l], L.Cin, L.Cout, L.wpk, L.bpk, nullptr));
+    if (L.Cin <= 4 && !L.pool && !(mw && (l == mw->tap_conv3 || l == mw->tap_conv4))) {
+      TRY(p->own.alloc(&L.w36, conv_first_elems(L.Cout) * sizeof(float)));
+      TRY(pack_conv_weights_first(a.conv_w[l], L.Cin, L.Cout, L.w36, nullptr));
+    }
+    if (L.Cin >= 16) {  // fewer input channels: direct kernels (the 3-channel first layer is bound by its output stores either way)
+      TRY(p->own.alloc(&L.wino, conv_wino_elems(L.Cin, L.Cout) * sizeof(float)));
+      TRY(pack_conv_weights_wino(a.conv_w[l], L.Cin, L.Cout, L.wino, nullptr));
+    }
+    b = act_bytes(L.Cout, h, w);
+    TRY(p->own.alloc(&L.out, b, true));
+    p->act_bufs.push_back({L.out, b});
+    if (mw && (l == mw->tap_conv3 || l == mw->tap_conv4 || l == n_conv - 1)) {  // range-max tables of the maps the towers pool
+      const int slot = l == n_conv - 1 ? 0 : (l == mw->tap_conv4 ? 1 : 2);
+      TRY(p->own.alloc(&p->vmax_tab[slot], (size_t)(vmax_levels_for(h) + 1) * b));  // levels 1..L (C8P form) or 0..L (pixel-major form)
+    }
+    if (L.pool) {
+      h = (h + 1) / 2; w = (w + 1) / 2;
+      b = act_bytes(L.Cout, h, w);
+      TRY(p->own.alloc(&L.pooled, b, true));
+      p->act_bufs.push_back({L.pooled, b});
+    }
+    cin = L.Cout;
+    p->conv.push_back(L);
+  }
+  p->feat_c = cin;
+  return MPN_OK;
+}
+
+// ResNet / op-list graph: the graph object owns the trunk and per-ROI weights and activations; the cls + bbox heads read its pooled vector
+static int build_graph_net(mpn_frcnn *p, const CreateArgs &a) {
+  const mpn_frcnn_config &c = p->cfg;
+  if (a.rw) TRY(resnet_build(a.rw, c.max_h, c.max_w, c.max_rois, c.pooled_h, &p->rn));
+  else TRY(graph_build(a.gw, c.max_h, c.max_w, c.max_rois, c.pooled_h, &p->rn));
+  p->feat_c = resnet_feat_channels(p->rn);
+  resnet_set_roi_bins(p->rn, c.roi_bin_rule);
+  p->cfg.fc_dim = resnet_out_channels(p->rn);
+  return MPN_OK;
+}
+
+// MultiPathNet (models/multipathnet.lua:64-120): the towers' mix / fc6 / fc7 weights, and which pair of them shares one pooled operand
+static int build_mpnet_towers(mpn_frcnn *p, const CreateArgs &a) {
+  const mpn_mpnet_weights *mw = a.mw;
+  const int PP = p->cfg.pooled_h * p->cfg.pooled_w, F = p->cfg.fc_dim;
+  const int c5 = p->feat_c, c4 = p->cout[p->tap4], c3 = p->cout[p->tap3];
+  for (int t = 0; t < mw->n_towers; ++t) {
+    mpn_frcnn::Tower T{};
+    T.region = mw->region[t]; T.use4 = mw->use_conv4[t]; T.use3 = mw->use_conv3[t];
+    T.total_feat = c5 + (T.use4 ? c4 : 0) + (T.use3 ? c3 : 0);
+    TRY(pack_linear(p, mw->mix_w[t], mw->mix_b[t], T.total_feat, c5, 1, &T.mix_w, &T.mix_b));
+    TRY(pack_linear(p, mw->fc6_w[t], mw->fc6_b[t], p->K6, F, PP, &T.w6, &T.b6));
+    TRY(pack_linear(p, mw->fc7_w[t], mw->fc7_b[t], F, F, 1, &T.w7, &T.b7));
+    if (p->cfg.fc_arith == MPN_FC_SPLIT3) {  // the towers' fc6 / fc7 weights as three bf16 planes
+      TRY(pack_split3(p, T.w6, p->K6, F, &T.w6_s3));
+      TRY(pack_split3(p, T.w7, F, F, &T.w7_s3));
+    }
+    p->towers.push_back(T);
+  }
+  for (int a_ = 0; a_ < (int)p->towers.size() && p->share_provider < 0; ++a_)      // the first (provider, consumer) pair, if any
+    for (int b = 0; b < (int)p->towers.size() && p->share_provider < 0; ++b) {
+      const mpn_frcnn::Tower &A = p->towers[a_], &B = p->towers[b];
+      if (a_ == b || A.region != B.region || A.total_feat <= B.total_feat) continue;
+      int la[3], lb[3], na = 0, nb = 0;   // the towers' map lists in concat order (conv345Combine: conv5, [conv4], [conv3])
+      la[na++] = 0; if (A.use4) la[na++] = 1; if (A.use3) la[na++] = 2;
+      lb[nb++] = 0; if (B.use4) lb[nb++] = 1; if (B.use3) lb[nb++] = 2;
+      bool prefix = nb <= na;
+      for (int i = 0; prefix && i < nb; ++i) prefix = la[i] == lb[i];
+      if (prefix) { p->share_provider = a_; p->share_consumer = b; }
+    }
+  return MPN_OK;
+}
+
+// MultiPathNet: the towers' pooled operands and mix / fc6 outputs of both lanes, the pooling events (the pooling stream is `side`: build_streams)
+static int build_mpnet_operands(mpn_frcnn *p) {
+  const int PP = p->cfg.pooled_h * p->cfg.pooled_w, F = p->cfg.fc_dim, c5 = p->feat_c;
+  int max_feat = 0;
+  for (const mpn_frcnn::Tower &T : p->towers) max_feat = std::max(max_feat, T.total_feat);
+  const size_t rows = (size_t)PP * p->Mp;
+  const size_t tx_bytes = (size_t)(round_up(max_feat, 64) / 8) * rows * 8 * sizeof(float);
+  const size_t ty_bytes = (size_t)(lin_np(c5) / 8) * rows * 8 * sizeof(float), tz_bytes = (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float);
+  TRY(p->own.alloc(&p->mix_scale, (size_t)3 * 3 * p->Mp * sizeof(float), true));
+  TRY(p->own.alloc(&p->tx2, tx_bytes, true));
+  if (p->share_provider >= 0) TRY(p->own.alloc(&p->tx3, tx_bytes, true));
+  p->pool_on_side = true;
+  for (int i = 0; i < 3; ++i) { TRY(p->own.event(&p->ev_pool_done[i])); TRY(p->own.event(&p->ev_mix_done[i])); }
+  TRY(p->own.event(&p->ev_pool_go));
+  TRY(p->own.alloc(&p->tx, tx_bytes, true));
+  TRY(p->own.alloc(&p->ty, ty_bytes, true));
+  TRY(p->own.alloc(&p->tz6, tz_bytes, true));
+  if (p->cfg.fc_arith == MPN_FC_SPLIT3)
+    for (int ln = 0; ln < 2; ++ln) {
+      TRY(p->own.alloc(&p->ty_s3[ln], split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
+      TRY(p->own.alloc(&p->tz6_s3[ln], split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
+    }
+  TRY(p->own.alloc(&p->ty2, ty_bytes, true));  // the second tower lane
+  return p->own.alloc(&p->tz6_2, tz_bytes, true);
+}
+
+// The integral classifier stage (model_utils.lua:296-313) behind `n_towers` towers, MultiPathNet's and the ResNet / op-list towers' alike:
+// K classifiers on the Foveal towers' concat, the bbox regressor on tower 0, the concat and row-major outputs, the second lane's stream.
+static int build_integral_classifier(mpn_frcnn *p, const CreateArgs &a, int n_towers, bool second_lane) {
+  const int C = p->cfg.n_classes, F = p->cfg.fc_dim, n_fov = n_towers - 1, K = p->n_integral;
+  const size_t M = p->cfg.max_rois;
+  TRY(pack_linear(p, a.cls_w, a.cls_b, n_fov * F, K * C, 1, &p->wcls, &p->bcls));
+  TRY(pack_linear(p, a.bbox_w, a.bbox_b, F, 4 * C, 1, &p->wbbox, &p->bbbox));
+  TRY(p->own.alloc(&p->fov, M * 20 * sizeof(float), true));
+  if (p->is_mpnet) TRY(build_mpnet_operands(p));  // here, between fov and cat: create's allocation order is kept as it was
+  TRY(p->own.alloc(&p->cat, (size_t)n_towers * (lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
+  TRY(p->own.alloc(&p->cls_rm, M * K * C * sizeof(float), true));
+  TRY(p->own.alloc(&p->bbox_rm, M * 4 * C * sizeof(float), true));
+  if (second_lane) {
+    TRY(p->own.stream(&p->tower_stream));
+    TRY(p->own.event(&p->ev_lane_go));
+    TRY(p->own.event(&p->ev_lane_done));
+  }
+  return MPN_OK;
+}
+
+// The plain Fast R-CNN head: fc6, fc7 (VGG trunks; a graph net ends in its own per-ROI stage), the fused cls + bbox GEMM, x6 / y6 / y7 / head,
+// the final map's pixel-major copy.  *tmp_w / *tmp_b: the concatenated head weights, which the caller frees once packing has completed.
+static int build_plain_head(mpn_frcnn *p, const CreateArgs &a, float **tmp_w, float **tmp_b) {
+  const bool graph_net = a.graph_net(), split3 = p->cfg.fc_arith == MPN_FC_SPLIT3;
+  const int PP = p->cfg.pooled_h * p->cfg.pooled_w, C = p->cfg.n_classes, F = p->cfg.fc_dim;
+  const size_t M = p->cfg.max_rois, y_bytes = (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float);
+  if (!graph_net) {
+    TRY(pack_linear(p, a.fc6_w, a.fc6_b, p->K6, F, PP, &p->w6, &p->b6));
+    if (split3) {  // the weights' planes once, the operand's per image
+      TRY(pack_split3(p, p->w6, p->K6, F, &p->w6_s3));
+      TRY(p->own.alloc(&p->x6_s3, split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
+    }
+    TRY(pack_linear(p, a.fc7_w, a.fc7_b, F, F, 1, &p->w7, &p->b7));
+    if (split3) {
+      TRY(pack_split3(p, p->w7, F, F, &p->w7_s3));
+      TRY(p->own.alloc(&p->y6_s3, split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
+    }
+  }
+  // cls and bbox heads share their input -> one [5C, F] GEMM (model_utils.lua:105-119 ConcatTable)
+  TRY(p->own.alloc(tmp_w, (size_t)5 * C * F * sizeof(float)));
+  TRY(p->own.alloc(tmp_b, (size_t)5 * C * sizeof(float), true));
+  hipError_t e = hipMemcpy(*tmp_w, a.cls_w, (size_t)C * F * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(*tmp_w + (size_t)C * F, a.bbox_w, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && a.cls_b) e = hipMemcpy(*tmp_b, a.cls_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && a.bbox_b) e = hipMemcpy(*tmp_b + C, a.bbox_b, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) { set_error("mpn_frcnn_create: head weight copy failed: %s", hipGetErrorString(e)); return MPN_EHIP; }
+  TRY(pack_linear(p, *tmp_w, *tmp_b, F, 5 * C, 1, &p->wh, &p->bh));
+  if (!graph_net) {
+    int fh = p->cfg.max_h, fw = p->cfg.max_w;  // pixel-major copy of the final map at its largest size
+    final_map_size(p, &fh, &fw);
+    TRY(p->own.alloc(&p->up.pm, (size_t)fh * fw * ((p->feat_c + 7) / 8) * 8 * sizeof(float)));
+    TRY(p->own.alloc(&p->x6, (size_t)(round_up(p->K6, 64) / 8) * p->Mp * 8 * sizeof(float), true));
+    TRY(p->own.alloc(&p->y6, y_bytes, true));
+  }
+  TRY(p->own.alloc(&p->y7, y_bytes, true));
+  return p->own.alloc(&p->head, M * 5 * C * sizeof(float), true);
+}
+
+// rois, score / box tables, the iterative-localisation tables, the two NMS buffer sets
+static int build_tail(mpn_frcnn *p) {
+  const mpn_frcnn_config &c = p->cfg;
+  const size_t M = c.max_rois, C = c.n_classes;
+  TRY(p->own.alloc(&p->rois, M * 5 * sizeof(float), true));
+  TRY(p->own.alloc(&p->scores, M * C * sizeof(float), true));
+  TRY(p->own.alloc(&p->bbox, M * 4 * C * sizeof(float), true));
+  TRY(p->own.alloc(&p->bbox_raw, M * 4 * C * sizeof(float), true));
+  const int n_it = p->cfg.num_iter = std::max(c.num_iter, 1);
+  const size_t MR = M * n_it;  // rows that reach NMS per class
+  if (n_it > 1) {
+    TRY(p->own.alloc(&p->it_scores, MR * C * sizeof(float), true));
+    TRY(p->own.alloc(&p->it_bbox, MR * 4 * C * sizeof(float), true));
+    TRY(p->own.alloc(&p->it_boxes, M * 4 * sizeof(float), true));
+  }
+  for (int i = 0; i < 2; ++i) {
+    TRY(p->own.alloc(&p->scored_b[i], (C - 1) * MR * 5 * sizeof(float), true));
+    TRY(p->own.alloc(&p->keep_b[i], (C - 1) * MR * 5 * sizeof(float), true));
+    if (c.bbox_voting) TRY(p->own.alloc(&p->voted_b[i], (C - 1) * MR * 5 * sizeof(float), true));
+    TRY(p->own.alloc(&p->keep_idx_b[i], (C - 1) * MR * sizeof(int), true));
+    TRY(p->own.alloc(&p->counts_b[i], (C - 1) * sizeof(int), true));
+    TRY(p->own.alloc(&p->n_keep_b[i], (C - 1) * sizeof(int), true));
+    TRY(p->own.alloc(&p->thresh_b[i], 16, true));
+  }
+  p->scored = p->scored_b[0]; p->keep = p->keep_b[0]; p->keep_idx = p->keep_idx_b[0];
+  p->counts = p->counts_b[0]; p->n_keep = p->n_keep_b[0]; p->thresh = p->thresh_b[0];
+  return MPN_OK;
+}
+
+// The side stream (NMS / top-k tail under the next image's trunk) has the DEFAULT priority since round 5.  Rounds 1-4 created it with
+// the highest one; what that bought the headline is nothing measurable (3.457-3.476 ms either way, six alternating runs), and what it can
+// cost is large: a priority stream lands in a different hardware-queue class, and depending on which queue HIP's round-robin hands it,
+// EVERY dispatch of the launch queue took 30-50 us longer while the two queues were both active — a mixed-size stream inside bench.py ran
+// at 4.59 ms per image with the highest priority, 4.05 with the lowest, 3.12 with the default (profiles/r05_mixed_sizes_timeline.txt).
+static int build_streams(mpn_frcnn *p) {
+  TRY(p->own.stream(&p->side));
+  for (int i = 0; i < 2; ++i) { TRY(p->own.event(&p->ev_head[i])); TRY(p->own.event(&p->ev_tail[i])); }
+  if (p->pool_on_side) p->pool_stream = p->side;
+  return MPN_OK;
+}
+
+static int create_handle(const CreateArgs &a, mpn_frcnn **out) {
+  MPN_CHECK_ARG(out != nullptr);
+  TRY(check_config(a));
+  const mpn_frcnn_config *cfg = a.cfg;
+  std::unique_ptr<mpn_frcnn, decltype(&mpn_frcnn_destroy)> h(new mpn_frcnn(), mpn_frcnn_destroy);  // from here on every return destroys the handle and what it owns
+  mpn_frcnn *p = h.get();
   p->cfg = *cfg;
   p->create_scale_target = cfg->scale_target;
   {  // captured launch graphs: OFF unless asked for (MPN_GRAPHS=1 in the environment, or mpn_frcnn_set_graphs per handle).  Measured on
@@ -563,270 +793,44 @@ static int create_impl(const mpn_frcnn_config *cfg, const float *const *d_conv_w
     const char *e = getenv("MPN_GRAPHS");
     if (e && (e[0] == '0' || e[0] == '1')) p->graphs_on = e[0] == '1';
   }
-  if (hipGetDevice(&p->device) != hipSuccess) { delete p; set_error("mpn_frcnn_create: no current HIP device"); return MPN_EHIP; }
+  if (hipGetDevice(&p->device) != hipSuccess) { set_error("mpn_frcnn_create: no current HIP device"); return MPN_EHIP; }
   p->scratch.device = p->device;
   ScratchScope scratch_scope(&p->scratch);
-  const int tower_heads = rw ? rw->n_heads : (gw ? gw->n_heads : 0);  // > 1: MultiPathNet towers on a ResNet / op-list backbone
-  const int *tower_region = rw ? rw->head_region : (gw ? gw->head_region : nullptr);
-  if (tower_heads > 1) p->n_integral = (rw ? rw->n_integral : gw->n_integral) > 0 ? (rw ? rw->n_integral : gw->n_integral) : 1;
-  if (mw) { p->is_mpnet = true; p->tap3 = mw->tap_conv3; p->tap4 = mw->tap_conv4; p->n_integral = mw->n_integral > 0 ? mw->n_integral : 1; p->conv345_norm = !mw->conv345_unnormalized; }
+  const bool graph_net = a.graph_net();
+  const int tower_heads = a.tower_heads();
+  if (tower_heads > 1) p->n_integral = (a.rw ? a.rw->n_integral : a.gw->n_integral) > 0 ? (a.rw ? a.rw->n_integral : a.gw->n_integral) : 1;
+  if (const mpn_mpnet_weights *mw = a.mw) { p->is_mpnet = true; p->tap3 = mw->tap_conv3; p->tap4 = mw->tap_conv4; p->n_integral = mw->n_integral > 0 ? mw->n_integral : 1; p->conv345_norm = !mw->conv345_unnormalized; }
   const int n_conv = graph_net ? 0 : cfg->n_conv;
   p->cfg.n_conv = n_conv;
   if (n_conv) { p->cout.assign(cfg->conv_cout, cfg->conv_cout + n_conv); p->pool_after.assign(cfg->pool_after, cfg->pool_after + n_conv); }
   p->cfg.conv_cout = p->cout.data();
   p->cfg.pool_after = p->pool_after.data();
-  int rc = MPN_OK;
-#define TRY(x) do { rc = (x); if (rc != MPN_OK) { mpn_frcnn_destroy(p); return rc; } } while (0)
-  TRY((cfg->fc_arith == MPN_FC_FP32 || (cfg->fc_arith == MPN_FC_SPLIT3 && !graph_net)) ? MPN_OK : (set_error("mpn_frcnn_config.fc_arith: %d (MPN_FC_SPLIT3 is for mpn_frcnn_create / mpn_mpnet_create pipelines)", cfg->fc_arith), MPN_EINVAL));
-  TRY((cfg->roi_bin_rule == MPN_ROI_BINS_CAFFE || cfg->roi_bin_rule == MPN_ROI_BINS_ADAPTIVE) ? MPN_OK : (set_error("mpn_frcnn_config.roi_bin_rule: %d is not an MPN_ROI_BINS_* value", cfg->roi_bin_rule), MPN_EINVAL));
-  // ---- trunk buffers + packed weights
-  int h = cfg->max_h, w = cfg->max_w, cin = 3;
-  size_t b = act_bytes(3, h, w);
-  TRY(dev_alloc(p, &p->img_c8p, b, true));
-  p->act_bufs.push_back({p->img_c8p, b});
-  for (int l = 0; l < n_conv; ++l) {
-    MPN_CHECK_ARG(d_conv_w[l] != nullptr);
-    ConvLayer L;
-    L.Cin = cin; L.Cout = p->cout[l]; L.pool = p->pool_after[l];
-    TRY(dev_alloc(p, &L.wpk, conv_wpk_elems(L.Cin, L.Cout) * sizeof(float), false));
-    TRY(dev_alloc(p, &L.bpk, (size_t)conv_coutp(L.Cout) * sizeof(float), false));
-    TRY(pack_conv_weights(d_conv_w[l], d_conv_b[l], L.Cin, L.Cout, L.wpk, L.bpk, nullptr));
-    if (L.Cin <= 4 && !L.pool && !(mw && (l == mw->tap_conv3 || l == mw->tap_conv4))) {
-      TRY(dev_alloc(p, &L.w36, conv_first_elems(L.Cout) * sizeof(float), false));
-      TRY(pack_conv_weights_first(d_conv_w[l], L.Cin, L.Cout, L.w36, nullptr));
-    }
-    if (L.Cin >= 16) {  // fewer input channels: direct kernels (the 3-channel first layer is bound by its output stores either way)
-      TRY(dev_alloc(p, &L.wino, conv_wino_elems(L.Cin, L.Cout) * sizeof(float), false));
-      TRY(pack_conv_weights_wino(d_conv_w[l], L.Cin, L.Cout, L.wino, nullptr));
-    }
-    b = act_bytes(L.Cout, h, w);
-    TRY(dev_alloc(p, &L.out, b, true));
-    p->act_bufs.push_back({L.out, b});
-    if (mw && (l == mw->tap_conv3 || l == mw->tap_conv4 || l == n_conv - 1)) {  // range-max tables of the maps the towers pool
-      const int slot = l == n_conv - 1 ? 0 : (l == mw->tap_conv4 ? 1 : 2);
-      TRY(dev_alloc(p, &p->vmax_tab[slot], (size_t)(vmax_levels_for(h) + 1) * b, false));  // levels 1..L (C8P form) or 0..L (pixel-major form)
-    }
-    if (L.pool) {
-      h = (h + 1) / 2; w = (w + 1) / 2;
-      b = act_bytes(L.Cout, h, w);
-      TRY(dev_alloc(p, &L.pooled, b, true));
-      p->act_bufs.push_back({L.pooled, b});
-    }
-    cin = L.Cout;
-    p->conv.push_back(L);
-  }
-  p->feat_c = cin;
-  if (graph_net) {  // ResNet / op-list graph: the graph object owns the trunk and per-ROI weights and activations; the cls + bbox heads read its pooled vector
-    if (rw) TRY(resnet_build(rw, cfg->max_h, cfg->max_w, cfg->max_rois, cfg->pooled_h, &p->rn));
-    else TRY(graph_build(gw, cfg->max_h, cfg->max_w, cfg->max_rois, cfg->pooled_h, &p->rn));
-    p->feat_c = resnet_feat_channels(p->rn);
-    resnet_set_roi_bins(p->rn, cfg->roi_bin_rule);
-  }
-  // ---- head
-  const int PP = cfg->pooled_h * cfg->pooled_w, C = cfg->n_classes, F = graph_net ? resnet_out_channels(p->rn) : cfg->fc_dim;
-  p->cfg.fc_dim = F;
+  TRY(build_vgg_trunk(p, a));
+  if (graph_net) TRY(build_graph_net(p, a));
   MPN_CHECK_ARG(p->feat_c % 8 == 0);
-  p->K6 = p->feat_c * PP;
+  p->K6 = p->feat_c * cfg->pooled_h * cfg->pooled_w;
   p->Mp = lin_mp(cfg->max_rois);
-  p->n_head = 5 * C;
-  const int K6_32 = round_up(p->K6, 64), F32 = round_up(F, 64);
-  const size_t M = cfg->max_rois;
-  if (mw) {
-    MPN_CHECK_ARG(mw->n_towers >= 2 && mw->n_towers <= 8 && p->tap3 >= 0 && p->tap4 > p->tap3 && p->tap4 < cfg->n_conv - 1);
-    MPN_CHECK_ARG(C <= 256 && F % 128 == 0);
-    const int c5 = p->feat_c, c4 = p->cout[p->tap4], c3 = p->cout[p->tap3];
-    MPN_CHECK_ARG(c4 % 8 == 0 && c3 % 8 == 0);
-    int max_feat = 0;
-    for (int t = 0; t < mw->n_towers; ++t) {
-      mpn_frcnn::Tower T{};
-      T.region = mw->region[t]; T.use4 = mw->use_conv4[t]; T.use3 = mw->use_conv3[t];
-      MPN_CHECK_ARG(T.region >= 0 && T.region < 4 && mw->mix_w[t] && mw->fc6_w[t] && mw->fc7_w[t]);
-      T.total_feat = c5 + (T.use4 ? c4 : 0) + (T.use3 ? c3 : 0);
-      if (T.total_feat > max_feat) max_feat = T.total_feat;
-      const int TF64 = round_up(T.total_feat, 64);
-      TRY(dev_alloc(p, &T.mix_w, lin_wpk_elems(TF64, c5) * sizeof(float), false));
-      TRY(dev_alloc(p, &T.mix_b, (size_t)lin_np(c5) * sizeof(float), false));
-      TRY(pack_linear_weights(mw->mix_w[t], mw->mix_b[t], T.total_feat, c5, 1, T.mix_w, T.mix_b, nullptr));
-      TRY(dev_alloc(p, &T.w6, lin_wpk_elems(K6_32, F) * sizeof(float), false));
-      TRY(dev_alloc(p, &T.b6, (size_t)lin_np(F) * sizeof(float), false));
-      TRY(pack_linear_weights(mw->fc6_w[t], mw->fc6_b[t], p->K6, F, PP, T.w6, T.b6, nullptr));
-      TRY(dev_alloc(p, &T.w7, lin_wpk_elems(F32, F) * sizeof(float), false));
-      TRY(dev_alloc(p, &T.b7, (size_t)lin_np(F) * sizeof(float), false));
-      TRY(pack_linear_weights(mw->fc7_w[t], mw->fc7_b[t], F, F, 1, T.w7, T.b7, nullptr));
-      if (cfg->fc_arith == MPN_FC_SPLIT3) {  // the towers' fc6 / fc7 weights as three bf16 planes (include/mpn.h)
-        TRY(dev_alloc(p, &T.w6_s3, split3_plane_elems(p->K6, lin_np(F)) * sizeof(unsigned short), true));
-        TRY(split3_planes(T.w6, p->K6, lin_np(F), lin_np(F), T.w6_s3, nullptr));
-        TRY(dev_alloc(p, &T.w7_s3, split3_plane_elems(F, lin_np(F)) * sizeof(unsigned short), true));
-        TRY(split3_planes(T.w7, F, lin_np(F), lin_np(F), T.w7_s3, nullptr));
-      }
-      p->towers.push_back(T);
-    }
-    const int n_fov = mw->n_towers - 1, K = p->n_integral;
-    const int KC64 = round_up(n_fov * F, 64);
-    TRY(dev_alloc(p, &p->wcls, lin_wpk_elems(KC64, K * C) * sizeof(float), false));
-    TRY(dev_alloc(p, &p->bcls, (size_t)lin_np(K * C) * sizeof(float), false));
-    TRY(pack_linear_weights(d_cls_w, d_cls_b, n_fov * F, K * C, 1, p->wcls, p->bcls, nullptr));
-    TRY(dev_alloc(p, &p->wbbox, lin_wpk_elems(F32, 4 * C) * sizeof(float), false));
-    TRY(dev_alloc(p, &p->bbbox, (size_t)lin_np(4 * C) * sizeof(float), false));
-    TRY(pack_linear_weights(d_bbox_w, d_bbox_b, F, 4 * C, 1, p->wbbox, p->bbbox, nullptr));
-    const size_t rows = (size_t)PP * p->Mp;
-    TRY(dev_alloc(p, &p->fov, M * 20 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->mix_scale, (size_t)3 * 3 * p->Mp * sizeof(float), true));
-    TRY(dev_alloc(p, &p->tx2, (size_t)(round_up(max_feat, 64) / 8) * rows * 8 * sizeof(float), true));
-    for (int a = 0; a < (int)p->towers.size() && p->share_provider < 0; ++a)      // the first (provider, consumer) pair, if any
-      for (int b = 0; b < (int)p->towers.size() && p->share_provider < 0; ++b) {
-        const mpn_frcnn::Tower &A = p->towers[a], &B = p->towers[b];
-        if (a == b || A.region != B.region || A.total_feat <= B.total_feat) continue;
-        int la[3], lb[3], na = 0, nb = 0;   // the towers' map lists in concat order (conv345Combine: conv5, [conv4], [conv3])
-        la[na++] = 0; if (A.use4) la[na++] = 1; if (A.use3) la[na++] = 2;
-        lb[nb++] = 0; if (B.use4) lb[nb++] = 1; if (B.use3) lb[nb++] = 2;
-        bool prefix = nb <= na;
-        for (int i = 0; prefix && i < nb; ++i) prefix = la[i] == lb[i];
-        if (prefix) { p->share_provider = a; p->share_consumer = b; }
-      }
-    if (p->share_provider >= 0) TRY(dev_alloc(p, &p->tx3, (size_t)(round_up(max_feat, 64) / 8) * rows * 8 * sizeof(float), true));
-    {
-      hipError_t e = hipSuccess;
-      p->pool_on_side = true;   // (p->side is created below)
-      for (int i = 0; i < 3 && e == hipSuccess; ++i) {
-        e = hipEventCreateWithFlags(&p->ev_pool_done[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_mix_done[i], hipEventDisableTiming);
-      }
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_pool_go, hipEventDisableTiming);
-      if (e != hipSuccess) { set_error("mpn_mpnet_create: pooling events: %s", hipGetErrorString(e)); mpn_frcnn_destroy(p); return MPN_EHIP; }
-    }
-    TRY(dev_alloc(p, &p->tx, (size_t)(round_up(max_feat, 64) / 8) * rows * 8 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->ty, (size_t)(lin_np(c5) / 8) * rows * 8 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->tz6, (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
-    if (cfg->fc_arith == MPN_FC_SPLIT3)
-      for (int ln = 0; ln < (mw->n_towers > 1 ? 2 : 1); ++ln) {
-        TRY(dev_alloc(p, &p->ty_s3[ln], split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
-        TRY(dev_alloc(p, &p->tz6_s3[ln], split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
-      }
-    if (mw->n_towers > 1) {  // the second tower lane
-      TRY(dev_alloc(p, &p->ty2, (size_t)(lin_np(c5) / 8) * rows * 8 * sizeof(float), true));
-      TRY(dev_alloc(p, &p->tz6_2, (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
-      hipError_t e = hipStreamCreateWithFlags(&p->tower_stream, hipStreamNonBlocking);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_lane_go, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_lane_done, hipEventDisableTiming);
-      if (e != hipSuccess) { set_error("mpn_mpnet_create: tower stream / events: %s", hipGetErrorString(e)); mpn_frcnn_destroy(p); return MPN_EHIP; }
-    }
-    TRY(dev_alloc(p, &p->cat, (size_t)mw->n_towers * (lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->cls_rm, M * K * C * sizeof(float), true));
-    TRY(dev_alloc(p, &p->bbox_rm, M * 4 * C * sizeof(float), true));
+  p->n_head = 5 * cfg->n_classes;
+  float *tmp_w = nullptr, *tmp_b = nullptr;
+  if (a.mw) {
+    TRY(build_mpnet_towers(p, a));
+    TRY(build_integral_classifier(p, a, a.mw->n_towers, true));
   } else if (tower_heads > 1) {  // ResNet / graph towers (this library's extension, see mpn_resnet_weights): same classifier stage as MultiPathNet
-    const int n_fov = tower_heads - 1, K = p->n_integral;
-    MPN_CHECK_ARG(C <= 256 && tower_heads <= 8);
-    const int KC64 = round_up(n_fov * F, 64);
-    TRY(dev_alloc(p, &p->wcls, lin_wpk_elems(KC64, K * C) * sizeof(float), false));
-    TRY(dev_alloc(p, &p->bcls, (size_t)lin_np(K * C) * sizeof(float), false));
-    TRY(pack_linear_weights(d_cls_w, d_cls_b, n_fov * F, K * C, 1, p->wcls, p->bcls, nullptr));
-    TRY(dev_alloc(p, &p->wbbox, lin_wpk_elems(F32, 4 * C) * sizeof(float), false));
-    TRY(dev_alloc(p, &p->bbbox, (size_t)lin_np(4 * C) * sizeof(float), false));
-    TRY(pack_linear_weights(d_bbox_w, d_bbox_b, F, 4 * C, 1, p->wbbox, p->bbbox, nullptr));
-    TRY(dev_alloc(p, &p->fov, M * 20 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->cat, (size_t)tower_heads * (lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->cls_rm, M * K * C * sizeof(float), true));
-    TRY(dev_alloc(p, &p->bbox_rm, M * 4 * C * sizeof(float), true));
-    for (int t = 0; t < tower_heads; ++t) { MPN_CHECK_ARG(tower_region[t] >= 0 && tower_region[t] < 4); p->rn_region.push_back(tower_region[t]); }
-    if (resnet_has_second_lane(p->rn)) {  // the second tower lane's stream (run_detect; debug flavour only)
-      hipError_t e = hipStreamCreateWithFlags(&p->tower_stream, hipStreamNonBlocking);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_lane_go, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_lane_done, hipEventDisableTiming);
-      if (e != hipSuccess) { set_error("mpn_resnet_create / mpn_graph_create: tower stream / events: %s", hipGetErrorString(e)); mpn_frcnn_destroy(p); return MPN_EHIP; }
-    }
+    const int *region = a.rw ? a.rw->head_region : a.gw->head_region;
+    p->rn_region.assign(region, region + tower_heads);
+    TRY(build_integral_classifier(p, a, tower_heads, resnet_has_second_lane(p->rn)));  // (that lane: debug flavour only)
   } else {
-  if (!graph_net) {
-  TRY(dev_alloc(p, &p->w6, lin_wpk_elems(K6_32, F) * sizeof(float), false));
-  TRY(dev_alloc(p, &p->b6, (size_t)lin_np(F) * sizeof(float), false));
-  TRY(pack_linear_weights(d_fc6_w, d_fc6_b, p->K6, F, PP, p->w6, p->b6, nullptr));
-  if (cfg->fc_arith == MPN_FC_SPLIT3) {  // the packed fp32 weights [K/8][NP][8] split once into three bf16 planes [3][K/8][NP↑256][8]; the operand's planes per image
-    TRY(dev_alloc(p, &p->w6_s3, split3_plane_elems(p->K6, lin_np(F)) * sizeof(unsigned short), true));
-    TRY(split3_planes(p->w6, p->K6, lin_np(F), lin_np(F), p->w6_s3, nullptr));
-    TRY(dev_alloc(p, &p->x6_s3, split3_plane_elems(p->K6, p->Mp) * sizeof(unsigned short), true));
+    TRY(build_plain_head(p, a, &tmp_w, &tmp_b));
   }
-  TRY(dev_alloc(p, &p->w7, lin_wpk_elems(F32, F) * sizeof(float), false));
-  TRY(dev_alloc(p, &p->b7, (size_t)lin_np(F) * sizeof(float), false));
-  TRY(pack_linear_weights(d_fc7_w, d_fc7_b, F, F, 1, p->w7, p->b7, nullptr));
-  if (cfg->fc_arith == MPN_FC_SPLIT3) {
-    TRY(dev_alloc(p, &p->w7_s3, split3_plane_elems(F, lin_np(F)) * sizeof(unsigned short), true));
-    TRY(split3_planes(p->w7, F, lin_np(F), lin_np(F), p->w7_s3, nullptr));
-    TRY(dev_alloc(p, &p->y6_s3, split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
-  }
-  }
-  {  // cls and bbox heads share their input -> one [5C, F] GEMM (model_utils.lua:105-119 ConcatTable)
-    float *tmp_w = nullptr, *tmp_b = nullptr;
-    TRY(dev_alloc(p, &tmp_w, (size_t)5 * C * F * sizeof(float), false));
-    TRY(dev_alloc(p, &tmp_b, (size_t)5 * C * sizeof(float), true));
-    hipError_t e = hipMemcpy(tmp_w, d_cls_w, (size_t)C * F * sizeof(float), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tmp_w + (size_t)C * F, d_bbox_w, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && d_cls_b) e = hipMemcpy(tmp_b, d_cls_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && d_bbox_b) e = hipMemcpy(tmp_b + C, d_bbox_b, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { set_error("mpn_frcnn_create: head weight copy failed: %s", hipGetErrorString(e)); mpn_frcnn_destroy(p); return MPN_EHIP; }
-    TRY(dev_alloc(p, &p->wh, lin_wpk_elems(F32, 5 * C) * sizeof(float), false));
-    TRY(dev_alloc(p, &p->bh, (size_t)lin_np(5 * C) * sizeof(float), false));
-    TRY(pack_linear_weights(tmp_w, tmp_b, F, 5 * C, 1, p->wh, p->bh, nullptr));
-  }
-  if (!graph_net) {
-  {  // pixel-major copy of the final map at its largest size
-    int fh = cfg->max_h, fw = cfg->max_w;
-    final_map_size(p, &fh, &fw);
-    TRY(dev_alloc(p, &p->up.pm, (size_t)fh * fw * ((p->feat_c + 7) / 8) * 8 * sizeof(float), false));
-  }
-  TRY(dev_alloc(p, &p->x6, (size_t)(K6_32 / 8) * p->Mp * 8 * sizeof(float), true));
-  TRY(dev_alloc(p, &p->y6, (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
-  }
-  TRY(dev_alloc(p, &p->y7, (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float), true));
-  TRY(dev_alloc(p, &p->head, M * 5 * C * sizeof(float), true));
-  }
-  TRY(dev_alloc(p, &p->rois, M * 5 * sizeof(float), true));
-  TRY(dev_alloc(p, &p->scores, M * C * sizeof(float), true));
-  TRY(dev_alloc(p, &p->bbox, M * 4 * C * sizeof(float), true));
-  TRY(dev_alloc(p, &p->bbox_raw, M * 4 * C * sizeof(float), true));
-  const int n_it = cfg->num_iter > 1 ? cfg->num_iter : 1;
-  MPN_CHECK_ARG((size_t)n_it * M <= MPN_NMS_MAX_BOXES);
-  MPN_CHECK_ARG(!cfg->use_rbox_scores || n_it > 1);  // Tester_FRCNN.lua:92 assert(#all_output > 1)
-  p->cfg.num_iter = n_it;
-  const size_t MR = M * n_it;  // rows that reach NMS per class
-  if (n_it > 1) {
-    TRY(dev_alloc(p, &p->it_scores, MR * C * sizeof(float), true));
-    TRY(dev_alloc(p, &p->it_bbox, MR * 4 * C * sizeof(float), true));
-    TRY(dev_alloc(p, &p->it_boxes, M * 4 * sizeof(float), true));
-  }
-  for (int i = 0; i < 2; ++i) {
-    TRY(dev_alloc(p, &p->scored_b[i], (size_t)(C - 1) * MR * 5 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->keep_b[i], (size_t)(C - 1) * MR * 5 * sizeof(float), true));
-    if (cfg->bbox_voting) TRY(dev_alloc(p, &p->voted_b[i], (size_t)(C - 1) * MR * 5 * sizeof(float), true));
-    TRY(dev_alloc(p, &p->keep_idx_b[i], (size_t)(C - 1) * MR * sizeof(int), true));
-    TRY(dev_alloc(p, &p->counts_b[i], (size_t)(C - 1) * sizeof(int), true));
-    TRY(dev_alloc(p, &p->n_keep_b[i], (size_t)(C - 1) * sizeof(int), true));
-    TRY(dev_alloc(p, &p->thresh_b[i], 16, true));
-  }
-  p->scored = p->scored_b[0]; p->keep = p->keep_b[0]; p->keep_idx = p->keep_idx_b[0];
-  p->counts = p->counts_b[0]; p->n_keep = p->n_keep_b[0]; p->thresh = p->thresh_b[0];
-  {
-    int lo = 0, hi = 0;
-    hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-    // The side stream (NMS / top-k tail under the next image's trunk) has the DEFAULT priority since round 5.  Rounds 1-4 created it with
-    // the highest one; what that bought the headline is nothing measurable (3.457-3.476 ms either way, six alternating runs), and what it can
-    // cost is large: a priority stream lands in a different hardware-queue class, and depending on which queue HIP's round-robin hands it,
-    // EVERY dispatch of the launch queue took 30-50 us longer while the two queues were both active — a mixed-size stream inside bench.py ran
-    // at 4.59 ms per image with the highest priority, 4.05 with the lowest, 3.12 with the default (profiles/r05_mixed_sizes_timeline.txt).
-    (void)lo; (void)hi;
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-      e = hipEventCreateWithFlags(&p->ev_head[i], hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_tail[i], hipEventDisableTiming);
-    }
-    if (e != hipSuccess) { set_error("mpn_frcnn_create: side stream/events: %s", hipGetErrorString(e)); mpn_frcnn_destroy(p); return MPN_EHIP; }
-    if (p->pool_on_side) p->pool_stream = p->side;
-  }
-#undef TRY
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) { set_error("mpn_frcnn_create: %s", hipGetErrorString(e)); mpn_frcnn_destroy(p); return MPN_EHIP; }
-  *out = p;
+  TRY(build_tail(p));
+  TRY(build_streams(p));
+  const hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) { set_error("mpn_frcnn_create: %s", hipGetErrorString(e)); return MPN_EHIP; }
+  for (float **q : {&tmp_w, &tmp_b}) p->own.free_now(q);  // the pack kernels have run: nothing reads the concatenated head weights again
+  *out = h.release();
   return MPN_OK;
 }
+#undef TRY
 
 // The trunk on an H x W image into the record `m` (the map goes to m->buf if set) — the only record it touches: invalid from the
 // start, valid again where the last launch is enqueued.  Hc > 0: the image is one level of an image pyramid, placed top-left in a
@@ -1111,8 +1115,8 @@ static int run_integral_heads(mpn_frcnn *p, const float *d_boxes, int N, int H, 
 
 // getImages' rescaled image buffers (ImageDetect.lua:34-43), grown to hold `need` / `need_t` bytes
 static int grow_scaled(mpn_frcnn *p, size_t need, size_t need_t, hipStream_t s) {
-  const int rc = grow_device_buffer((void **)&p->scaled, &p->scaled_bytes, need, s);
-  return rc ? rc : grow_device_buffer((void **)&p->scale_tmp, &p->scale_tmp_bytes, need_t, s);
+  const int rc = p->own.grow(&p->scaled, &p->scaled_bytes, need, s);
+  return rc ? rc : p->own.grow(&p->scale_tmp, &p->scale_tmp_bytes, need_t, s);
 }
 
 // getImages with a scale table (ImageDetect.lua:22-52; include/mpn.h mpn_frcnn_set_scales): level l's image, resampled and transformed as
@@ -1360,7 +1364,7 @@ static int run_detect_aug(mpn_frcnn *p, const float *d_image, int H0, int W0, co
     return MPN_EINVAL;
   }
   MPN_CHECK_ARG(d_boxes && H0 > 0 && W0 > 0 && N > 0 && N <= p->cfg.max_rois);
-  int rc = d_image ? grow_device_buffer((void **)&p->aug_img, &p->aug_img_bytes, (size_t)3 * H0 * W0 * sizeof(float), s) : MPN_OK;
+  int rc = d_image ? p->own.grow(&p->aug_img, &p->aug_img_bytes, (size_t)3 * H0 * W0 * sizeof(float), s) : MPN_OK;
   if (rc) return rc;
   rc = run_detect(p, d_image, H0, W0, d_boxes, N, s, 0, &p->up);
   if (rc) return rc;
@@ -1467,7 +1471,7 @@ static int run_segment(mpn_frcnn *p, int kind, const mpn_frcnn::GraphKey &key, c
   }
   ++e.seen;
   if (!same_shape || e.failed || (!stable_ptrs && e.seen < 2)) return direct();  // the warm-up run for this shape / this key
-  if (!p->cap_stream && hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); e.failed = true; return direct(); }
+  if (!p->cap_stream && p->own.stream(&p->cap_stream) != MPN_OK) { (void)hipGetLastError(); e.failed = true; return direct(); }
   if (hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); e.failed = true; return direct(); }
   const int rc_body = body(p->cap_stream);  // host bookkeeping happens, the stream work is recorded instead of executed
   hipGraph_t g = nullptr;
@@ -1727,7 +1731,7 @@ extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const fl
   const size_t floats[4] = {rr, rr * world, cr, cr * world};
   int rc;
   for (int i = 0; i < 4; ++i)
-    if ((rc = grow_device_buffer((void **)&p->sh_buf[i], &p->sh_bytes[i], floats[i] * sizeof(float), s)) != MPN_OK) return rc;
+    if ((rc = p->own.grow(&p->sh_buf[i], &p->sh_bytes[i], floats[i] * sizeof(float), s)) != MPN_OK) return rc;
   rc = mpn_frcnn_shard_head(p, d_image, H, W, d_boxes, N, rank, world, p->sh_buf[0], stream);
   if (rc) return rc;
   rc = mpn_gather_rows(comm, p->sh_buf[0], rr, p->sh_buf[1], stream);
@@ -1768,12 +1772,15 @@ static int pipelined_impl(mpn_frcnn *p, const float *d_image, int H, int W, cons
   // heads + softmax + decode + select on the side stream too (plain VGG head, one localisation pass, no captured graphs, not profiling)
   const bool defer = g_defer_heads && !p->is_mpnet && !p->rn && p->cfg.num_iter == 1 && !p->graphs_on && !p->prof && d_image && d_boxes;
   if (defer) {
-    if (!p->y7_b[1]) {
+    if (!p->ev_fc7) {  // first use.  All or nothing, as in mpn_frcnn_set_augment: ev_fc7 comes last, its presence says that all of them exist
       p->y7_b[0] = p->y7;
-      int rca = dev_alloc(p, &p->y7_b[1], (size_t)(lin_np(p->cfg.fc_dim) / 8) * p->Mp * 8 * sizeof(float), true);
-      for (int i = 0; i < 2 && !rca; ++i) rca = dev_alloc(p, &p->boxes_b[i], (size_t)p->cfg.max_rois * 4 * sizeof(float), false);
-      if (rca) return rca;
-      MPN_CHECK_HIP(hipEventCreateWithFlags(&p->ev_fc7, hipEventDisableTiming));
+      int rca = p->own.alloc(&p->y7_b[1], (size_t)(lin_np(p->cfg.fc_dim) / 8) * p->Mp * 8 * sizeof(float), true);
+      for (int i = 0; i < 2 && !rca; ++i) rca = p->own.alloc(&p->boxes_b[i], (size_t)p->cfg.max_rois * 4 * sizeof(float));
+      if (!rca) rca = p->own.event(&p->ev_fc7);
+      if (rca) {  // the next call starts from scratch
+        for (float **q : {&p->y7_b[1], &p->boxes_b[0], &p->boxes_b[1]}) p->own.free_now(q);
+        return rca;
+      }
     }
     p->defer_stream = p->side; p->defer_set = b;
   } else if (p->was_deferred) {  // the form changed under us (graphs / profiling switched on): the side stream may still read y7_b[0] == y7
@@ -1811,19 +1818,23 @@ extern "C" int mpn_frcnn_test_one_pipelined_host(mpn_frcnn *p, const float *h_im
   if (int rp = refuse_multi_pass(p, "mpn_frcnn_test_one_pipelined_host")) return rp;
   hipStream_t s = as_stream(stream);
   const size_t img_bytes = (size_t)3 * H * W * sizeof(float);
-  if (!p->copy) {  // first use: copy stream, events, the two box staging buffers
-    MPN_CHECK_HIP(hipStreamCreateWithFlags(&p->copy, hipStreamNonBlocking));
-    for (int i = 0; i < mpn_frcnn::kStage; ++i) {
-      MPN_CHECK_HIP(hipEventCreateWithFlags(&p->ev_up[i], hipEventDisableTiming));
-      MPN_CHECK_HIP(hipEventCreateWithFlags(&p->ev_consumed[i], hipEventDisableTiming));
-      int rc0 = dev_alloc(p, &p->stage_boxes[i], (size_t)p->cfg.max_rois * 4 * sizeof(float), false);
-      if (rc0) return rc0;
+  if (!p->copy) {  // first use: events, the box staging buffers, the copy stream.  All or nothing, as in mpn_frcnn_set_augment: the stream
+    int rc0 = MPN_OK;  // comes last, its presence says that all of them exist
+    for (int i = 0; i < mpn_frcnn::kStage && !rc0; ++i) {
+      rc0 = p->own.event(&p->ev_up[i]);
+      if (!rc0) rc0 = p->own.event(&p->ev_consumed[i]);
+      if (!rc0) rc0 = p->own.alloc(&p->stage_boxes[i], (size_t)p->cfg.max_rois * 4 * sizeof(float));
+    }
+    if (!rc0) rc0 = p->own.stream(&p->copy);
+    if (rc0) {  // the next call starts from scratch
+      for (int i = 0; i < mpn_frcnn::kStage; ++i) { p->own.drop(&p->ev_up[i]); p->own.drop(&p->ev_consumed[i]); p->own.free_now(&p->stage_boxes[i]); }
+      return rc0;
     }
   }
   const int b = (int)(p->up_seq % mpn_frcnn::kStage);
   if (img_bytes > p->stage_bytes[b]) {  // image staging grows on demand (getImages may be handed images larger than max_h x max_w)
     MPN_CHECK_HIP(hipStreamSynchronize(p->copy));  // the set's last upload (grow_device_buffer waits for `s`)
-    const int rcg = grow_device_buffer((void **)&p->stage_img[b], &p->stage_bytes[b], std::max(img_bytes, (size_t)3 * p->cfg.max_h * p->cfg.max_w * sizeof(float)), s);
+    const int rcg = p->own.grow(&p->stage_img[b], &p->stage_bytes[b], std::max(img_bytes, (size_t)3 * p->cfg.max_h * p->cfg.max_w * sizeof(float)), s);
     if (rcg) return rcg;
   }
   // The staging set is free once the image that used it (three calls ago) has been consumed.  Waited for on the HOST, not with
@@ -1850,26 +1861,26 @@ extern "C" int mpn_frcnn_create(const mpn_frcnn_config *cfg, const float *const 
                                 const float *d_fc6_w, const float *d_fc6_b, const float *d_fc7_w, const float *d_fc7_b,
                                 const float *d_cls_w, const float *d_cls_b, const float *d_bbox_w, const float *d_bbox_b,
                                 mpn_frcnn **out) {
-  return create_impl(cfg, d_conv_w, d_conv_b, d_fc6_w, d_fc6_b, d_fc7_w, d_fc7_b, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, out);
+  return create_handle(CreateArgs{cfg, d_conv_w, d_conv_b, d_fc6_w, d_fc6_b, d_fc7_w, d_fc7_b, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, nullptr, nullptr}, out);
 }
 
 extern "C" int mpn_mpnet_create(const mpn_frcnn_config *cfg, const float *const *d_conv_w, const float *const *d_conv_b,
                                 const mpn_mpnet_weights *mw, const float *d_cls_w, const float *d_cls_b,
                                 const float *d_bbox_w, const float *d_bbox_b, mpn_frcnn **out) {
   MPN_CHECK_ARG(mw != nullptr);
-  return create_impl(cfg, d_conv_w, d_conv_b, nullptr, nullptr, nullptr, nullptr, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, mw, out);
+  return create_handle(CreateArgs{cfg, d_conv_w, d_conv_b, nullptr, nullptr, nullptr, nullptr, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, mw, nullptr, nullptr}, out);
 }
 
 extern "C" int mpn_resnet_create(const mpn_frcnn_config *cfg, const mpn_resnet_weights *rw, const float *d_cls_w, const float *d_cls_b,
                                  const float *d_bbox_w, const float *d_bbox_b, mpn_frcnn **out) {
   MPN_CHECK_ARG(rw != nullptr);
-  return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, out, rw);
+  return create_handle(CreateArgs{cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, rw, nullptr}, out);
 }
 
 extern "C" int mpn_graph_create(const mpn_frcnn_config *cfg, const mpn_graph_weights *gw, const float *d_cls_w, const float *d_cls_b,
                                 const float *d_bbox_w, const float *d_bbox_b, mpn_frcnn **out) {
   MPN_CHECK_ARG(gw != nullptr);
-  return create_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, out, nullptr, gw);
+  return create_handle(CreateArgs{cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, nullptr, gw}, out);
 }
 
 extern "C" int mpn_frcnn_set_graphs(mpn_frcnn *p, int enable) {
@@ -1923,13 +1934,12 @@ extern "C" int mpn_frcnn_set_scales(mpn_frcnn *p, int n_scales, const double *h_
     final_map_size(p, &fh, &fw);
     const size_t slot = act_bytes(p->feat_c, fh, fw) / sizeof(float), pm_slot = pixel_major_elems(make_act(nullptr, p->feat_c, fh, fw));
     bump_alloc_generation();  // (behind drop_graphs_and_features' device synchronise; both buffers go, then both come back cleared)
-    if (p->ms_feat) (void)hipFree(p->ms_feat);
-    if (p->ms_pm) (void)hipFree(p->ms_pm);
-    p->ms_feat = p->ms_pm = nullptr; p->ms_cap = 0; p->n_scales = 0;
-    MPN_CHECK_HIP(hipMalloc(&p->ms_feat, slot * n_scales * sizeof(float)));
-    MPN_CHECK_HIP(hipMalloc(&p->ms_pm, pm_slot * n_scales * sizeof(float)));
-    MPN_CHECK_HIP(hipMemset(p->ms_feat, 0, slot * n_scales * sizeof(float)));
-    MPN_CHECK_HIP(hipMemset(p->ms_pm, 0, pm_slot * n_scales * sizeof(float)));
+    p->own.free_now(&p->ms_feat);
+    p->own.free_now(&p->ms_pm);
+    p->ms_cap = 0; p->n_scales = 0;
+    int rc = p->own.alloc_slot(&p->ms_feat, slot * n_scales * sizeof(float), true);
+    if (!rc) rc = p->own.alloc_slot(&p->ms_pm, pm_slot * n_scales * sizeof(float), true);
+    if (rc) return rc;
     p->ms_slot = slot; p->ms_pm_slot = pm_slot; p->ms_cap = n_scales;
   }
   p->n_scales = n_scales;
@@ -1959,22 +1969,20 @@ extern "C" int mpn_frcnn_set_augment(mpn_frcnn *p, int enable) {
     const size_t M = (size_t)p->cfg.max_rois, C = (size_t)p->cfg.n_classes;
     const size_t img_bytes = (size_t)3 * p->cfg.max_h * p->cfg.max_w * sizeof(float);
     bump_alloc_generation();
-    for (float **q : {&p->aug_img, &p->aug_boxes, &p->aug_bbox, &p->mir.buf, &p->mir.pm}) if (*q) { (void)hipFree(*q); *q = nullptr; }  // (an earlier attempt that ran out of memory)
+    for (float **q : {&p->aug_img, &p->aug_boxes, &p->aug_bbox, &p->mir.buf, &p->mir.pm}) p->own.free_now(q);  // (an earlier attempt that ran out of memory)
     p->aug_img_bytes = 0;
-    MPN_CHECK_HIP(hipMalloc(&p->aug_img, img_bytes));
+    if ((rc = p->own.alloc_slot(&p->aug_img, img_bytes))) return rc;
     p->aug_img_bytes = img_bytes;
-    MPN_CHECK_HIP(hipMalloc(&p->aug_boxes, M * 4 * sizeof(float)));
-    MPN_CHECK_HIP(hipMalloc(&p->aug_bbox, M * 4 * C * sizeof(float)));
+    if ((rc = p->own.alloc_slot(&p->aug_boxes, M * 4 * sizeof(float)))) return rc;
+    if ((rc = p->own.alloc_slot(&p->aug_bbox, M * 4 * C * sizeof(float)))) return rc;
     if (plain) {
       int fh = p->cfg.max_h, fw = p->cfg.max_w;
       final_map_size(p, &fh, &fw);
       const size_t feat_bytes = act_bytes(p->feat_c, fh, fw), pm_bytes = pixel_major_elems(make_act(nullptr, p->feat_c, fh, fw)) * sizeof(float);
-      MPN_CHECK_HIP(hipMalloc(&p->mir.buf, feat_bytes));
-      MPN_CHECK_HIP(hipMemset(p->mir.buf, 0, feat_bytes));
-      MPN_CHECK_HIP(hipMalloc(&p->mir.pm, pm_bytes));
-      MPN_CHECK_HIP(hipMemset(p->mir.pm, 0, pm_bytes));
+      if ((rc = p->own.alloc_slot(&p->mir.buf, feat_bytes, true))) return rc;
+      if ((rc = p->own.alloc_slot(&p->mir.pm, pm_bytes, true))) return rc;
     }
-    MPN_CHECK_HIP(hipMalloc(&p->aug_scores, M * C * sizeof(float)));  // last: its presence says that all of them exist
+    if ((rc = p->own.alloc_slot(&p->aug_scores, M * C * sizeof(float)))) return rc;  // last: its presence says that all of them exist
   }
   p->augment = 1;
   return MPN_OK;
@@ -2060,10 +2068,9 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
   const mpn_frcnn_config &c = p->cfg;
   const int F = c.fc_dim, C = c.n_classes;
   const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
-  mpn_frcnn::Train *t = new mpn_frcnn::Train();
+  std::unique_ptr<mpn_frcnn::Train> t(new mpn_frcnn::Train());  // (its DeviceOwner gives back what a failed attempt made)
   t->depth = depth; t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
-  p->train = t;
-  auto alloc0 = [&](float **q, size_t bytes) -> bool { return hipMalloc(q, bytes) == hipSuccess && hipMemset(*q, 0, bytes) == hipSuccess; };
+  auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
   bool ok = alloc0(&t->vh, lin_wpk_elems(round_up(F, 64), 5 * C) * sizeof(float)) && alloc0(&t->vbh, (size_t)lin_np(5 * C) * sizeof(float));
   ok = ok && alloc0(&t->gh, (size_t)(lin_np(5 * C) / 8) * rec);
   ok = ok && alloc0(&t->x6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->y6, (size_t)(lin_np(F) / 8) * rec) && alloc0(&t->y7, (size_t)(lin_np(F) / 8) * rec);
@@ -2077,13 +2084,13 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
     ok = ok && alloc0(&t->g6, (size_t)(lin_np(F) / 8) * rec);
   }
   ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
-  ok = ok && hipMalloc(&t->labels, M * sizeof(int)) == hipSuccess && hipMemset(t->labels, 0, M * sizeof(int)) == hipSuccess;
+  ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
   if (ok) ok = hipDeviceSynchronize() == hipSuccess;
   if (!ok) {
     set_error("mpn_frcnn_train_begin: allocating the momentum / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
-    free_train_state(p);
     return MPN_ENOMEM;
   }
+  p->train = t.release();  // all or nothing, as in mpn_frcnn_set_augment: published last, its presence says that every buffer exists
   return MPN_OK;
 }
 
@@ -2193,6 +2200,23 @@ extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d
 }
 
 #ifdef MPN_DEBUG_HOOKS
+// the mpn_debug_bench_* hooks' clock: two warm-up calls, then `iters` calls back to back on the NULL stream between two events of its own
+template <typename F>
+static int time_back_to_back(int iters, float *ms_out, F call) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = MPN_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = MPN_EHIP;
+  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = call();
+  if (rc == MPN_OK && (hipDeviceSynchronize() != hipSuccess || hipEventRecord(e0, nullptr) != hipSuccess)) rc = MPN_EHIP;
+  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = call();
+  float ms = 0.f;
+  if (rc == MPN_OK && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) rc = MPN_EHIP;
+  if (rc == MPN_EHIP) set_error("mpn_debug_bench: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
+  *ms_out = ms / iters;
+  for (hipEvent_t e : {e0, e1}) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
 // tools/bench_train.py (debug flavour only): fc6's fused weight-gradient + SGD kernel issued `iters` times BACK TO BACK on the operands the
 // last mpn_frcnn_train_step left (depth MPN_TRAIN_FC6), with lr = momentum = wd = 0 — the weights keep their values, the momentum
 // buffer ends as the plain gradient; the traffic is the real step's: w and v read and written once.
@@ -2201,20 +2225,7 @@ extern "C" int mpn_debug_bench_train_fc6(mpn_frcnn *p, int iters, float *ms_out)
   mpn_frcnn::Train *t = p->train;
   if (!t || t->depth < MPN_TRAIN_FC6 || t->last_rows <= 0) { set_error("mpn_debug_bench_train_fc6: needs a mpn_frcnn_train_step at depth MPN_TRAIN_FC6"); return MPN_ESTATE; }
   const int F = p->cfg.fc_dim, PP = p->cfg.pooled_h * p->cfg.pooled_w;
-  hipEvent_t e0, e1;
-  MPN_CHECK_HIP(hipEventCreate(&e0)); MPN_CHECK_HIP(hipEventCreate(&e1));
-  int rc = MPN_OK;
-  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr);
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  MPN_CHECK_HIP(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr);
-  MPN_CHECK_HIP(hipEventRecord(e1, nullptr));
-  MPN_CHECK_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  MPN_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-  *ms_out = ms / iters;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return rc;
+  return time_back_to_back(iters, ms_out, [&] { return sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr); });
 }
 
 // bench.py's `power_sensitivity` leg (debug flavour only): fc6 of the VGG Fast R-CNN pipeline issued `iters` times BACK TO BACK on the
@@ -2225,22 +2236,19 @@ extern "C" int mpn_debug_bench_fc6(mpn_frcnn *p, int iters, float *ms_out) {
   if (p->rn || p->is_mpnet || p->last_n <= 0) { set_error("mpn_debug_bench_fc6: needs a VGG Fast R-CNN handle after a detect()"); return MPN_ESTATE; }
   ScratchScope scratch_scope(&p->scratch);
   const int N = p->last_n, F = p->cfg.fc_dim;
-  hipEvent_t e0, e1;
-  MPN_CHECK_HIP(hipEventCreate(&e0)); MPN_CHECK_HIP(hipEventCreate(&e1));
-  int rc = MPN_OK;
-  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = linear_c8(p->x6, N, p->K6, p->w6, p->b6, F, 1, p->y6, nullptr, nullptr, 0, nullptr, 1);
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  MPN_CHECK_HIP(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = linear_c8(p->x6, N, p->K6, p->w6, p->b6, F, 1, p->y6, nullptr, nullptr, 0, nullptr, 1);
-  MPN_CHECK_HIP(hipEventRecord(e1, nullptr));
-  MPN_CHECK_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  MPN_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-  *ms_out = ms / iters;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return rc;
+  return time_back_to_back(iters, ms_out, [&] { return linear_c8(p->x6, N, p->K6, p->w6, p->b6, F, 1, p->y6, nullptr, nullptr, 0, nullptr, 1); });
 }
 #endif
+
+// the debug tensor's buffer (the caller has synchronised the device).  Not DeviceOwner::grow: no kernel of a captured graph reads dbg, and
+// a generation bump here would cost the caller its graphs
+static int grow_dbg(mpn_frcnn *p, size_t bytes) {
+  if (bytes <= p->dbg_bytes) return MPN_OK;
+  p->own.free_now(&p->dbg);
+  const int rc = p->own.alloc_slot(&p->dbg, bytes);
+  p->dbg_bytes = rc == MPN_OK ? bytes : 0;
+  return rc;
+}
 
 extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems) {
   MPN_CHECK_ARG(p && name && d_ptr && n_elems);
@@ -2249,12 +2257,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
     const int PPt = p->cfg.pooled_h * p->cfg.pooled_w;
     const size_t nt = (size_t)p->train->last_rows * p->feat_c * PPt;
     MPN_CHECK_HIP(hipDeviceSynchronize());
-    if (nt * sizeof(float) > p->dbg_bytes) {
-      if (p->dbg) (void)hipFree(p->dbg);
-      p->dbg = nullptr; p->dbg_bytes = 0;
-      MPN_CHECK_HIP(hipMalloc(&p->dbg, nt * sizeof(float)));
-      p->dbg_bytes = nt * sizeof(float);
-    }
+    if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
     hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(nt, 256)), dim3(256), 0, nullptr, p->train->x6, p->train->last_rows, p->feat_c, PPt, p->Mp, p->dbg);
     MPN_CHECK_LAUNCH();
     MPN_CHECK_HIP(hipDeviceSynchronize());
@@ -2288,12 +2291,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   if (p->is_mpnet && nm != "conv5" && nm != "bbox_raw" && nm != "cls_k" && nm != "cat") { set_error("mpn_frcnn_debug_tensor: '%s' is not kept by the MultiPathNet head", name); return MPN_EINVAL; }
   if (p->rn && nm != "bbox_raw" && nm != "cls_k" && nm != "cat" && !((nm == "cls" || nm == "fc7") && p->rn_region.empty())) { set_error("mpn_frcnn_debug_tensor: '%s' is not kept by the op-list / ResNet pipelines", name); return MPN_EINVAL; }
   MPN_CHECK_HIP(hipDeviceSynchronize());
-  if (n * sizeof(float) > p->dbg_bytes) {  // not grow_device_buffer: no kernel of a captured graph reads dbg, and a bump here would cost the caller its graphs
-    if (p->dbg) (void)hipFree(p->dbg);
-    p->dbg = nullptr; p->dbg_bytes = 0;
-    MPN_CHECK_HIP(hipMalloc(&p->dbg, n * sizeof(float)));
-    p->dbg_bytes = n * sizeof(float);
-  }
+  if (int rcd = grow_dbg(p, n * sizeof(float))) return rcd;
   int rc = MPN_OK;
   if (level >= 0 || (nm == "conv5" && p->n_scales > 1)) {
     const int l = p->ms_src[level >= 0 ? level : 0];

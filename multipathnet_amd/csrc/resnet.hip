@@ -2540,27 +2540,18 @@ struct ResNetGraph {
   std::vector<GTensor> t_head2;
   float *hb2[4] = {nullptr, nullptr, nullptr, nullptr};
   bool has_lane2 = false;
-  std::vector<void *> allocs;
+  DeviceOwner own;  // of every device buffer above (mpn_internal.h)
 };
 constexpr size_t SPLITK_WS_BYTES = (size_t)96 << 20;
 
-static int rn_alloc(ResNetGraph *g, float **p, size_t bytes) {
-  void *q = nullptr;
-  MPN_CHECK_HIP(hipMalloc(&q, bytes ? bytes : 4));
-  g->allocs.push_back(q);
-  *p = static_cast<float *>(q);
-  return MPN_OK;
-}
+static int rn_alloc(ResNetGraph *g, float **p, size_t bytes) { return g->own.alloc(p, bytes); }
 
 // a buffer that grows with the image size (outside the steady state): the old block is released (hipFree waits for the device, so
-// kernels still reading it have finished) instead of staying on g->allocs until the handle dies
+// kernels still reading it have finished) instead of staying with the owner until the handle dies
 static int rn_regrow(ResNetGraph *g, float **p, size_t bytes) {
   if (*p) {
-    auto it = std::find(g->allocs.begin(), g->allocs.end(), static_cast<void *>(*p));
-    if (it != g->allocs.end()) g->allocs.erase(it);
-    MPN_CHECK_HIP(hipFree(*p));
-    *p = nullptr;
-    bump_alloc_generation();  // captured launch graphs (pipeline.hip) hold the old pointer
+    bump_alloc_generation();  // captured launch graphs (pipeline.hip) hold the old pointer: bump, THEN free
+    g->own.free_now(p);
   }
   return rn_alloc(g, p, bytes);
 }
@@ -3004,6 +2995,14 @@ static void rn_shape(const RnConv &c, int &h, int &w) {
   w = (w + 2 * c.pw - c.KW) / c.sw + 1;
 }
 
+// the builders' last step: the pack kernels and zero fills of a new graph have run
+static int sync_built(const char *who) {
+  const hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) return MPN_OK;
+  set_error("%s: hipDeviceSynchronize failed: %s", who, hipGetErrorString(e));
+  return MPN_EHIP;
+}
+
 int resnet_build(const mpn_resnet_weights *rw, int max_h, int max_w, int max_rois, int pooled, ResNetGraph **out) {
   MPN_CHECK_ARG(rw && out && rw->n_convs > 0 && rw->n_blocks > 0 && rw->n_trunk_blocks > 0 && rw->n_trunk_blocks < rw->n_blocks);
   MPN_CHECK_ARG(rw->w && rw->cin && rw->cout && rw->ksize && rw->stride && rw->pad && rw->block_n_convs && rw->block_has_shortcut);
@@ -3107,23 +3106,23 @@ int resnet_build(const mpn_resnet_weights *rw, int max_h, int max_w, int max_roi
   const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
   RTRY(rn_alloc(g, &g->img, c8i_elems(1, 16, max_h, max_w) * esz));
   if (g->conv1.col_w) RTRY(rn_alloc(g, &g->img_planar, (size_t)3 * max_h * max_w * sizeof(float)));
-  for (int i = 0; i < 4; ++i) { RTRY(rn_alloc(g, &g->tb[i], te * esz)); MPN_CHECK_HIP(hipMemset(g->tb[i], 0, te * esz)); }
-  for (int i = 0; i < 4; ++i) { RTRY(rn_alloc(g, &g->hb[i], he * esz)); MPN_CHECK_HIP(hipMemset(g->hb[i], 0, he * esz)); }  // pad planes must hold finite values
+  for (int i = 0; i < 4; ++i) RTRY(g->own.alloc(&g->tb[i], te * esz, true));
+  for (int i = 0; i < 4; ++i) RTRY(g->own.alloc(&g->hb[i], he * esz, true));  // pad planes must hold finite values
 #ifdef MPN_DEBUG_HOOKS
   if (g->heads.size() > 1) {  // the second lane's rotating buffers
-    for (int i = 0; i < 4; ++i) { RTRY(rn_alloc(g, &g->hb2[i], he * esz)); MPN_CHECK_HIP(hipMemset(g->hb2[i], 0, he * esz)); }
+    for (int i = 0; i < 4; ++i) RTRY(g->own.alloc(&g->hb2[i], he * esz, true));
     g->has_lane2 = true;
   }
 #endif
+  RTRY(sync_built("mpn_resnet_create"));
 #undef RTRY
-  MPN_CHECK_HIP(hipDeviceSynchronize());
   *out = g;
   return MPN_OK;
 }
 
 void resnet_free(ResNetGraph *g) {
   if (!g) return;
-  for (void *q : g->allocs) (void)hipFree(q);
+  g->own.release();
   delete g;
 }
 
@@ -3332,12 +3331,12 @@ static int graph_parse(ResNetGraph *g, int n_ops, const mpn_graph_op *ops_in, in
 
 int graph_build(const mpn_graph_weights *gw, int max_h, int max_w, int max_rois, int pooled, ResNetGraph **out) {
   MPN_CHECK_ARG(gw && out && gw->feat_tensor > 0 && gw->feat_tensor < gw->n_trunk_tensors && gw->out_tensor > 0 && gw->out_tensor < gw->n_head_tensors);
+  const int n_heads = gw->n_heads > 1 ? gw->n_heads : 1;
+  MPN_CHECK_ARG(n_heads <= 8);
   ResNetGraph *g = new ResNetGraph();
   g->is_graph = true; g->pooled = pooled; g->max_rois = max_rois; g->bf16 = gw->bf16 != 0;
   g->feat_tensor = gw->feat_tensor; g->out_tensor = gw->out_tensor;
   int rc = graph_parse(g, gw->n_trunk_ops, gw->trunk_ops, gw->n_trunk_tensors, gw->trunk_tensor_c, g->g_trunk, g->t_trunk);
-  const int n_heads = gw->n_heads > 1 ? gw->n_heads : 1;
-  MPN_CHECK_ARG(n_heads <= 8);
   g->g_heads.resize(n_heads);
   for (int t = 0; rc == MPN_OK && t < n_heads; ++t) {
     rc = graph_parse(g, gw->n_head_ops, gw->head_ops + (size_t)t * gw->n_head_ops, gw->n_head_tensors, gw->head_tensor_c, g->g_heads[t], g->t_head, true);
@@ -3422,7 +3421,8 @@ int graph_build(const mpn_graph_weights *gw, int max_h, int max_w, int max_rois,
       if (rc != MPN_OK) { resnet_free(g); return rc; }
     }
   g->heads.resize(n_heads);
-  MPN_CHECK_HIP(hipDeviceSynchronize());
+  rc = sync_built("mpn_graph_create");
+  if (rc != MPN_OK) { resnet_free(g); return rc; }
   *out = g;
   return MPN_OK;
 }
