@@ -488,6 +488,33 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {  // a - b as ONE v_p
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+// max as ONE instruction each.  __builtin_elementwise_max / fmaxf put a v_max x, x, x canonicalisation in front of every operand the
+// compiler cannot prove quiet (accumulator reads, inline-asm results); every operand here is the result of an fp32 add or an earlier
+// max, never a signalling NaN, so the hardware's rule is the builtin's: a NaN operand is ignored, +0 > -0.
+__device__ __forceinline__ f32x2 vmax_2(f32x2 a, f32x2 b) {
+  f32x2 r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r[0]) : "v"(a[0]), "v"(b[0]));
+  asm("v_max_f32 %0, %1, %2" : "=v"(r[1]) : "v"(a[1]), "v"(b[1]));
+  return r;
+}
+__device__ __forceinline__ f32x2 vrelu_2(f32x2 a) {  // max(a, 0): NaN -> 0
+  f32x2 r;
+  asm("v_max_f32 %0, 0, %1" : "=v"(r[0]) : "v"(a[0]));
+  asm("v_max_f32 %0, 0, %1" : "=v"(r[1]) : "v"(a[1]));
+  return r;
+}
+__device__ __forceinline__ f32x2 vmax3_2(f32x2 a, f32x2 b, f32x2 c) {
+  f32x2 r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r[0]) : "v"(a[0]), "v"(b[0]), "v"(c[0]));
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r[1]) : "v"(a[1]), "v"(b[1]), "v"(c[1]));
+  return r;
+}
+__device__ __forceinline__ f32x2 vmax3_2s(f32x2 a, f32x2 b, float c_uniform) {  // third operand wave-uniform (one SGPR)
+  f32x2 r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r[0]) : "v"(a[0]), "v"(b[0]), "s"(c_uniform));
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r[1]) : "v"(a[1]), "v"(b[1]), "s"(c_uniform));
+  return r;
+}
 // Two block geometries over the same 64 Winograd tiles: TC = 8 -> 8 x 8 tiles = 16 x 16 output px (raw halo tile 18 x 18 px),
 // TC = 16 -> 4 x 16 tiles = 8 rows x 32 columns (raw tile 10 x 34 px).  The host picks per layer whichever pads the map
 // less (VGG conv5 at 38 x 63: 48 x 64 px of tiles vs 40 x 64).  Both need 11 wave-loads for the raw tile.
@@ -613,19 +640,14 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(ConvArgs a) {
 
   const int c0 = split * cps;
   const int c1 = min(a.nchunks, c0 + cps);
-  // prologue: one DMA round trip for both raw tiles and the first weight slices (the accumulator zeroing
-  // overlaps it), then the first input transform
+  // prologue: one DMA round trip for both raw tiles and the first weight slices, then the first input transform
   const int n_more = c1 - 1 - c0;  // chunks that prefetch a successor
   const int b0 = n_more & 1;       // chunk c lives in buffer (c - c0 + b0) & 1, so that the LAST chunk is always in buffer 0
   issue_raw(c0, b0);
 #pragma unroll
   for (int i = 0; i < 8; ++i) issue_u(c0, b0, i);
   issue_raw(min(c0 + 1, c1 - 1), b0 ^ 1);
-  f32x16 acc[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.0f;
+  f32x16 acc[16];  // not zeroed: the first chunk's first MFMA of every accumulator takes a zero C operand (FIRST below)
   // ABL bit 7 (round 5, timing only, garbage results): the prologue's DMA round trip is NOT waited for — what a persistent launch that
   // prefetched the next tile's first chunk under the previous tile's epilogue could hide at the very best (tools/ablate_wino_prologue.py)
   if constexpr ((ABL & 128) == 0) dma_wait_all();
@@ -661,9 +683,10 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(ConvArgs a) {
   };
   load_frags(b0, 0, 0);
   unsigned long long tr0 = 0, tr1 = 0, tr2 = 0;
-  auto body = [&](int c, auto more_tag, auto parity_tag) {  // buffer parity s is a compile-time tag: LDS offsets become immediates
+  auto body = [&](int c, auto more_tag, auto parity_tag, auto first_tag) {  // buffer parity s is a compile-time tag: LDS offsets become immediates
     constexpr bool MORE = decltype(more_tag)::value;
     constexpr int s = decltype(parity_tag)::value;
+    constexpr bool FIRST = decltype(first_tag)::value;  // the block's first chunk: the accumulators start from an inline zero C operand
 #pragma unroll
     for (int p = 0; p < 8; ++p) {  // component pair (2p, 2p+1): two independent accumulator chains
       const int cur = p & 1;
@@ -689,7 +712,11 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {  // MFMA i of the pair: accumulator 2p + (i&1), k-pair i>>1
         __builtin_amdgcn_sched_barrier(0);
-        acc[2 * p + (i & 1)] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][i & 1][i >> 1], bf[cur][i & 1][i >> 1], acc[2 * p + (i & 1)], 0, 0, 0);
+        if constexpr (FIRST) {
+          if (i < 2) acc[2 * p + (i & 1)] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][i & 1][0], bf[cur][i & 1][0], f32x16{}, 0, 0, 0);
+        }
+        if (!FIRST || i >= 2)
+          acc[2 * p + (i & 1)] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][i & 1][i >> 1], bf[cur][i & 1][i >> 1], acc[2 * p + (i & 1)], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (i == 0 && p + 1 < 8 && !(ABL & 16)) load_frags(s, p + 1, cur ^ 1);
         if constexpr (MORE) {
@@ -717,19 +744,41 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(ConvArgs a) {
   if constexpr ((ABL & 64) != 0) tk1 = __builtin_amdgcn_s_memtime();
   using P0 = std::integral_constant<int, 0>;
   using P1 = std::integral_constant<int, 1>;
-  int cc = c0;
-  if (n_more & 1) { body(cc, std::true_type{}, P1{}); ++cc; }   // the first chunk sits in buffer n_more & 1, the last in buffer 0
-  for (; cc < c1 - 1; cc += 2) { body(cc, std::true_type{}, P0{}); body(cc + 1, std::true_type{}, P1{}); }
+  using T = std::true_type;
+  using F = std::false_type;
   // the epilogue's bias vectors are fetched under the last chunk's MFMAs (the transform registers are free there): a
   // global load inside the epilogue would sit behind an s_waitcnt vmcnt(0) that also waits for the previous channel
   // group's STORES to be acknowledged (measured: 9.8k-cycle epilogue)
   f32x4 bias4[4];
+  auto load_bias = [&]() {
 #pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int cb = min((cout0 + mbase) / 8 + g, a.out_cb - 1);
-    bias4[g] = *reinterpret_cast<const f32x4 *>(a.bpk + cb * 8 + half * 4);
+    for (int g = 0; g < 4; ++g) {
+      const int cb = min((cout0 + mbase) / 8 + g, a.out_cb - 1);
+      bias4[g] = *reinterpret_cast<const f32x4 *>(a.bpk + cb * 8 + half * 4);
+    }
+  };
+  // the first chunk sits in buffer n_more & 1, the last in buffer 0.  The first chunk runs the FIRST copy of its parity's body; a
+  // one-chunk block (Cin = 8, or a split down to one chunk) zeroes the accumulators instead and runs the common last body, so that
+  // every path reaches the epilogue through the same copy (a FIRST copy of the last body made the compiler move all 256
+  // accumulator registers where the two met)
+  if (n_more == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[k][r] = 0.0f;
+  } else {
+    int cc = c0;
+    if (n_more & 1) { body(cc, T{}, P1{}, T{}); ++cc; }
+    else { body(cc, T{}, P0{}, T{}); body(cc + 1, T{}, P1{}, F{}); cc += 2; }
+    for (; cc < c1 - 1; cc += 2) { body(cc, T{}, P0{}, F{}); body(cc + 1, T{}, P1{}, F{}); }
   }
-  body(c1 - 1, std::false_type{}, P0{});
+  load_bias();
+  body(c1 - 1, F{}, P0{}, F{});
+  // the bias loads are waited for HERE, once, before the first store: the compiler's vmcnt bookkeeping does not follow the stores
+  // through the epilogue's branches, so a bias register first used in channel block g > 0 got an s_waitcnt vmcnt(3 - g) in front of
+  // it, which also waits for every store of the blocks before to be acknowledged
+#pragma unroll
+  for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(bias4[g]));
   if constexpr ((ABL & 64) != 0) tk2 = __builtin_amdgcn_s_memtime();
 
   // ---- output transform A^T M A (register-local), bias, ReLU, stores, fused 2x2 max-pool
@@ -740,31 +789,31 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(ConvArgs a) {
     }
     return;
   }
-  // VALU time is fully exposed here (nothing left to overlap it with), so the epilogue is written for instruction count:
-  // two accumulator registers per packed op (v_pk_add_f32 / v_pk_max_f32), one wave-uniform 64-bit base per channel block
-  // and 32-bit per-lane byte offsets for the stores (no 64-bit VALU address arithmetic).
+  // VALU time is fully exposed here (nothing left to overlap it with: one wave per SIMD issues every instruction at ~4 cycles), so the
+  // epilogue is written for instruction count: two accumulator registers per packed add, single-instruction max, one wave-uniform
+  // 64-bit base per channel block and 32-bit per-lane byte offsets for the stores (no 64-bit VALU address arithmetic).  A block whose
+  // 64 tiles all lie inside the map (and the pooled map) takes a copy without any per-lane predicate; edge blocks take the
+  // predicated one.
   const int tau = nbase + l31;
   const int y = y0 + 2 * (tau / TC), x = x0 + 2 * (tau % TC);
   float *const obase = partial ? a.part + (size_t)split * a.part_slab : a.out;
   const unsigned off00 = (unsigned)((((y + 1) * a.out_Wp + x + 1) * 8 + half * 4) * 4);  // byte offset of output pixel (y, x) in a plane
   const unsigned row_b = (unsigned)(a.out_Wp * 32);
-  const bool okx1 = x + 1 < a.W, oky1 = y + 1 < a.H, ok00 = y < a.H && x < a.W;
-  const bool okk[4] = {ok00, ok00 && okx1, ok00 && oky1, ok00 && okx1 && oky1};
   const unsigned offk[4] = {off00, off00 + 32u, off00 + row_b, off00 + row_b + 32u};
   const int py = y >> 1, px = x >> 1;
-  const bool okp = a.pool && py < a.pool_H && px < a.pool_W;
   const unsigned offp = (unsigned)((((py + 1) * a.pool_Wp + px + 1) * 8 + half * 4) * 4);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int cb = (cout0 + mbase) / 8 + g;  // wave-uniform
-    if (cb >= a.out_cb) continue;
-    f32x2 Y[4][2];  // [output pixel k][element pair]
+  auto out_transform = [&](int g, f32x2 (&Y)[4][2]) {  // Y[output pixel k][element pair] of channel block g = A^T M A
 #pragma unroll
     for (int ep = 0; ep < 2; ++ep) {
       const int r = g * 4 + ep * 2;
       f32x2 m[16];
 #pragma unroll
-      for (int k = 0; k < 16; ++k) m[k] = f32x2{acc[k][r], acc[k][r + 1]};
+      for (int k = 0; k < 16; ++k) {
+        // each accumulator register is read ONCE, where its channel block is transformed (left to itself the compiler copies whole
+        // accumulators to VGPRs ahead of the loop, runs out of registers and spills)
+        asm("v_accvgpr_read_b32 %0, %1" : "=v"(m[k][0]) : "a"(acc[k][r]));
+        asm("v_accvgpr_read_b32 %0, %1" : "=v"(m[k][1]) : "a"(acc[k][r + 1]));
+      }
       const f32x2 s0 = m[0] + m[4] + m[8], s1 = m[1] + m[5] + m[9], s2 = m[2] + m[6] + m[10], s3 = m[3] + m[7] + m[11];
       // (the compiler scalarises a packed fsub whose operands come out of accumulator registers: spell it as the instruction)
       const f32x2 u0 = pk_sub(pk_sub(m[4], m[8]), m[12]), u1 = pk_sub(pk_sub(m[5], m[9]), m[13]);
@@ -772,25 +821,68 @@ __global__ __launch_bounds__(256) void conv3x3_wino_kernel(ConvArgs a) {
       Y[0][ep] = s0 + s1 + s2; Y[1][ep] = pk_sub(pk_sub(s1, s2), s3);
       Y[2][ep] = u0 + u1 + u2; Y[3][ep] = pk_sub(pk_sub(u1, u2), u3);
     }
-    if (partial) {  // raw partial sums; conv_splitk_reduce_kernel finishes the layer (or the layer's tail tiles)
-      char *const pb = reinterpret_cast<char *>(obase + (size_t)cb * a.out_plane);
+  };
+  const int cb0 = (cout0 + mbase) / 8;  // wave-uniform; channel block g of this wave is cb0 + g
+  const bool interior = y0 + 2 * TR <= a.H && x0 + 2 * TC <= a.W &&
+                        (partial || !a.pool || ((y0 >> 1) + TR <= a.pool_H && (x0 >> 1) + TC <= a.pool_W));  // wave-uniform
+  // one output transform per channel block, then ONE wave-uniform branch to the block's finish (separate loops per finish made the
+  // compiler hoist every accumulator read above the branch and spill)
+  enum { FIN_EDGE, FIN_PARTIAL, FIN_POOLED, FIN_FULL };
+  const int fin = !interior ? FIN_EDGE : partial ? FIN_PARTIAL : a.out == nullptr ? FIN_POOLED : FIN_FULL;
+  const float ninf = -INFINITY;  // the pool's seed rides in the second max3: a window of NaNs gives -inf, as on the edge path
+  const bool okx1 = x + 1 < a.W, oky1 = y + 1 < a.H, ok00 = y < a.H && x < a.W;
+  const bool okk[4] = {ok00, ok00 && okx1, ok00 && oky1, ok00 && okx1 && oky1};
+  const bool okp = a.pool && py < a.pool_H && px < a.pool_W;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int cb = cb0 + g;
+    if (cb >= a.out_cb) continue;
+    f32x2 Y[4][2];
+    out_transform(g, Y);
+    const f32x2 b01 = f32x2{bias4[g][0], bias4[g][1]}, b23 = f32x2{bias4[g][2], bias4[g][3]};
+    char *const ob = reinterpret_cast<char *>(obase + (size_t)cb * a.out_plane);  // partial: the split's slab
+    char *const pb = reinterpret_cast<char *>(a.pool + (size_t)cb * a.pool_plane);
+    if (fin == FIN_POOLED) {
+      // pooled map only: the 2x2 maximum of the four transform outputs first, then ONE bias add and ONE ReLU per element.  Rounding is
+      // monotone, so max_k fl(y_k + b) == fl(max_k y_k + b) for every finite bias; a NaN y_k is ignored by either order and a window of
+      // NaNs gives fl(-inf + b) = -inf (ReLU: 0), as before.
+      f32x2 v0 = vmax3_2s(vmax3_2(Y[0][0], Y[1][0], Y[2][0]), Y[3][0], ninf) + b01;
+      f32x2 v1 = vmax3_2s(vmax3_2(Y[0][1], Y[1][1], Y[2][1]), Y[3][1], ninf) + b23;
+      if (a.relu) { v0 = vrelu_2(v0); v1 = vrelu_2(v1); }
+      if (a.pool) *reinterpret_cast<f32x4 *>(pb + offp) = f32x4{v0[0], v0[1], v1[0], v1[1]};
+    } else if (fin == FIN_FULL) {
+      f32x2 V[4][2];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { V[k][0] = Y[k][0] + b01; V[k][1] = Y[k][1] + b23; }
+      if (a.relu) {  // one branch per channel block
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { V[k][0] = vrelu_2(V[k][0]); V[k][1] = vrelu_2(V[k][1]); }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4 *>(ob + offk[k]) = f32x4{V[k][0][0], V[k][0][1], V[k][1][0], V[k][1][1]};
+      if (a.pool) {  // tap layer: the full map and its pooled map
+        const f32x2 mx0 = vmax3_2s(vmax3_2(V[0][0], V[1][0], V[2][0]), V[3][0], ninf), mx1 = vmax3_2s(vmax3_2(V[0][1], V[1][1], V[2][1]), V[3][1], ninf);
+        *reinterpret_cast<f32x4 *>(pb + offp) = f32x4{mx0[0], mx0[1], mx1[0], mx1[1]};
+      }
+    } else if (fin == FIN_PARTIAL) {  // raw partial sums; conv_splitk_reduce_kernel finishes the layer (or the layer's tail tiles)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4 *>(ob + offk[k]) = f32x4{Y[k][0][0], Y[k][0][1], Y[k][1][0], Y[k][1][1]};
+    } else if (partial) {  // edge blocks: every store under its own predicate
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (okk[k]) *reinterpret_cast<f32x4 *>(pb + offk[k]) = f32x4{Y[k][0][0], Y[k][0][1], Y[k][1][0], Y[k][1][1]};
-      continue;
-    }
-    const f32x2 b01 = f32x2{bias4[g][0], bias4[g][1]}, b23 = f32x2{bias4[g][2], bias4[g][3]};
-    const f32x2 zero2 = f32x2{0.0f, 0.0f};
-    f32x2 mx0 = f32x2{-INFINITY, -INFINITY}, mx1 = mx0;
-    char *const ob = reinterpret_cast<char *>(a.out + (size_t)cb * a.out_plane);
+        if (okk[k]) *reinterpret_cast<f32x4 *>(ob + offk[k]) = f32x4{Y[k][0][0], Y[k][0][1], Y[k][1][0], Y[k][1][1]};
+    } else {
+      f32x2 mx0 = f32x2{-INFINITY, -INFINITY}, mx1 = mx0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      f32x2 v0 = Y[k][0] + b01, v1 = Y[k][1] + b23;
-      if (a.relu) { v0 = __builtin_elementwise_max(v0, zero2); v1 = __builtin_elementwise_max(v1, zero2); }
-      if (okk[k] && a.out) *reinterpret_cast<f32x4 *>(ob + offk[k]) = f32x4{v0[0], v0[1], v1[0], v1[1]};
-      if (okk[k]) { mx0 = __builtin_elementwise_max(mx0, v0); mx1 = __builtin_elementwise_max(mx1, v1); }
+      for (int k = 0; k < 4; ++k) {
+        f32x2 v0 = Y[k][0] + b01, v1 = Y[k][1] + b23;
+        if (a.relu) { v0 = vrelu_2(v0); v1 = vrelu_2(v1); }
+        if (okk[k] && a.out) *reinterpret_cast<f32x4 *>(ob + offk[k]) = f32x4{v0[0], v0[1], v1[0], v1[1]};
+        if (okk[k]) { mx0 = vmax_2(mx0, v0); mx1 = vmax_2(mx1, v1); }
+      }
+      if (okp) *reinterpret_cast<f32x4 *>(pb + offp) = f32x4{mx0[0], mx0[1], mx1[0], mx1[1]};
     }
-    if (okp) *reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(a.pool + (size_t)cb * a.pool_plane) + offp) = f32x4{mx0[0], mx0[1], mx1[0], mx1[1]};
+    __builtin_amdgcn_sched_barrier(0);  // one channel block's transform registers at a time
   }
   if constexpr ((ABL & 64) != 0) {
     const unsigned long long tk3 = __builtin_amdgcn_s_memtime();
