@@ -160,6 +160,12 @@ int mpn_flip_boxes(const float *d_boxes, int n, int image_width, float *d_out, v
  * start=round((x1-coord_offset)*scale), end=round((x2-coord_offset)*scale)+end_adjust, ROI forced
  * >= 1x1, bins floor/ceil of fp32 bin size, clipped to the map, empty bin -> 0.
  * Reference default ("v2" fix, README.md:202-203): coord_offset=1, end_adjust=0. */
+/* inn.ROIPooling:updateGradInput: d_grad_in [B,C,H,W] from d_grad_out [N,C,PH,PW] and the argmax mpn_roi_pool_forward wrote
+ * (column 0 of d_rois [N,5] is the 1-based map index, clamped as the forward clamps it).  Every cell is written:
+ *   grad_in[b,c,y,x] = sum of grad_out[n,c,bin] over the rows n of map b ASCENDING and, inside a row, the bins ascending
+ *   (ph * PW + pw), wherever argmax[n,c,bin] == y * W + x — fp32 adds from +0.0, no atomics: the order is part of the contract. */
+int mpn_roi_pool_backward(const float *d_grad_out, const int32_t *d_argmax, const float *d_rois, int B, int C, int H, int W, int N,
+                          int PH, int PW, float *d_grad_in, void *stream);
 int mpn_roi_pool_forward(const float *d_feat, int B, int C, int H, int W, const float *d_rois, int N, int PH, int PW,
                          float scale, float coord_offset, int end_adjust, float *d_out, int32_t *d_argmax,
                          void *stream);
@@ -201,6 +207,17 @@ int mpn_softmax_forward(const float *d_x, int M, int C, float *d_y, void *stream
  * fp32 MFMA implicit GEMM.  The activations are converted to the library's channel-blocked HBM layout
  * inside `ws`; mpn_conv3x3_workspace_bytes gives the size needed. */
 size_t mpn_conv3x3_workspace_bytes(int B, int Cin, int H, int W, int Cout);
+/* nn.SpatialConvolution:updateGradInput + accGradParameters of the module mpn_conv3x3_forward mirrors (no fused ReLU: d_grad_out is the
+ * gradient at the convolution's output), NCHW in and out:
+ *   d_grad_in [B,Cin,H,W]   = conv3x3(d_grad_out, W rotated by 180 degrees with cin / cout swapped)   (needs d_w)
+ *   d_grad_w  [Cout,Cin,3,3] = sum over the B maps, in order, of sum_{y,x} grad_out[co,y,x] in[ci,y+ky-1,x+kx-1]   (needs d_in)
+ *   d_grad_b  [Cout]         = sum over the maps and pixels of grad_out
+ * Each of the three may be NULL; gradients are OVERWRITTEN, not accumulated.  The same kernels as the training pipeline
+ * (mpn_frcnn_train_step at depth MPN_TRAIN_CONV(k)): fixed summation orders, no atomics — the same bits in every run.  Workspace and
+ * stream conventions of mpn_conv3x3_forward; mpn_conv3x3_backward_workspace_bytes gives the size. */
+size_t mpn_conv3x3_backward_workspace_bytes(int B, int Cin, int H, int W, int Cout);
+int mpn_conv3x3_backward(const float *d_in, int B, int Cin, int H, int W, const float *d_w, const float *d_grad_out, int Cout,
+                         float *d_grad_in, float *d_grad_w, float *d_grad_b, void *ws, size_t ws_bytes, void *stream);
 int mpn_conv3x3_forward(const float *d_in, int B, int Cin, int H, int W, const float *d_w, const float *d_b,
                         int Cout, int relu, float *d_out, void *d_ws, size_t ws_bytes, void *stream);
 
@@ -635,10 +652,40 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
  *   mpn_frcnn_get_head_weights  the current weights back in Torch layout ([out, in]; fc6's `in` index as at creation; cls and bbox split out
  *                          of the fused head); any pointer may be NULL; with or without a train_begin; any mpn_frcnn_create handle.  The exact
  *                          inverse of creation: unpack -> create -> unpack is bit-identical.
- * Debug tensor "train_pooled": fc6's operand of the last step, [B, C, PH, PW] (valid until the next mpn_frcnn_train_add). */
+ * Debug tensor "train_pooled": fc6's operand of the last step, [B, C, PH, PW] (valid until the next mpn_frcnn_train_add).
+ *
+ * Below the pooled features: depth MPN_TRAIN_CONV(k), k = 1..K, also trains the last k conv layers of the trunk.  K = the number of conv
+ * layers behind the trunk's last pool_after layer (VGG-16: K = 3; k = 1 trains conv5_3, k = 2 adds conv5_2, k = 3 adds conv5_1 — the
+ * reference, models/vgg.lua:19, trains conv3_1 and up); k > K answers MPN_EINVAL naming K: a pooling layer is in the way.  With B
+ * pending rows of I <= MPN_TRAIN_MAX_IMAGES images (one more mpn_frcnn_train_add: MPN_EINVAL), g6 the gradient at fc6's output:
+ *   dx6 = (g6 W6) .* [x6 > 0]      the mask is the last conv layer's ReLU mask (pooled values are post-ReLU map values); it also
+ *                                  kills every bin whose argmax sits on a zero cell and every empty bin
+ *   per image, in train_add order: dY = mpn_roi_pool_backward's ordered sum over that image's rows into a zero-haloed map; then, last
+ *   trained layer to first, with X the layer's saved input map and G the (masked) gradient at its output:
+ *     db[co] += sum_pixels G[co]                                    (32 interleaved pixel-ascending sums, then a fixed tree)
+ *     dW[co,ci,ky,kx] += sum_{y,x} G[co,y,x] X[ci,y+ky-1,x+kx-1]     (fp32 MFMA over row-major pixel pairs in segments of 512 pixels,
+ *                                                                   the segments added in order: fixed by the layer and map size)
+ *     dX = conv3x3(G, W rotated by 180 degrees, cin / cout swapped) .* [X > 0]   when a trained layer lies below (the forward's kernels)
+ *   optim.sgd exactly as for the head; every input gradient is computed before any weight is updated.
+ * The master copy of a trained conv layer is its direct-kernel pack, updated in place; the Winograd pack (and the K = 36 pack of a
+ * first layer) are rebuilt in place from it with the packers creation uses, so after a step every form is bit-identical to what
+ * creation would build from mpn_frcnn_get_trunk_weights' output, and detect and captured graphs read the same addresses.
+ * mpn_frcnn_train_add at these depths also keeps the rows' argmax and copies the block's input map and the trained layers' outputs
+ * into per-image slots; mpn_frcnn_train_begin allocates all of it, all or nothing, only at these depths.  VGG-16 at 600 x 1000 with
+ * max_rois 1000: 8 images x 4 maps x 6.8 MB = 218 MB, argmax 100 MB, dx6 103 MB, two gradient maps 14 MB, and per trained layer
+ * (2.4 M weights) momentum + gradient + the input gradient's two packs, 110 MB for the three, 47 MB of partial sums, 19 MB of
+ * Torch-layout scratch: 0.6 GB in all.
+ * Still not trained: anything under a pooling layer, MultiPathNet / ResNet / op-list handles, dropout.
+ * Debug tensors after such a step, until the next mpn_frcnn_train_add: "train_act.<i>.<j>" (image i; j = 0 the block's input map,
+ * j = 1..k the trained layers' outputs; [C,h,w]) and "train_dx6" ([B, C, PH, PW]).
+ *   mpn_frcnn_get_trunk_weights  conv layer `layer`'s current weights [Cout,Cin,3,3] and bias [Cout] in Torch layout (either may be
+ *                          NULL); any mpn_frcnn_create handle, with or without training.  The exact inverse of creation. */
 #define MPN_TRAIN_HEADS 0   /* cls + bbox linear only          */
 #define MPN_TRAIN_FC7   1   /* + fc7                           */
 #define MPN_TRAIN_FC6   2   /* + fc6 (the whole ROI head)      */
+#define MPN_TRAIN_MAX_IMAGES 8
+#define MPN_TRAIN_CONV(k) (MPN_TRAIN_FC6 + (k))   /* + the last k conv layers, k = 1..K (see above) */
+enum { MPN_TRAIN_MAX_CONV = 7 };   /* K is capped here: a trunk with more conv layers behind its last pooling layer trains the last 7 */
 int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight);
 int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_rois /*[n,4]*/,
                         const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);
@@ -646,6 +693,7 @@ int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss /*[2]: cls, bbox*
 int mpn_frcnn_train_end(mpn_frcnn *p);
 int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b,
                                float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
+int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w /*[Cout,Cin,3,3]*/, float *d_b /*[Cout]*/, void *stream);
 
 /* Captured launch graphs.  The kernel chains of the per-image path — the head (transform .. decode) and the tail (per-class NMS,
  * voting, top-k) of mpn_frcnn_test_one / _pipelined / _pipelined_host, and the bodies of mpn_frcnn_shard_head / _shard_nms /

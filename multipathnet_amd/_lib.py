@@ -100,6 +100,7 @@ def load(flavour=None):
     lib.mpn_pick_scale.restype = C.c_double
     lib.mpn_pick_scale.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
     lib.mpn_conv3x3_workspace_bytes.restype = C.c_size_t
+    lib.mpn_conv3x3_backward_workspace_bytes.restype = C.c_size_t
     lib.mpn_det_record_floats.restype = C.c_size_t
     lib.mpn_frcnn_shard_rows_floats.restype = C.c_size_t
     lib.mpn_frcnn_shard_class_floats.restype = C.c_size_t

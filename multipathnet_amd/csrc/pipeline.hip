@@ -393,7 +393,7 @@ struct mpn_frcnn {
   float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
   // ---- training the head (mpn_frcnn_train_*): exists between train_begin and train_end
   struct Train {
-    int depth = 0;                       // MPN_TRAIN_HEADS / _FC7 / _FC6
+    int depth = 0;                       // MPN_TRAIN_HEADS / _FC7 / _FC6 / _CONV(k)
     float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
     float *vh = nullptr, *vbh = nullptr, *v7 = nullptr, *vb7 = nullptr, *v6 = nullptr, *vb6 = nullptr;  // momentum, in the layout of the weight it goes with
     // the minibatch's own activations, C8 matrices at row pitch Mp (head: row-major [B, 5C]) — not detect's buffers, so a detect between
@@ -403,6 +403,24 @@ struct mpn_frcnn {
     float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
     int *labels = nullptr;
     int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
+    // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] above the last pooling layer
+    struct ConvT {
+      float *v = nullptr, *vb = nullptr;       // momentum: `wpk` layout, [CoutP]
+      float *dw = nullptr, *db = nullptr;      // the step's gradients, summed over the images in train_add order
+      float *wpk_t = nullptr, *wino_t = nullptr, *zero_b = nullptr;  // the input gradient's convolution (pack_conv_weights_dgrad); wino_t where Cout >= 16
+    };
+    int kconv = 0, first = 0;
+    std::vector<ConvT> cl;               // [kconv], cl[j] goes with conv[first + j]
+    float *dx6 = nullptr;                // gradient at the pooled features, x6's layout
+    int32_t *argmax = nullptr;           // [max_rois, C, PH, PW] of the pending rows
+    float *prois = nullptr;              // [max_rois, 5] the pending rows' projected ROIs (the bins' windows)
+    float *acts = nullptr;               // per image: the block's input map and the kconv trained layers' outputs, whole C8P planes
+    size_t act_off[MPN_TRAIN_MAX_CONV + 1] = {}, act_img = 0; // floats: map j inside an image's slot; between two images' slots
+    float *gmap[2] = {nullptr, nullptr}; // the gradient maps of the image being worked on (ping-pong through the layers)
+    size_t gmap_bytes = 0;
+    float *wtmp = nullptr, *part = nullptr;  // a layer's weights in Torch layout (x 2: W, W'); conv3x3_wgrad's partial sums
+    int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
+    int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // map size, row range
     DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
   };
   Train *train = nullptr;
@@ -2057,12 +2075,33 @@ static int refuse_train(const mpn_frcnn *p, const char *fn) {
   return MPN_OK;
 }
 
+// The forms of a conv layer that are derived from its master `wpk`: (forward) the Winograd and K = 36 packs detect's kernels read, rebuilt
+// IN PLACE by the packers creation used from the layer unpacked to Torch layout — bit-identical to what creation would build from the
+// exported weights; and, where the layer hands a gradient down (T.wpk_t), the input gradient's packs.  d_wtmp: 2 x Cout * Cin * 9 floats.
+static int refresh_conv_forms(const ConvLayer &L, const mpn_frcnn::Train::ConvT &T, float *d_wtmp, bool forward, hipStream_t s) {
+  int rc = unpack_conv_weights(L.wpk, nullptr, L.Cin, L.Cout, d_wtmp, nullptr, s);
+  if (rc == MPN_OK && forward && L.wino) rc = pack_conv_weights_wino(d_wtmp, L.Cin, L.Cout, L.wino, s);
+  if (rc == MPN_OK && forward && L.w36) rc = pack_conv_weights_first(d_wtmp, L.Cin, L.Cout, L.w36, s);
+  if (rc == MPN_OK && T.wpk_t) rc = pack_conv_weights_dgrad(d_wtmp, L.Cin, L.Cout, d_wtmp + (size_t)L.Cout * L.Cin * 9, T.wpk_t, T.zero_b, T.wino_t, s);
+  return rc;
+}
+
 extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight) {
   MPN_CHECK_ARG(p != nullptr);
   int rc = refuse_train(p, "mpn_frcnn_train_begin");
   if (rc) return rc;
   if (p->train) { set_error("mpn_frcnn_train_begin: training has already begun on this handle (mpn_frcnn_train_end first)"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(depth >= MPN_TRAIN_HEADS && depth <= MPN_TRAIN_FC6);
+  MPN_CHECK_ARG(depth >= MPN_TRAIN_HEADS);
+  const int n_conv = (int)p->conv.size();
+  int Kmax = 0;  // conv layers behind the trunk's last pooling layer (none when the trunk has no pooling layer: the block's input would be the image)
+  while (Kmax < n_conv && !p->conv[n_conv - 1 - Kmax].pool) ++Kmax;
+  if (Kmax == n_conv) Kmax = 0;
+  if (Kmax > MPN_TRAIN_MAX_CONV) Kmax = MPN_TRAIN_MAX_CONV;
+  if (depth > MPN_TRAIN_CONV(Kmax)) {
+    set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_CONV(%d), but only K = %d conv layers lie above the trunk's last pooling layer: a pooling layer is in the way (it has no backward pass)",
+              depth, depth - MPN_TRAIN_FC6, Kmax);
+    return MPN_EINVAL;
+  }
   MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
   MPN_CHECK_HIP(hipDeviceSynchronize());
   const mpn_frcnn_config &c = p->cfg;
@@ -2085,6 +2124,41 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
   }
   ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
   ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
+  if (depth > MPN_TRAIN_FC6) {
+    const int k = depth - MPN_TRAIN_FC6, PP = c.pooled_h * c.pooled_w;
+    t->kconv = k; t->first = n_conv - k;
+    int mh = c.max_h, mw = c.max_w;
+    final_map_size(p, &mh, &mw);
+    ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
+    ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
+    size_t off = 0, wmax = 0, pmax = 0;
+    int cmax = 0;
+    for (int j = 0; j <= k; ++j) {  // map 0: the block's input; map j: the output of conv[first + j - 1]
+      t->act_off[j] = off;
+      const int cj = j == 0 ? p->conv[t->first].Cin : p->conv[t->first + j - 1].Cout;
+      off += act_bytes(cj, mh, mw) / sizeof(float);
+      cmax = cj > cmax ? cj : cmax;
+    }
+    t->act_img = off;
+    ok = ok && alloc0(&t->acts, off * MPN_TRAIN_MAX_IMAGES * sizeof(float));
+    t->gmap_bytes = act_bytes(cmax, mh, mw);
+    ok = ok && alloc0(&t->gmap[0], t->gmap_bytes) && alloc0(&t->gmap[1], t->gmap_bytes);
+    t->cl.resize(k);
+    for (int j = 0; j < k && ok; ++j) {
+      const ConvLayer &L = p->conv[t->first + j];
+      mpn_frcnn::Train::ConvT &T = t->cl[j];
+      const size_t we = conv_wpk_elems(L.Cin, L.Cout) * sizeof(float), be = (size_t)conv_coutp(L.Cout) * sizeof(float);
+      ok = alloc0(&T.v, we) && alloc0(&T.vb, be) && alloc0(&T.dw, we) && alloc0(&T.db, be);
+      if (j > 0) {  // a trained layer lies below: this layer hands a gradient down
+        ok = ok && alloc0(&T.wpk_t, conv_wpk_elems(L.Cout, L.Cin) * sizeof(float)) && alloc0(&T.zero_b, (size_t)conv_coutp(L.Cin) * sizeof(float));
+        if (L.Cout >= 16) ok = ok && alloc0(&T.wino_t, conv_wino_elems(L.Cout, L.Cin) * sizeof(float));
+      }
+      wmax = std::max(wmax, (size_t)L.Cout * L.Cin * 9);
+      pmax = std::max(pmax, conv_wgrad_part_elems(L.Cin, L.Cout, mh, mw));
+    }
+    ok = ok && alloc0(&t->wtmp, 2 * wmax * sizeof(float)) && alloc0(&t->part, pmax * sizeof(float));
+    for (int j = 1; j < k && ok; ++j) ok = refresh_conv_forms(p->conv[t->first + j], t->cl[j], t->wtmp, false, nullptr) == MPN_OK;
+  }
   if (ok) ok = hipDeviceSynchronize() == hipSuccess;
   if (!ok) {
     set_error("mpn_frcnn_train_begin: allocating the momentum / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
@@ -2122,6 +2196,10 @@ extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, i
     set_error("mpn_frcnn_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
     return MPN_EINVAL;
   }
+  if (t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
+    set_error("mpn_frcnn_train_add: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", t->n_img, MPN_TRAIN_MAX_IMAGES);
+    return MPN_EINVAL;
+  }
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers and the ROI table are rewritten: the next head segment runs for real
@@ -2133,13 +2211,64 @@ extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, i
   rc = mpn_project_im_rois(d_rois, n, sc, p->rois, s);
   if (rc) return rc;
   // this image's rows behind the pending ones: a shifted base pointer with the buffer's row pitch
-  rc = roi_pool_c8(feat, p->rois, n, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, t->x6 + (size_t)t->pending * 8, nullptr, s, 5, p->Mp);
+  rc = roi_pool_c8(feat, p->rois, n, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, t->x6 + (size_t)t->pending * 8,
+                   t->kconv ? t->argmax + (size_t)t->pending * p->feat_c * c.pooled_h * c.pooled_w : nullptr, s, 5, p->Mp);
   if (rc) return rc;
+  if (t->kconv) {  // what the conv block's backward pass reads: the block's input, every trained layer's output, the rows' windows
+    const int i = t->n_img, h = feat.H, w = feat.W;
+    for (int j = 0; j <= t->kconv; ++j) {
+      const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones (k == K: a pooling layer)
+      const float *src = j == t->kconv ? feat.p : (L.pool ? L.pooled : L.out);
+      const int cj = L.Cout;
+      MPN_CHECK_HIP(hipMemcpyAsync(t->acts + (size_t)i * t->act_img + t->act_off[j], src, act_bytes(cj, h, w), hipMemcpyDeviceToDevice, s));
+    }
+    MPN_CHECK_HIP(hipMemcpyAsync(t->prois + (size_t)t->pending * 5, p->rois, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    t->img_h[i] = h; t->img_w[i] = w; t->img_row0[i] = t->pending; t->img_rows[i] = n;
+    ++t->n_img;
+  }
   MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
   MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
   MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
   t->pending += n;
   return MPN_OK;
+}
+
+// The backward pass below fc6 (depth MPN_TRAIN_CONV(k)): the gradient at the pooled features, then per image — in train_add order — the
+// ROI-pooling backward into a zero-haloed gradient map and, last trained layer to first, the bias and weight gradients (added to the
+// step's sums) and the input gradient masked with the ReLU of the layer below.  No weight is touched: the caller updates afterwards.
+static int train_conv_backward(mpn_frcnn *p, mpn_frcnn::Train *t, int B, hipStream_t s) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp, k = t->kconv;
+  // dx6 = (g6 W6) .* [x6 > 0]: fc6's packed chunk order is x6's.  The mask is the last conv layer's ReLU mask (pooled values are map values)
+  int rc = linear_dgrad_c8(t->g6, Mp, B, c.fc_dim, p->w6, p->K6, t->x6, t->dx6, Mp, s);
+  for (int i = 0; i < t->n_img && rc == MPN_OK; ++i) {
+    const int h = t->img_h[i], w = t->img_w[i];
+    auto saved = [&](int j) { return make_act(t->acts + (size_t)i * t->act_img + t->act_off[j], j == 0 ? p->conv[t->first].Cin : p->conv[t->first + j - 1].Cout, h, w); };
+    for (float *gm : t->gmap) MPN_CHECK_HIP(hipMemsetAsync(gm, 0, t->gmap_bytes, s));  // the halo is the input gradient's padding
+    int cur = 0;
+    Act G = make_act(t->gmap[cur], p->feat_c, h, w);
+    RoiBwd a{};
+    a.g = t->dx6; a.argmax = t->argmax; a.rois = t->prois; a.by_batch = 0; a.n0 = t->img_row0[i]; a.n1 = a.n0 + t->img_rows[i];
+    a.B = 1; a.C = p->feat_c; a.H = h; a.W = w; a.PH = c.pooled_h; a.PW = c.pooled_w; a.windows = (c.pooled_h <= 32 && c.pooled_w <= 32) ? 1 : 0;
+    a.g_n = 8; a.g_cb = (long)PP * Mp * 8; a.g_c = 1; a.g_bin = (long)Mp * 8;
+    a.o_b = 0; a.o_cb = (long)G.plane(); a.o_c = 1; a.o_y = (long)G.Wp * 8; a.o_x = 8;
+    a.scale = c.spatial_scale; a.rr = RoiRule{1.0f, 0, c.roi_bin_rule};
+    a.out = G.p + ((size_t)G.Wp + 1) * 8;
+    rc = roi_pool_backward(a, s);
+    for (int j = k; j >= 1 && rc == MPN_OK; --j) {
+      const ConvLayer &L = p->conv[t->first + j - 1];
+      const mpn_frcnn::Train::ConvT &T = t->cl[j - 1];
+      const Act X = saved(j - 1);
+      rc = conv_bias_grad(G, T.db, i > 0, s);
+      if (rc == MPN_OK) rc = conv3x3_wgrad(X, G, t->part, T.dw, i > 0, s);
+      if (rc != MPN_OK || j == 1) break;
+      Act dX = make_act(t->gmap[cur ^ 1], L.Cin, h, w);
+      rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
+      if (rc == MPN_OK) rc = relu_mask_c8p(dX, X, s);
+      G = dX; cur ^= 1;
+    }
+  }
+  return rc;
 }
 
 extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
@@ -2167,6 +2296,7 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   // backward: every input gradient before the update of the weights it was computed with
   if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC7) rc = linear_dgrad_c8(t->gh, Mp, B, 5 * C, p->wh, F, t->y7, t->g7, Mp, s);
   if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC6) rc = linear_dgrad_c8(t->g7, Mp, B, F, p->w7, F, t->y6, t->g6, Mp, s);
+  if (rc == MPN_OK && t->kconv) rc = train_conv_backward(p, t, B, s);
   if (rc == MPN_OK) rc = sgd_wgrad_c8(t->gh, Mp, t->y7, Mp, B, 5 * C, F, 1, p->wh, t->vh, lr, t->momentum, t->weight_decay, s);
   if (rc == MPN_OK) rc = sgd_bias_c8(t->gh, Mp, B, 5 * C, p->bh, t->vbh, lr, t->momentum, s);
   if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC7) {
@@ -2177,6 +2307,14 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
     rc = sgd_wgrad_c8(t->g6, Mp, t->x6, Mp, B, F, p->K6, PP, p->w6, t->v6, lr, t->momentum, t->weight_decay, s);
     if (rc == MPN_OK) rc = sgd_bias_c8(t->g6, Mp, B, F, p->b6, t->vb6, lr, t->momentum, s);
   }
+  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {  // the conv block: the master `wpk` in place, then every form derived from it
+    const ConvLayer &L = p->conv[t->first + j];
+    const mpn_frcnn::Train::ConvT &T = t->cl[j];
+    rc = conv_sgd(L.wpk, T.v, T.dw, L.Cin, L.Cout, lr, t->momentum, t->weight_decay, s);
+    if (rc == MPN_OK) rc = vec_sgd(L.bpk, T.vb, T.db, L.Cout, lr, t->momentum, s);
+    if (rc == MPN_OK) rc = refresh_conv_forms(L, T, t->wtmp, true, s);
+  }
+  t->last_img = t->n_img; t->n_img = 0;
   t->last_rows = B;
   t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
   return rc;
@@ -2197,6 +2335,17 @@ extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d
   if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, 0, C, d_cls_w, d_cls_b, s);
   if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, C, 5 * C, d_bbox_w, d_bbox_b, s);
   return rc;
+}
+
+extern "C" int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w, float *d_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (p->is_mpnet || p->rn) {
+    set_error("mpn_frcnn_get_trunk_weights: a %s handle is not supported: only mpn_frcnn_create's VGG trunk is unpacked", handle_kind_name(p));
+    return MPN_ESTATE;
+  }
+  if (layer < 0 || layer >= (int)p->conv.size()) { set_error("mpn_frcnn_get_trunk_weights: layer %d of a %d-layer trunk", layer, (int)p->conv.size()); return MPN_EINVAL; }
+  const ConvLayer &L = p->conv[layer];
+  return unpack_conv_weights(L.wpk, L.bpk, L.Cin, L.Cout, d_w, d_b, as_stream(stream));
 }
 
 #ifdef MPN_DEBUG_HOOKS
@@ -2226,6 +2375,19 @@ extern "C" int mpn_debug_bench_train_fc6(mpn_frcnn *p, int iters, float *ms_out)
   if (!t || t->depth < MPN_TRAIN_FC6 || t->last_rows <= 0) { set_error("mpn_debug_bench_train_fc6: needs a mpn_frcnn_train_step at depth MPN_TRAIN_FC6"); return MPN_ESTATE; }
   const int F = p->cfg.fc_dim, PP = p->cfg.pooled_h * p->cfg.pooled_w;
   return time_back_to_back(iters, ms_out, [&] { return sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr); });
+}
+
+// tools/bench_train.py (debug flavour only): conv3x3_wgrad (the MFMA kernel + its segment reduce) of the LAST trained conv layer issued
+// `iters` times back to back on image 0 of the last mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1); the gradient map holds whatever
+// that step left (the kernel's time does not depend on values).  Overwrites that layer's dW sum: take a step afterwards before reading it.
+extern "C" int mpn_debug_bench_train_wgrad(mpn_frcnn *p, int iters, float *ms_out) {
+  MPN_CHECK_ARG(p && iters > 0 && ms_out);
+  mpn_frcnn::Train *t = p->train;
+  if (!t || !t->kconv || t->last_img <= 0) { set_error("mpn_debug_bench_train_wgrad: needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)"); return MPN_ESTATE; }
+  const int k = t->kconv, h = t->img_h[0], w = t->img_w[0];
+  const ConvLayer &L = p->conv[t->first + k - 1];
+  const Act X = make_act(t->acts + t->act_off[k - 1], L.Cin, h, w), G = make_act(t->gmap[0], L.Cout, h, w);
+  return time_back_to_back(iters, ms_out, [&] { return conv3x3_wgrad(X, G, t->part, t->cl[k - 1].dw, 0, nullptr); });
 }
 
 // bench.py's `power_sensitivity` leg (debug flavour only): fc6 of the VGG Fast R-CNN pipeline issued `iters` times BACK TO BACK on the
@@ -2260,6 +2422,32 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
     if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
     hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(nt, 256)), dim3(256), 0, nullptr, p->train->x6, p->train->last_rows, p->feat_c, PPt, p->Mp, p->dbg);
     MPN_CHECK_LAUNCH();
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    *d_ptr = p->dbg; *n_elems = nt;
+    return MPN_OK;
+  }
+  if (!strncmp(name, "train_act.", 10) || !strcmp(name, "train_dx6")) {  // the conv block's saved maps [C,h,w] / the gradient at the pooled features
+    const mpn_frcnn::Train *t = p->train;
+    if (!t || !t->kconv || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)", name); return MPN_ESTATE; }
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    size_t nt = 0;
+    if (!strcmp(name, "train_dx6")) {
+      const int PPt = p->cfg.pooled_h * p->cfg.pooled_w;
+      nt = (size_t)t->last_rows * p->feat_c * PPt;
+      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+      hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(nt, 256)), dim3(256), 0, nullptr, t->dx6, t->last_rows, p->feat_c, PPt, p->Mp, p->dbg);
+      MPN_CHECK_LAUNCH();
+    } else {
+      int i = -1, j = -1;
+      if (sscanf(name + 10, "%d.%d", &i, &j) != 2 || i < 0 || i >= t->last_img || j < 0 || j > t->kconv) {
+        set_error("mpn_frcnn_debug_tensor: '%s': the last step had %d images and maps 0..%d", name, t->last_img, t->kconv);
+        return MPN_EINVAL;
+      }
+      const Act a = make_act(t->acts + (size_t)i * t->act_img + t->act_off[j], j == 0 ? p->conv[t->first].Cin : p->conv[t->first + j - 1].Cout, t->img_h[i], t->img_w[i]);
+      nt = (size_t)a.C * a.H * a.W;
+      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+      if (int rcc = c8p_to_nchw(a, p->dbg, nullptr)) return rcc;
+    }
     MPN_CHECK_HIP(hipDeviceSynchronize());
     *d_ptr = p->dbg; *n_elems = nt;
     return MPN_OK;

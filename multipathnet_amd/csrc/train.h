@@ -36,4 +36,48 @@ int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_
 // The inverse of pack_linear_weights for output rows [n0, n1): d_w [n1 - n0, K] Torch layout, d_b [n1 - n0]; either may be null.
 int unpack_linear_weights(const float *d_wpk, const float *d_bpk, int K, int N, int inner, int n0, int n1, float *d_w, float *d_b, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The conv block above the last pooling layer (MPN_TRAIN_CONV(k)): ROI-pooling backward, the 3x3 convolution's
+// weight / bias / input gradients and optim.sgd on a packed conv weight.  Maps are C8P activations (dense.h), weights `wpk` packs.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// inn.ROIPooling:updateGradInput as a per-cell GATHER: out[b][c][y][x] = sum of g[n][c][bin] over the rows n of map b ascending and,
+// inside a row, the bins ascending (ph * PW + pw), wherever argmax[n][c][bin] == y * W + x — fp32 adds from +0.0, no atomics, so the
+// order is the same in every run.  Every cell of every map is written (cells nothing pooled from get +0.0); a C8P destination's halo
+// and pad lanes are the caller's.  The two operand layouts are given by strides:
+//   g[n * g_n + (c / 8) * g_cb + (c % 8) * g_c + bin * g_bin],  out[b * o_b + (c / 8) * o_cb + (c % 8) * o_c + y * o_y + x * o_x].
+// Rows: by_batch != 0 — all N rows, a row belongs to map clamp((int)rois[n][0] - 1, 0, B - 1) (the forward's rule); otherwise the rows
+// [n0, n1) all belong to the ONE map (B == 1).  d_rois is [N,5] (the projected ROIs); with windows != 0 only the bins whose window
+// (roi_bin_bounds with `scale`, `rr`: the forward's) holds the cell are visited — the same sum, fewer argmax reads (PH, PW <= 32).
+struct RoiBwd {
+  const float *g; const int32_t *argmax; const float *rois;
+  int by_batch, n0, n1, B, C, H, W, PH, PW, windows;
+  long g_n, g_cb, g_c, g_bin, o_b, o_cb, o_c, o_y, o_x;
+  float scale; RoiRule rr;
+  float *out;
+};
+int roi_pool_backward(const RoiBwd &a, hipStream_t s);
+
+struct Act;
+constexpr int kWgradSegPx = 512;  // pixels per partial sum of the weight gradient
+// floats of the partial-sum buffer conv3x3_wgrad needs for an H x W map
+size_t conv_wgrad_part_elems(int Cin, int Cout, int H, int W);
+// dW[co][ci][ky][kx] (+)= sum_{y,x} G[co][y][x] * X[ci][y + ky - 1][x + kx - 1] in the `wpk` layout [Cin8/8][9][CoutP][8], pad lanes +0.0.
+// v_mfma_f32_32x32x2_f32 over the pixels in row-major pairs, cut into segments of kWgradSegPx pixels, each accumulated from zero by its
+// own block into d_part; conv_wgrad_reduce_kernel then adds the segments in ascending order and (accumulate) adds that sum to d_dw:
+// the order depends on (Cin, Cout, H, W) alone.  X's halo must be zero (it is the padding); G's halo is never read.
+int conv3x3_wgrad(const Act &x, const Act &g, float *d_part, float *d_dw, int accumulate, hipStream_t s);
+// db[co] (+)= sum_{y,x} G[co][y][x]: 32 interleaved pixel-ascending partial sums, then a fixed tree (as sgd_bias_kernel)
+int conv_bias_grad(const Act &g, float *d_db, int accumulate, hipStream_t s);
+// g .*= [x > 0] on the interior of the planes (x: the post-ReLU output of the layer the gradient flows into)
+int relu_mask_c8p(const Act &g, const Act &x, hipStream_t s);
+// optim.sgd on a packed conv weight: g' = dW + wd * w, v = momentum * v + g', w = w - lr * v (each rounded on its own), pad lanes untouched
+int conv_sgd(float *d_wpk, float *d_vpk, const float *d_dw, int Cin, int Cout, float lr, float momentum, float wd, hipStream_t s);
+int vec_sgd(float *d_b, float *d_vb, const float *d_db, int n, float lr, float momentum, hipStream_t s);
+// the exact inverse of pack_conv_weights: d_w [Cout,Cin,3,3], d_b [Cout]; either may be null
+int unpack_conv_weights(const float *d_wpk, const float *d_bpk, int Cin, int Cout, float *d_w, float *d_b, hipStream_t s);
+// the input gradient's weights W'[ci][co][2 - ky][2 - kx] = W[co][ci][ky][kx] in the `wpk` layout of a Cout -> Cin convolution (pack_conv_w_dgrad_kernel),
+// its zero bias [conv_coutp(Cin)] and — d_wino_t non-null — the Winograd form of W' (d_tmp: Cout * Cin * 9 floats, W' in Torch layout).
+// dX = conv3x3_c8p(G, d_wpk_t, d_zero_b, Cin, relu 0, ..., d_wino_t): the forward's kernels.
+int pack_conv_weights_dgrad(const float *d_w, int Cin, int Cout, float *d_tmp, float *d_wpk_t, float *d_zero_b, float *d_wino_t, hipStream_t s);
+
 }  // namespace mpn

@@ -324,4 +324,368 @@ int unpack_linear_weights(const float *d_wpk, const float *d_bpk, int K, int N, 
   return MPN_OK;
 }
 
+// =================================================================================================================================
+// The conv block above the last pooling layer (train.h)
+// =================================================================================================================================
+// One thread per (c, y, x) cell, x fastest: it walks the rows of its map and the bins in the contract's order and adds in that order.
+__global__ __launch_bounds__(256) void roi_pool_backward_kernel(RoiBwd a) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)a.C * a.H * a.W) return;
+  const int x = (int)(t % a.W), y = (int)((t / a.W) % a.H), c = (int)(t / ((size_t)a.W * a.H));
+  const int b = blockIdx.y, cell = y * a.W + x, PP = a.PH * a.PW;
+  const float *gc = a.g + (long)(c >> 3) * a.g_cb + (long)(c & 7) * a.g_c;
+  float sum = 0.0f;
+  for (int n = a.n0; n < a.n1; ++n) {
+    const float *ro = a.rois + (size_t)n * 5;
+    if (a.by_batch) {
+      int rb = (int)ro[0] - 1;
+      rb = rb < 0 ? 0 : (rb >= a.B ? a.B - 1 : rb);
+      if (rb != b) continue;
+    }
+    unsigned phm = 0xffffffffu, pwm = 0xffffffffu;
+    if (a.windows) {  // the bins whose window holds the cell: rows and columns of bins are independent in both bin rules
+      phm = pwm = 0u;
+      int hs, he, ws, we;
+      for (int ph = 0; ph < a.PH; ++ph) {
+        roi_bin_bounds(ro, a.scale, a.rr, a.H, a.W, a.PH, a.PW, ph, 0, hs, he, ws, we);
+        if (y >= hs && y < he) phm |= 1u << ph;
+      }
+      if (!phm) continue;
+      for (int pw = 0; pw < a.PW; ++pw) {
+        roi_bin_bounds(ro, a.scale, a.rr, a.H, a.W, a.PH, a.PW, 0, pw, hs, he, ws, we);
+        if (x >= ws && x < we) pwm |= 1u << pw;
+      }
+      if (!pwm) continue;
+    }
+    const int32_t *am = a.argmax + ((size_t)n * a.C + c) * PP;
+    const float *gn = gc + (long)n * a.g_n;
+    for (int ph = 0; ph < a.PH; ++ph) {
+      if (!((phm >> (ph & 31)) & 1u)) continue;
+      for (int pw = 0; pw < a.PW; ++pw) {
+        if (!((pwm >> (pw & 31)) & 1u)) continue;
+        const int bin = ph * a.PW + pw;
+        if (am[bin] == cell) sum += gn[(long)bin * a.g_bin];
+      }
+    }
+  }
+  a.out[(long)b * a.o_b + (long)(c >> 3) * a.o_cb + (long)(c & 7) * a.o_c + (long)y * a.o_y + (long)x * a.o_x] = sum;
+}
+
+int roi_pool_backward(const RoiBwd &a, hipStream_t s) {
+  MPN_CHECK_ARG(a.g && a.argmax && a.rois && a.out && a.B > 0 && a.C > 0 && a.H > 0 && a.W > 0 && a.PH > 0 && a.PW > 0 && a.n0 >= 0 && a.n1 >= a.n0);
+  MPN_CHECK_ARG(a.by_batch || a.B == 1);
+  MPN_CHECK_ARG(!a.windows || (a.PH <= 32 && a.PW <= 32));
+  const size_t cells = (size_t)a.C * a.H * a.W;
+  hipLaunchKernelGGL(roi_pool_backward_kernel, dim3((unsigned)cdiv_sz(cells, 256), (unsigned)a.B), dim3(256), 0, s, a);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// 3x3 convolution weight gradient
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct ConvWgradArgs {
+  const float *x, *g;
+  size_t plane, part_stride;
+  int Wp, H, W, Cout, CoutP, nq;
+  float *part;
+};
+
+// sgd_wgrad_kernel's record mapping on a convolution.  The `wpk` layout [chunk][tap][CoutP][8] is a packed linear weight whose K chunks are
+// the pairs q = chunk * 9 + tap: A = the 32-byte record of X's channel chunk at the pixel shifted by the tap (i = q, 32 of them per
+// block), B = G[co][pixel] (j = co, 4 waves x 32), contraction over the pixels of the block's segment, row-major, in pairs (pixel
+// p0 + 2 s + lane / 32).  A lane ends with whole `wpk` records of the segment's partial dW: q0 + 8 (r / 4) + 4 (lane / 32) + r % 4, cout co.
+// Grid: (CoutP / 128, ceil(nq / 32), segments).  Nothing outside the H x W interior of G is read; X is read one cell into its halo.
+__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(ConvWgradArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
+  const int co0 = (blockIdx.x * 4 + wave) * 32, co = co0 + l31;
+  if (co0 >= a.Cout) return;  // (wave-uniform) a wave of pad couts only
+  const int q0 = blockIdx.y * 32, q = q0 + l31;
+  const bool q_ok = q < a.nq, co_ok = co < a.Cout;
+  const int HW = a.H * a.W, p0 = blockIdx.z * kWgradSegPx, p1 = min(p0 + kWgradSegPx, HW);
+  f32x16 acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[e][r] = 0.0f;
+  const int qq = q_ok ? q : 0, chunk = qq / 9, tap = qq - chunk * 9, ky = tap / 3, kx = tap - ky * 3;
+  const float *xp = a.x + (size_t)chunk * a.plane + ((size_t)ky * a.Wp + kx) * 8;           // cell (y + ky - 1, x + kx - 1) of pixel (y, x)
+  const float *gp = a.g + (size_t)((co_ok ? co : 0) >> 3) * a.plane + ((size_t)a.Wp + 1) * 8 + (co & 7);
+  auto load = [&](int m0, f32x4 &lo, f32x4 &hi, float &b) {  // pixels >= p1 contribute exact zeros on both sides
+    const int pi = m0 + half;
+    lo = f32x4{0.f, 0.f, 0.f, 0.f}; hi = lo; b = 0.0f;
+    if (pi < p1) {
+      const int y = pi / a.W, x = pi - y * a.W;
+      const size_t off = ((size_t)y * a.Wp + x) * 8;
+      if (q_ok) { lo = *reinterpret_cast<const f32x4 *>(xp + off); hi = *reinterpret_cast<const f32x4 *>(xp + off + 4); }
+      if (co_ok) b = gp[off];
+    }
+  };
+  f32x4 lo, hi; float b;
+  load(p0, lo, hi, b);
+  for (int m0 = p0; m0 < p1; m0 += 2) {
+    f32x4 nlo, nhi; float nb;
+    load(m0 + 2, nlo, nhi, nb);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(lo[e], b, acc[e], 0, 0, 0);
+      acc[4 + e] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi[e], b, acc[4 + e], 0, 0, 0);
+    }
+    lo = nlo; hi = nhi; b = nb;
+  }
+  if (!co_ok) return;
+  float *part = a.part + (size_t)blockIdx.z * a.part_stride;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int qr = q0 + 8 * (r >> 2) + 4 * half + (r & 3);
+    if (qr >= a.nq) continue;
+    float *o = part + ((size_t)qr * a.CoutP + co) * 8;
+    *reinterpret_cast<f32x4 *>(o) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+    *reinterpret_cast<f32x4 *>(o + 4) = f32x4{acc[4][r], acc[5][r], acc[6][r], acc[7][r]};
+  }
+}
+
+// dW (+)= ((part[0] + part[1]) + part[2]) + ...; lanes outside the layer (pad couts, pad cins: never written by the kernel above) get +0.0
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__restrict__ part, size_t stride, int nseg, int Cin, int Cout, int CoutP,
+                                                                size_t total, float *__restrict__ dw, int accumulate) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int e = (int)(t & 7);
+  const size_t r = t >> 3;
+  const int co = (int)(r % CoutP), q = (int)(r / CoutP), ci = (q / 9) * 8 + e;
+  float v = 0.0f;
+  if (co < Cout && ci < Cin) {
+    for (int sg = 0; sg < nseg; ++sg) v += part[(size_t)sg * stride + t];
+    if (accumulate) v = dw[t] + v;
+  }
+  dw[t] = v;
+}
+
+size_t conv_wgrad_part_elems(int Cin, int Cout, int H, int W) { return (size_t)cdiv(H * W, kWgradSegPx) * conv_wpk_elems(Cin, Cout); }
+
+int conv3x3_wgrad(const Act &x, const Act &g, float *d_part, float *d_dw, int accumulate, hipStream_t s) {
+  MPN_CHECK_ARG(x.p && g.p && d_part && d_dw && x.H == g.H && x.W == g.W && x.Hp == g.Hp && x.Wp == g.Wp && x.H > 0 && x.W > 0);
+  ConvWgradArgs a{};
+  a.x = x.p; a.g = g.p; a.plane = x.plane(); a.Wp = x.Wp; a.H = x.H; a.W = x.W;
+  a.Cout = g.C; a.CoutP = conv_coutp(g.C); a.nq = x.Cb() * 9;
+  a.part = d_part; a.part_stride = conv_wpk_elems(x.C, g.C);
+  const int nseg = cdiv(x.H * x.W, kWgradSegPx);
+  hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3((unsigned)(a.CoutP / 128), (unsigned)cdiv(a.nq, 32), (unsigned)nseg), dim3(256), 0, s, a);
+  MPN_CHECK_LAUNCH();
+  const size_t total = a.part_stride;
+  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, d_part, a.part_stride, nseg, x.C, g.C, a.CoutP,
+                     total, d_dw, accumulate);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// Block = one 8-channel block of G: thread t sums channel t % 8 over the pixels t / 8 (mod 32) of the row-major interior, ascending, then
+// a fixed LDS tree over the 32 partial sums (sgd_bias_kernel's order, over pixels)
+__global__ __launch_bounds__(256) void conv_bias_grad_kernel(const float *__restrict__ g, size_t plane, int Wp, int H, int W, int Cout,
+                                                             float *__restrict__ db, int accumulate) {
+  __shared__ float part[32][8];
+  const int e = threadIdx.x & 7, slot = threadIdx.x >> 3, co = blockIdx.x * 8 + e;
+  const float *gp = g + (size_t)blockIdx.x * plane + ((size_t)Wp + 1) * 8 + e;
+  float sum = 0.0f;
+  for (int pi = slot; pi < H * W; pi += 32) {
+    const int y = pi / W, x = pi - y * W;
+    sum += gp[((size_t)y * Wp + x) * 8];
+  }
+  part[slot][e] = sum;
+  __syncthreads();
+  for (int w = 16; w > 0; w >>= 1) {
+    if (slot < w) part[slot][e] += part[slot + w][e];
+    __syncthreads();
+  }
+  if (slot != 0 || co >= Cout) return;
+  db[co] = accumulate ? db[co] + part[0][e] : part[0][e];
+}
+
+int conv_bias_grad(const Act &g, float *d_db, int accumulate, hipStream_t s) {
+  MPN_CHECK_ARG(g.p && d_db && g.H > 0 && g.W > 0);
+  hipLaunchKernelGGL(conv_bias_grad_kernel, dim3((unsigned)g.Cb()), dim3(256), 0, s, g.p, g.plane(), g.Wp, g.H, g.W, g.C, d_db, accumulate);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+__global__ __launch_bounds__(256) void relu_mask_c8p_kernel(float *__restrict__ g, const float *__restrict__ x, int Cb, size_t plane, int Wp, int H, int W) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // one half-record per thread
+  if (t >= (size_t)Cb * H * W * 2) return;
+  const int h = (int)(t & 1);
+  const size_t r = t >> 1;
+  const int px = (int)(r % W), py = (int)((r / W) % H), cb = (int)(r / ((size_t)W * H));
+  const size_t off = (size_t)cb * plane + ((size_t)(py + 1) * Wp + px + 1) * 8 + h * 4;
+  const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + off);
+  f32x4 gv = *reinterpret_cast<const f32x4 *>(g + off);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) gv[e] = xv[e] > 0.0f ? gv[e] : 0.0f;
+  *reinterpret_cast<f32x4 *>(g + off) = gv;
+}
+
+int relu_mask_c8p(const Act &g, const Act &x, hipStream_t s) {
+  MPN_CHECK_ARG(g.p && x.p && g.C == x.C && g.H == x.H && g.W == x.W && g.Hp == x.Hp && g.Wp == x.Wp);
+  const size_t total = (size_t)g.Cb() * g.H * g.W * 2;
+  hipLaunchKernelGGL(relu_mask_c8p_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, g.p, x.p, g.Cb(), g.plane(), g.Wp, g.H, g.W);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+__global__ __launch_bounds__(256) void conv_sgd_kernel(float *__restrict__ w, float *__restrict__ v, const float *__restrict__ dw, int Cin, int Cout,
+                                                       int CoutP, size_t total, float lr, float mom, float wd) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const size_t r = t >> 3;
+  const int co = (int)(r % CoutP), q = (int)(r / CoutP), ci = (q / 9) * 8 + (int)(t & 7);
+  if (co >= Cout || ci >= Cin) return;  // pad lanes of the packing stay +0.0
+  const float wv = w[t];
+  const float gr = dw[t] + wd * wv;
+  const float vv = mom * v[t] + gr;
+  v[t] = vv;
+  w[t] = wv - lr * vv;
+}
+
+int conv_sgd(float *d_wpk, float *d_vpk, const float *d_dw, int Cin, int Cout, float lr, float momentum, float wd, hipStream_t s) {
+  MPN_CHECK_ARG(d_wpk && d_vpk && d_dw && Cin > 0 && Cout > 0);
+  const size_t total = conv_wpk_elems(Cin, Cout);
+  hipLaunchKernelGGL(conv_sgd_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, d_wpk, d_vpk, d_dw, Cin, Cout, conv_coutp(Cout), total, lr,
+                     momentum, wd);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+__global__ void vec_sgd_kernel(float *__restrict__ b, float *__restrict__ vb, const float *__restrict__ db, int n, float lr, float mom) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const float v = mom * vb[t] + db[t];
+  vb[t] = v;
+  b[t] = b[t] - lr * v;
+}
+
+int vec_sgd(float *d_b, float *d_vb, const float *d_db, int n, float lr, float momentum, hipStream_t s) {
+  MPN_CHECK_ARG(d_b && d_vb && d_db && n > 0);
+  hipLaunchKernelGGL(vec_sgd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, d_b, d_vb, d_db, n, lr, momentum);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+__global__ void unpack_conv_w_kernel(const float *__restrict__ wpk, const float *__restrict__ bpk, int Cin, int Cout, int CoutP,
+                                     float *__restrict__ w, float *__restrict__ b) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b && t < (size_t)Cout) b[t] = bpk[t];
+  if (!w || t >= (size_t)Cout * Cin * 9) return;
+  const int tap = (int)(t % 9), ci = (int)((t / 9) % Cin), co = (int)(t / ((size_t)9 * Cin));
+  w[t] = wpk[(((size_t)(ci >> 3) * 9 + tap) * CoutP + co) * 8 + (ci & 7)];
+}
+
+int unpack_conv_weights(const float *d_wpk, const float *d_bpk, int Cin, int Cout, float *d_w, float *d_b, hipStream_t s) {
+  MPN_CHECK_ARG(d_wpk && (d_bpk || !d_b) && Cin > 0 && Cout > 0);
+  if (!d_w && !d_b) return MPN_OK;
+  const size_t total = d_w ? (size_t)Cout * Cin * 9 : (size_t)Cout;
+  hipLaunchKernelGGL(unpack_conv_w_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, d_wpk, d_bpk, Cin, Cout, conv_coutp(Cout), d_w, d_b);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// W'[ci][co][2 - ky][2 - kx] = W[co][ci][ky][kx]: the `wpk` pack of the Cout -> Cin convolution that computes the input gradient, its
+// zero bias, and (wt non-null) W' in Torch layout for the Winograd packer
+__global__ void pack_conv_w_dgrad_kernel(const float *__restrict__ w, int Cin, int Cout, int CinP, int nchunks, float *__restrict__ wpk_t,
+                                         float *__restrict__ zero_b, float *__restrict__ wt) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < (size_t)CinP) zero_b[t] = 0.0f;
+  if (wt && t < (size_t)Cout * Cin * 9) {
+    const int tap = (int)(t % 9), co = (int)((t / 9) % Cout), ci = (int)(t / ((size_t)9 * Cout));
+    wt[t] = w[((size_t)co * Cin + ci) * 9 + (8 - tap)];
+  }
+  if (t >= (size_t)nchunks * 9 * CinP * 8) return;
+  const int j = (int)(t & 7);
+  size_t r = t >> 3;
+  const int ci = (int)(r % CinP); r /= CinP;
+  const int tap = (int)(r % 9), co = (int)(r / 9) * 8 + j;
+  wpk_t[t] = (ci < Cin && co < Cout) ? w[((size_t)co * Cin + ci) * 9 + (8 - tap)] : 0.0f;
+}
+
+int pack_conv_weights_dgrad(const float *d_w, int Cin, int Cout, float *d_tmp, float *d_wpk_t, float *d_zero_b, float *d_wino_t, hipStream_t s) {
+  MPN_CHECK_ARG(d_w && d_wpk_t && d_zero_b && Cin > 0 && Cout > 0 && (d_tmp || !d_wino_t));
+  const int nchunks = (Cout + 7) / 8, CinP = conv_coutp(Cin);
+  size_t total = (size_t)nchunks * 9 * CinP * 8;
+  if (d_wino_t && (size_t)Cout * Cin * 9 > total) total = (size_t)Cout * Cin * 9;
+  hipLaunchKernelGGL(pack_conv_w_dgrad_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, d_w, Cin, Cout, CinP, nchunks, d_wpk_t, d_zero_b,
+                     d_wino_t ? d_tmp : nullptr);
+  MPN_CHECK_LAUNCH();
+  return d_wino_t ? pack_conv_weights_wino(d_tmp, Cout, Cin, d_wino_t, s) : MPN_OK;
+}
+
 }  // namespace mpn
+
+// ---- module-level C entry points (NCHW Torch layouts) -----------------------------------------------------------------------------
+using namespace mpn;
+
+extern "C" int mpn_roi_pool_backward(const float *d_grad_out, const int32_t *d_argmax, const float *d_rois, int B, int C, int H, int W, int N,
+                                     int PH, int PW, float *d_grad_in, void *stream) {
+  MPN_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && PH > 0 && PW > 0 && N >= 0 && d_grad_in);
+  MPN_CHECK_ARG(N == 0 || (d_grad_out && d_argmax && d_rois));
+  if (N == 0) { MPN_CHECK_HIP(hipMemsetAsync(d_grad_in, 0, (size_t)B * C * H * W * sizeof(float), as_stream(stream))); return MPN_OK; }
+  RoiBwd a{};
+  const long PP = (long)PH * PW;
+  a.g = d_grad_out; a.argmax = d_argmax; a.rois = d_rois; a.by_batch = 1; a.n0 = 0; a.n1 = N; a.B = B; a.C = C; a.H = H; a.W = W; a.PH = PH; a.PW = PW;
+  a.g_n = (long)C * PP; a.g_cb = 8 * PP; a.g_c = PP; a.g_bin = 1;
+  a.o_b = (long)C * H * W; a.o_cb = 8L * H * W; a.o_c = (long)H * W; a.o_y = W; a.o_x = 1;
+  a.out = d_grad_in;
+  return roi_pool_backward(a, as_stream(stream));
+}
+
+static bool dgrad_has_wino(int Cout) { return Cout >= 16; }  // build_vgg_trunk's rule on the transposed layer (its input channels = Cout)
+
+extern "C" size_t mpn_conv3x3_backward_workspace_bytes(int B, int Cin, int H, int W, int Cout) {
+  (void)B;
+  const size_t acts = 2 * act_bytes(Cin, H, W) + act_bytes(Cout, H, W);
+  const size_t w = ((size_t)Cout * Cin * 9 + conv_wpk_elems(Cout, Cin) + conv_wino_elems(Cout, Cin) + (size_t)conv_coutp(Cin) +
+                    conv_wpk_elems(Cin, Cout) + (size_t)conv_coutp(Cout) + conv_wgrad_part_elems(Cin, Cout, H, W)) * sizeof(float);
+  return acts + w + 1024;
+}
+
+extern "C" int mpn_conv3x3_backward(const float *d_in, int B, int Cin, int H, int W, const float *d_w, const float *d_grad_out, int Cout,
+                                    float *d_grad_in, float *d_grad_w, float *d_grad_b, void *d_ws, size_t ws_bytes, void *stream) {
+  MPN_CHECK_ARG(d_grad_out && d_ws && B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0);
+  MPN_CHECK_ARG((d_in || !d_grad_w) && (d_w || !d_grad_in));
+  const size_t need = mpn_conv3x3_backward_workspace_bytes(B, Cin, H, W, Cout);
+  if (ws_bytes < need) { set_error("mpn_conv3x3_backward: workspace too small (%zu < %zu)", ws_bytes, need); return MPN_ENOMEM; }
+  hipStream_t s = as_stream(stream);
+  char *ws = static_cast<char *>(d_ws);
+  const size_t ab = act_bytes(Cin, H, W), gb = act_bytes(Cout, H, W);
+  Act ax = make_act(reinterpret_cast<float *>(ws), Cin, H, W);
+  Act adx = make_act(reinterpret_cast<float *>(ws + ab), Cin, H, W);
+  Act ag = make_act(reinterpret_cast<float *>(ws + 2 * ab), Cout, H, W);
+  float *wpk_t = reinterpret_cast<float *>(ws + 2 * ab + gb);
+  float *wino_t = wpk_t + conv_wpk_elems(Cout, Cin);
+  float *zero_b = wino_t + conv_wino_elems(Cout, Cin);
+  float *dw = zero_b + conv_coutp(Cin);
+  float *db = dw + conv_wpk_elems(Cin, Cout);
+  float *part = db + conv_coutp(Cout);
+  float *wt = part + conv_wgrad_part_elems(Cin, Cout, H, W);     // W' in Torch layout (last: its size is no multiple of a record)
+  int rc = MPN_OK;
+  if (d_grad_in) {
+    rc = pack_conv_weights_dgrad(d_w, Cin, Cout, wt, wpk_t, zero_b, dgrad_has_wino(Cout) ? wino_t : nullptr, s);
+    if (rc) return rc;
+  }
+  // the halos of all three maps (the convolutions' padding) and their pad channels: zeroed here, whatever the workspace held
+  MPN_CHECK_HIP(hipMemsetAsync(ws, 0, 2 * ab + gb, s));
+  for (int b = 0; b < B; ++b) {
+    rc = nchw_to_c8p(d_grad_out + (size_t)b * Cout * H * W, Cout, H, W, ag, s);
+    if (rc) return rc;
+    if (d_grad_b) { rc = conv_bias_grad(ag, db, b > 0, s); if (rc) return rc; }
+    if (d_grad_w) {
+      rc = nchw_to_c8p(d_in + (size_t)b * Cin * H * W, Cin, H, W, ax, s);
+      if (rc == MPN_OK) rc = conv3x3_wgrad(ax, ag, part, dw, b > 0, s);
+      if (rc) return rc;
+    }
+    if (d_grad_in) {
+      rc = conv3x3_c8p(ag, wpk_t, zero_b, Cin, 0, adx, Act{}, s, dgrad_has_wino(Cout) ? wino_t : nullptr);
+      if (rc == MPN_OK) rc = c8p_to_nchw(adx, d_grad_in + (size_t)b * Cin * H * W, s);
+      if (rc) return rc;
+    }
+  }
+  if (d_grad_w) { rc = unpack_conv_weights(dw, nullptr, Cin, Cout, d_grad_w, nullptr, s); if (rc) return rc; }
+  if (d_grad_b) MPN_CHECK_HIP(hipMemcpyAsync(d_grad_b, db, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return MPN_OK;
+}

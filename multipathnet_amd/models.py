@@ -801,9 +801,11 @@ class FastRCNN(object):
 
     # ---- fine-tuning the head on the device, trunk frozen (mpn_frcnn_train_*, include/mpn.h) ----
     def train_begin(self, depth=2, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0):
-        """Start training: depth 0 = cls + bbox linear only, 1 = + fc7, 2 = + fc6 (the whole ROI head); optim.sgd's momentum and weight
-        decay (engines/Optim.lua; biases never decay), the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN handles in fp32
-        only; no dropout (the reference's opt.train_remove_dropouts configuration)."""
+        """Start training: depth 0 = cls + bbox linear only, 1 = + fc7, 2 = + fc6 (the whole ROI head), 2 + k = + the last k conv layers
+        of the trunk, k = 1..K with K the number of conv layers above the trunk's last pooling layer (VGG-16: 3 = + conv5_3, 4 = + conv5_2,
+        5 = + conv5_1; beyond K a pooling layer is in the way: MpnError).  At depth >= 3 a step takes at most 8 images.  optim.sgd's
+        momentum and weight decay (engines/Optim.lua; biases never decay), the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN
+        handles in fp32 only; no dropout (the reference's opt.train_remove_dropouts configuration)."""
         check(self._lib.mpn_frcnn_train_begin(self._h, int(depth), C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)),
               "mpn_frcnn_train_begin")
 
@@ -835,6 +837,17 @@ class FastRCNN(object):
         check(self._lib.mpn_frcnn_get_head_weights(self._h, *[_f(P[k]) for k in ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")],
                                                    _stream()), "mpn_frcnn_get_head_weights")
         return P
+
+    def trunk_weights(self):
+        """The trunk's current conv weights and biases in Torch layout, {"conv_w": [...], "conv_b": [...]} as synthetic_params names them
+        (device tensors): with head_weights() everything a new FastRCNN of the trained network needs."""
+        ws, bs, cin = [], [], 3
+        for l, co in enumerate(self._cout):
+            w = torch.empty((co, cin, 3, 3), dtype=torch.float32, device=self.device)
+            b = torch.empty(co, dtype=torch.float32, device=self.device)
+            check(self._lib.mpn_frcnn_get_trunk_weights(self._h, l, _f(w), _f(b), _stream()), "mpn_frcnn_get_trunk_weights")
+            ws.append(w); bs.append(b); cin = co
+        return {"conv_w": ws, "conv_b": bs}
 
     def set_graphs(self, on):
         """captured launch graphs (mpn_frcnn_set_graphs): replay the per-image kernel chains with hipGraphLaunch.

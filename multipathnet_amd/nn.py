@@ -105,6 +105,19 @@ class ROIPooling(Module):
                   "ROIPooling")
         return self.output
 
+    def updateGradInput(self, input, gradOutput):
+        """inn.ROIPooling:updateGradInput with the `indices` of the last updateOutput (mpn_roi_pool_backward: per cell, the rows of
+        its map ascending and the bins of a row ascending — a fixed order, no atomics) -> gradInput w.r.t. the features [B,C,h,w]."""
+        feat, rois = input
+        B, Cc, h, w = feat.shape
+        N = rois.size(0)
+        assert self.indices is not None and tuple(self.indices.shape) == (N, Cc, self.H, self.W) and tuple(gradOutput.shape) == (N, Cc, self.H, self.W)
+        self.gradInput = torch.empty((B, Cc, h, w), dtype=torch.float32, device=feat.device)
+        check(_lib.load().mpn_roi_pool_backward(_f(gradOutput, "gradOutput") if N else None, _i(self.indices) if N else None,
+                                                _f(rois, "rois") if N else None, B, Cc, h, w, N, self.H, self.W, _f(self.gradInput), _stream()),
+              "ROIPooling.updateGradInput")
+        return self.gradInput
+
 
 class Foveal(Module):
     def updateOutput(self, input):
@@ -212,7 +225,8 @@ class SpatialConvolution(Module):
         self.nInputPlane, self.nOutputPlane, self.relu = nInputPlane, nOutputPlane, relu
         self.weight = None  # [nOut, nIn, 3, 3]
         self.bias = None
-        self._ws = None
+        self.gradWeight = self.gradBias = None
+        self._ws = self._bws = None
 
     def updateOutput(self, input):
         x = input if input.dim() == 4 else input.unsqueeze(0)
@@ -229,6 +243,41 @@ class SpatialConvolution(Module):
               "SpatialConvolution")
         self.output = out if input.dim() == 4 else out[0]
         return self.output
+
+    def _backward(self, input, gradOutput, want_in, want_w, want_b):
+        assert not self.relu, "the backward pass is the plain convolution's (no fused ReLU)"
+        x = input if input.dim() == 4 else input.unsqueeze(0)
+        g = gradOutput if gradOutput.dim() == 4 else gradOutput.unsqueeze(0)
+        B, Cin, H, W = x.shape
+        Co = self.nOutputPlane
+        assert Cin == self.nInputPlane and tuple(g.shape) == (B, Co, H, W)
+        lib = _lib.load()
+        need = lib.mpn_conv3x3_backward_workspace_bytes(B, Cin, H, W, Co)
+        if self._bws is None or self._bws.numel() < need:
+            self._bws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+        gi, gw, gb = (z(B, Cin, H, W) if want_in else None), (z(Co, Cin, 3, 3) if want_w else None), (z(Co) if want_b else None)
+        p = lambda t: _f(t) if t is not None else None
+        check(lib.mpn_conv3x3_backward(_f(x, "input"), B, Cin, H, W, _f(self.weight, "weight"), _f(g, "gradOutput"), Co, p(gi), p(gw), p(gb),
+                                       C.c_void_p(self._bws.data_ptr()), C.c_size_t(need), _stream()), "SpatialConvolution backward")
+        return gi, gw, gb
+
+    def updateGradInput(self, input, gradOutput):
+        """gradInput = the convolution of gradOutput with the weights rotated by 180 degrees, cin / cout swapped (mpn_conv3x3_backward)"""
+        gi = self._backward(input, gradOutput, True, False, False)[0]
+        self.gradInput = gi if input.dim() == 4 else gi[0]
+        return self.gradInput
+
+    def accGradParameters(self, input, gradOutput, scale=1.0):
+        """gradWeight += scale * dW, gradBias += scale * db — the library overwrites, the sums are kept here, as Torch keeps them"""
+        _, gw, gb = self._backward(input, gradOutput, False, True, self.bias is not None)
+        if self.gradWeight is None:
+            self.gradWeight = torch.zeros_like(gw)
+        self.gradWeight.add_(gw, alpha=scale)
+        if gb is not None:
+            if self.gradBias is None:
+                self.gradBias = torch.zeros_like(gb)
+            self.gradBias.add_(gb, alpha=scale)
 
 
 class SpatialMaxPooling(Module):

@@ -1,9 +1,11 @@
 """Cost of one training step of the Fast R-CNN head on one GPU: VGG-16 at 600 x 1000, the reference's minibatch
 of 2 images x 64 ROIs (BatchProviderROI.lua:18-24 with 128 rows in all), frozen trunk.
-Per depth (0 = cls + bbox, 1 = + fc7, 2 = + fc6): ms of mpn_frcnn_train_step alone and of the whole iteration (two train_add — trunk,
+Per depth (0 = cls + bbox, 1 = + fc7, 2 = + fc6, 3 / 4 / 5 = + conv5_3 / conv5_2 / conv5_1): ms of mpn_frcnn_train_step alone and of the whole iteration (two train_add — trunk,
 projection, ROI pooling each — plus the step), HIP events, median of --steps after --warmup.  Then fc6's fused weight-gradient + SGD
 kernel alone (debug flavour, mpn_debug_bench_train_fc6: back-to-back launches) and its GB/s against the bytes it must move — the packed
-weights and their momentum, each read and written once.  One JSON line per measurement.
+weights and their momentum, each read and written once — and, at depth 3, the conv weight-gradient kernel alone on conv5_3 (512 -> 512 at
+38 x 63, mpn_debug_bench_train_wgrad) against its floor: 2 * 9 * 512 * 512 * 38 * 63 = 11.3 GFLOP at the fp32 MFMA peak of 157.3 TFLOP/s.
+One JSON line per measurement.
 
     python tools/bench_train.py [--steps 20] [--warmup 5]
 """
@@ -48,7 +50,7 @@ def main():
     with _lib.debug_hooks() as lib:
         net = models.FastRCNN(P, max_h=H, max_w=W, max_rois=IMAGES * ROWS)
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        for depth in (0, 1, 2):
+        for depth in (0, 1, 2, 3, 4, 5):
             net.train_begin(depth=depth, momentum=0.9, weight_decay=5e-4)
             step_ms, iter_ms = [], []
             for i in range(a.warmup + a.steps):
@@ -72,6 +74,14 @@ def main():
                 gb = 4 * (k6 * F * 4) / 1e9   # w read + w write + v read + v write (pad lanes of the packing: none at 25088 x 4096)
                 print(json.dumps({"what": "fc6_wgrad_sgd_kernel", "ms": round(ms.value, 4), "gbytes_moved": round(gb, 3),
                                   "gbytes_per_s": round(gb / (ms.value * 1e-3), 1), "floor_ms_at_6.3TBps": round(gb / 6.3e3 * 1e3, 3), "device": name}), flush=True)
+            if depth == 3:
+                ms = C.c_float()
+                _lib.check(lib.mpn_debug_bench_train_wgrad(net._h, 20, C.byref(ms)), "mpn_debug_bench_train_wgrad")
+                gflop = 2 * 9 * 512 * 512 * 38 * 63 / 1e9
+                floor_ms = gflop / 157.3e3 * 1e3
+                print(json.dumps({"what": "conv3x3_wgrad_kernel", "layer": "conv5_3 512->512 38x63, one image", "ms": round(ms.value, 4), "gflop": round(gflop, 2),
+                                  "tflops": round(gflop / ms.value, 1), "floor_ms_at_157.3TF": round(floor_ms, 4), "share_of_floor": round(floor_ms / ms.value, 3),
+                                  "device": name}), flush=True)
             net.train_end()
         net.close()
 
