@@ -1203,14 +1203,20 @@ struct GemmArgs {
   int xp;                        // row pitch of x between K chunks (Mp unless the rows are packed: the last row tile then reads past the
                                  // chunk's rows — into the next chunk or the buffer's slack — and never stores them)
   int bin_rows, out_Mp;          // bin_rows > 0: the scatter above into [NP/8][M / bin_rows][out_Mp][8]
+  unsigned long long *trace;     // tools/gemm_trace.py: stamps of wave 0 of blocks 0..3 (the TRACE instantiation, debug flavour), else nullptr
 };
 
 // C8 GEMM  y[NP/8][Mp][8] = x[K/8][Mp][8] . wpk[K/8][NP][8]: 128 x 128 tile per block, KCH 8-wide K chunks per LDS stage (4 -> 32 k, 32 KiB per
 // stage), two stages in LDS, operands by LDS-DMA.  Software-pipelined by hand (see the scheduling notes in conv3x3_wino_kernel): branch-free stage body,
 // operand fragments double-buffered in registers one K chunk ahead, each chunk's first MFMA issued BEFORE the next
-// chunk's fragment loads (so the lgkmcnt(0) the compiler forces after LDS-DMA only covers loads issued 15 MFMAs
-// earlier), the next stage's DMA spread behind MFMAs 1-4 of the first chunk, and the stage barrier placed before the
-// LAST chunk's MFMAs so the next stage's first fragments are fetched under them.
+// chunk's fragment loads (so the lgkmcnt(0) the compiler forces after LDS-DMA only covers loads issued 12-15 MFMAs
+// earlier), and the stage barrier placed before the LAST chunk's MFMAs so the next stage's first fragments are fetched
+// under them.  ONE LDS / DMA instruction per MFMA shadow (round 8): the four waves of a block leave the stage barrier in
+// lockstep, so four ds_read_b128 in one shadow are 16 reads asked of the LDS pipe at once, and two LDS-DMA issues
+// (~60 cycles of issue each among bare MFMAs) overrun the 64-cycle shadow.  The next chunk's four fragment reads sit
+// behind MFMAs 0-3 of a chunk, the next stage's 2 * KCH DMA issues behind MFMAs 4-11 of the stage's first chunk(s);
+// nothing sits behind MFMAs 12-15, so no LDS item is in flight just ahead of the stage's lgkmcnt(0) / vmcnt(0) / barrier.
+// A fragment slot is written only by reads issued after the last MFMA that takes it (chunk kk - 1's sixteenth).
 // FOLD: the launch folds its accumulator into a running total at K-segment boundaries (row-invariant summation / per-row-scaled segments).
 // A separate instantiation because the total costs 64 more registers (264 > 256: one block per CU instead of two); launches that never
 // fold — split-K pieces, ResNet's pointwise convolutions, the un-scaled mix — keep the two-blocks-per-CU form.
@@ -1219,9 +1225,13 @@ struct GemmArgs {
 // scale.  Mathematically the FOLD form's sum_k s_k P_k with two or three more roundings per element (2^-24 each, far inside the 1e-4 of the
 // path's parity gate), for 64 fewer registers: 196 + 8 instead of 264 — two blocks per CU, and, what matters more on the MultiPathNet path, a
 // mix-GEMM block can share a CU with a block of the other tower lane's fc6 / fc7 (264 registers per lane: 264 + 264 > 512, 204 + 264 fits).
-template <int KCH, bool FOLD, bool RSI = false>
+// TRACE (debug flavour only, tools/gemm_trace.py): s_memtime stamps of wave 0 of blocks 0..3 into a.trace; no production launch carries one.
+template <int KCH, bool FOLD, bool RSI = false, bool TRACE = false>
 __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
   static_assert(!(FOLD && RSI), "row scales are applied either through the running total or in place");
+  static_assert(!TRACE || KCH == 4, "the trace record holds the chunk starts of a 4-chunk stage");
+  unsigned long long tk0 = 0, tk1 = 0, tk2 = 0;
+  if constexpr (TRACE) tk0 = __builtin_amdgcn_s_memtime();
   constexpr int OP_FLOATS = KCH * 128 * 8;
   constexpr int STAGE = 2 * OP_FLOATS;
   constexpr int IT = OP_FLOATS / 256 / 4;
@@ -1243,10 +1253,22 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
   const int st1 = min(a.nstages, st0 + a.stages_per_split);
   const int wm = wave >> 1, wn = wave & 1;
 
-  // DMA item i of this wave = K chunk i of the stage (uniform), 16-byte piece wave*64 + lane of its 128 rows: SADDR form,
-  // no VALU address arithmetic in the loop (see glds16_saddr)
+  // DMA item i of this wave = K chunk i of the stage (uniform), LDS slots wave*64 .. wave*64 + 63 of its 128 rows' 256 16-byte slots: SADDR
+  // form, no VALU address arithmetic in the loop (see glds16_saddr).
+  // Bank swizzle.  A record is [row][8 floats] = two 16-byte halves (k 0-3, k 4-7) and a fragment read is one ds_read_b128 per lane at row
+  // (lane & 31), half (lane >> 5).  ds_read_b128 is serviced in four 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, +32
+  // (MI355X_MICROARCH.md, LDS).  With half 0 always in the even 16-byte slots a group touches 8 of the 16 slots of a 256-byte bank row: a
+  // 2-way conflict on every fragment read (SQ_LDS_BANK_CONFLICT 2.99e7 per fc6 launch, 5.8 % of its cycles).  As in conv3x3_wino_kernel the
+  // halves of rows with bit 3 set are swapped.  The LDS side of an LDS-DMA is lane-linear, so the SOURCE is swizzled: slot p = wave*64 + lane
+  // (row p >> 1, slot p & 1) receives global piece p ^ ((p >> 4) & 1), and a fragment read takes slot half ^ (row bit 3) — the tile rows
+  // wm*64 + mi*32 are multiples of 32, so row bit 3 is lane bit 3.  16-byte slot (mod 16) each lane of a group then reads, half 0 (lanes
+  // 0-31; half 1 is the same with every slot ^ 1):
+  //   group {0-3, 12-15, 20-27}:   rows 0-3 -> 0 2 4 6,  rows 12-15 -> 9 11 13 15,  rows 20-23 -> 8 10 12 14,  rows 24-27 -> 1 3 5 7
+  //   group {4-11, 16-19, 28-31}:  rows 4-7 -> 8 10 12 14,  rows 8-11 -> 1 3 5 7,  rows 16-19 -> 0 2 4 6,  rows 28-31 -> 9 11 13 15
+  // 16 distinct slots per group in all four groups.  Not one instruction is added to the loop: both offsets are computed once per block.
   static_assert(IT == KCH, "one 1-KiB wave-load per wave per K chunk per operand");
-  const unsigned dma_lane = (unsigned)((wave * 64 + lane) * 16);
+  const unsigned dma_piece = (unsigned)(wave * 64 + lane);
+  const unsigned dma_lane = (dma_piece ^ ((dma_piece >> 4) & 1u)) * 16u;
   const size_t a_stage = (size_t)KCH * a.NP * 8, b_stage = (size_t)KCH * a.xp * 8;
   const float *const a_tile = a.wpk + (size_t)n0 * 8, *const b_tile = a.x + (size_t)m0 * 8;
   const unsigned lds0 = lds_byte_addr(lds) + (unsigned)(wave * 256) * 4;
@@ -1290,7 +1312,7 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
       }
     }
   }
-  const int lane_off = l31 * 8 + half * 4;
+  const int lane_off = l31 * 8 + ((half ^ ((l31 >> 3) & 1)) * 4);  // the bank swizzle: see dma_lane
   f32x4 af[2][2], bf[2][2];
   auto load_frags = [&](int s, int kk, int slot) {
     const float *Al = lds + s * STAGE + lane_off, *Bl = Al + OP_FLOATS;
@@ -1298,6 +1320,16 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
     for (int mi = 0; mi < 2; ++mi) af[slot][mi] = *reinterpret_cast<const f32x4 *>(Al + (kk * 128 + wm * 64 + mi * 32) * 8);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) bf[slot][ni] = *reinterpret_cast<const f32x4 *>(Bl + (kk * 128 + wn * 64 + ni * 32) * 8);
+  };
+  auto load_frag_item = [&](int s, int kk, int slot, int i) {  // the same four reads as single-shadow items, in the order the MFMAs first take them
+    const float *Al = lds + s * STAGE + lane_off, *Bl = Al + OP_FLOATS;
+    if (i == 0) af[slot][0] = *reinterpret_cast<const f32x4 *>(Al + (kk * 128 + wm * 64) * 8);
+    else if (i == 1) bf[slot][0] = *reinterpret_cast<const f32x4 *>(Bl + (kk * 128 + wn * 64) * 8);
+    else if (i == 2) bf[slot][1] = *reinterpret_cast<const f32x4 *>(Bl + (kk * 128 + wn * 64 + 32) * 8);
+    else af[slot][1] = *reinterpret_cast<const f32x4 *>(Al + (kk * 128 + wm * 64 + 32) * 8);
+  };
+  auto issue_item = [&](int st, int s, int i) {  // DMA item i of 2 * KCH: chunk i / 2 of the weights (even i) or of the activations (odd i)
+    if (i & 1) issue_b(st, s, i >> 1); else issue_a(st, s, i >> 1);
   };
   if (st0 >= st1) return;  // (never: every split owns at least one stage)
   const int n_more = st1 - 1 - st0;  // stages that prefetch a successor
@@ -1307,19 +1339,31 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
   dma_wait_all();
   __syncthreads();
   load_frags(b0, 0, 0);
+  if constexpr (TRACE) tk1 = __builtin_amdgcn_s_memtime();
 
   static_assert(KCH % 2 == 0, "fragment slot parity assumes an even chunk count per stage");
+  static_assert(2 * KCH <= 8 * (KCH - 2), "the DMA issues must end before the chunk ahead of the stage barrier");
+  unsigned long long tc[4] = {0, 0, 0, 0}, tr1 = 0, tr2 = 0;  // (TRACE) chunk starts of the stage, before / after the lgkmcnt(0)
   auto body = [&](int st, auto more_tag, auto parity_tag) {  // buffer parity is a compile-time tag: LDS offsets become immediates
     constexpr bool MORE = decltype(more_tag)::value;
     constexpr int s = decltype(parity_tag)::value;
 #pragma unroll
     for (int kk = 0; kk < KCH; ++kk) {
       const int cur = kk & 1;
+      if constexpr (TRACE && MORE) tc[kk] = __builtin_amdgcn_s_memtime();
       if (kk == KCH - 1 && MORE) {
+        if constexpr (TRACE) tr1 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's last reads of stage s are done
+        if constexpr (TRACE) tr2 = __builtin_amdgcn_s_memtime();
         dma_wait_all();                      // and the next stage it issued has landed
         __syncthreads();
-        load_frags(s ^ 1, 0, 0);
+        if constexpr (TRACE) {  // [stage start, chunk 1 / 2 / 3 start, before lgkmcnt(0), after it, after vmcnt(0) + barrier] of the first 64 stages
+          const unsigned long long tr3 = __builtin_amdgcn_s_memtime();
+          if (a.trace && blockIdx.x < 4 && blockIdx.y == 0 && tid == 0 && st - st0 < 64) {
+            unsigned long long *o = a.trace + ((size_t)blockIdx.x * 64 + (st - st0)) * 8;
+            o[0] = tc[0]; o[1] = tc[1] - tc[0]; o[2] = tc[2] - tc[0]; o[3] = tc[3] - tc[0]; o[4] = tr1 - tc[0]; o[5] = tr2 - tr1; o[6] = tr3 - tr2;
+          }
+        }
       }
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
@@ -1327,9 +1371,14 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cur][mi][j], bf[cur][ni][j], acc[mi][ni], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (t == 0 && kk + 1 < KCH) load_frags(s, kk + 1, cur ^ 1);
+        // side work, one LDS / DMA instruction per shadow: the next chunk's fragments (after the barrier: the next stage's first) behind
+        // MFMAs 0-3, the next stage's DMA behind MFMAs 4-11 of the first chunk(s)
+        if (t < 4) {
+          if (kk + 1 < KCH) load_frag_item(s, kk + 1, cur ^ 1, t);
+          else if (MORE) load_frag_item(s ^ 1, 0, 0, t);
+        }
         if constexpr (MORE) {
-          if (kk == 0 && t >= 1 && t <= IT) { issue_a(st + 1, s ^ 1, t - 1); issue_b(st + 1, s ^ 1, t - 1); }
+          if (t >= 4 && t < 12 && kk * 8 + (t - 4) < 2 * KCH) issue_item(st + 1, s ^ 1, kk * 8 + (t - 4));
         }
       }
     }
@@ -1391,6 +1440,7 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
     if (st + 2 == next_fold) { fold(); advance(); }
   }
   body(st1 - 1, std::false_type{}, P0{});
+  if constexpr (TRACE) tk2 = __builtin_amdgcn_s_memtime();
   if constexpr (RSI) {  // the last segment's scale
     if (a.rs0) {
 #pragma unroll
@@ -1452,6 +1502,12 @@ __global__ __launch_bounds__(256) void gemm_c8_pf_kernel(GemmArgs a) {
         if (m < a.M) *reinterpret_cast<f32x4 *>(yb + ((size_t)nb8 * cb_rows + row_off[ni]) * 8 + half * 4) = v;
       }
     }
+  if constexpr (TRACE) {  // [prologue, K loop, epilogue issue, stages] of the block
+    if (a.trace && blockIdx.x < 4 && blockIdx.y == 0 && tid == 0) {
+      unsigned long long *o = a.trace + 4 * 64 * 8 + blockIdx.x * 4;
+      o[0] = tk1 - tk0; o[1] = tk2 - tk1; o[2] = __builtin_amdgcn_s_memtime() - tk2; o[3] = (unsigned long long)(st1 - st0);
+    }
+  }
 }
 
 // sums the split-K slabs in split order (deterministic), adds bias, ReLU; writes C8 and/or row-major
@@ -1492,6 +1548,7 @@ MPN_KNOB(int, g_gemm_kch, 0);       // test/bench hook: force 4 or 8 K chunks pe
 MPN_KNOB(int, g_gemm_split, 0);  // test/bench hook: force a split-K factor
 
 MPN_KNOB(int, g_split3_ranges, 0);  // mpn_debug_set_split3_ranges: forced number of K ranges of linear_c8_split3 (0 = its own rule)
+MPN_KNOB(unsigned long long *, g_gemm_trace, nullptr);  // mpn_debug_set_gemm_trace (tools/gemm_trace.py): 4 * 64 * 8 + 16 stamps
 MPN_KNOB(int, g_gemm_rsi, 1);  // mpn_debug_set_gemm_rsi: 0 = per-row-scaled K segments through the running total (the FOLD kernel, rounds 3-5)
 static thread_local ScratchSlot t_gemm_splitk_slot = SCR_GEMM_SPLITK;
 SplitkSlotScope::SplitkSlotScope(ScratchSlot slot) : prev(t_gemm_splitk_slot) { t_gemm_splitk_slot = slot; }
@@ -1525,6 +1582,7 @@ static int linear_c8_impl(const float *d_x_c8, int M, int K, const float *d_wpk,
   a.x = d_x_c8; a.Mp = Mp_override ? Mp_override : lin_mp(M); a.wpk = d_wpk; a.NP = lin_np(N); a.bpk = d_bpk;
   a.M = M; a.relu = relu;
   a.xp = a.Mp;
+  a.trace = g_gemm_trace;
   if (rs && rs->bin_rows > 0) {  // packed (bin, roi) rows scattered into the consumer's [cout block][bin][out_Mp][8] operand
     MPN_CHECK_ARG(rs->bin_rows % 4 == 0 && M % rs->bin_rows == 0 && rs->out_Mp >= rs->bin_rows && rs->x_pitch >= M);
     a.xp = rs->x_pitch; a.bin_rows = rs->bin_rows; a.out_Mp = rs->out_Mp;
@@ -1601,7 +1659,15 @@ static int linear_c8_impl(const float *d_x_c8, int M, int K, const float *d_wpk,
       int rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(gemm_c8_pf_kernel<4, false, true>), 2 * 2 * 4 * 128 * 8 * 4);
       if (rc_attr) return rc_attr;
       hipLaunchKernelGGL((gemm_c8_pf_kernel<4, false, true>), grid, dim3(256), (size_t)2 * 2 * 4 * 128 * 8 * 4, s, a);
-    } else if (folds) hipLaunchKernelGGL((gemm_c8_pf_kernel<4, true>), grid, dim3(256), (size_t)2 * 2 * 4 * 128 * 8 * 4, s, a);
+    }
+#ifdef MPN_DEBUG_HOOKS
+    else if (folds && a.trace) {  // the stamped copy of fc6 / fc7's form
+      int rc_attr = set_max_dyn_lds(reinterpret_cast<const void *>(gemm_c8_pf_kernel<4, true, false, true>), 2 * 2 * 4 * 128 * 8 * 4);
+      if (rc_attr) return rc_attr;
+      hipLaunchKernelGGL((gemm_c8_pf_kernel<4, true, false, true>), grid, dim3(256), (size_t)2 * 2 * 4 * 128 * 8 * 4, s, a);
+    }
+#endif
+    else if (folds) hipLaunchKernelGGL((gemm_c8_pf_kernel<4, true>), grid, dim3(256), (size_t)2 * 2 * 4 * 128 * 8 * 4, s, a);
     else hipLaunchKernelGGL((gemm_c8_pf_kernel<4, false>), grid, dim3(256), (size_t)2 * 2 * 4 * 128 * 8 * 4, s, a);
   }
   MPN_CHECK_LAUNCH();
@@ -2715,6 +2781,7 @@ extern "C" void mpn_debug_set_wino_tc(int v) { g_wino_tc = v; }
 extern "C" void mpn_debug_set_conv_split(int v) { g_conv_split = v; }
 extern "C" void mpn_debug_set_gemm_split(int v) { g_gemm_split = v; }
 extern "C" void mpn_debug_set_gemm_rsi(int v) { g_gemm_rsi = v; }
+extern "C" void mpn_debug_set_gemm_trace(void *p) { g_gemm_trace = static_cast<unsigned long long *>(p); }
 extern "C" void mpn_debug_set_split3_ranges(int v) { g_split3_ranges = v; }
 extern "C" void mpn_debug_set_gemm_kch(int v) { g_gemm_kch = (v == 4 || v == 8) ? v : 0; }
 extern "C" void mpn_debug_set_gemm_ablate(int v) { g_gemm_ablate = v; }
@@ -2813,8 +2880,9 @@ extern "C" int mpn_debug_bench_roipool(const float *h_rois, int N, int C, int H,
   return rc;
 }
 
-extern "C" int mpn_debug_bench_linear(int M, int K, int N, int iters, float *ms_out) {
-  MPN_CHECK_ARG(M > 0 && K > 0 && N > 0 && iters > 0 && ms_out);
+// row_invariant as linear_c8 takes it: 1 is how the pipelines run fc6 / fc7 (the folding launch; tools/gemm_trace.py)
+static int bench_linear(int M, int K, int N, int row_invariant, int iters, float *ms_out) {
+  MPN_CHECK_ARG(M > 0 && K > 0 && N > 0 && iters > 0 && ms_out && row_invariant >= 0 && row_invariant <= 2);
   const int K32 = round_up(K, 64);
   size_t xe = mat_c8_elems(M, K32), we = lin_wpk_elems(K32, N), ye = (size_t)(lin_np(N) / 8) * lin_mp(M) * 8;
   float *x = nullptr, *w = nullptr, *b = nullptr, *y = nullptr;
@@ -2832,10 +2900,10 @@ extern "C" int mpn_debug_bench_linear(int M, int K, int N, int iters, float *ms_
   hipEvent_t e0, e1;
   MPN_CHECK_HIP(hipEventCreate(&e0)); MPN_CHECK_HIP(hipEventCreate(&e1));
   int rc = MPN_OK;
-  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = linear_c8(x, M, K, w, b, N, 1, y, nullptr, nullptr);
+  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = linear_c8(x, M, K, w, b, N, 1, y, nullptr, nullptr, 0, nullptr, row_invariant);
   MPN_CHECK_HIP(hipDeviceSynchronize());
   MPN_CHECK_HIP(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = linear_c8(x, M, K, w, b, N, 1, y, nullptr, nullptr);
+  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = linear_c8(x, M, K, w, b, N, 1, y, nullptr, nullptr, 0, nullptr, row_invariant);
   MPN_CHECK_HIP(hipEventRecord(e1, nullptr));
   MPN_CHECK_HIP(hipEventSynchronize(e1));
   float ms = 0.f;
@@ -2844,6 +2912,10 @@ extern "C" int mpn_debug_bench_linear(int M, int K, int N, int iters, float *ms_
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   (void)hipFree(x); (void)hipFree(w); (void)hipFree(b); (void)hipFree(y);
   return rc;
+}
+extern "C" int mpn_debug_bench_linear(int M, int K, int N, int iters, float *ms_out) { return bench_linear(M, K, N, 0, iters, ms_out); }
+extern "C" int mpn_debug_bench_linear_ri(int M, int K, int N, int row_invariant, int iters, float *ms_out) {
+  return bench_linear(M, K, N, row_invariant, iters, ms_out);
 }
 
 // test hook: direct vs range-max-table ROI pooling of the same NCHW map; returns the number of output words that differ
