@@ -289,7 +289,7 @@ __global__ void roi_pool_c8i_kernel(const float *__restrict__ feat, int Cb, int 
 
 // the same pooling with the bin arithmetic done once per (roi, bin): a thread owns one output row for CBG channel blocks, reads
 // whole 32-byte records and a wave stores 64 consecutive records (the kernel above spends most of its instructions on the
-// per-thread bin arithmetic for 16 output bytes).  Same cells, same comparisons: bit-identical.
+// per-thread bin arithmetic for 16 output bytes).  Same cells, same comparisons, same order: bit-identical to it.
 template <int CBG>
 __global__ __launch_bounds__(256) void roi_pool_c8i_rows_kernel(const float *__restrict__ feat, int H, int W, size_t pitch_f, const float *__restrict__ rois,
                                                                  int roi_stride, int N, int PH, int PW, float scale, float *__restrict__ out, size_t pitch_o,
@@ -2015,18 +2015,28 @@ __global__ void roi_pool_c8i_bf16_kernel(const bf16_t *__restrict__ feat, int Cb
 // ---- ROI max-pooling, bf16, fast path ---------------------------------------------------------------------------------------
 // The kernel above spends ~200 instructions per 8 output bytes (per-thread bin arithmetic, 4 channels per thread).  Here the
 // feature map is first re-coded so that bf16 order is int16 order (negative values: magnitude bits flipped — a monotone,
-// self-inverse map, so max commutes with it and the result is bit-identical), and a thread owns one (roi, bin) for a run of
+// self-inverse map, so max commutes with it), and a thread owns one (roi, bin) for a run of
 // channel blocks: the bin arithmetic is done once, each pixel record (8 channels) costs one 16-byte load + 4 v_pk_max_i16, and a
-// wave's stores are 64 consecutive records.
+// wave's stores are 64 consecutive records.  Against roi_pool_c8i_bf16_kernel's `f > m` the result is the same VALUE everywhere and the same
+// bits except the sign of a zero: a window whose maximum is zero and that holds both zeros gives +0 here (code 0 > code -1) and the zero met
+// first there.  NaNs: the encoder below gives a NaN of either sign -inf's code, so — as `f > m` from -inf does — the maxima ignore the NaNs of
+// a window and a window of NaNs alone gives -inf (include/mpn.h); the raw order would have put +NaN above +inf.
 typedef short i16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned bf16x2_sortable(unsigned x) { return x ^ (((x >> 15) & 0x00010001u) * 0x7fffu); }
+
+__device__ __forceinline__ unsigned bf16x2_sortable_enc(unsigned x) {  // bf16x2_sortable, NaN -> the code of -inf (0x807f)
+  unsigned c = bf16x2_sortable(x);
+  if ((x & 0x00007fffu) > 0x00007f80u) c = (c & 0xffff0000u) | 0x0000807fu;
+  if ((x & 0x7fff0000u) > 0x7f800000u) c = (c & 0x0000ffffu) | 0x807f0000u;
+  return c;
+}
 
 __global__ void bf16_sortable_kernel(const u32x4 *__restrict__ in, size_t n, u32x4 *__restrict__ out) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   u32x4 v = in[t];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = bf16x2_sortable(v[e]);
+  for (int e = 0; e < 4; ++e) v[e] = bf16x2_sortable_enc(v[e]);
   out[t] = v;
 }
 
@@ -2660,6 +2670,21 @@ static int g_dbg_conv_form = 0;
 #define RN_FORM(v) (g_dbg_conv_form = (v))
 #else
 #define RN_FORM(v) ((void)0)
+#endif
+// Which pooling / LRN launch ran (mpn_debug_graph_op, mpn_debug_head_pool: tests/test_gpu_graph_pool_numerics.py asserts it per case).  An
+// id's high nibble is its stage, so one head forward records the ROI pooling, the fused max-pool and the closing average side by side.
+enum PoolKernel : int {
+  PK_MAX_F32 = 1, PK_MAX_BF16 = 2, PK_AVG_F32 = 3, PK_AVG_BF16 = 4, PK_AVG_BF16_SMALL = 5, PK_LRN = 6,  // graph_run's pool / LRN block
+  PK_ROI_F32 = 16, PK_ROI_ROWS4 = 17, PK_ROI_BF16 = 18, PK_ROI_SORTED = 19, PK_ROI_PM = 20,             // resnet_head_forward: ROI pooling
+  PK_ROI_SORTED_EXP = 21,                                                                               //   (debug flavour: the sorted kernel's mpn_debug_set_pool_exp variants)
+  PK_ROIMAX_SORTED = 32, PK_ROIMAX_SORTED_TABLES = 33,                                                  //   the fused max-pool (with range-max tables)
+  PK_GAVG_F32 = 48, PK_GAVG_BF16 = 49, PK_GAVG_BF16_LDS = 50,                                           //   the closing average
+};
+#ifdef MPN_DEBUG_HOOKS
+static int g_dbg_pool_kernel[4] = {0, 0, 0, 0};
+#define RN_POOL(v) (g_dbg_pool_kernel[(v) >> 4] = (v))
+#else
+#define RN_POOL(v) ((void)0)
 #endif
 MPN_KNOB(int, g_roi_invariant, 1);  // mpn_debug_set_roi_invariant: 0 = per-ROI layers pick kernel / split by batch size as round 3 did (tests, timing)
 // the fields GConvArgs and GConvArgsB share, from the layer and its input; *o = the output batch
@@ -3329,6 +3354,11 @@ static int graph_parse(ResNetGraph *g, int n_ops, const mpn_graph_op *ops_in, in
   return MPN_OK;
 }
 
+// a head op that max-pools the ROI-pooled input itself (all of tensor 0's channels, square, floor mode): GOp::from_rois.  (A macro, shared with
+// mpn_debug_head_pool: the expression expands in place, so graph_build compiles to the code it had.)
+#define MPN_GOP_POOLS_ROIS(op, c0) \
+  ((op).kind == 1 && (op).src == 0 && (op).src_c_off == 0 && (op).cin == (c0) && (op).kh == (op).kw && (op).sh == (op).sw && (op).ph == (op).pw && !(op).ceil_mode)
+
 int graph_build(const mpn_graph_weights *gw, int max_h, int max_w, int max_rois, int pooled, ResNetGraph **out) {
   MPN_CHECK_ARG(gw && out && gw->feat_tensor > 0 && gw->feat_tensor < gw->n_trunk_tensors && gw->out_tensor > 0 && gw->out_tensor < gw->n_head_tensors);
   const int n_heads = gw->n_heads > 1 ? gw->n_heads : 1;
@@ -3349,7 +3379,7 @@ int graph_build(const mpn_graph_weights *gw, int max_h, int max_w, int max_rois,
         }
     if (rc == MPN_OK)
       for (GOp &op : g->g_heads[t])
-        if (op.kind == 1 && op.src == 0 && op.src_c_off == 0 && op.cin == g->t_head[0].C && op.kh == op.kw && op.sh == op.sw && op.ph == op.pw && !op.ceil_mode)
+        if (MPN_GOP_POOLS_ROIS(op, g->t_head[0].C))
           op.from_rois = true;
   }
   if (rc == MPN_OK && (g->t_trunk[0].C != 3 || g->t_head[0].C != g->t_trunk[g->feat_tensor].C)) {
@@ -3519,28 +3549,36 @@ static int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GT
       const dim3 grid((unsigned)cdiv_sz(total, 256)), grid16((unsigned)cdiv_sz(total / 2, 256));  // fp32: half records, bf16: whole records per thread
       if (op.kind == 3) {
         const size_t rows = (size_t)B * src.H * src.W;
+        RN_POOL(PK_LRN);
         hipLaunchKernelGGL(lrn_c8i_kernel, dim3((unsigned)cdiv_sz(rows * in.Cb(), 256)), dim3(256), 0, s, src.buf, in.Cb(), src.C, rows, in.pitch(), op.kh,
                            op.lrn_alpha, op.lrn_beta, op.lrn_k, od.pitch(), reinterpret_cast<float *>(outp));
       } else if (op.kind == 1) {
         MPN_CHECK_ARG(op.kh == op.kw && op.sh == op.sw && op.ph == op.pw);
-        if (g->bf16)
+        if (g->bf16) {
+          RN_POOL(PK_MAX_BF16);
           hipLaunchKernelGGL(maxpool2d_c8i_bf16_kernel, grid16, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(src.buf), in.Cb(), B, src.H, src.W, in.pitch(),
                              op.kh, op.sh, op.ph, dst.H, dst.W, od.pitch(), reinterpret_cast<bf16_t *>(outp));
-        else
+        } else {
+          RN_POOL(PK_MAX_F32);
           hipLaunchKernelGGL(maxpool2d_c8i_kernel, grid, dim3(256), 0, s, src.buf, in.Cb(), B, src.H, src.W, in.pitch(), op.kh, op.sh, op.ph, dst.H, dst.W,
                              od.pitch(), reinterpret_cast<float *>(outp));
+        }
       } else {
         if (g->bf16 && op.sh == 1 && op.sw == 1 && dst.H == src.H && dst.W == src.W && src.H * src.W <= 256) {
           const int mpb = 256 / (src.H * src.W);
+          RN_POOL(PK_AVG_BF16_SMALL);
           hipLaunchKernelGGL(avgpool2d_c8i_bf16_small_kernel, dim3((unsigned)((B + mpb - 1) / mpb), (unsigned)in.Cb()), dim3(256), 0, s,
                              reinterpret_cast<const bf16_t *>(src.buf), B, src.H, src.W, in.pitch(), op.kh, op.kw, op.ph, op.pw, od.pitch(),
                              reinterpret_cast<bf16_t *>(outp), op.pool_bias, op.relu);
-        } else if (g->bf16)
+        } else if (g->bf16) {
+          RN_POOL(PK_AVG_BF16);
           hipLaunchKernelGGL(avgpool2d_c8i_bf16_kernel, grid16, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(src.buf), in.Cb(), B, src.H, src.W,
                              in.pitch(), op.kh, op.kw, op.sh, op.sw, op.ph, op.pw, dst.H, dst.W, od.pitch(), reinterpret_cast<bf16_t *>(outp), op.pool_bias, op.relu);
-        else
+        } else {
+          RN_POOL(PK_AVG_F32);
           hipLaunchKernelGGL((avgpool2d_c8i_kernel<float>), grid, dim3(256), 0, s, src.buf, in.Cb(), B, src.H, src.W, in.pitch(), op.kh, op.kw, op.sh, op.sw,
                              op.ph, op.pw, dst.H, dst.W, od.pitch(), reinterpret_cast<float *>(outp), op.pool_bias, op.relu);
+        }
       }
       MPN_CHECK_LAUNCH();
     }
@@ -3671,6 +3709,7 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
 #ifdef MPN_DEBUG_HOOKS
       if (g_tower_knock & 1) {}
       else if ((g_pool_exp & 3) && Cb % 8 == 0) {  // mpn_debug_set_pool_exp (timing experiments): 1 = 8 channel blocks per thread / ordinary stores, 2 = 4 blocks / ordinary stores (rounds 3-5), 3 = 8 blocks / non-temporal
+        RN_POOL(PK_ROI_SORTED_EXP);
         const dim3 g8((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 8)), g4((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4));
 #define MPN_POOL_ARGS reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale, reinterpret_cast<u32x4 *>(pool_dst), pa.pitch(), g->roi_bins
         if ((g_pool_exp & 3) == 1) hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<8, false>), g8, dim3(256), 0, s, MPN_POOL_ARGS);
@@ -3681,9 +3720,12 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
 #endif
       // non-temporal stores: the 0.4-0.9 GB pooled tensor streams past the L2 instead of evicting the sorted map the launch gathers from
       // (measured, profiles/r06_pool_exp.txt: configs[4] 24.28 -> 24.10 ms, configs[3] bf16 11.06 -> 10.99; 8 channel blocks per thread: slower)
-      hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<4, true>), dim3((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4)), dim3(256), 0, s,
-                         reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale,
-                         reinterpret_cast<u32x4 *>(pool_dst), pa.pitch(), g->roi_bins);
+      {
+        RN_POOL(PK_ROI_SORTED);
+        hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<4, true>), dim3((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4)), dim3(256), 0, s,
+                           reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale,
+                           reinterpret_cast<u32x4 *>(pool_dst), pa.pitch(), g->roi_bins);
+      }
       if (fuse_mp)
         for (const GOp &op : g->g_heads[head]) {
           if (!op.from_rois) continue;
@@ -3691,15 +3733,18 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
           const GTensor &dst = t_head[op.dst];
           const ActI od{dst.buf, N, dst.C, dst.H, dst.W};
           char *outp = reinterpret_cast<char *>(dst.buf) + (size_t)(op.dst_c_off / 8) * od.pitch() * 8 * sizeof(bf16_t);  // plane offset = the concat
+          RN_POOL(want_levels > 0 ? PK_ROIMAX_SORTED_TABLES : PK_ROIMAX_SORTED);
           hipLaunchKernelGGL(roi_maxpool_c8i_bf16_sorted_kernel<4>, dim3((unsigned)cdiv_sz((size_t)N * dst.H * dst.W, 256), (unsigned)(Cb / 4)), dim3(256), 0, s,
                              reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale,
                              op.kh, op.sh, op.ph, dst.H, dst.W, reinterpret_cast<u32x4 *>(outp), od.pitch(),
                              want_levels > 0 ? reinterpret_cast<const u32x4 *>(g->feat_vmax) : nullptr, g->feat_vmax_elems / 8, want_levels);
         }
-    } else if (g->bf16)
+    } else if (g->bf16) {
+      RN_POOL(PK_ROI_BF16);
       hipLaunchKernelGGL(roi_pool_c8i_bf16_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, reinterpret_cast<const bf16_t *>(g->feat), Cb, g->feat_h,
                          g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale, reinterpret_cast<bf16_t *>(pool_dst), pa.pitch(), g->roi_bins);
-    else if (fc_gemm && (g_graph_fuse & 256)) {
+    } else if (fc_gemm && (g_graph_fuse & 256)) {
+      RN_POOL(PK_ROI_PM);
       // the fully-connected operand is the VGG pipeline's (bin, roi)-row matrix: its pooling kernel too (a wave = one (roi, bin) over 256
       // channels of a pixel-major copy of the map, four ROIs per block leaving as whole 128-byte lines) — 37 -> 12 us on AlexNet
       void *pm = nullptr;
@@ -3710,12 +3755,15 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
       const Act fdim{nullptr, g->feat_c, g->feat_h, g->feat_w, 0, 0};
       int rcp = roi_pool_pm(fdim, static_cast<const float *>(pm), d_rois, N, PH, PH, spatial_scale, RoiRule{1.0f, 0, g->roi_bins}, g->fc_x, s, roi_stride, round_up(N, 128));
       if (rcp) return rcp;
-    } else if ((g_bf16_fast_pool & 1) && Cb % 4 == 0)
+    } else if ((g_bf16_fast_pool & 1) && Cb % 4 == 0) {
+      RN_POOL(PK_ROI_ROWS4);
       hipLaunchKernelGGL(roi_pool_c8i_rows_kernel<4>, dim3((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4)), dim3(256), 0, s, g->feat, g->feat_h,
                          g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale, fc_gemm ? g->fc_x : pool_dst, pa.pitch(), fc_gemm ? round_up(N, 128) : 0, g->roi_bins);
-    else
+    } else {
+      RN_POOL(PK_ROI_F32);
       hipLaunchKernelGGL(roi_pool_c8i_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, g->feat, Cb, g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride,
                          N, PH, PH, spatial_scale, pool_dst, pa.pitch(), g->roi_bins);
+    }
     MPN_CHECK_LAUNCH();
   }
   ActI cur{pool_dst, N, g->feat_c, PH, PH}, y;
@@ -3737,15 +3785,19 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
     cur = y;
   }
   const size_t total = (size_t)N * cur.Cb() * 2;
-  if (g->bf16 && (g_bf16_fast_pool & 2) && (size_t)16 * cur.H * cur.W * 9 * sizeof(float) <= 64 * 1024)
+  if (g->bf16 && (g_bf16_fast_pool & 2) && (size_t)16 * cur.H * cur.W * 9 * sizeof(float) <= 64 * 1024) {
+    RN_POOL(PK_GAVG_BF16_LDS);
     hipLaunchKernelGGL(avgpool_c8i_bf16_to_c8_lds_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)cur.Cb()), dim3(256), (size_t)16 * cur.H * cur.W * 9 * sizeof(float), s,
                        reinterpret_cast<const bf16_t *>(cur.p), N, cur.H * cur.W, cur.pitch(), 1.0f / (float)(cur.H * cur.W), d_feat_c8, Mp);
-  else if (g->bf16)
+  } else if (g->bf16) {
+    RN_POOL(PK_GAVG_BF16);
     hipLaunchKernelGGL(avgpool_c8i_bf16_to_c8_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, reinterpret_cast<const bf16_t *>(cur.p), N, cur.Cb(),
                        cur.H * cur.W, cur.pitch(), 1.0f / (float)(cur.H * cur.W), d_feat_c8, Mp);
-  else
+  } else {
+    RN_POOL(PK_GAVG_F32);
     hipLaunchKernelGGL(avgpool_c8i_to_c8_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, cur.p, N, cur.Cb(), cur.H * cur.W, cur.pitch(),
                        1.0f / (float)(cur.H * cur.W), d_feat_c8, Mp);
+  }
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
@@ -3834,14 +3886,14 @@ extern "C" int mpn_debug_bench_conv_bf16(int Cin, int Cout, int KH, int KW, int 
 // (optional, raw_cap bytes): the last run's whole output buffer, raw_bytes (optional) its size.  form_out: mpn_debug_conv_last_form().
 namespace mpn {
 __global__ void dbg_nchw_to_c8i_kernel(const float *__restrict__ x, int B, int C, int H, int W, size_t pitch, size_t total, float pad_fill, int bf16,
-                                       void *__restrict__ out) {
+                                       void *__restrict__ out, int one_sign = 0) {  // one_sign: the pad pattern is pad_fill * (1 .. 5)
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
   const int j = (int)(t & 7);
   const size_t r = (t >> 3) % pitch;
   const int c = (int)((t >> 3) / pitch) * 8 + j;
   const size_t HW = (size_t)H * W;
-  float v = pad_fill * (float)(1 + (int)(t % 5)) * ((t & 8) ? -1.0f : 1.0f);
+  float v = pad_fill * (float)(1 + (int)(t % 5)) * ((t & 8) && !one_sign ? -1.0f : 1.0f);
   if (c < C && r < (size_t)B * HW) v = x[((r / HW) * C + c) * HW + r % HW];
   if (bf16) static_cast<bf16_t *>(out)[t] = f2bf(v);
   else static_cast<float *>(out)[t] = v;
@@ -3938,6 +3990,153 @@ extern "C" int mpn_debug_conv_form(const float *d_x, int Cin, int H, int W, cons
   if (in) (void)hipFree(in);
   if (out) (void)hipFree(out);
   if (res) (void)hipFree(res);
+  resnet_free(g);
+  return rc;
+}
+
+// Test hooks (tests/test_gpu_graph_pool_numerics.py): the pooling, LRN and ROI-pooling launches of the graph executor, one at a time, through
+// the dispatch code the product runs (graph_parse / graph_dims / graph_run, resnet_head_forward) on a scratch graph.
+//
+// mpn_debug_graph_op: ONE op of kind 1 (max-pool), 2 (average pool; op->b = the commuted pool's bias, with op->relu) or 3 (LRN) on the NCHW fp32
+// device tensor x [B, C, H, W]; the op reads channels [op->src_c_off, + op->cin) of it (op->src / dst / dst_c_off / w / cout are ignored).  The
+// source is laid out as C8I (bf16: rounded RNE) with the finite one-signed pattern pad_fill * (1 .. 5) in the pad lanes of a ragged last channel block,
+// in its pad planes and in the rows from B*H*W up to the pitch; the destination is an out_c-channel tensor written at out_c_off whose every
+// element first holds the sentinel NaN 0x7fa5a5a5 (bf16: 0x7fa5).  y [B, op->cin, OH, OW] fp32 (y_cap elements), oh / ow the output size,
+// raw (optional, raw_cap bytes) the whole output buffer [round_up(out_c, 128) / 8][pitch][8], kernel_out the PoolKernel id that ran.
+extern "C" int mpn_debug_graph_op(const float *d_x, int B, int C, int H, int W, const mpn_graph_op *op_in, int bf16, int out_c, int out_c_off, float pad_fill,
+                                  float *d_y, size_t y_cap, int *oh_out, int *ow_out, void *d_raw, size_t raw_cap, size_t *raw_bytes, int *kernel_out) {
+  using namespace mpn;
+  MPN_CHECK_ARG(d_x && d_y && op_in && B > 0 && C > 0 && H > 0 && W > 0 && out_c > 0 && out_c_off >= 0 && std::isfinite(pad_fill));
+  MPN_CHECK_ARG(op_in->kind >= 1 && op_in->kind <= 3);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  ResNetGraph *g = new ResNetGraph();
+  g->is_graph = true; g->bf16 = bf16 != 0;
+  const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
+  mpn_graph_op o = *op_in;
+  o.src = 0; o.dst = 1; o.dst_c_off = out_c_off; o.w = nullptr; o.cout = 0;
+  const int tc[2] = {C, out_c};
+  std::vector<GOp> ops;
+  int rc = graph_parse(g, 1, &o, 2, tc, ops, g->t_head, true);
+  if (rc == MPN_OK) rc = graph_dims(ops, g->t_head, H, W);
+  size_t oe = 0, pitch_o = 0;
+  int OH = 0, OW = 0;
+  if (rc == MPN_OK) {
+    GTensor &ti = g->t_head[0], &to = g->t_head[1];
+    OH = to.H; OW = to.W;
+    const ActI ai{nullptr, B, C, H, W}, ao{nullptr, B, out_c, OH, OW};
+    const size_t ie = c8i_elems(B, C, H, W);
+    pitch_o = ao.pitch(); oe = c8i_elems(B, out_c, OH, OW);
+    if ((size_t)B * o.cin * OH * OW > y_cap) { set_error("mpn_debug_graph_op: y needs %zu elements", (size_t)B * o.cin * OH * OW); rc = MPN_EINVAL; }
+    if (rc == MPN_OK) rc = rn_alloc(g, &ti.buf, ie * esz);
+    if (rc == MPN_OK) rc = rn_alloc(g, &to.buf, oe * esz);
+    if (rc == MPN_OK) {
+      hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(ie, 256)), dim3(256), 0, nullptr, d_x, B, C, H, W, ai.pitch(), ie, pad_fill, bf16, ti.buf, 1);
+      if (g->bf16) hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe / 2, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(to.buf), oe / 2, 0x7fa57fa5u);
+      else hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(to.buf), oe, 0x7fa5a5a5u);
+      if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
+    }
+  }
+  g_dbg_pool_kernel[0] = 0;
+  if (rc == MPN_OK) rc = graph_run(g, ops, g->t_head, B, nullptr);
+  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
+  if (rc == MPN_OK) {
+    const size_t total = (size_t)B * o.cin * OH * OW;
+    hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, g->t_head[1].buf, B, o.cin, OH, OW, pitch_o, out_c_off / 8, bf16, d_y);
+    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
+  }
+  if (rc == MPN_OK) {
+    if (oh_out) *oh_out = OH;
+    if (ow_out) *ow_out = OW;
+    if (raw_bytes) *raw_bytes = oe * esz;
+    if (kernel_out) *kernel_out = g_dbg_pool_kernel[0];
+    if (d_raw && raw_cap < oe * esz) { set_error("mpn_debug_graph_op: raw needs %zu bytes", oe * esz); rc = MPN_EINVAL; }
+    else if (d_raw && hipMemcpy(d_raw, g->t_head[1].buf, oe * esz, hipMemcpyDeviceToDevice) != hipSuccess) rc = MPN_EHIP;
+  }
+  if (hipDeviceSynchronize() != hipSuccess && rc == MPN_OK) rc = MPN_EHIP;
+  resnet_free(g);
+  return rc;
+}
+// mpn_debug_head_pool: resnet_head_forward on a scratch graph head without convolutions — the ROI pooling of the one-map NCHW fp32 feature
+// [C, H, W] (laid out as above, pad_fill in its pad lanes / planes / rows) for the table d_rois [N][roi_stride] into head tensor 0, optionally ONE
+// max-pool op of it (op_in: kind 1 reading all C channels of tensor 0 into tensor 1; from_rois by graph_build's rule, so the fused kernel takes it
+// where resnet_head_forward fuses), and the closing average of tensor 0 into the C8 matrix d_c8 [Cb][Mp][8] (pre-filled with the sentinel).
+// Every head tensor first holds the sentinel.  d_pooled [N, C, pooled, pooled], d_mp [N, C, OH, OW] (with op_in; mp_cap elements) fp32;
+// kernels_out[4] = the PoolKernel ids of {graph_run's op, ROI pooling, fused max-pool, closing average} (0 = none ran), levels_out = the range-max
+// levels built.  The fully-connected route (roi_pool_pm) needs an fc_w op and is not reachable from here.
+extern "C" int mpn_debug_head_pool(const float *d_feat, int C, int H, int W, const float *d_rois, int roi_stride, int N, int pooled, float spatial_scale,
+                                   int roi_bins, int bf16, const mpn_graph_op *op_in, float pad_fill, int Mp, float *d_pooled, float *d_mp, size_t mp_cap,
+                                   int *oh_out, int *ow_out, float *d_c8, int *kernels_out, int *levels_out) {
+  using namespace mpn;
+  MPN_CHECK_ARG(d_feat && d_rois && d_pooled && d_c8 && C > 0 && H > 0 && W > 0 && N > 0 && pooled > 0 && Mp >= N && roi_stride >= 5);
+  MPN_CHECK_ARG((roi_bins == MPN_ROI_BINS_CAFFE || roi_bins == MPN_ROI_BINS_ADAPTIVE) && std::isfinite(pad_fill) && (!op_in || (op_in->kind == 1 && d_mp)));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  ResNetGraph *g = new ResNetGraph();
+  g->is_graph = true; g->bf16 = bf16 != 0; g->feat_c = C; g->feat_h = H; g->feat_w = W; g->pooled = pooled; g->max_rois = N; g->roi_bins = roi_bins;
+  g->out_tensor = 0; g->heads.resize(1); g->g_heads.resize(1);
+  const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
+  const int Cb = (C + 7) / 8;
+  int rc = MPN_OK;
+  if (op_in) {
+    mpn_graph_op o = *op_in;
+    o.src = 0; o.dst = 1; o.dst_c_off = 0; o.src_c_off = 0; o.cin = C; o.w = nullptr; o.cout = 0;
+    const int tc[2] = {C, C};
+    rc = graph_parse(g, 1, &o, 2, tc, g->g_heads[0], g->t_head, true);
+    if (rc == MPN_OK)
+      for (GOp &op : g->g_heads[0])
+        if (MPN_GOP_POOLS_ROIS(op, g->t_head[0].C))
+          op.from_rois = true;
+  } else {
+    g->t_head.resize(1);
+    g->t_head[0].C = C;
+  }
+  if (rc == MPN_OK) rc = graph_dims(g->g_heads[0], g->t_head, pooled, pooled);
+  const size_t fe = c8i_elems(1, C, H, W);
+  float *feat = nullptr;
+  if (rc == MPN_OK) rc = rn_alloc(g, &feat, fe * esz);
+  if (rc == MPN_OK) {
+    const ActI fa{nullptr, 1, C, H, W};
+    hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(fe, 256)), dim3(256), 0, nullptr, d_feat, 1, C, H, W, fa.pitch(), fe, pad_fill, bf16, feat, 1);
+    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
+    g->feat = feat;
+  }
+  for (size_t i = 0; rc == MPN_OK && i < g->t_head.size(); ++i) {
+    GTensor &t = g->t_head[i];
+    const size_t te = c8i_elems(N, t.C, t.H, t.W);
+    rc = rn_alloc(g, &t.buf, te * esz);
+    if (rc != MPN_OK) break;
+    hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(te * esz / 4, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(t.buf), te * esz / 4,
+                       g->bf16 ? 0x7fa57fa5u : 0x7fa5a5a5u);
+    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
+  }
+  if (rc == MPN_OK) {
+    const size_t ce = (size_t)Cb * Mp * 8;
+    hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(ce, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(d_c8), ce, 0x7fa5a5a5u);
+    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
+  }
+  if (rc == MPN_OK && g->t_head.size() > 1 && (size_t)N * C * g->t_head[1].H * g->t_head[1].W > mp_cap) {
+    set_error("mpn_debug_head_pool: mp needs %zu elements", (size_t)N * C * g->t_head[1].H * g->t_head[1].W);
+    rc = MPN_EINVAL;
+  }
+  for (int i = 0; i < 4; ++i) g_dbg_pool_kernel[i] = 0;
+  if (rc == MPN_OK) rc = resnet_head_forward(g, 0, d_rois, roi_stride, N, spatial_scale, d_c8, Mp, nullptr, 0);
+  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
+  if (rc == MPN_OK) {
+    const ActI pa{nullptr, N, C, pooled, pooled};
+    const size_t total = (size_t)N * C * pooled * pooled;
+    hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, g->t_head[0].buf, N, C, pooled, pooled, pa.pitch(), 0, bf16, d_pooled);
+    if (g->t_head.size() > 1) {
+      const GTensor &t = g->t_head[1];
+      const ActI ma{nullptr, N, C, t.H, t.W};
+      const size_t tot2 = (size_t)N * C * t.H * t.W;
+      hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(tot2, 256)), dim3(256), 0, nullptr, t.buf, N, C, t.H, t.W, ma.pitch(), 0, bf16, d_mp);
+      if (oh_out) *oh_out = t.H;
+      if (ow_out) *ow_out = t.W;
+    }
+    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
+    if (kernels_out) for (int i = 0; i < 4; ++i) kernels_out[i] = g_dbg_pool_kernel[i];
+    if (levels_out) *levels_out = g->feat_vmax_valid ? g->feat_vmax_levels : 0;
+  }
+  if (hipDeviceSynchronize() != hipSuccess && rc == MPN_OK) rc = MPN_EHIP;
   resnet_free(g);
   return rc;
 }
