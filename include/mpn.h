@@ -223,6 +223,17 @@ int mpn_conv3x3_forward(const float *d_in, int B, int Cin, int H, int W, const f
 
 /* nn.SpatialMaxPooling(2,2,2,2):ceil():updateOutput.  [B*C,H,W] -> [B*C,ceil(H/2),ceil(W/2)]. */
 int mpn_maxpool2x2_ceil_forward(const float *d_in, int BC, int H, int W, float *d_out, void *stream);
+/* nn.SpatialMaxPooling(2,2,2,2):ceil():updateGradInput.  d_in [B*C,H,W] the forward's input, d_grad_out [B*C,ceil(H/2),ceil(W/2)],
+ * d_grad_in [B*C,H,W].  Windows do not overlap, so every input cell belongs to exactly one window (Y, X) = (y / 2, x / 2):
+ *   d_grad_in[c,y,x] = d_grad_out[c,Y,X]  if (y, x) is the cell on which the forward's scan of the window ends — the scan starts from
+ *                                         -inf, tests v > m and visits (2Y,2X), (2Y,2X+1), (2Y+1,2X), (2Y+1,2X+1), skipping cells outside
+ *                                         the map: the FIRST maximum in row-major order wins, a window holding only NaN routes nowhere;
+ *                      +0.0               everywhere else.
+ * Pure routing: no additions, no atomics, every cell of d_grad_in written exactly once — bit-exact by construction.  The maxima are
+ * recomputed from d_in (no argmax plane, no pooled map).  relu_mask != 0 is the form the training pipeline uses, fused with the ReLU
+ * of the layer the gradient flows into: a cell also gets +0.0 where d_in <= 0 (d_in post-ReLU: an all-zero window routes nothing). */
+int mpn_maxpool2x2_ceil_backward(const float *d_in, const float *d_grad_out, int BC, int H, int W, int relu_mask, float *d_grad_in,
+                                 void *stream);
 
 /* nn.Linear(K,N):updateOutput (+ fused nn.ReLU) (vgg.lua:16,30 `top`; model_utils.lua:105-119).
  * y[M,N] = x[M,K] W[N,K]^T + b.  fp32 MFMA; per-output k-ascending fmaf chain, independent of M
@@ -678,9 +689,20 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
  * max_rois 1000: 8 images x 4 maps x 6.8 MB = 218 MB, argmax 100 MB, dx6 103 MB, two gradient maps 14 MB, and per trained layer
  * (2.4 M weights) momentum + gradient + the input gradient's two packs, 110 MB for the three, 47 MB of partial sums, 19 MB of
  * Torch-layout scratch: 0.6 GB in all.
- * Still not trained: anything under a pooling layer, MultiPathNet / ResNet / op-list handles, dropout.
+ * Through the pooling layers: depth MPN_TRAIN_TRUNK(k), k = 1..min(n_conv - 1, MPN_TRAIN_MAX_TRUNK), trains the ROI head and the last
+ * k conv layers counted straight through the pool_after layers (VGG-16, k = 9: conv3_1 and up, the reference's models/vgg.lua:19).  The
+ * first conv layer is never trained (its input is the image); a larger k answers MPN_EINVAL naming the limit.  For k <= K it IS
+ * MPN_TRAIN_CONV(k): the same code, the same bits.  Beyond K every map has its own size (halved, rounding up, at each pool); per image
+ * mpn_frcnn_train_add keeps the first trained layer's input map, every trained layer's post-ReLU output (where the layer is pooled:
+ * the map BEFORE the pool) and the pooled map wherever it is the next trained layer's input.  The chain above runs with each layer's
+ * own size, and at a pooled layer the gradient arriving at its pooled output first goes through mpn_maxpool2x2_ceil_backward's rule
+ * in its relu_mask form (X = the saved pre-pool map) into a zero-haloed map of the larger size — one pass instead of the [X > 0]
+ * mask; the input gradient handed to a pooled layer is therefore not masked on its own.  Everything else — the summation orders,
+ * every gradient before any update, optim.sgd, the re-pack of the derived forms — is as above.  MPN_TRAIN_MAX_IMAGES applies.
+ * Still not trained: the first conv layer, MultiPathNet / ResNet / op-list handles, dropout.
  * Debug tensors after such a step, until the next mpn_frcnn_train_add: "train_act.<i>.<j>" (image i; j = 0 the block's input map,
- * j = 1..k the trained layers' outputs; [C,h,w]) and "train_dx6" ([B, C, PH, PW]).
+ * j = 1..k the trained layers' outputs — before the pool where the layer is pooled; [C,h,w], each map its own h x w) and "train_dx6"
+ * ([B, C, PH, PW]).
  *   mpn_frcnn_get_trunk_weights  conv layer `layer`'s current weights [Cout,Cin,3,3] and bias [Cout] in Torch layout (either may be
  *                          NULL); any mpn_frcnn_create handle, with or without training.  The exact inverse of creation. */
 #define MPN_TRAIN_HEADS 0   /* cls + bbox linear only          */
@@ -689,6 +711,8 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
 #define MPN_TRAIN_MAX_IMAGES 8
 #define MPN_TRAIN_CONV(k) (MPN_TRAIN_FC6 + (k))   /* + the last k conv layers, k = 1..K (see above) */
 enum { MPN_TRAIN_MAX_CONV = 7 };   /* K is capped here: a trunk with more conv layers behind its last pooling layer trains the last 7 */
+#define MPN_TRAIN_TRUNK(k) (32 + (k))    /* the ROI head + the last k conv layers of the trunk, pooling layers crossed */
+enum { MPN_TRAIN_MAX_TRUNK = 12 };
 int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight);
 int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_rois /*[n,4]*/,
                         const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);

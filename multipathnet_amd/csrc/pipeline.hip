@@ -255,6 +255,7 @@ struct mpn_frcnn {
   float *img_c8p = nullptr;
   std::vector<std::pair<float *, size_t>> act_bufs;  // for re-zeroing when the image size changes
   int last_h = -1, last_w = -1;                       // the (canvas) geometry the halos are laid for
+  int keep_prepool_from = -1;                         // >= 0: run_trunk also writes the pre-pool map (L.out) of the pooled layers from this one up (mpn_frcnn_train_add only)
   int feat_c = 0;
   // One cached final trunk map (VGG trunks): what a detect on cached features pools from.  run_trunk fills the record it is handed and no other.
   struct CachedMap {
@@ -393,7 +394,7 @@ struct mpn_frcnn {
   float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
   // ---- training the head (mpn_frcnn_train_*): exists between train_begin and train_end
   struct Train {
-    int depth = 0;                       // MPN_TRAIN_HEADS / _FC7 / _FC6 / _CONV(k)
+    int depth = 0;                       // MPN_TRAIN_HEADS / _FC7 / _FC6 / _CONV(k) / _TRUNK(k) (k <= K: stored as MPN_TRAIN_CONV(k))
     float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
     float *vh = nullptr, *vbh = nullptr, *v7 = nullptr, *vb7 = nullptr, *v6 = nullptr, *vb6 = nullptr;  // momentum, in the layout of the weight it goes with
     // the minibatch's own activations, C8 matrices at row pitch Mp (head: row-major [B, 5C]) — not detect's buffers, so a detect between
@@ -403,7 +404,8 @@ struct mpn_frcnn {
     float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
     int *labels = nullptr;
     int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
-    // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] above the last pooling layer
+    // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
+    // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
     struct ConvT {
       float *v = nullptr, *vb = nullptr;       // momentum: `wpk` layout, [CoutP]
       float *dw = nullptr, *db = nullptr;      // the step's gradients, summed over the images in train_add order
@@ -414,13 +416,15 @@ struct mpn_frcnn {
     float *dx6 = nullptr;                // gradient at the pooled features, x6's layout
     int32_t *argmax = nullptr;           // [max_rois, C, PH, PW] of the pending rows
     float *prois = nullptr;              // [max_rois, 5] the pending rows' projected ROIs (the bins' windows)
-    float *acts = nullptr;               // per image: the block's input map and the kconv trained layers' outputs, whole C8P planes
-    size_t act_off[MPN_TRAIN_MAX_CONV + 1] = {}, act_img = 0; // floats: map j inside an image's slot; between two images' slots
+    float *acts = nullptr;               // per image: the block's input map and the kconv trained layers' outputs (before the pool where pooled), whole C8P planes,
+                                         // then the pooled map of every pooled trained layer but the last (the next trained layer's input)
+    size_t act_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, pool_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, act_img = 0; // floats: map j / pooled map j inside an image's slot; between two images' slots
     float *gmap[2] = {nullptr, nullptr}; // the gradient maps of the image being worked on (ping-pong through the layers)
     size_t gmap_bytes = 0;
     float *wtmp = nullptr, *part = nullptr;  // a layer's weights in Torch layout (x 2: W, W'); conv3x3_wgrad's partial sums
     int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
-    int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // map size, row range
+    int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // final map size, row range
+    int img_nh[MPN_TRAIN_MAX_IMAGES] = {}, img_nw[MPN_TRAIN_MAX_IMAGES] = {};  // network-input size (every layer's map size follows from it)
     DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
   };
   Train *train = nullptr;
@@ -889,13 +893,14 @@ static int run_trunk(mpn_frcnn *p, const float *d_image, int H, int W, hipStream
     Act out = make_act(final_here && !L.pool ? final_here : L.out, L.Cout, h, w);
     const int ctag = conv3x3_variant_for(L.Cout, L.wino != nullptr) == 7 ? MPN_PROF_CONV_WINO : MPN_PROF_CONV_DIRECT;
     const bool is_tap = p->is_mpnet && (li == p->tap3 || li == p->tap4);
+    const bool keep_out = is_tap || (p->keep_prepool_from >= 0 && li >= p->keep_prepool_from);  // a training image: the backward pass reads the pre-pool map
     if (is_tap) p->tap_act[li == p->tap4 ? 1 : 2] = out;
     ++li;
     if (L.pool) {
       Act pooled = make_act(final_here ? final_here : L.pooled, L.Cout, (h + 1) / 2, (w + 1) / 2);
       if (g_fuse_pool) {
         ProfScope ps(p, ctag, s);
-        rc = conv3x3_c8p(cur, L.wpk, L.bpk, L.Cout, 1, is_tap ? out : Act{}, pooled, s, L.wino);  // tap layers keep the pre-pool map too
+        rc = conv3x3_c8p(cur, L.wpk, L.bpk, L.Cout, 1, keep_out ? out : Act{}, pooled, s, L.wino);  // tap layers keep the pre-pool map too
       } else {
         { ProfScope ps(p, ctag, s); rc = conv3x3_c8p(cur, L.wpk, L.bpk, L.Cout, 1, out, Act{}, s, L.wino); }
         if (rc == MPN_OK) { ProfScope ps(p, MPN_PROF_POOL, s); rc = maxpool2x2_c8p(out, pooled, s); }
@@ -2086,6 +2091,24 @@ static int refresh_conv_forms(const ConvLayer &L, const mpn_frcnn::Train::ConvT 
   return rc;
 }
 
+// the size of conv[l]'s input and output maps for an H x W network input: halved (rounding up) at every pooling layer below it
+static void layer_map_size(const mpn_frcnn *p, int l, int H, int W, int *h, int *w) {
+  for (int i = 0; i < l; ++i) if (p->conv[i].pool) { H = (H + 1) / 2; W = (W + 1) / 2; }
+  *h = H; *w = W;
+}
+// Saved map j of the trained block for an H x W network input, at `base` (an image's slot): j = 0 the input of conv[first], j = 1..k the
+// post-ReLU output of conv[first + j - 1] before its pool; pooled: the pooled output of that layer (1 <= j < k, the layer pooled)
+static Act train_map(const mpn_frcnn *p, const mpn_frcnn::Train *t, float *base, int j, bool pooled, int H, int W) {
+  const int l = j == 0 ? t->first : t->first + j - 1;
+  int h, w;
+  layer_map_size(p, pooled ? l + 1 : l, H, W, &h, &w);
+  return make_act(base ? base + (pooled ? t->pool_off[j] : t->act_off[j]) : nullptr, j == 0 ? p->conv[l].Cin : p->conv[l].Cout, h, w);  // (no base: the geometry alone)
+}
+// the input map of trained layer j (1..k): saved map j - 1, or its pooled form where the layer below is pooled
+static Act train_in_map(const mpn_frcnn *p, const mpn_frcnn::Train *t, float *base, int j, int H, int W) {
+  return train_map(p, t, base, j - 1, j > 1 && p->conv[t->first + j - 2].pool, H, W);
+}
+
 extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight) {
   MPN_CHECK_ARG(p != nullptr);
   int rc = refuse_train(p, "mpn_frcnn_train_begin");
@@ -2097,7 +2120,17 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
   while (Kmax < n_conv && !p->conv[n_conv - 1 - Kmax].pool) ++Kmax;
   if (Kmax == n_conv) Kmax = 0;
   if (Kmax > MPN_TRAIN_MAX_CONV) Kmax = MPN_TRAIN_MAX_CONV;
-  if (depth > MPN_TRAIN_CONV(Kmax)) {
+  int trunk_k = 0;  // > 0: MPN_TRAIN_TRUNK(k) with k > K — pooling layers among the trained ones
+  if (depth >= MPN_TRAIN_TRUNK(0)) {
+    const int k = depth - MPN_TRAIN_TRUNK(0), lim = std::min(n_conv - 1, (int)MPN_TRAIN_MAX_TRUNK);
+    if (k < 1 || k > lim) {
+      set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_TRUNK(%d), but k runs from 1 to %d on this trunk of %d conv layers: min(n_conv - 1, MPN_TRAIN_MAX_TRUNK = %d) — the first conv layer is never trained (its input is the image)",
+                depth, k, lim, n_conv, (int)MPN_TRAIN_MAX_TRUNK);
+      return MPN_EINVAL;
+    }
+    if (k <= Kmax) depth = MPN_TRAIN_CONV(k);  // no pooling layer among them: the same code, the same bits
+    else trunk_k = k;
+  } else if (depth > MPN_TRAIN_CONV(Kmax)) {
     set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_CONV(%d), but only K = %d conv layers lie above the trunk's last pooling layer: a pooling layer is in the way (it has no backward pass)",
               depth, depth - MPN_TRAIN_FC6, Kmax);
     return MPN_EINVAL;
@@ -2125,23 +2158,26 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
   ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
   ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
   if (depth > MPN_TRAIN_FC6) {
-    const int k = depth - MPN_TRAIN_FC6, PP = c.pooled_h * c.pooled_w;
+    const int k = trunk_k ? trunk_k : depth - MPN_TRAIN_FC6, PP = c.pooled_h * c.pooled_w;
     t->kconv = k; t->first = n_conv - k;
     int mh = c.max_h, mw = c.max_w;
     final_map_size(p, &mh, &mw);
     ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
     ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
     size_t off = 0, wmax = 0, pmax = 0;
-    int cmax = 0;
-    for (int j = 0; j <= k; ++j) {  // map 0: the block's input; map j: the output of conv[first + j - 1]
+    t->gmap_bytes = act_bytes(p->feat_c, mh, mw);  // the gradient maps: the largest of the saved maps' sizes (and the final map's)
+    auto slot = [&](const Act &a) { const size_t b = act_bytes(a.C, a.H, a.W); off += b / sizeof(float); t->gmap_bytes = std::max(t->gmap_bytes, b); };
+    for (int j = 0; j <= k; ++j) {  // map 0: the block's input; map j: the output of conv[first + j - 1], each at its own layer's size
       t->act_off[j] = off;
-      const int cj = j == 0 ? p->conv[t->first].Cin : p->conv[t->first + j - 1].Cout;
-      off += act_bytes(cj, mh, mw) / sizeof(float);
-      cmax = cj > cmax ? cj : cmax;
+      slot(train_map(p, t.get(), nullptr, j, false, c.max_h, c.max_w));
+    }
+    for (int j = 1; j < k; ++j) {   // MPN_TRAIN_TRUNK: the pooled map of a pooled layer is the next trained layer's input
+      if (!p->conv[t->first + j - 1].pool) continue;
+      t->pool_off[j] = off;
+      slot(train_map(p, t.get(), nullptr, j, true, c.max_h, c.max_w));
     }
     t->act_img = off;
     ok = ok && alloc0(&t->acts, off * MPN_TRAIN_MAX_IMAGES * sizeof(float));
-    t->gmap_bytes = act_bytes(cmax, mh, mw);
     ok = ok && alloc0(&t->gmap[0], t->gmap_bytes) && alloc0(&t->gmap[1], t->gmap_bytes);
     t->cl.resize(k);
     for (int j = 0; j < k && ok; ++j) {
@@ -2154,7 +2190,9 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
         if (L.Cout >= 16) ok = ok && alloc0(&T.wino_t, conv_wino_elems(L.Cout, L.Cin) * sizeof(float));
       }
       wmax = std::max(wmax, (size_t)L.Cout * L.Cin * 9);
-      pmax = std::max(pmax, conv_wgrad_part_elems(L.Cin, L.Cout, mh, mw));
+      int lh, lw;
+      layer_map_size(p, t->first + j, c.max_h, c.max_w, &lh, &lw);
+      pmax = std::max(pmax, conv_wgrad_part_elems(L.Cin, L.Cout, lh, lw));
     }
     ok = ok && alloc0(&t->wtmp, 2 * wmax * sizeof(float)) && alloc0(&t->part, pmax * sizeof(float));
     for (int j = 1; j < k && ok; ++j) ok = refresh_conv_forms(p->conv[t->first + j], t->cl[j], t->wtmp, false, nullptr) == MPN_OK;
@@ -2204,7 +2242,11 @@ extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, i
   hipStream_t s = as_stream(stream);
   p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers and the ROI table are rewritten: the next head segment runs for real
   Act feat;
+  bool pools = false;  // a pooled layer among the trained ones (MPN_TRAIN_TRUNK): this trunk pass also writes their pre-pool maps
+  for (int j = 0; j < t->kconv; ++j) pools = pools || p->conv[t->first + j].pool;
+  if (pools) p->keep_prepool_from = t->first;
   rc = obtain_features(p, d_image, H0, W0, H, W, sc, &p->up, s, &feat);  // getImages' rescale + the frozen trunk, exactly as detect
+  p->keep_prepool_from = -1;
   // the map now belongs to a training image: nothing a detect on cached features may pool from
   p->up.invalidate(); p->mir.invalidate();
   if (rc) return rc;
@@ -2215,15 +2257,21 @@ extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, i
                    t->kconv ? t->argmax + (size_t)t->pending * p->feat_c * c.pooled_h * c.pooled_w : nullptr, s, 5, p->Mp);
   if (rc) return rc;
   if (t->kconv) {  // what the conv block's backward pass reads: the block's input, every trained layer's output, the rows' windows
-    const int i = t->n_img, h = feat.H, w = feat.W;
-    for (int j = 0; j <= t->kconv; ++j) {
-      const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones (k == K: a pooling layer)
-      const float *src = j == t->kconv ? feat.p : (L.pool ? L.pooled : L.out);
-      const int cj = L.Cout;
-      MPN_CHECK_HIP(hipMemcpyAsync(t->acts + (size_t)i * t->act_img + t->act_off[j], src, act_bytes(cj, h, w), hipMemcpyDeviceToDevice, s));
+    const int i = t->n_img, h = feat.H, w = feat.W, k = t->kconv;
+    float *slot = t->acts + (size_t)i * t->act_img;
+    for (int j = 0; j <= k; ++j) {
+      const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones
+      // j == 0: what conv[first] read; j >= 1: the layer's output before its pool (the last layer's unpooled output is the final map)
+      const float *src = j == 0 ? (L.pool ? L.pooled : L.out) : ((j == k && !L.pool) ? feat.p : L.out);
+      const Act a = train_map(p, t, slot, j, false, H, W);
+      MPN_CHECK_HIP(hipMemcpyAsync(a.p, src, act_bytes(a.C, a.H, a.W), hipMemcpyDeviceToDevice, s));
+      if (j >= 1 && j < k && L.pool) {
+        const Act ap = train_map(p, t, slot, j, true, H, W);
+        MPN_CHECK_HIP(hipMemcpyAsync(ap.p, L.pooled, act_bytes(ap.C, ap.H, ap.W), hipMemcpyDeviceToDevice, s));
+      }
     }
     MPN_CHECK_HIP(hipMemcpyAsync(t->prois + (size_t)t->pending * 5, p->rois, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    t->img_h[i] = h; t->img_w[i] = w; t->img_row0[i] = t->pending; t->img_rows[i] = n;
+    t->img_h[i] = h; t->img_w[i] = w; t->img_nh[i] = H; t->img_nw[i] = W; t->img_row0[i] = t->pending; t->img_rows[i] = n;
     ++t->n_img;
   }
   MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -2236,14 +2284,18 @@ extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, i
 // The backward pass below fc6 (depth MPN_TRAIN_CONV(k)): the gradient at the pooled features, then per image — in train_add order — the
 // ROI-pooling backward into a zero-haloed gradient map and, last trained layer to first, the bias and weight gradients (added to the
 // step's sums) and the input gradient masked with the ReLU of the layer below.  No weight is touched: the caller updates afterwards.
+// MPN_TRAIN_TRUNK(k): every layer at its own size; at a pooled layer the gradient at its pooled output first goes through
+// maxpool2x2_backward_c8p (fused with the ReLU mask of the pre-pool map, so the input gradient handed to a pooled layer is not masked
+// on its own) into the other gradient map, whose halo is laid for the larger size first — as is every map written after it.
 static int train_conv_backward(mpn_frcnn *p, mpn_frcnn::Train *t, int B, hipStream_t s) {
   const mpn_frcnn_config &c = p->cfg;
   const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp, k = t->kconv;
   // dx6 = (g6 W6) .* [x6 > 0]: fc6's packed chunk order is x6's.  The mask is the last conv layer's ReLU mask (pooled values are map values)
   int rc = linear_dgrad_c8(t->g6, Mp, B, c.fc_dim, p->w6, p->K6, t->x6, t->dx6, Mp, s);
   for (int i = 0; i < t->n_img && rc == MPN_OK; ++i) {
-    const int h = t->img_h[i], w = t->img_w[i];
-    auto saved = [&](int j) { return make_act(t->acts + (size_t)i * t->act_img + t->act_off[j], j == 0 ? p->conv[t->first].Cin : p->conv[t->first + j - 1].Cout, h, w); };
+    const int h = t->img_h[i], w = t->img_w[i], nh = t->img_nh[i], nw = t->img_nw[i];
+    float *slot = t->acts + (size_t)i * t->act_img;
+    bool relaid = false;  // a pooling layer has been crossed: the memset below no longer is the halo of the maps' sizes
     for (float *gm : t->gmap) MPN_CHECK_HIP(hipMemsetAsync(gm, 0, t->gmap_bytes, s));  // the halo is the input gradient's padding
     int cur = 0;
     Act G = make_act(t->gmap[cur], p->feat_c, h, w);
@@ -2258,13 +2310,22 @@ static int train_conv_backward(mpn_frcnn *p, mpn_frcnn::Train *t, int B, hipStre
     for (int j = k; j >= 1 && rc == MPN_OK; --j) {
       const ConvLayer &L = p->conv[t->first + j - 1];
       const mpn_frcnn::Train::ConvT &T = t->cl[j - 1];
-      const Act X = saved(j - 1);
+      const Act X = train_in_map(p, t, slot, j, nh, nw);
+      if (L.pool) {  // G is the gradient at the pooled output: route it to the pre-pool map's maxima, masked with that map's ReLU
+        const Act Y = train_map(p, t, slot, j, false, nh, nw);
+        Act Gl = make_act(t->gmap[cur ^ 1], L.Cout, Y.H, Y.W);
+        rc = c8p_zero_halos(&Gl, 1, s);
+        if (rc == MPN_OK) rc = maxpool2x2_backward_c8p(Y, G, Gl, 1, s);
+        if (rc != MPN_OK) break;
+        G = Gl; cur ^= 1; relaid = true;
+      }
       rc = conv_bias_grad(G, T.db, i > 0, s);
       if (rc == MPN_OK) rc = conv3x3_wgrad(X, G, t->part, T.dw, i > 0, s);
       if (rc != MPN_OK || j == 1) break;
-      Act dX = make_act(t->gmap[cur ^ 1], L.Cin, h, w);
-      rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
-      if (rc == MPN_OK) rc = relu_mask_c8p(dX, X, s);
+      Act dX = make_act(t->gmap[cur ^ 1], L.Cin, X.H, X.W);
+      if (relaid) rc = c8p_zero_halos(&dX, 1, s);
+      if (rc == MPN_OK) rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
+      if (rc == MPN_OK && !p->conv[t->first + j - 2].pool) rc = relu_mask_c8p(dX, X, s);  // (a pooled layer below: its pool's backward masks)
       G = dX; cur ^= 1;
     }
   }
@@ -2384,10 +2445,25 @@ extern "C" int mpn_debug_bench_train_wgrad(mpn_frcnn *p, int iters, float *ms_ou
   MPN_CHECK_ARG(p && iters > 0 && ms_out);
   mpn_frcnn::Train *t = p->train;
   if (!t || !t->kconv || t->last_img <= 0) { set_error("mpn_debug_bench_train_wgrad: needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)"); return MPN_ESTATE; }
-  const int k = t->kconv, h = t->img_h[0], w = t->img_w[0];
+  const int k = t->kconv;
   const ConvLayer &L = p->conv[t->first + k - 1];
-  const Act X = make_act(t->acts + t->act_off[k - 1], L.Cin, h, w), G = make_act(t->gmap[0], L.Cout, h, w);
+  const Act X = train_in_map(p, t, t->acts, k, t->img_nh[0], t->img_nw[0]), G = make_act(t->gmap[0], L.Cout, X.H, X.W);
   return time_back_to_back(iters, ms_out, [&] { return conv3x3_wgrad(X, G, t->part, t->cl[k - 1].dw, 0, nullptr); });
+}
+
+// tools/bench_train.py (debug flavour only): maxpool2x2_backward_c8p in its fused form issued `iters` times back to back on the LARGEST
+// pooled trained layer of the last mpn_frcnn_train_step at depth MPN_TRAIN_TRUNK(k), k > K (image 0's saved pre-pool map; dY and dX are
+// the two gradient maps with whatever that step left: the kernel's time does not depend on values).  *layer_out: that layer's index.
+extern "C" int mpn_debug_bench_train_poolbwd(mpn_frcnn *p, int iters, float *ms_out, int *layer_out) {
+  MPN_CHECK_ARG(p && iters > 0 && ms_out);
+  mpn_frcnn::Train *t = p->train;
+  int jb = 0;
+  for (int j = 1; t && j <= t->kconv; ++j) if (p->conv[t->first + j - 1].pool && !jb) jb = j;  // the lowest pooled layer has the largest map
+  if (!t || !jb || t->last_img <= 0) { set_error("mpn_debug_bench_train_poolbwd: needs a mpn_frcnn_train_step at a depth MPN_TRAIN_TRUNK(k) that crosses a pooling layer"); return MPN_ESTATE; }
+  const Act Y = train_map(p, t, t->acts, jb, false, t->img_nh[0], t->img_nw[0]);
+  const Act dY = make_act(t->gmap[0], Y.C, (Y.H + 1) / 2, (Y.W + 1) / 2), dX = make_act(t->gmap[1], Y.C, Y.H, Y.W);
+  if (layer_out) *layer_out = t->first + jb - 1;
+  return time_back_to_back(iters, ms_out, [&] { return maxpool2x2_backward_c8p(Y, dY, dX, 1, nullptr); });
 }
 
 // bench.py's `power_sensitivity` leg (debug flavour only): fc6 of the VGG Fast R-CNN pipeline issued `iters` times BACK TO BACK on the
@@ -2443,7 +2519,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
         set_error("mpn_frcnn_debug_tensor: '%s': the last step had %d images and maps 0..%d", name, t->last_img, t->kconv);
         return MPN_EINVAL;
       }
-      const Act a = make_act(t->acts + (size_t)i * t->act_img + t->act_off[j], j == 0 ? p->conv[t->first].Cin : p->conv[t->first + j - 1].Cout, t->img_h[i], t->img_w[i]);
+      const Act a = train_map(p, t, t->acts + (size_t)i * t->act_img, j, false, t->img_nh[i], t->img_nw[i]);
       nt = (size_t)a.C * a.H * a.W;
       if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
       if (int rcc = c8p_to_nchw(a, p->dbg, nullptr)) return rcc;

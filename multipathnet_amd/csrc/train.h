@@ -59,17 +59,38 @@ int roi_pool_backward(const RoiBwd &a, hipStream_t s);
 
 struct Act;
 constexpr int kWgradSegPx = 512;  // pixels per partial sum of the weight gradient
+constexpr int kWgradSegGroup = 8; // segments per group of the segment sum (a 150 x 250 map has 74 segments: chains of 8 and 10, not 74)
 // floats of the partial-sum buffer conv3x3_wgrad needs for an H x W map
 size_t conv_wgrad_part_elems(int Cin, int Cout, int H, int W);
 // dW[co][ci][ky][kx] (+)= sum_{y,x} G[co][y][x] * X[ci][y + ky - 1][x + kx - 1] in the `wpk` layout [Cin8/8][9][CoutP][8], pad lanes +0.0.
 // v_mfma_f32_32x32x2_f32 over the pixels in row-major pairs, cut into segments of kWgradSegPx pixels, each accumulated from zero by its
-// own block into d_part; conv_wgrad_reduce_kernel then adds the segments in ascending order and (accumulate) adds that sum to d_dw:
+// own block into d_part; conv_wgrad_reduce_kernel then adds the segments in ascending order in groups of kWgradSegGroup, adds the group
+// sums in ascending order (up to kWgradSegGroup segments: one group, the plain ascending sum) and (accumulate) adds that sum to d_dw:
 // the order depends on (Cin, Cout, H, W) alone.  X's halo must be zero (it is the padding); G's halo is never read.
 int conv3x3_wgrad(const Act &x, const Act &g, float *d_part, float *d_dw, int accumulate, hipStream_t s);
 // db[co] (+)= sum_{y,x} G[co][y][x]: 32 interleaved pixel-ascending partial sums, then a fixed tree (as sgd_bias_kernel)
 int conv_bias_grad(const Act &g, float *d_db, int accumulate, hipStream_t s);
 // g .*= [x > 0] on the interior of the planes (x: the post-ReLU output of the layer the gradient flows into)
 int relu_mask_c8p(const Act &g, const Act &x, hipStream_t s);
+// nn.SpatialMaxPooling(2,2,2,2):ceil():updateGradInput fused (relu_mask != 0) with the ReLU mask of the layer the gradient flows into
+// (include/mpn.h mpn_maxpool2x2_ceil_backward states the contract): per window the maximum is recomputed from X with the forward's
+// scan (from -inf, v > m, row-major, cells outside the map skipped) and dY's value goes to the cell the scan ends on — with relu_mask
+// only where that cell is > 0 —, every other cell of the window gets +0.0.  Pure routing: every interior cell of dX is written exactly
+// once, nothing is added.  The three operands are given by strides, in floats, over (channel block, row, column):
+//   X[cb * x_cb + y * x_y + x * x_x + e],  dY[cb * g_cb + Y * g_y + X * g_x + e],  dX[cb * d_cb + y * d_y + x * d_x + e],  e < vec
+// with vec = 8 for C8P maps (a channel block is a plane, a cell a 32-byte record read and written as two float4; the pointers are those
+// of the interior's first record) and vec = 1 for NCHW (a channel block is one channel).  One thread per (channel block, window),
+// windows along x fastest.  Only the H x W interior is stored: halo and pitch padding stay the caller's zeros; the pad lanes
+// (channels >= C) of a C8P map's last block are written +0.0, as conv3x3_c8p does.  No LDS.
+struct PoolBwd {
+  const float *x, *dy;
+  float *dx;
+  int vec, CB, C, H, W, relu_mask;   // CB channel blocks of `vec` channels, C channels in all
+  long x_cb, x_y, x_x, g_cb, g_y, g_x, d_cb, d_y, d_x;
+};
+int maxpool2x2_backward(const PoolBwd &a, hipStream_t s);
+// the C8P form: x, dx [C, H, W], dy [C, ceil(H/2), ceil(W/2)]
+int maxpool2x2_backward_c8p(const Act &x, const Act &dy, const Act &dx, int relu_mask, hipStream_t s);
 // optim.sgd on a packed conv weight: g' = dW + wd * w, v = momentum * v + g', w = w - lr * v (each rounded on its own), pad lanes untouched
 int conv_sgd(float *d_wpk, float *d_vpk, const float *d_dw, int Cin, int Cout, float lr, float momentum, float wd, hipStream_t s);
 int vec_sgd(float *d_b, float *d_vb, const float *d_db, int n, float lr, float momentum, hipStream_t s);

@@ -445,7 +445,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(ConvWgradArgs a) 
   }
 }
 
-// dW (+)= ((part[0] + part[1]) + part[2]) + ...; lanes outside the layer (pad couts, pad cins: never written by the kernel above) get +0.0
+// dW (+)= (g[0] + g[1]) + ... with g[i] = ((part[8 i] + part[8 i + 1]) + ...) + part[8 i + 7] (train.h kWgradSegGroup); lanes outside the layer (pad couts, pad cins: never written by the kernel above) get +0.0
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__restrict__ part, size_t stride, int nseg, int Cin, int Cout, int CoutP,
                                                                 size_t total, float *__restrict__ dw, int accumulate) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -455,7 +455,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__r
   const int co = (int)(r % CoutP), q = (int)(r / CoutP), ci = (q / 9) * 8 + e;
   float v = 0.0f;
   if (co < Cout && ci < Cin) {
-    for (int sg = 0; sg < nseg; ++sg) v += part[(size_t)sg * stride + t];
+    for (int g0 = 0; g0 < nseg; g0 += kWgradSegGroup) {  // groups of segments, each summed from zero in ascending order
+      const int g1 = min(g0 + kWgradSegGroup, nseg);
+      float gs = 0.0f;
+      for (int sg = g0; sg < g1; ++sg) gs += part[(size_t)sg * stride + t];
+      v = g0 == 0 ? gs : v + gs;
+    }
     if (accumulate) v = dw[t] + v;
   }
   dw[t] = v;
@@ -528,6 +533,92 @@ int relu_mask_c8p(const Act &g, const Act &x, hipStream_t s) {
   hipLaunchKernelGGL(relu_mask_c8p_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, g.p, x.p, g.Cb(), g.plane(), g.Wp, g.H, g.W);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// 2x2 ceil-mode max-pool backward (+ the ReLU mask of the pre-pool map)
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <int V>
+__device__ __forceinline__ void pool_load(const float *p, float (&v)[V]) {
+  if constexpr (V == 8) {
+    const f32x4 lo = *reinterpret_cast<const f32x4 *>(p), hi = *reinterpret_cast<const f32x4 *>(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] = lo[e]; v[4 + e] = hi[e]; }
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int V>
+__device__ __forceinline__ void pool_store(float *p, const float (&v)[V]) {
+  if constexpr (V == 8) {
+    *reinterpret_cast<f32x4 *>(p) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4 *>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+  } else {
+    p[0] = v[0];
+  }
+}
+
+// One thread per (channel block, window), windows along x fastest: with C8P operands a wave reads 64 windows = 128 consecutive records
+// (4 KiB) of each of the two rows of X, 2 KiB of dY, and writes the same 2 x 4 KiB of dX.  Cells outside the map (ceil mode: the last
+// row / column of windows of an odd size) are neither read nor written.
+template <int V>
+__global__ __launch_bounds__(256) void maxpool2x2_backward_kernel(PoolBwd a) {
+  const int Ho = (a.H + 1) / 2, Wo = (a.W + 1) / 2;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)a.CB * Ho * Wo) return;
+  const int X = (int)(t % Wo), Y = (int)((t / Wo) % Ho), cb = (int)(t / ((size_t)Wo * Ho));
+  const int y0 = 2 * Y, x0 = 2 * X;
+  const bool in[4] = {true, x0 + 1 < a.W, y0 + 1 < a.H, x0 + 1 < a.W && y0 + 1 < a.H};   // the forward's scan order
+  const float *xp = a.x + (long)cb * a.x_cb + (long)y0 * a.x_y + (long)x0 * a.x_x;
+  float v[4][V], g[V], o[4][V];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (in[q]) pool_load<V>(xp + (long)(q >> 1) * a.x_y + (long)(q & 1) * a.x_x, v[q]);
+    else {
+#pragma unroll
+      for (int e = 0; e < V; ++e) v[q][e] = 0.0f;
+    }
+  }
+  pool_load<V>(a.dy + (long)cb * a.g_cb + (long)Y * a.g_y + (long)X * a.g_x, g);
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    float m = -INFINITY;
+    int win = -1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (in[q] && v[q][e] > m) { m = v[q][e]; win = q; }
+    if (a.relu_mask && !(m > 0.0f)) win = -1;
+    if (cb * V + e >= a.C) win = -1;   // pad lanes of the last channel block
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q][e] = win == q ? g[e] : 0.0f;
+  }
+  float *dp = a.dx + (long)cb * a.d_cb + (long)y0 * a.d_y + (long)x0 * a.d_x;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (in[q]) pool_store<V>(dp + (long)(q >> 1) * a.d_y + (long)(q & 1) * a.d_x, o[q]);
+}
+
+int maxpool2x2_backward(const PoolBwd &a, hipStream_t s) {
+  MPN_CHECK_ARG(a.x && a.dy && a.dx && a.CB > 0 && a.C > 0 && a.H > 0 && a.W > 0 && (a.vec == 1 || a.vec == 8));
+  MPN_CHECK_ARG(a.C <= a.CB * a.vec && a.C > (a.CB - 1) * a.vec);
+  const size_t total = (size_t)a.CB * ((a.H + 1) / 2) * ((a.W + 1) / 2);
+  const dim3 grid((unsigned)cdiv_sz(total, 256));
+  if (a.vec == 8) hipLaunchKernelGGL(maxpool2x2_backward_kernel<8>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(maxpool2x2_backward_kernel<1>, grid, dim3(256), 0, s, a);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+int maxpool2x2_backward_c8p(const Act &x, const Act &dy, const Act &dx, int relu_mask, hipStream_t s) {
+  MPN_CHECK_ARG(x.p && dy.p && dx.p && x.C == dy.C && x.C == dx.C && dx.H == x.H && dx.W == x.W && dx.Hp == x.Hp && dx.Wp == x.Wp);
+  MPN_CHECK_ARG(dy.H == (x.H + 1) / 2 && dy.W == (x.W + 1) / 2);
+  PoolBwd a{};
+  a.x = x.p + ((size_t)x.Wp + 1) * 8; a.dy = dy.p + ((size_t)dy.Wp + 1) * 8; a.dx = dx.p + ((size_t)dx.Wp + 1) * 8;
+  a.vec = 8; a.CB = x.Cb(); a.C = x.C; a.H = x.H; a.W = x.W; a.relu_mask = relu_mask;
+  a.x_cb = (long)x.plane(); a.x_y = (long)x.Wp * 8; a.x_x = 8;
+  a.g_cb = (long)dy.plane(); a.g_y = (long)dy.Wp * 8; a.g_x = 8;
+  a.d_cb = (long)dx.plane(); a.d_y = (long)dx.Wp * 8; a.d_x = 8;
+  return maxpool2x2_backward(a, s);
 }
 
 __global__ __launch_bounds__(256) void conv_sgd_kernel(float *__restrict__ w, float *__restrict__ v, const float *__restrict__ dw, int Cin, int Cout,
@@ -632,6 +723,19 @@ extern "C" int mpn_roi_pool_backward(const float *d_grad_out, const int32_t *d_a
   a.o_b = (long)C * H * W; a.o_cb = 8L * H * W; a.o_c = (long)H * W; a.o_y = W; a.o_x = 1;
   a.out = d_grad_in;
   return roi_pool_backward(a, as_stream(stream));
+}
+
+extern "C" int mpn_maxpool2x2_ceil_backward(const float *d_in, const float *d_grad_out, int BC, int H, int W, int relu_mask, float *d_grad_in,
+                                            void *stream) {
+  MPN_CHECK_ARG(d_in && d_grad_out && d_grad_in && BC > 0 && H > 0 && W > 0);
+  const long Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  PoolBwd a{};
+  a.x = d_in; a.dy = d_grad_out; a.dx = d_grad_in;
+  a.vec = 1; a.CB = BC; a.C = BC; a.H = H; a.W = W; a.relu_mask = relu_mask != 0;
+  a.x_cb = (long)H * W; a.x_y = W; a.x_x = 1;
+  a.g_cb = Ho * Wo; a.g_y = Wo; a.g_x = 1;
+  a.d_cb = (long)H * W; a.d_y = W; a.d_x = 1;
+  return maxpool2x2_backward(a, as_stream(stream));
 }
 
 static bool dgrad_has_wino(int Cout) { return Cout >= 16; }  // build_vgg_trunk's rule on the transposed layer (its input channels = Cout)

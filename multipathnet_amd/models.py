@@ -800,13 +800,20 @@ class FastRCNN(object):
         return keep, idx, n
 
     # ---- fine-tuning the head on the device, trunk frozen (mpn_frcnn_train_*, include/mpn.h) ----
-    def train_begin(self, depth=2, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0):
-        """Start training: depth 0 = cls + bbox linear only, 1 = + fc7, 2 = + fc6 (the whole ROI head), 2 + k = + the last k conv layers
-        of the trunk, k = 1..K with K the number of conv layers above the trunk's last pooling layer (VGG-16: 3 = + conv5_3, 4 = + conv5_2,
-        5 = + conv5_1; beyond K a pooling layer is in the way: MpnError).  At depth >= 3 a step takes at most 8 images.  optim.sgd's
-        momentum and weight decay (engines/Optim.lua; biases never decay), the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN
-        handles in fp32 only; no dropout (the reference's opt.train_remove_dropouts configuration)."""
-        check(self._lib.mpn_frcnn_train_begin(self._h, int(depth), C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)),
+    def train_begin(self, depth=None, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0, trunk_layers=None):
+        """Start training: depth 0 = cls + bbox linear only, 1 = + fc7, 2 = + fc6 (the whole ROI head, the default), 2 + k = + the last k
+        conv layers of the trunk, k = 1..K with K the number of conv layers above the trunk's last pooling layer (VGG-16: 3 = + conv5_3,
+        4 = + conv5_2, 5 = + conv5_1; beyond K a pooling layer is in the way: MpnError).  trunk_layers = k instead of depth (both:
+        ValueError) is MPN_TRAIN_TRUNK(k): the whole ROI head and the last k conv layers counted straight THROUGH the pooling layers, whose
+        backward pass routes each gradient to its window's first maximum; k = 1..min(n_conv - 1, 12) — the first conv layer is never
+        trained — and VGG-16 at k = 9 (conv3_1 and up) is the reference's configuration; k <= K gives the bits of depth 2 + k.  With conv
+        layers trained a step takes at most 8 images.  optim.sgd's momentum and weight decay (engines/Optim.lua; biases never decay),
+        the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN handles in fp32 only; no dropout (the reference's
+        opt.train_remove_dropouts configuration)."""
+        if depth is not None and trunk_layers is not None:
+            raise ValueError("train_begin: give depth or trunk_layers, not both")
+        d = 32 + int(trunk_layers) if trunk_layers is not None else (2 if depth is None else int(depth))   # MPN_TRAIN_TRUNK(k)
+        check(self._lib.mpn_frcnn_train_begin(self._h, d, C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)),
               "mpn_frcnn_train_begin")
 
     def train_add(self, image, rois, gt_boxes, labels):

@@ -294,6 +294,20 @@ class SpatialMaxPooling(Module):
         check(_lib.load().mpn_maxpool2x2_ceil_forward(_f(x), bc, H, W, _f(self.output), _stream()), "SpatialMaxPooling")
         return self.output
 
+    def updateGradInput(self, input, gradOutput):
+        """gradInput[c,y,x] = gradOutput[c,y/2,x/2] on the cell the forward's scan of the window ends on (the first maximum in row-major
+        order), +0.0 elsewhere (mpn_maxpool2x2_ceil_backward, relu_mask 0: pure routing, bit-exact)."""
+        x, g = input.contiguous(), gradOutput.contiguous()
+        H, W = x.shape[-2:]
+        assert tuple(g.shape) == tuple(x.shape[:-2]) + ((H + 1) // 2, (W + 1) // 2)
+        bc = 1
+        for d in x.shape[:-2]:
+            bc *= d
+        self.gradInput = torch.empty_like(x)
+        check(_lib.load().mpn_maxpool2x2_ceil_backward(_f(x, "input"), _f(g, "gradOutput"), bc, H, W, 0, _f(self.gradInput), _stream()),
+              "SpatialMaxPooling.updateGradInput")
+        return self.gradInput
+
 
 class Linear(Module):
     """nn.Linear(inputSize, outputSize) with an optionally fused nn.ReLU."""

@@ -5,9 +5,13 @@ projection, ROI pooling each — plus the step), HIP events, median of --steps a
 kernel alone (debug flavour, mpn_debug_bench_train_fc6: back-to-back launches) and its GB/s against the bytes it must move — the packed
 weights and their momentum, each read and written once — and, at depth 3, the conv weight-gradient kernel alone on conv5_3 (512 -> 512 at
 38 x 63, mpn_debug_bench_train_wgrad) against its floor: 2 * 9 * 512 * 512 * 38 * 63 = 11.3 GFLOP at the fp32 MFMA peak of 157.3 TFLOP/s.
+--trunk-layers k adds, after the depths above, the depth MPN_TRAIN_TRUNK(k) — k = 9 is the reference's conv3_1
+and up, through two pooling layers — with the same two numbers, and the max-pool backward kernel alone on the largest pooled trained layer
+(k = 9: conv3_3, 256 x 150 x 250; mpn_debug_bench_train_poolbwd) against the bytes it must move: X and dX once each, dY once, at the
+6.3 TB/s a float4 copy reaches.
 One JSON line per measurement.
 
-    python tools/bench_train.py [--steps 20] [--warmup 5]
+    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9]
 """
 import argparse
 import ctypes as C
@@ -38,6 +42,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--trunk-layers", type=int, default=0, help="also measure MPN_TRAIN_TRUNK(k) (9: conv3_1 and up, the reference's configuration)")
     a = ap.parse_args()
     import torch
     from multipathnet_amd import _lib, models
@@ -50,8 +55,11 @@ def main():
     with _lib.debug_hooks() as lib:
         net = models.FastRCNN(P, max_h=H, max_w=W, max_rois=IMAGES * ROWS)
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        for depth in (0, 1, 2, 3, 4, 5):
-            net.train_begin(depth=depth, momentum=0.9, weight_decay=5e-4)
+        for depth in (0, 1, 2, 3, 4, 5) + (("trunk",) if a.trunk_layers > 0 else ()):
+            if depth == "trunk":
+                net.train_begin(trunk_layers=a.trunk_layers, momentum=0.9, weight_decay=5e-4)
+            else:
+                net.train_begin(depth=depth, momentum=0.9, weight_decay=5e-4)
             step_ms, iter_ms = [], []
             for i in range(a.warmup + a.steps):
                 e[0].record()
@@ -64,7 +72,7 @@ def main():
                 if i >= a.warmup:
                     step_ms.append(e[1].elapsed_time(e[2]))
                     iter_ms.append(e[0].elapsed_time(e[2]))
-            print(json.dumps({"what": "train_step", "depth": depth, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
+            print(json.dumps({"what": "train_step", "depth": "MPN_TRAIN_TRUNK(%d)" % a.trunk_layers if depth == "trunk" else depth, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
                               "ms_step_min": round(float(np.min(step_ms)), 3), "ms_iteration_median": round(float(np.median(iter_ms)), 3),
                               "steps": a.steps, "device": name}), flush=True)
             if depth == 2:
@@ -82,6 +90,18 @@ def main():
                 print(json.dumps({"what": "conv3x3_wgrad_kernel", "layer": "conv5_3 512->512 38x63, one image", "ms": round(ms.value, 4), "gflop": round(gflop, 2),
                                   "tflops": round(gflop / ms.value, 1), "floor_ms_at_157.3TF": round(floor_ms, 4), "share_of_floor": round(floor_ms / ms.value, 3),
                                   "device": name}), flush=True)
+            if depth == "trunk":
+                ms, layer = C.c_float(), C.c_int()
+                _lib.check(lib.mpn_debug_bench_train_poolbwd(net._h, 50, C.byref(ms), C.byref(layer)), "mpn_debug_bench_train_poolbwd")
+                cout, h, w = P["conv_w"][layer.value].shape[0], H, W
+                for l in range(layer.value):   # the layer's own map size: halved, rounding up, at every pool below it
+                    if net._pool[l]:
+                        h, w = (h + 1) // 2, (w + 1) // 2
+                mb = 4 * cout * (2 * h * w + ((h + 1) // 2) * ((w + 1) // 2)) / 1e6
+                floor_us = mb / 6.3
+                print(json.dumps({"what": "maxpool2x2_backward_kernel", "layer": "conv layer %d, %d x %d x %d, one image" % (layer.value, cout, h, w),
+                                  "us": round(ms.value * 1e3, 2), "mbytes_moved": round(mb, 1), "floor_us_at_6.3TBps": round(floor_us, 2),
+                                  "share_of_floor": round(floor_us / (ms.value * 1e3), 3), "device": name}), flush=True)
             net.train_end()
         net.close()
 
