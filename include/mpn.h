@@ -246,14 +246,21 @@ int mpn_linear_forward(const float *d_x, int M, int K, const float *d_w, const f
  * ---------------------------------------------------------------------------------------------- */
 
 /* utils.convertFrom, 2-D path, for every 4-column class block (utils.lua:229-247,
- * ImageDetect.lua:183-185).  d_boxes [N,4] original-image boxes, d_deltas [N,4C] -> d_out [N,4C]. */
+ * ImageDetect.lua:183-185).  d_boxes [N,4] original-image boxes, d_deltas [N,4C] -> d_out [N,4C].
+ * Alignment: the kernel moves whole 4-vectors, so d_boxes, d_deltas and d_out must each be 16-byte aligned (any
+ * hipMalloc'd base is; a view that starts at a row of a contiguous table is too, one that starts inside a row may not
+ * be).  A pointer that is not is refused with MPN_EINVAL and a message naming the argument; nothing is launched. */
 int mpn_bbox_decode(const float *d_boxes, const float *d_deltas, int N, int C, float *d_out, void *stream);
 
-/* Tester_FRCNN.lua:75-78: in place, x -> [1,im_w], y -> [1,im_h] on the (x,y) pairs of d_bbox. */
+/* Tester_FRCNN.lua:75-78: in place, x -> [1,im_w], y -> [1,im_h] on the (x,y) pairs of d_bbox.  A NaN stays a NaN.
+ * Alignment: d_bbox must be 8-byte aligned (the kernel moves whole pairs); otherwise MPN_EINVAL naming it, nothing launched. */
 int mpn_clamp_boxes(float *d_bbox, size_t n_pairs, float im_w, float im_h, void *stream);
 
 /* Tester_FRCNN.lua:106-116 for all classes j = first_cls .. C-1 at once: rows with score > thresh,
- * in row order -> d_scored [C-first_cls, N, 5], d_counts [C-first_cls], d_src_idx (may be NULL). */
+ * in row order -> d_scored [C-first_cls, N, 5], d_counts [C-first_cls], d_src_idx (may be NULL).  A NaN score is not
+ * greater than any threshold: its row is dropped.  Rows of d_scored beyond d_counts[c] are not written.
+ * Alignment: d_bbox [N,4C] must be 16-byte aligned (each class's 4-vector is read whole); otherwise MPN_EINVAL naming
+ * it, nothing launched.  d_scores and d_scored (5-float rows) need only their natural 4 bytes. */
 int mpn_select_scored(const float *d_scores, const float *d_bbox, int N, int C, int first_cls, float thresh,
                       float *d_scored, int *d_counts, int *d_src_idx, void *stream);
 

@@ -3,6 +3,7 @@
 // clamp, per-class scored-box selection and the global top-k.  Each kernel cites the reference
 // lines it mirrors; fp32 arithmetic follows the reference's operation order (no FMA contraction).
 #include <cmath>
+#include <cstdint>
 
 #include "mpn_internal.h"
 
@@ -882,14 +883,27 @@ int launch_bbox_decode(const float *d_boxes, const float *d_deltas, int N, int C
 }
 }  // namespace mpn
 
+// The decode, clamp and selection kernels read and write whole float4 / float2 vectors: a pointer off that boundary is refused by name
+// (include/mpn.h) before anything is launched.
+static int check_aligned(const char *fn, const char *arg, const void *ptr, size_t bytes) {
+  if ((reinterpret_cast<uintptr_t>(ptr) & (bytes - 1)) == 0) return MPN_OK;
+  set_error("%s: invalid argument: %s must be %zu-byte aligned", fn, arg, bytes);
+  return MPN_EINVAL;
+}
+#define MPN_CHECK_ALIGNED(ptr, bytes) do { if (int rc_al_ = check_aligned(__func__, #ptr, ptr, bytes)) return rc_al_; } while (0)
+
 extern "C" int mpn_bbox_decode(const float *d_boxes, const float *d_deltas, int N, int C, float *d_out, void *stream) {
   MPN_CHECK_ARG(N >= 0 && C > 0);
+  MPN_CHECK_ALIGNED(d_boxes, 16);
+  MPN_CHECK_ALIGNED(d_deltas, 16);
+  MPN_CHECK_ALIGNED(d_out, 16);
   if (N == 0) return MPN_OK;
   MPN_CHECK_ARG(d_boxes && d_deltas && d_out);
   return launch_bbox_decode(d_boxes, d_deltas, N, C, d_out, 0, 0.f, 0.f, as_stream(stream));
 }
 
 extern "C" int mpn_clamp_boxes(float *d_bbox, size_t n_pairs, float im_w, float im_h, void *stream) {
+  MPN_CHECK_ALIGNED(d_bbox, 8);
   if (n_pairs == 0) return MPN_OK;
   MPN_CHECK_ARG(d_bbox);
   hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)cdiv_sz(n_pairs, 256)), dim3(256), 0, as_stream(stream), d_bbox, n_pairs,
@@ -901,6 +915,7 @@ extern "C" int mpn_clamp_boxes(float *d_bbox, size_t n_pairs, float im_w, float 
 extern "C" int mpn_select_scored(const float *d_scores, const float *d_bbox, int N, int C, int first_cls, float thresh,
                                  float *d_scored, int *d_counts, int *d_src_idx, void *stream) {
   MPN_CHECK_ARG(N >= 0 && C > 0 && first_cls >= 0 && first_cls <= C && d_counts);
+  MPN_CHECK_ALIGNED(d_bbox, 16);
   int n_cls = C - first_cls;
   if (n_cls == 0) return MPN_OK;
   if (N == 0) {
@@ -946,6 +961,18 @@ extern "C" int mpn_keep_top_k_sorted(const float *d_keep, const int *d_n_keep, i
 }
 
 #ifdef MPN_DEBUG_HOOKS
+// tests/test_gpu_box_kernels_numerics.py: launch_bbox_decode with its fused clamp, which no product entry reaches (mpn_bbox_decode never clamps)
+extern "C" int mpn_debug_bbox_decode_clamp(const float *d_boxes, const float *d_deltas, int N, int C, float *d_out, int clamp, float im_w, float im_h,
+                                           void *stream) {
+  MPN_CHECK_ARG(N >= 0 && C > 0);
+  MPN_CHECK_ALIGNED(d_boxes, 16);
+  MPN_CHECK_ALIGNED(d_deltas, 16);
+  MPN_CHECK_ALIGNED(d_out, 16);
+  if (N == 0) return MPN_OK;
+  MPN_CHECK_ARG(d_boxes && d_deltas && d_out);
+  return launch_bbox_decode(d_boxes, d_deltas, N, C, d_out, clamp, im_w, im_h, as_stream(stream));
+}
+
 extern "C" int mpn_debug_get_topk_trace(unsigned long long *h_out8) {
   MPN_CHECK_ARG(h_out8);
   MPN_CHECK_HIP(hipMemcpyFromSymbol(h_out8, HIP_SYMBOL(mpn::g_topk_trace), 8 * sizeof(unsigned long long)));

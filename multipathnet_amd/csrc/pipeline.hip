@@ -128,6 +128,32 @@ __global__ __launch_bounds__(256) void integral_softmax_mean_kernel(const float 
   for (int c = lane; c < C; c += 64, ++q) scores[(size_t)row * C + c] = accv[q] * inv;
 }
 
+// The four score / box kernels' launches, in one place each: the pipeline stages below and (debug flavour) mpn_debug_head_post run the same geometry.
+static int launch_head_softmax(const float *head, int ld, int M, int C, float *scores, hipStream_t s) {
+  hipLaunchKernelGGL(head_softmax_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, head, ld, M, C, scores);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+static int launch_integral_softmax_mean(const float *logits, int M, int K, int C, float *scores, hipStream_t s) {
+  hipLaunchKernelGGL(integral_softmax_mean_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, logits, M, K, C, scores);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+// mean4 / std4: the BBoxNorm constants; std4[0] == 0 means the model has no BBoxNorm (the deltas are used as they are)
+static int launch_head_decode(const float *head, int ld, int col0, int M, int C, const float *boxes, const float *mean4, const float *std4, int clamp,
+                              float im_w, float im_h, float *raw, float *out, hipStream_t s) {
+  const bool norm = std4[0] != 0.0f;
+  hipLaunchKernelGGL(head_decode_kernel, dim3((unsigned)cdiv_sz((size_t)M * C, 256)), dim3(256), 0, s, head, ld, col0, M, C, boxes,
+                     norm ? 1 : 0, mean4[0], mean4[1], mean4[2], mean4[3], std4[0], std4[1], std4[2], std4[3], clamp, im_w, im_h, raw, out);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+static int launch_augment_merge(const float *sA, const float *bA, float *s_io, float *b_io, int M, int C, int clamp, float im_w, float im_h, hipStream_t s) {
+  hipLaunchKernelGGL(augment_merge_kernel, dim3((unsigned)cdiv_sz((size_t)M * C, 256)), dim3(256), 0, s, sA, bA, s_io, b_io, M, C, clamp, im_w, im_h);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
 // pooled C8 matrix [cb*PP+bin][Mp][8] -> reference order [N, C*PP] (debug / parity only)
 __global__ void unpack_pooled_kernel(const float *__restrict__ xc8, int N, int C, int PP, int Mp, float *__restrict__ out) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1126,14 +1152,9 @@ static int run_integral_heads(mpn_frcnn *p, const float *d_boxes, int N, int H, 
     if (rc == MPN_OK) rc = linear_c8(p->cat + (size_t)n_fov * Fcb * Mp * 8, N, F, p->wbbox, p->bbbox, 4 * C, 0, nullptr, p->bbox_rm, s, Mp, nullptr, 1); }
   if (rc) return rc;
   ProfScope ps_post(p, MPN_PROF_POST, s);
-  hipLaunchKernelGGL(integral_softmax_mean_kernel, dim3(cdiv(N, 4)), dim3(256), 0, s, p->cls_rm, N, K, C, p->scores);
-  MPN_CHECK_LAUNCH();
-  const bool norm = c.bbox_std[0] != 0.0f;
-  hipLaunchKernelGGL(head_decode_kernel, dim3((unsigned)cdiv_sz((size_t)N * C, 256)), dim3(256), 0, s, p->bbox_rm, 4 * C, 0, N, C, d_boxes,
-                     norm ? 1 : 0, c.bbox_mean[0], c.bbox_mean[1], c.bbox_mean[2], c.bbox_mean[3], c.bbox_std[0], c.bbox_std[1],
-                     c.bbox_std[2], c.bbox_std[3], clamp, (float)W, (float)H, p->bbox_raw, p->bbox);
-  MPN_CHECK_LAUNCH();
-  return MPN_OK;
+  rc = launch_integral_softmax_mean(p->cls_rm, N, K, C, p->scores, s);
+  if (rc) return rc;
+  return launch_head_decode(p->bbox_rm, 4 * C, 0, N, C, d_boxes, c.bbox_mean, c.bbox_std, clamp, (float)W, (float)H, p->bbox_raw, p->bbox, s);
 }
 
 // getImages' rescaled image buffers (ImageDetect.lua:34-43), grown to hold `need` / `need_t` bytes
@@ -1279,13 +1300,10 @@ static int run_plain_heads(mpn_frcnn *p, const float *y7, const float *dec_boxes
     rc = linear_c8(y7, N, F, p->wh, p->bh, 5 * C, 0, nullptr, p->head, hs, 0, nullptr, 1); }
   if (rc) return rc;
   ProfScope ps_post(p, MPN_PROF_POST, hs);
-  hipLaunchKernelGGL(head_softmax_kernel, dim3(cdiv(N, 4)), dim3(256), 0, hs, p->head, 5 * C, N, C, p->scores);
-  MPN_CHECK_LAUNCH();
-  const bool norm = c.bbox_std[0] != 0.0f;
-  hipLaunchKernelGGL(head_decode_kernel, dim3((unsigned)cdiv_sz((size_t)N * C, 256)), dim3(256), 0, hs, p->head, 5 * C, C, N, C, dec_boxes,
-                     norm ? 1 : 0, c.bbox_mean[0], c.bbox_mean[1], c.bbox_mean[2], c.bbox_mean[3], c.bbox_std[0], c.bbox_std[1],
-                     c.bbox_std[2], c.bbox_std[3], clamp, (float)W, (float)H, p->bbox_raw, p->bbox);
-  MPN_CHECK_LAUNCH();
+  rc = launch_head_softmax(p->head, 5 * C, N, C, p->scores, hs);
+  if (rc) return rc;
+  rc = launch_head_decode(p->head, 5 * C, C, N, C, dec_boxes, c.bbox_mean, c.bbox_std, clamp, (float)W, (float)H, p->bbox_raw, p->bbox, hs);
+  if (rc) return rc;
   p->last_n = N;
   return MPN_OK;
 }
@@ -1403,10 +1421,7 @@ static int run_detect_aug(mpn_frcnn *p, const float *d_image, int H0, int W0, co
   rc = run_detect(p, d_image ? p->aug_img : nullptr, H0, W0, p->aug_boxes, N, s, 0, two_maps ? &p->mir : &p->up);
   if (rc) return rc;
   ProfScope ps(p, MPN_PROF_POST, s);
-  hipLaunchKernelGGL(augment_merge_kernel, dim3((unsigned)cdiv_sz((size_t)N * C, 256)), dim3(256), 0, s, p->aug_scores, p->aug_bbox, p->scores,
-                     p->bbox, N, C, clamp, (float)W0, (float)H0);
-  MPN_CHECK_LAUNCH();
-  return MPN_OK;
+  return launch_augment_merge(p->aug_scores, p->aug_bbox, p->scores, p->bbox, N, C, clamp, (float)W0, (float)H0, s);
 }
 
 extern "C" int mpn_frcnn_detect(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N,
@@ -2475,6 +2490,40 @@ extern "C" int mpn_debug_bench_fc6(mpn_frcnn *p, int iters, float *ms_out) {
   ScratchScope scratch_scope(&p->scratch);
   const int N = p->last_n, F = p->cfg.fc_dim;
   return time_back_to_back(iters, ms_out, [&] { return linear_c8(p->x6, N, p->K6, p->w6, p->b6, F, 1, p->y6, nullptr, nullptr, 0, nullptr, 1); });
+}
+// tests/test_gpu_box_kernels_numerics.py (debug flavour only): ONE of the four score / box kernels between the last GEMM and NMS, through the
+// pipeline's own launcher, on caller-supplied device buffers.  `which`: 0 head_softmax_kernel (d_a = head [M, ld], d_out = scores [M, C]);
+// 1 integral_softmax_mean_kernel (d_a = logits [M, K*C], d_out = scores [M, C]); 2 head_decode_kernel (d_a = head [M, ld], deltas at columns
+// col0 .. col0 + 4C, d_b = boxes [M, 4], h_mean4 / h_std4 = the BBoxNorm constants or both NULL for none, d_raw [M, 4C] or NULL, d_out = boxes
+// [M, 4C]); 3 augment_merge_kernel (d_a = upright scores [M, C], d_b = upright boxes [M, 4C], d_raw = the mirrored half's scores and d_out its
+// boxes, both merged in place).  Refuses what handle creation refuses for the pipeline (C < 1, C > 256 for the integral kernel, M < 0); M == 0
+// launches nothing.
+extern "C" int mpn_debug_head_post(int which, const float *d_a, const float *d_b, int ld, int col0, int M, int C, int K, const float *h_mean4,
+                                   const float *h_std4, int clamp, float im_w, float im_h, float *d_raw, float *d_out, void *stream) {
+  MPN_CHECK_ARG(which >= 0 && which <= 3 && M >= 0 && C >= 1);
+  hipStream_t s = as_stream(stream);
+  static const float zero4[4] = {0.f, 0.f, 0.f, 0.f};
+  switch (which) {
+    case 0:
+      MPN_CHECK_ARG(ld >= C);
+      if (M == 0) return MPN_OK;
+      MPN_CHECK_ARG(d_a && d_out);
+      return launch_head_softmax(d_a, ld, M, C, d_out, s);
+    case 1:
+      MPN_CHECK_ARG(C <= 256 && K >= 1);
+      if (M == 0) return MPN_OK;
+      MPN_CHECK_ARG(d_a && d_out);
+      return launch_integral_softmax_mean(d_a, M, K, C, d_out, s);
+    case 2:
+      MPN_CHECK_ARG(col0 >= 0 && ld >= col0 + 4 * C && (h_mean4 != nullptr) == (h_std4 != nullptr));
+      if (M == 0) return MPN_OK;
+      MPN_CHECK_ARG(d_a && d_b && d_out);
+      return launch_head_decode(d_a, ld, col0, M, C, d_b, h_mean4 ? h_mean4 : zero4, h_std4 ? h_std4 : zero4, clamp, im_w, im_h, d_raw, d_out, s);
+    default:
+      if (M == 0) return MPN_OK;
+      MPN_CHECK_ARG(d_a && d_b && d_raw && d_out);
+      return launch_augment_merge(d_a, d_b, d_raw, d_out, M, C, clamp, im_w, im_h, s);
+  }
 }
 #endif
 

@@ -87,13 +87,20 @@ def boxoverlap(a, b):
     return out
 
 
+def _vec4(t):
+    """mpn_bbox_decode moves whole 4-vectors (include/mpn.h: 16-byte aligned pointers).  A fresh allocation and a row of a contiguous table are
+    aligned; a contiguous view that starts inside a row (flat[1:]) is not, and is copied to a fresh allocation."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def convertFrom(out, bbox, y):
     """utils.convertFrom(out, bbox [N,4], y [N,4]) — decodes regression deltas into `out` (may alias y)."""
     assert bbox.size(1) == y.size(1) and bbox.size(0) == y.size(0)
     res = torch.empty_like(y)
     if y.size(0):
-        check(_lib.load().mpn_bbox_decode(_f(bbox.contiguous()), _f(y.contiguous()), y.size(0), 1, _f(res), _stream()),
-              "convertFrom")
+        b, d = _vec4(bbox), _vec4(y)  # named: two temporaries in one call could share a block (the first is freed before the second is made)
+        check(_lib.load().mpn_bbox_decode(_f(b), _f(d), y.size(0), 1, _f(res), _stream()), "convertFrom")
     out.copy_(res)
     return out
 
@@ -114,8 +121,8 @@ def decode_all_classes(boxes, deltas):
     """ImageDetect.lua:183-185: convertFrom over every 4-column class block at once."""
     res = torch.empty_like(deltas)
     if deltas.size(0):
-        check(_lib.load().mpn_bbox_decode(_f(boxes), _f(deltas), deltas.size(0), deltas.size(1) // 4, _f(res), _stream()),
-              "convertFrom")
+        b, d = _vec4(boxes), _vec4(deltas)
+        check(_lib.load().mpn_bbox_decode(_f(b), _f(d), deltas.size(0), deltas.size(1) // 4, _f(res), _stream()), "convertFrom")
     return res
 
 
