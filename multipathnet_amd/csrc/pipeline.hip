@@ -20,7 +20,7 @@
 
 #include "dense.h"
 #include "resnet.h"
-#include "train.h"
+#include "pipeline.h"
 
 namespace mpn {
 int launch_bbox_decode(const float *d_boxes, const float *d_deltas, int N, int C, float *d_out, int clamp, float im_w,
@@ -164,6 +164,12 @@ __global__ void unpack_pooled_kernel(const float *__restrict__ xc8, int N, int C
   out[t] = xc8[(((size_t)(c >> 3) * PP + bin) * Mp + n) * 8 + (c & 7)];
 }
 
+int launch_unpack_pooled(const float *xc8, int N, int C, int PP, int Mp, float *out) {
+  hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz((size_t)N * C * PP, 256)), dim3(256), 0, nullptr, xc8, N, C, PP, Mp, out);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
 __global__ void copy_cols_kernel(const float *__restrict__ src, int ld, int col0, int M, int ncols, float *__restrict__ dst) {
   size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)M * ncols) return;
@@ -266,203 +272,6 @@ __global__ void shard_unpack_classes_kernel(const float *__restrict__ all, int n
 
 using namespace mpn;
 
-struct ConvLayer {
-  int Cin, Cout, pool;
-  float *wpk = nullptr, *bpk = nullptr, *wino = nullptr;  // direct-conv and Winograd-transformed weights
-  float *w36 = nullptr;     // first layer (<= 4 input channels, no pool): the K = 36 formulation's weights
-  float *out = nullptr;     // C8P buffer for the conv output (max image size)
-  float *pooled = nullptr;  // C8P buffer for the pooled output (when pool)
-};
-
-struct mpn_frcnn {
-  mpn_frcnn_config cfg;
-  std::vector<int> cout, pool_after;
-  std::vector<ConvLayer> conv;
-  float *img_c8p = nullptr;
-  std::vector<std::pair<float *, size_t>> act_bufs;  // for re-zeroing when the image size changes
-  int last_h = -1, last_w = -1;                       // the (canvas) geometry the halos are laid for
-  int keep_prepool_from = -1;                         // >= 0: run_trunk also writes the pre-pool map (L.out) of the pooled layers from this one up (mpn_frcnn_train_add only)
-  int feat_c = 0;
-  // One cached final trunk map (VGG trunks): what a detect on cached features pools from.  run_trunk fills the record it is handed and no other.
-  struct CachedMap {
-    Act act = Act{};           // the map
-    float *buf = nullptr;      // where the trunk writes it (nullptr: the last layer's own buffer)
-    float *pm = nullptr;       // its pixel-major copy (roi_pool_pm) ...
-    bool pm_valid = false;     // ... once the first pooling after a trunk run has built it
-    int h = -1, w = -1;        // network-input size of the image it was computed from (-1: none cached)
-    void invalidate() { act = Act{}; h = w = -1; pm_valid = false; }
-  };
-  CachedMap up, mir;           // of the upright image; of the mirrored one (plain Fast R-CNN handles under mpn_frcnn_set_augment: buf and pm exist)
-  // head
-  int K6 = 0, Mp = 0, n_head = 0;
-  float *w6 = nullptr, *b6 = nullptr, *w7 = nullptr, *b7 = nullptr, *wh = nullptr, *bh = nullptr;
-  float *rois = nullptr, *x6 = nullptr, *y6 = nullptr, *y7 = nullptr, *head = nullptr;
-  float *scores = nullptr, *bbox = nullptr, *bbox_raw = nullptr;
-  // NMS-stage buffers: two sets so that image i's NMS (side stream) overlaps image i+1's trunk
-  float *scored_b[2] = {nullptr, nullptr}, *keep_b[2] = {nullptr, nullptr}, *thresh_b[2] = {nullptr, nullptr};
-  float *voted_b[2] = {nullptr, nullptr}, *voted = nullptr;      // bbox-voted tables (opt.test_bbox_voting)
-  float *it_scores = nullptr, *it_bbox = nullptr, *it_boxes = nullptr;  // iterative localisation: rows of both passes
-  float *scaled = nullptr, *scale_tmp = nullptr;  // getImages' rescaled image (ImageDetect.lua:34-43), grown on demand
-  size_t scaled_bytes = 0, scale_tmp_bytes = 0;
-  int *counts_b[2] = {nullptr, nullptr}, *keep_idx_b[2] = {nullptr, nullptr}, *n_keep_b[2] = {nullptr, nullptr};
-  float *scored = nullptr, *keep = nullptr, *thresh = nullptr;   // set of the most recent call
-  int *counts = nullptr, *keep_idx = nullptr, *n_keep = nullptr;
-  hipStream_t side = nullptr;           // side stream (default priority: see create) for the heads and the NMS / top-k tail of the pipelined forms
-  // Deferred heads (pipelined forms of the plain Fast R-CNN head): cls / bbox GEMM + softmax + decode + select of image i run on `side`
-  // too, under image i + 1's first trunk layers — they are 51 us of kernels that leave most of the GPU idle.  What they read is held per
-  // buffer set: fc7's output (y7_b) and a copy of the caller's boxes (boxes_b); join_tail(b) orders their reuse two calls later.
-  hipStream_t defer_stream = nullptr;   // non-null while run_detect is to hand the heads over to it
-  bool was_deferred = false;            // the previous pipelined call handed its heads over
-  int defer_set = 0;
-  float *y7_b[2] = {nullptr, nullptr}, *boxes_b[2] = {nullptr, nullptr}, *y7_last = nullptr;  // y7_last: where the last head left fc7's output
-  hipEvent_t ev_fc7 = nullptr;
-  hipEvent_t ev_head[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
-  bool tail_pending[2] = {false, false};
-  unsigned long long seq = 0;
-  float *dbg = nullptr;
-  size_t dbg_bytes = 0;
-  int last_n = 0, last_rows = 0;
-  // ---- MultiPathNet head (models/multipathnet.lua:64-120); empty for plain Fast R-CNN
-  struct Tower { int region, use4, use3, total_feat; float *mix_w, *mix_b, *w6, *b6, *w7, *b7; unsigned short *w6_s3 = nullptr, *w7_s3 = nullptr; };
-  bool is_mpnet = false;
-  std::vector<int> rn_region;   // ResNet towers: Foveal region per tower (empty = plain resnet.lua)
-  ResNetGraph *rn = nullptr;  // ResNet Fast R-CNN (mpn_resnet_create): trunk + per-ROI layer4 replace the VGG convs / fc6 / fc7
-  int tap3 = -1, tap4 = -1, n_integral = 1;
-  bool conv345_norm = true;  // model_conv345_norm (model_utils.lua:209): false = the MulConstant(1, 1/30, 1/200) branch
-  std::vector<Tower> towers;
-  float *fov = nullptr, *tx = nullptr, *ty = nullptr, *tz6 = nullptr, *cat = nullptr, *cls_rm = nullptr, *bbox_rm = nullptr;
-  float *wcls = nullptr, *bcls = nullptr, *wbbox = nullptr, *bbbox = nullptr;
-  Act tap_act[3];  // [1], [2]: conv4, conv3 of the last trunk run ([0], conv5, is the upright record's map: up.act)
-  float *vmax_tab[3] = {nullptr, nullptr, nullptr};  // vertical range-max tables of the three maps (MultiPathNet ROI pools)
-  bool vmax_built[3] = {false, false, false};         // built for the current tap_act maps (per map: the pooling stream builds a map's tables where its first pooling is enqueued)
-  bool vmax_pm = false;                               // ... in the pixel-major form
-  float *mix_scale = nullptr;                         // [2 tower parities][3][Mp]: per-(map, ROI) nn.Normalize scales the mix GEMM applies
-  // tower t + 1's skip pooling (L2 -> L1 bound, no matrix work) runs on its own stream under tower t's GEMMs (matrix-bound):
-  float *tx2 = nullptr;                               // second pooled-operand buffer (towers alternate between tx and tx2)
-  // round 6: two towers that pool the SAME Foveal region, one's maps a prefix of the other's (models/multipathnet.lua:74-113: the "het"
-  // tower = region 2 with conv5 + conv4 + conv3, tower 2 = region 2 with conv5 + conv4), share ONE pooled operand: the wider one is pooled
-  // once into tx3, the narrower tower's mix GEMM reads its K prefix (the per-map nn.Normalize scales are per (map, region, ROI): the same)
-  float *tx3 = nullptr;
-  int share_provider = -1, share_consumer = -1;       // tower indices (-1: no such pair)
-  // The pooling stream IS the side stream (the NMS / top-k tail's) since the end of round 6: the tail of image i - 1 runs under image i's
-  // trunk and is long over when image i's first pooling is enqueued behind it, and the handle needs one stream fewer.  With a stream of its own
-  // the host-fed form drove five streams on ROCm's four hardware queues, and whichever stream shared a queue with the upload stream waited
-  // behind the upload's completion marker: 0.2 ms per image (configs[2] host-fed 13.26-13.31 -> 13.07-13.13 ms, profiles/r06_hw_queues.txt).
-  hipStream_t pool_stream = nullptr;   // alias of `side` (never destroyed on its own); nullptr = no overlapped pooling (plain Fast R-CNN handles)
-  bool pool_on_side = false;
-  hipEvent_t ev_pool_done[3] = {nullptr, nullptr, nullptr}, ev_mix_done[3] = {nullptr, nullptr, nullptr}, ev_pool_go = nullptr;
-  unsigned short *w6_s3 = nullptr, *x6_s3 = nullptr;  // MPN_FC_SPLIT3: fc6's weights (packed once) and operand (per image) as three bf16 planes
-  unsigned short *w7_s3 = nullptr, *y6_s3 = nullptr;  // ... and fc7's
-  unsigned short *ty_s3[2] = {nullptr, nullptr}, *tz6_s3[2] = {nullptr, nullptr};  // MultiPathNet towers: the per-lane fc6 / fc7 operands as planes
-  // two tower LANES (round 6): the towers of one image are independent until the concat (ModelParallelTable.lua:195-242 ran them on
-  // different GPUs), so towers 1, 3 run on the handle's second tower stream with their own mix / fc6 buffers beside towers 0, 2, 4 on the
-  // caller's stream: one lane's short-K mix GEMM (6.1 block rounds on 256 CUs, 40 stages per tile) and the prologue / epilogue of every
-  // launch run under the other lane's fc6 / fc7 instead of leaving the matrix pipe idle.  Pure scheduling: bit-identical results.
-  hipStream_t tower_stream = nullptr;
-  hipEvent_t ev_lane_go = nullptr, ev_lane_done = nullptr;
-  float *ty2 = nullptr, *tz6_2 = nullptr;
-  DeviceOwner own;  // every device buffer, stream and event below that lives as long as the handle (mpn_internal.h)
-  Scratch scratch;  // split-K slabs, NMS masks, ... of THIS handle (bound to the calling thread by ScratchScope in every entry point)
-  int device = 0;   // the handle lives on the device that was current at creation
-  // host-fed throughput form (mpn_frcnn_test_one_pipelined_host): three staging sets filled by the copy stream
-  hipStream_t copy = nullptr;
-  static constexpr int kStage = 3;
-  float *stage_img[kStage] = {}, *stage_boxes[kStage] = {};
-  size_t stage_bytes[kStage] = {};
-  hipEvent_t ev_up[kStage] = {}, ev_consumed[kStage] = {};
-  bool used_pending[kStage] = {};
-  unsigned long long up_seq = 0;
-  // proposal sharding (mpn_frcnn_test_one_sharded): this rank's row / class records and the gathered ones, grown on demand
-  float *sh_buf[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t sh_bytes[4] = {0, 0, 0, 0};
-  // ---- captured launch graphs (round 4): the kernel chain of a SEGMENT of the per-image path — the head (transform .. decode, the
-  // iterative-localisation passes) or the tail (per-class NMS, voting, top-k) — is captured once per (pointers, shape) with
-  // hipStreamBeginCapture on the handle's capture stream and replayed with hipGraphLaunch on the caller's stream: one host call instead
-  // of 30-60 launches.  A segment is replayed only when (a) the previous execution of that segment kind on this handle had the same
-  // shape — the host-side state a real run leaves (cached-feature flags, sizes) is then exactly what it would be — (b) no library buffer
-  // was replaced since the capture (alloc_generation), (c) profiling is off.  Everything between the segments (cross-stream events,
-  // the select kernel, uploads) stays ordinary stream work, so the pipelined forms keep their overlap.
-  struct GraphKey {
-    int kind; const void *a, *b, *c, *d; int i0, i1, i2, i3;
-    bool operator<(const GraphKey &o) const {
-      return std::tie(kind, a, b, c, d, i0, i1, i2, i3) < std::tie(o.kind, o.a, o.b, o.c, o.d, o.i0, o.i1, o.i2, o.i3);
-    }
-  };
-  struct GraphEntry { hipGraphExec_t exec = nullptr; unsigned long long gen = 0, last_use = 0; bool failed = false; int seen = 0; hipStream_t last_stream = nullptr; bool launched = false; };
-  unsigned long long graph_clock = 0;
-  std::map<GraphKey, GraphEntry> graphs;
-  // the last few caller-pointer keys seen ONCE, per segment kind (a small ring: the pipelined forms alternate two output buffer sets, a host
-  // may rotate a handful): such a key enters `graphs` only at its second sighting while still in the ring, so a host that hands in fresh
-  // buffers every call never occupies the cache
-  static constexpr int kUnseen = 8;
-  GraphKey unseen[4][kUnseen] = {};
-  bool unseen_valid[4][kUnseen] = {};
-  int unseen_next[4] = {0, 0, 0, 0};
-  int graphs_on = 0;                 // mpn_frcnn_set_graphs / MPN_GRAPHS (opt-in: see create_handle)
-  hipStream_t cap_stream = nullptr;  // capture happens here (the caller's stream may be the legacy NULL stream, which cannot capture)
-  int seg_shape[4][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};  // shape of the last execution per segment kind
-  long graph_replays = 0, graph_captures = 0;
-  // ---- multi-scale testing (mpn_frcnn_set_scales): the image pyramid of the plain Fast R-CNN head
-  int n_scales = 0;                             // >= 2: a pyramid of scale_targets; otherwise the single scale cfg.scale_target
-  double scale_targets[MPN_MAX_SCALES] = {};
-  double create_scale_target = 0.0;             // cfg.scale_target at creation (set_scales(0) restores it)
-  float *ms_feat = nullptr, *ms_pm = nullptr;   // per-level final maps (C8P, canvas geometry) and their pixel-major copies
-  size_t ms_slot = 0, ms_pm_slot = 0;           // floats between levels (sized for the max_h x max_w canvas)
-  int ms_cap = 0;                               // levels allocated
-  double ms_scales[MPN_MAX_SCALES] = {};        // s_l of the cached maps
-  int ms_src[MPN_MAX_SCALES] = {};              // the level whose map level l uses (an earlier level with the same scale, or l)
-  int ms_h0 = -1, ms_w0 = -1;                   // original image size of the cached maps (-1: none)
-  bool ms_pm_valid = false;                     // the pixel-major copies go with the cached maps
-  // ---- horizontal-flip test-time augmentation (mpn_frcnn_set_augment)
-  int augment = 0;
-  float *aug_img = nullptr;                     // the mirrored ORIGINAL image (grown on demand: an image that getImages scales down may exceed max_h x max_w)
-  size_t aug_img_bytes = 0;
-  float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
-  // ---- training the head (mpn_frcnn_train_*): exists between train_begin and train_end
-  struct Train {
-    int depth = 0;                       // MPN_TRAIN_HEADS / _FC7 / _FC6 / _CONV(k) / _TRUNK(k) (k <= K: stored as MPN_TRAIN_CONV(k))
-    float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
-    float *vh = nullptr, *vbh = nullptr, *v7 = nullptr, *vb7 = nullptr, *v6 = nullptr, *vb6 = nullptr;  // momentum, in the layout of the weight it goes with
-    // the minibatch's own activations, C8 matrices at row pitch Mp (head: row-major [B, 5C]) — not detect's buffers, so a detect between
-    // two training calls disturbs nothing: fc6's operand (the ROI-pooled rows of the pending images), fc6's / fc7's outputs, the head's
-    float *x6 = nullptr, *y6 = nullptr, *y7 = nullptr, *head = nullptr;
-    float *gh = nullptr, *g7 = nullptr, *g6 = nullptr;       // gradients w.r.t. the head's output, fc7's and fc6's: C8 matrices at row pitch Mp
-    float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
-    int *labels = nullptr;
-    int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
-    // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
-    // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
-    struct ConvT {
-      float *v = nullptr, *vb = nullptr;       // momentum: `wpk` layout, [CoutP]
-      float *dw = nullptr, *db = nullptr;      // the step's gradients, summed over the images in train_add order
-      float *wpk_t = nullptr, *wino_t = nullptr, *zero_b = nullptr;  // the input gradient's convolution (pack_conv_weights_dgrad); wino_t where Cout >= 16
-    };
-    int kconv = 0, first = 0;
-    std::vector<ConvT> cl;               // [kconv], cl[j] goes with conv[first + j]
-    float *dx6 = nullptr;                // gradient at the pooled features, x6's layout
-    int32_t *argmax = nullptr;           // [max_rois, C, PH, PW] of the pending rows
-    float *prois = nullptr;              // [max_rois, 5] the pending rows' projected ROIs (the bins' windows)
-    float *acts = nullptr;               // per image: the block's input map and the kconv trained layers' outputs (before the pool where pooled), whole C8P planes,
-                                         // then the pooled map of every pooled trained layer but the last (the next trained layer's input)
-    size_t act_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, pool_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, act_img = 0; // floats: map j / pooled map j inside an image's slot; between two images' slots
-    float *gmap[2] = {nullptr, nullptr}; // the gradient maps of the image being worked on (ping-pong through the layers)
-    size_t gmap_bytes = 0;
-    float *wtmp = nullptr, *part = nullptr;  // a layer's weights in Torch layout (x 2: W, W'); conv3x3_wgrad's partial sums
-    int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
-    int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // final map size, row range
-    int img_nh[MPN_TRAIN_MAX_IMAGES] = {}, img_nw[MPN_TRAIN_MAX_IMAGES] = {};  // network-input size (every layer's map size follows from it)
-    DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
-  };
-  Train *train = nullptr;
-  // optional per-kernel-group timing with HIP events recorded on the launch stream
-  bool prof = false;
-  std::vector<hipEvent_t> ev_pool;
-  std::vector<int> ev_tag;   // one tag per (begin,end) pair
-  size_t ev_used = 0;
-  double prof_ms[MPN_PROF_NTAGS] = {0};
-  long prof_cnt[MPN_PROF_NTAGS] = {0};
-};
-
 struct ProfScope {
   mpn_frcnn *p; hipStream_t s; bool on;
   ProfScope(mpn_frcnn *p_, int tag, hipStream_t s_) : p(p_), s(s_), on(p_->prof) {
@@ -519,12 +328,12 @@ extern "C" void mpn_debug_set_defer_heads(int v) { g_defer_heads = v; }
 #endif
 
 // the final trunk map's size for an h x w network input: halved (rounding up) at every pooling layer
-static void final_map_size(const mpn_frcnn *p, int *h, int *w) {
+void mpn::final_map_size(const mpn_frcnn *p, int *h, int *w) {
   for (auto &L : p->conv) if (L.pool) { *h = (*h + 1) / 2; *w = (*w + 1) / 2; }
 }
 // getImages (ImageDetect.lua:34-43): s = target / min side, capped so that round(s * max side) <= cap (cap <= 0: none); the image is
 // resampled to (long)(H0 * s) x (long)(W0 * s), or kept as it is when s == 1.  Returns s.
-static double getimages_size(int H0, int W0, double target, double cap, int *H, int *W) {
+double mpn::getimages_size(int H0, int W0, double target, double cap, int *H, int *W) {
   const double sc = mpn_pick_scale(H0, W0, target, cap > 0.0 ? cap : 1e30);
   *H = H0; *W = W0;
   if (sc != 1.0) { *H = (int)((double)H0 * sc); *W = (int)((double)W0 * sc); }
@@ -537,13 +346,8 @@ static void joined_tables(const mpn_frcnn *p, float **scores, float **bbox) {
   const bool joined = p->cfg.num_iter > 1;
   *scores = joined ? p->it_scores : p->scores; *bbox = joined ? p->it_bbox : p->bbox;
 }
-static const char *handle_kind_name(const mpn_frcnn *p) {
+const char *mpn::handle_kind_name(const mpn_frcnn *p) {
   return p->is_mpnet ? "MultiPathNet (mpn_mpnet_create)" : "ResNet / op-list (mpn_resnet_create / mpn_graph_create)";
-}
-
-static void free_train_state(mpn_frcnn *p) {
-  delete p->train;  // (its DeviceOwner gives the buffers back)
-  p->train = nullptr;
 }
 
 // Everything the handle holds on the device goes back through its DeviceOwner (mpn_internal.h): no buffer, stream or event is named here.
@@ -1220,7 +1024,7 @@ static int run_pyramid_trunk(mpn_frcnn *p, const float *d_image, int H0, int W0,
 // The features of a detect: *feat = the final map to pool from (ResNet / op-list handles keep theirs inside the graph object).  H x W: the
 // network-input size of the H0 x W0 image at getImages' scale sc.  d_image == nullptr: recompute_features = false (ImageDetect.lua:107-111)
 // — the last call's map is reused (iterative localisation, Tester_FRCNN.lua:82-89).  `m`: the VGG trunk's record to fill or to read.
-static int obtain_features(mpn_frcnn *p, const float *d_image, int H0, int W0, int H, int W, double sc, mpn_frcnn::CachedMap *m, hipStream_t s, Act *feat) {
+int mpn::obtain_features(mpn_frcnn *p, const float *d_image, int H0, int W0, int H, int W, double sc, mpn_frcnn::CachedMap *m, hipStream_t s, Act *feat) {
   const mpn_frcnn_config &c = p->cfg;
   if (p->n_scales > 1) return run_pyramid_trunk(p, d_image, H0, W0, s, feat);  // getImages per level
   const float *img = d_image;
@@ -2067,420 +1871,10 @@ extern "C" int mpn_frcnn_nms_results(mpn_frcnn *p, const float **d_keep, const i
   return MPN_OK;
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------
-// Training the head with the trunk frozen (include/mpn.h mpn_frcnn_train_*; kernels: train.hip)
-// ------------------------------------------------------------------------------------------------------------------------------
-// the handle kinds and states that cannot train, each named (as refuse_multi_pass does for the throughput forms)
-static int refuse_train(const mpn_frcnn *p, const char *fn) {
-  if (p->is_mpnet || p->rn) {
-    set_error("%s: a %s handle cannot be trained: only mpn_frcnn_create's VGG Fast R-CNN head (fc6, fc7, cls + bbox) has a backward pass", fn, handle_kind_name(p));
-    return MPN_ESTATE;
-  }
-  if (p->cfg.fc_arith != MPN_FC_FP32) {
-    set_error("%s: an MPN_FC_SPLIT3 handle cannot be trained (its bf16 weight planes would go stale): create it with MPN_FC_FP32", fn);
-    return MPN_ESTATE;
-  }
-  if (p->n_scales > 1) {
-    set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales): restore a single scale first", fn, p->n_scales);
-    return MPN_ESTATE;
-  }
-  if (p->augment) {
-    set_error("%s: not supported with horizontal-flip augmentation (mpn_frcnn_set_augment): switch it off; flip training images with mpn_image_hflip / mpn_flip_boxes", fn);
-    return MPN_ESTATE;
-  }
-  if (p->tail_pending[0] || p->tail_pending[1]) {
-    set_error("%s: a pipelined call's tail is still pending on this handle: call mpn_frcnn_flush first", fn);
-    return MPN_ESTATE;
-  }
-  return MPN_OK;
-}
-
-// The forms of a conv layer that are derived from its master `wpk`: (forward) the Winograd and K = 36 packs detect's kernels read, rebuilt
-// IN PLACE by the packers creation used from the layer unpacked to Torch layout — bit-identical to what creation would build from the
-// exported weights; and, where the layer hands a gradient down (T.wpk_t), the input gradient's packs.  d_wtmp: 2 x Cout * Cin * 9 floats.
-static int refresh_conv_forms(const ConvLayer &L, const mpn_frcnn::Train::ConvT &T, float *d_wtmp, bool forward, hipStream_t s) {
-  int rc = unpack_conv_weights(L.wpk, nullptr, L.Cin, L.Cout, d_wtmp, nullptr, s);
-  if (rc == MPN_OK && forward && L.wino) rc = pack_conv_weights_wino(d_wtmp, L.Cin, L.Cout, L.wino, s);
-  if (rc == MPN_OK && forward && L.w36) rc = pack_conv_weights_first(d_wtmp, L.Cin, L.Cout, L.w36, s);
-  if (rc == MPN_OK && T.wpk_t) rc = pack_conv_weights_dgrad(d_wtmp, L.Cin, L.Cout, d_wtmp + (size_t)L.Cout * L.Cin * 9, T.wpk_t, T.zero_b, T.wino_t, s);
-  return rc;
-}
-
-// the size of conv[l]'s input and output maps for an H x W network input: halved (rounding up) at every pooling layer below it
-static void layer_map_size(const mpn_frcnn *p, int l, int H, int W, int *h, int *w) {
-  for (int i = 0; i < l; ++i) if (p->conv[i].pool) { H = (H + 1) / 2; W = (W + 1) / 2; }
-  *h = H; *w = W;
-}
-// Saved map j of the trained block for an H x W network input, at `base` (an image's slot): j = 0 the input of conv[first], j = 1..k the
-// post-ReLU output of conv[first + j - 1] before its pool; pooled: the pooled output of that layer (1 <= j < k, the layer pooled)
-static Act train_map(const mpn_frcnn *p, const mpn_frcnn::Train *t, float *base, int j, bool pooled, int H, int W) {
-  const int l = j == 0 ? t->first : t->first + j - 1;
-  int h, w;
-  layer_map_size(p, pooled ? l + 1 : l, H, W, &h, &w);
-  return make_act(base ? base + (pooled ? t->pool_off[j] : t->act_off[j]) : nullptr, j == 0 ? p->conv[l].Cin : p->conv[l].Cout, h, w);  // (no base: the geometry alone)
-}
-// the input map of trained layer j (1..k): saved map j - 1, or its pooled form where the layer below is pooled
-static Act train_in_map(const mpn_frcnn *p, const mpn_frcnn::Train *t, float *base, int j, int H, int W) {
-  return train_map(p, t, base, j - 1, j > 1 && p->conv[t->first + j - 2].pool, H, W);
-}
-
-extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight) {
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, "mpn_frcnn_train_begin");
-  if (rc) return rc;
-  if (p->train) { set_error("mpn_frcnn_train_begin: training has already begun on this handle (mpn_frcnn_train_end first)"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(depth >= MPN_TRAIN_HEADS);
-  const int n_conv = (int)p->conv.size();
-  int Kmax = 0;  // conv layers behind the trunk's last pooling layer (none when the trunk has no pooling layer: the block's input would be the image)
-  while (Kmax < n_conv && !p->conv[n_conv - 1 - Kmax].pool) ++Kmax;
-  if (Kmax == n_conv) Kmax = 0;
-  if (Kmax > MPN_TRAIN_MAX_CONV) Kmax = MPN_TRAIN_MAX_CONV;
-  int trunk_k = 0;  // > 0: MPN_TRAIN_TRUNK(k) with k > K — pooling layers among the trained ones
-  if (depth >= MPN_TRAIN_TRUNK(0)) {
-    const int k = depth - MPN_TRAIN_TRUNK(0), lim = std::min(n_conv - 1, (int)MPN_TRAIN_MAX_TRUNK);
-    if (k < 1 || k > lim) {
-      set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_TRUNK(%d), but k runs from 1 to %d on this trunk of %d conv layers: min(n_conv - 1, MPN_TRAIN_MAX_TRUNK = %d) — the first conv layer is never trained (its input is the image)",
-                depth, k, lim, n_conv, (int)MPN_TRAIN_MAX_TRUNK);
-      return MPN_EINVAL;
-    }
-    if (k <= Kmax) depth = MPN_TRAIN_CONV(k);  // no pooling layer among them: the same code, the same bits
-    else trunk_k = k;
-  } else if (depth > MPN_TRAIN_CONV(Kmax)) {
-    set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_CONV(%d), but only K = %d conv layers lie above the trunk's last pooling layer: a pooling layer is in the way (it has no backward pass)",
-              depth, depth - MPN_TRAIN_FC6, Kmax);
-    return MPN_EINVAL;
-  }
-  MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  const mpn_frcnn_config &c = p->cfg;
-  const int F = c.fc_dim, C = c.n_classes;
-  const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
-  std::unique_ptr<mpn_frcnn::Train> t(new mpn_frcnn::Train());  // (its DeviceOwner gives back what a failed attempt made)
-  t->depth = depth; t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
-  auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
-  bool ok = alloc0(&t->vh, lin_wpk_elems(round_up(F, 64), 5 * C) * sizeof(float)) && alloc0(&t->vbh, (size_t)lin_np(5 * C) * sizeof(float));
-  ok = ok && alloc0(&t->gh, (size_t)(lin_np(5 * C) / 8) * rec);
-  ok = ok && alloc0(&t->x6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->y6, (size_t)(lin_np(F) / 8) * rec) && alloc0(&t->y7, (size_t)(lin_np(F) / 8) * rec);
-  ok = ok && alloc0(&t->head, M * 5 * C * sizeof(float));
-  if (depth >= MPN_TRAIN_FC7) {
-    ok = ok && alloc0(&t->v7, lin_wpk_elems(round_up(F, 64), F) * sizeof(float)) && alloc0(&t->vb7, (size_t)lin_np(F) * sizeof(float));
-    ok = ok && alloc0(&t->g7, (size_t)(lin_np(F) / 8) * rec);
-  }
-  if (depth >= MPN_TRAIN_FC6) {
-    ok = ok && alloc0(&t->v6, lin_wpk_elems(round_up(p->K6, 64), F) * sizeof(float)) && alloc0(&t->vb6, (size_t)lin_np(F) * sizeof(float));
-    ok = ok && alloc0(&t->g6, (size_t)(lin_np(F) / 8) * rec);
-  }
-  ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
-  ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
-  if (depth > MPN_TRAIN_FC6) {
-    const int k = trunk_k ? trunk_k : depth - MPN_TRAIN_FC6, PP = c.pooled_h * c.pooled_w;
-    t->kconv = k; t->first = n_conv - k;
-    int mh = c.max_h, mw = c.max_w;
-    final_map_size(p, &mh, &mw);
-    ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
-    ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
-    size_t off = 0, wmax = 0, pmax = 0;
-    t->gmap_bytes = act_bytes(p->feat_c, mh, mw);  // the gradient maps: the largest of the saved maps' sizes (and the final map's)
-    auto slot = [&](const Act &a) { const size_t b = act_bytes(a.C, a.H, a.W); off += b / sizeof(float); t->gmap_bytes = std::max(t->gmap_bytes, b); };
-    for (int j = 0; j <= k; ++j) {  // map 0: the block's input; map j: the output of conv[first + j - 1], each at its own layer's size
-      t->act_off[j] = off;
-      slot(train_map(p, t.get(), nullptr, j, false, c.max_h, c.max_w));
-    }
-    for (int j = 1; j < k; ++j) {   // MPN_TRAIN_TRUNK: the pooled map of a pooled layer is the next trained layer's input
-      if (!p->conv[t->first + j - 1].pool) continue;
-      t->pool_off[j] = off;
-      slot(train_map(p, t.get(), nullptr, j, true, c.max_h, c.max_w));
-    }
-    t->act_img = off;
-    ok = ok && alloc0(&t->acts, off * MPN_TRAIN_MAX_IMAGES * sizeof(float));
-    ok = ok && alloc0(&t->gmap[0], t->gmap_bytes) && alloc0(&t->gmap[1], t->gmap_bytes);
-    t->cl.resize(k);
-    for (int j = 0; j < k && ok; ++j) {
-      const ConvLayer &L = p->conv[t->first + j];
-      mpn_frcnn::Train::ConvT &T = t->cl[j];
-      const size_t we = conv_wpk_elems(L.Cin, L.Cout) * sizeof(float), be = (size_t)conv_coutp(L.Cout) * sizeof(float);
-      ok = alloc0(&T.v, we) && alloc0(&T.vb, be) && alloc0(&T.dw, we) && alloc0(&T.db, be);
-      if (j > 0) {  // a trained layer lies below: this layer hands a gradient down
-        ok = ok && alloc0(&T.wpk_t, conv_wpk_elems(L.Cout, L.Cin) * sizeof(float)) && alloc0(&T.zero_b, (size_t)conv_coutp(L.Cin) * sizeof(float));
-        if (L.Cout >= 16) ok = ok && alloc0(&T.wino_t, conv_wino_elems(L.Cout, L.Cin) * sizeof(float));
-      }
-      wmax = std::max(wmax, (size_t)L.Cout * L.Cin * 9);
-      int lh, lw;
-      layer_map_size(p, t->first + j, c.max_h, c.max_w, &lh, &lw);
-      pmax = std::max(pmax, conv_wgrad_part_elems(L.Cin, L.Cout, lh, lw));
-    }
-    ok = ok && alloc0(&t->wtmp, 2 * wmax * sizeof(float)) && alloc0(&t->part, pmax * sizeof(float));
-    for (int j = 1; j < k && ok; ++j) ok = refresh_conv_forms(p->conv[t->first + j], t->cl[j], t->wtmp, false, nullptr) == MPN_OK;
-  }
-  if (ok) ok = hipDeviceSynchronize() == hipSuccess;
-  if (!ok) {
-    set_error("mpn_frcnn_train_begin: allocating the momentum / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
-    return MPN_ENOMEM;
-  }
-  p->train = t.release();  // all or nothing, as in mpn_frcnn_set_augment: published last, its presence says that every buffer exists
-  return MPN_OK;
-}
-
-extern "C" int mpn_frcnn_train_end(mpn_frcnn *p) {
-  MPN_CHECK_ARG(p != nullptr);
-  if (!p->train) { set_error("mpn_frcnn_train_end: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  free_train_state(p);
-  return MPN_OK;
-}
-
-extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
-                                   const int *d_labels, int n, void *stream) {
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, "mpn_frcnn_train_add");
-  if (rc) return rc;
-  mpn_frcnn::Train *t = p->train;
-  if (!t) { set_error("mpn_frcnn_train_add: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
-  const mpn_frcnn_config &c = p->cfg;
-  if (t->pending + n > c.max_rois) {
-    set_error("mpn_frcnn_train_add: %d pending rows + %d exceed the handle's max_rois (%d)", t->pending, n, c.max_rois);
-    return MPN_EINVAL;
-  }
-  double sc = 1.0;
-  int H = H0, W = W0;
-  if (c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
-  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
-    set_error("mpn_frcnn_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
-    return MPN_EINVAL;
-  }
-  if (t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
-    set_error("mpn_frcnn_train_add: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", t->n_img, MPN_TRAIN_MAX_IMAGES);
-    return MPN_EINVAL;
-  }
-  ScratchScope scratch_scope(&p->scratch);
-  hipStream_t s = as_stream(stream);
-  p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers and the ROI table are rewritten: the next head segment runs for real
-  Act feat;
-  bool pools = false;  // a pooled layer among the trained ones (MPN_TRAIN_TRUNK): this trunk pass also writes their pre-pool maps
-  for (int j = 0; j < t->kconv; ++j) pools = pools || p->conv[t->first + j].pool;
-  if (pools) p->keep_prepool_from = t->first;
-  rc = obtain_features(p, d_image, H0, W0, H, W, sc, &p->up, s, &feat);  // getImages' rescale + the frozen trunk, exactly as detect
-  p->keep_prepool_from = -1;
-  // the map now belongs to a training image: nothing a detect on cached features may pool from
-  p->up.invalidate(); p->mir.invalidate();
-  if (rc) return rc;
-  rc = mpn_project_im_rois(d_rois, n, sc, p->rois, s);
-  if (rc) return rc;
-  // this image's rows behind the pending ones: a shifted base pointer with the buffer's row pitch
-  rc = roi_pool_c8(feat, p->rois, n, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, t->x6 + (size_t)t->pending * 8,
-                   t->kconv ? t->argmax + (size_t)t->pending * p->feat_c * c.pooled_h * c.pooled_w : nullptr, s, 5, p->Mp);
-  if (rc) return rc;
-  if (t->kconv) {  // what the conv block's backward pass reads: the block's input, every trained layer's output, the rows' windows
-    const int i = t->n_img, h = feat.H, w = feat.W, k = t->kconv;
-    float *slot = t->acts + (size_t)i * t->act_img;
-    for (int j = 0; j <= k; ++j) {
-      const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones
-      // j == 0: what conv[first] read; j >= 1: the layer's output before its pool (the last layer's unpooled output is the final map)
-      const float *src = j == 0 ? (L.pool ? L.pooled : L.out) : ((j == k && !L.pool) ? feat.p : L.out);
-      const Act a = train_map(p, t, slot, j, false, H, W);
-      MPN_CHECK_HIP(hipMemcpyAsync(a.p, src, act_bytes(a.C, a.H, a.W), hipMemcpyDeviceToDevice, s));
-      if (j >= 1 && j < k && L.pool) {
-        const Act ap = train_map(p, t, slot, j, true, H, W);
-        MPN_CHECK_HIP(hipMemcpyAsync(ap.p, L.pooled, act_bytes(ap.C, ap.H, ap.W), hipMemcpyDeviceToDevice, s));
-      }
-    }
-    MPN_CHECK_HIP(hipMemcpyAsync(t->prois + (size_t)t->pending * 5, p->rois, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    t->img_h[i] = h; t->img_w[i] = w; t->img_nh[i] = H; t->img_nw[i] = W; t->img_row0[i] = t->pending; t->img_rows[i] = n;
-    ++t->n_img;
-  }
-  MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
-  t->pending += n;
-  return MPN_OK;
-}
-
-// The backward pass below fc6 (depth MPN_TRAIN_CONV(k)): the gradient at the pooled features, then per image — in train_add order — the
-// ROI-pooling backward into a zero-haloed gradient map and, last trained layer to first, the bias and weight gradients (added to the
-// step's sums) and the input gradient masked with the ReLU of the layer below.  No weight is touched: the caller updates afterwards.
-// MPN_TRAIN_TRUNK(k): every layer at its own size; at a pooled layer the gradient at its pooled output first goes through
-// maxpool2x2_backward_c8p (fused with the ReLU mask of the pre-pool map, so the input gradient handed to a pooled layer is not masked
-// on its own) into the other gradient map, whose halo is laid for the larger size first — as is every map written after it.
-static int train_conv_backward(mpn_frcnn *p, mpn_frcnn::Train *t, int B, hipStream_t s) {
-  const mpn_frcnn_config &c = p->cfg;
-  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp, k = t->kconv;
-  // dx6 = (g6 W6) .* [x6 > 0]: fc6's packed chunk order is x6's.  The mask is the last conv layer's ReLU mask (pooled values are map values)
-  int rc = linear_dgrad_c8(t->g6, Mp, B, c.fc_dim, p->w6, p->K6, t->x6, t->dx6, Mp, s);
-  for (int i = 0; i < t->n_img && rc == MPN_OK; ++i) {
-    const int h = t->img_h[i], w = t->img_w[i], nh = t->img_nh[i], nw = t->img_nw[i];
-    float *slot = t->acts + (size_t)i * t->act_img;
-    bool relaid = false;  // a pooling layer has been crossed: the memset below no longer is the halo of the maps' sizes
-    for (float *gm : t->gmap) MPN_CHECK_HIP(hipMemsetAsync(gm, 0, t->gmap_bytes, s));  // the halo is the input gradient's padding
-    int cur = 0;
-    Act G = make_act(t->gmap[cur], p->feat_c, h, w);
-    RoiBwd a{};
-    a.g = t->dx6; a.argmax = t->argmax; a.rois = t->prois; a.by_batch = 0; a.n0 = t->img_row0[i]; a.n1 = a.n0 + t->img_rows[i];
-    a.B = 1; a.C = p->feat_c; a.H = h; a.W = w; a.PH = c.pooled_h; a.PW = c.pooled_w; a.windows = (c.pooled_h <= 32 && c.pooled_w <= 32) ? 1 : 0;
-    a.g_n = 8; a.g_cb = (long)PP * Mp * 8; a.g_c = 1; a.g_bin = (long)Mp * 8;
-    a.o_b = 0; a.o_cb = (long)G.plane(); a.o_c = 1; a.o_y = (long)G.Wp * 8; a.o_x = 8;
-    a.scale = c.spatial_scale; a.rr = RoiRule{1.0f, 0, c.roi_bin_rule};
-    a.out = G.p + ((size_t)G.Wp + 1) * 8;
-    rc = roi_pool_backward(a, s);
-    for (int j = k; j >= 1 && rc == MPN_OK; --j) {
-      const ConvLayer &L = p->conv[t->first + j - 1];
-      const mpn_frcnn::Train::ConvT &T = t->cl[j - 1];
-      const Act X = train_in_map(p, t, slot, j, nh, nw);
-      if (L.pool) {  // G is the gradient at the pooled output: route it to the pre-pool map's maxima, masked with that map's ReLU
-        const Act Y = train_map(p, t, slot, j, false, nh, nw);
-        Act Gl = make_act(t->gmap[cur ^ 1], L.Cout, Y.H, Y.W);
-        rc = c8p_zero_halos(&Gl, 1, s);
-        if (rc == MPN_OK) rc = maxpool2x2_backward_c8p(Y, G, Gl, 1, s);
-        if (rc != MPN_OK) break;
-        G = Gl; cur ^= 1; relaid = true;
-      }
-      rc = conv_bias_grad(G, T.db, i > 0, s);
-      if (rc == MPN_OK) rc = conv3x3_wgrad(X, G, t->part, T.dw, i > 0, s);
-      if (rc != MPN_OK || j == 1) break;
-      Act dX = make_act(t->gmap[cur ^ 1], L.Cin, X.H, X.W);
-      if (relaid) rc = c8p_zero_halos(&dX, 1, s);
-      if (rc == MPN_OK) rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
-      if (rc == MPN_OK && !p->conv[t->first + j - 2].pool) rc = relu_mask_c8p(dX, X, s);  // (a pooled layer below: its pool's backward masks)
-      G = dX; cur ^= 1;
-    }
-  }
-  return rc;
-}
-
-extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, "mpn_frcnn_train_step");
-  if (rc) return rc;
-  mpn_frcnn::Train *t = p->train;
-  if (!t) { set_error("mpn_frcnn_train_step: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  if (t->pending <= 0) { set_error("mpn_frcnn_train_step: no pending rows (mpn_frcnn_train_add first)"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(std::isfinite(lr));
-  const mpn_frcnn_config &c = p->cfg;
-  const int B = t->pending, F = c.fc_dim, C = c.n_classes, Mp = p->Mp, PP = c.pooled_h * c.pooled_w;
-  ScratchScope scratch_scope(&p->scratch);
-  hipStream_t s = as_stream(stream);
-  // forward: detect's GEMMs on the pending rows (row pitch Mp); no dropout (opt.train_remove_dropouts)
-  rc = linear_c8(t->x6, B, p->K6, p->w6, p->b6, F, 1, t->y6, nullptr, s, Mp, nullptr, 1);
-  if (rc == MPN_OK) rc = linear_c8(t->y6, B, F, p->w7, p->b7, F, 1, t->y7, nullptr, s, Mp, nullptr, 1);
-  if (rc == MPN_OK) rc = linear_c8(t->y7, B, F, p->wh, p->bh, 5 * C, 0, nullptr, t->head, s, Mp, nullptr, 1);
-  if (rc) return rc;
-  LossCfg lc{};
-  for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
-  lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
-  lc.bbox_weight = t->bbox_weight;
-  rc = train_loss(t->head, B, C, t->rois, t->gt, t->labels, lc, t->gh, Mp, d_loss ? d_loss : t->loss, s);
-  // backward: every input gradient before the update of the weights it was computed with
-  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC7) rc = linear_dgrad_c8(t->gh, Mp, B, 5 * C, p->wh, F, t->y7, t->g7, Mp, s);
-  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC6) rc = linear_dgrad_c8(t->g7, Mp, B, F, p->w7, F, t->y6, t->g6, Mp, s);
-  if (rc == MPN_OK && t->kconv) rc = train_conv_backward(p, t, B, s);
-  if (rc == MPN_OK) rc = sgd_wgrad_c8(t->gh, Mp, t->y7, Mp, B, 5 * C, F, 1, p->wh, t->vh, lr, t->momentum, t->weight_decay, s);
-  if (rc == MPN_OK) rc = sgd_bias_c8(t->gh, Mp, B, 5 * C, p->bh, t->vbh, lr, t->momentum, s);
-  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC7) {
-    rc = sgd_wgrad_c8(t->g7, Mp, t->y6, Mp, B, F, F, 1, p->w7, t->v7, lr, t->momentum, t->weight_decay, s);
-    if (rc == MPN_OK) rc = sgd_bias_c8(t->g7, Mp, B, F, p->b7, t->vb7, lr, t->momentum, s);
-  }
-  if (rc == MPN_OK && t->depth >= MPN_TRAIN_FC6) {
-    rc = sgd_wgrad_c8(t->g6, Mp, t->x6, Mp, B, F, p->K6, PP, p->w6, t->v6, lr, t->momentum, t->weight_decay, s);
-    if (rc == MPN_OK) rc = sgd_bias_c8(t->g6, Mp, B, F, p->b6, t->vb6, lr, t->momentum, s);
-  }
-  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {  // the conv block: the master `wpk` in place, then every form derived from it
-    const ConvLayer &L = p->conv[t->first + j];
-    const mpn_frcnn::Train::ConvT &T = t->cl[j];
-    rc = conv_sgd(L.wpk, T.v, T.dw, L.Cin, L.Cout, lr, t->momentum, t->weight_decay, s);
-    if (rc == MPN_OK) rc = vec_sgd(L.bpk, T.vb, T.db, L.Cout, lr, t->momentum, s);
-    if (rc == MPN_OK) rc = refresh_conv_forms(L, T, t->wtmp, true, s);
-  }
-  t->last_img = t->n_img; t->n_img = 0;
-  t->last_rows = B;
-  t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
-  return rc;
-}
-
-extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b, float *d_cls_w,
-                                          float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream) {
-  MPN_CHECK_ARG(p != nullptr);
-  if (p->is_mpnet || p->rn) {
-    set_error("mpn_frcnn_get_head_weights: a %s handle has no fc6 / fc7 / fused cls + bbox head to unpack", handle_kind_name(p));
-    return MPN_ESTATE;
-  }
-  const mpn_frcnn_config &c = p->cfg;
-  const int F = c.fc_dim, C = c.n_classes;
-  hipStream_t s = as_stream(stream);
-  int rc = unpack_linear_weights(p->w6, p->b6, p->K6, F, c.pooled_h * c.pooled_w, 0, F, d_fc6_w, d_fc6_b, s);
-  if (rc == MPN_OK) rc = unpack_linear_weights(p->w7, p->b7, F, F, 1, 0, F, d_fc7_w, d_fc7_b, s);
-  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, 0, C, d_cls_w, d_cls_b, s);
-  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, C, 5 * C, d_bbox_w, d_bbox_b, s);
-  return rc;
-}
-
-extern "C" int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w, float *d_b, void *stream) {
-  MPN_CHECK_ARG(p != nullptr);
-  if (p->is_mpnet || p->rn) {
-    set_error("mpn_frcnn_get_trunk_weights: a %s handle is not supported: only mpn_frcnn_create's VGG trunk is unpacked", handle_kind_name(p));
-    return MPN_ESTATE;
-  }
-  if (layer < 0 || layer >= (int)p->conv.size()) { set_error("mpn_frcnn_get_trunk_weights: layer %d of a %d-layer trunk", layer, (int)p->conv.size()); return MPN_EINVAL; }
-  const ConvLayer &L = p->conv[layer];
-  return unpack_conv_weights(L.wpk, L.bpk, L.Cin, L.Cout, d_w, d_b, as_stream(stream));
-}
+// Training (mpn_frcnn_train_*, mpn_frcnn_get_head_weights / _get_trunk_weights and their debug hooks) is a translation unit of its own:
+// train_driver.hip, over pipeline.h.  This file meets it in mpn_frcnn_destroy and mpn_frcnn_debug_tensor alone.
 
 #ifdef MPN_DEBUG_HOOKS
-// the mpn_debug_bench_* hooks' clock: two warm-up calls, then `iters` calls back to back on the NULL stream between two events of its own
-template <typename F>
-static int time_back_to_back(int iters, float *ms_out, F call) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = MPN_OK;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = MPN_EHIP;
-  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = call();
-  if (rc == MPN_OK && (hipDeviceSynchronize() != hipSuccess || hipEventRecord(e0, nullptr) != hipSuccess)) rc = MPN_EHIP;
-  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = call();
-  float ms = 0.f;
-  if (rc == MPN_OK && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) rc = MPN_EHIP;
-  if (rc == MPN_EHIP) set_error("mpn_debug_bench: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
-  *ms_out = ms / iters;
-  for (hipEvent_t e : {e0, e1}) if (e) (void)hipEventDestroy(e);
-  return rc;
-}
-
-// tools/bench_train.py (debug flavour only): fc6's fused weight-gradient + SGD kernel issued `iters` times BACK TO BACK on the operands the
-// last mpn_frcnn_train_step left (depth MPN_TRAIN_FC6), with lr = momentum = wd = 0 — the weights keep their values, the momentum
-// buffer ends as the plain gradient; the traffic is the real step's: w and v read and written once.
-extern "C" int mpn_debug_bench_train_fc6(mpn_frcnn *p, int iters, float *ms_out) {
-  MPN_CHECK_ARG(p && iters > 0 && ms_out);
-  mpn_frcnn::Train *t = p->train;
-  if (!t || t->depth < MPN_TRAIN_FC6 || t->last_rows <= 0) { set_error("mpn_debug_bench_train_fc6: needs a mpn_frcnn_train_step at depth MPN_TRAIN_FC6"); return MPN_ESTATE; }
-  const int F = p->cfg.fc_dim, PP = p->cfg.pooled_h * p->cfg.pooled_w;
-  return time_back_to_back(iters, ms_out, [&] { return sgd_wgrad_c8(t->g6, p->Mp, t->x6, p->Mp, t->last_rows, F, p->K6, PP, p->w6, t->v6, 0.f, 0.f, 0.f, nullptr); });
-}
-
-// tools/bench_train.py (debug flavour only): conv3x3_wgrad (the MFMA kernel + its segment reduce) of the LAST trained conv layer issued
-// `iters` times back to back on image 0 of the last mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1); the gradient map holds whatever
-// that step left (the kernel's time does not depend on values).  Overwrites that layer's dW sum: take a step afterwards before reading it.
-extern "C" int mpn_debug_bench_train_wgrad(mpn_frcnn *p, int iters, float *ms_out) {
-  MPN_CHECK_ARG(p && iters > 0 && ms_out);
-  mpn_frcnn::Train *t = p->train;
-  if (!t || !t->kconv || t->last_img <= 0) { set_error("mpn_debug_bench_train_wgrad: needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)"); return MPN_ESTATE; }
-  const int k = t->kconv;
-  const ConvLayer &L = p->conv[t->first + k - 1];
-  const Act X = train_in_map(p, t, t->acts, k, t->img_nh[0], t->img_nw[0]), G = make_act(t->gmap[0], L.Cout, X.H, X.W);
-  return time_back_to_back(iters, ms_out, [&] { return conv3x3_wgrad(X, G, t->part, t->cl[k - 1].dw, 0, nullptr); });
-}
-
-// tools/bench_train.py (debug flavour only): maxpool2x2_backward_c8p in its fused form issued `iters` times back to back on the LARGEST
-// pooled trained layer of the last mpn_frcnn_train_step at depth MPN_TRAIN_TRUNK(k), k > K (image 0's saved pre-pool map; dY and dX are
-// the two gradient maps with whatever that step left: the kernel's time does not depend on values).  *layer_out: that layer's index.
-extern "C" int mpn_debug_bench_train_poolbwd(mpn_frcnn *p, int iters, float *ms_out, int *layer_out) {
-  MPN_CHECK_ARG(p && iters > 0 && ms_out);
-  mpn_frcnn::Train *t = p->train;
-  int jb = 0;
-  for (int j = 1; t && j <= t->kconv; ++j) if (p->conv[t->first + j - 1].pool && !jb) jb = j;  // the lowest pooled layer has the largest map
-  if (!t || !jb || t->last_img <= 0) { set_error("mpn_debug_bench_train_poolbwd: needs a mpn_frcnn_train_step at a depth MPN_TRAIN_TRUNK(k) that crosses a pooling layer"); return MPN_ESTATE; }
-  const Act Y = train_map(p, t, t->acts, jb, false, t->img_nh[0], t->img_nw[0]);
-  const Act dY = make_act(t->gmap[0], Y.C, (Y.H + 1) / 2, (Y.W + 1) / 2), dX = make_act(t->gmap[1], Y.C, Y.H, Y.W);
-  if (layer_out) *layer_out = t->first + jb - 1;
-  return time_back_to_back(iters, ms_out, [&] { return maxpool2x2_backward_c8p(Y, dY, dX, 1, nullptr); });
-}
-
 // bench.py's `power_sensitivity` leg (debug flavour only): fc6 of the VGG Fast R-CNN pipeline issued `iters` times BACK TO BACK on the
 // operand the last detect() left in HBM (the ROI-pooled, post-ReLU conv5 features and the handle's own fc6 weights) — the same GEMM that
 // mpn_debug_bench_linear times on dense random operands.  Inside the pipeline fc6 follows the trunk's phases and runs at a higher clock.
@@ -2529,7 +1923,7 @@ extern "C" int mpn_debug_head_post(int which, const float *d_a, const float *d_b
 
 // the debug tensor's buffer (the caller has synchronised the device).  Not DeviceOwner::grow: no kernel of a captured graph reads dbg, and
 // a generation bump here would cost the caller its graphs
-static int grow_dbg(mpn_frcnn *p, size_t bytes) {
+int mpn::grow_dbg(mpn_frcnn *p, size_t bytes) {
   if (bytes <= p->dbg_bytes) return MPN_OK;
   p->own.free_now(&p->dbg);
   const int rc = p->own.alloc_slot(&p->dbg, bytes);
@@ -2539,43 +1933,10 @@ static int grow_dbg(mpn_frcnn *p, size_t bytes) {
 
 extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems) {
   MPN_CHECK_ARG(p && name && d_ptr && n_elems);
-  if (!strcmp(name, "train_pooled")) {  // fc6's operand of the last mpn_frcnn_train_step, [rows, C, PH, PW]: rows at pitch Mp, valid until the next train_add
-    if (!p->train || p->train->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: 'train_pooled' needs a mpn_frcnn_train_step"); return MPN_ESTATE; }
-    const int PPt = p->cfg.pooled_h * p->cfg.pooled_w;
-    const size_t nt = (size_t)p->train->last_rows * p->feat_c * PPt;
-    MPN_CHECK_HIP(hipDeviceSynchronize());
-    if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
-    hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(nt, 256)), dim3(256), 0, nullptr, p->train->x6, p->train->last_rows, p->feat_c, PPt, p->Mp, p->dbg);
-    MPN_CHECK_LAUNCH();
-    MPN_CHECK_HIP(hipDeviceSynchronize());
-    *d_ptr = p->dbg; *n_elems = nt;
-    return MPN_OK;
-  }
-  if (!strncmp(name, "train_act.", 10) || !strcmp(name, "train_dx6")) {  // the conv block's saved maps [C,h,w] / the gradient at the pooled features
-    const mpn_frcnn::Train *t = p->train;
-    if (!t || !t->kconv || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)", name); return MPN_ESTATE; }
-    MPN_CHECK_HIP(hipDeviceSynchronize());
-    size_t nt = 0;
-    if (!strcmp(name, "train_dx6")) {
-      const int PPt = p->cfg.pooled_h * p->cfg.pooled_w;
-      nt = (size_t)t->last_rows * p->feat_c * PPt;
-      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
-      hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(nt, 256)), dim3(256), 0, nullptr, t->dx6, t->last_rows, p->feat_c, PPt, p->Mp, p->dbg);
-      MPN_CHECK_LAUNCH();
-    } else {
-      int i = -1, j = -1;
-      if (sscanf(name + 10, "%d.%d", &i, &j) != 2 || i < 0 || i >= t->last_img || j < 0 || j > t->kconv) {
-        set_error("mpn_frcnn_debug_tensor: '%s': the last step had %d images and maps 0..%d", name, t->last_img, t->kconv);
-        return MPN_EINVAL;
-      }
-      const Act a = train_map(p, t, t->acts + (size_t)i * t->act_img, j, false, t->img_nh[i], t->img_nw[i]);
-      nt = (size_t)a.C * a.H * a.W;
-      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
-      if (int rcc = c8p_to_nchw(a, p->dbg, nullptr)) return rcc;
-    }
-    MPN_CHECK_HIP(hipDeviceSynchronize());
-    *d_ptr = p->dbg; *n_elems = nt;
-    return MPN_OK;
+  if (!strncmp(name, "train_", 6)) {  // the training state's tensors (train_driver.hip)
+    bool known = false;
+    const int rct = train_debug_tensor(p, name, d_ptr, n_elems, &known);
+    if (known) return rct;
   }
   if (p->last_n <= 0 || (!p->rn && p->last_h <= 0)) { set_error("mpn_frcnn_debug_tensor: run detect first"); return MPN_ESTATE; }
   const mpn_frcnn_config &c = p->cfg;
@@ -2615,8 +1976,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   } else if (nm == "rois") {
     MPN_CHECK_HIP(hipMemcpy(p->dbg, p->rois, n * sizeof(float), hipMemcpyDeviceToDevice));
   } else if (nm == "pooled") {
-    hipLaunchKernelGGL(unpack_pooled_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, p->x6, N, p->feat_c, PP, lin_mp(N), p->dbg);
-    MPN_CHECK_LAUNCH();
+    rc = launch_unpack_pooled(p->x6, N, p->feat_c, PP, lin_mp(N), p->dbg);
   } else if (nm == "fc7") {
     rc = c8_to_rowmajor(p->y7_last ? p->y7_last : p->y7, N, F, p->dbg, nullptr);  // rows at stride lin_mp(N), as linear_c8 wrote them
   } else if (nm == "cls_k") {

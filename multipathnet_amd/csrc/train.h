@@ -1,6 +1,6 @@
 // train.h — internal interface of the head-training kernels (train.hip): the Fast R-CNN loss, the backward pass of the three
 // Linear layers behind the ROI pooling and the SGD step, all on the layouts of dense.h (C8 matrices, packed linear weights).
-// Used by the mpn_frcnn_train_* entry points (pipeline.hip).  DESIGN.md section 13.
+// Used by the mpn_frcnn_train_* entry points (train_driver.hip).  DESIGN.md section 13.
 #pragma once
 #include "mpn_internal.h"
 

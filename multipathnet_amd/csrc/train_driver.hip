@@ -1,0 +1,506 @@
+// train_driver.hip — training a VGG Fast R-CNN handle on the device (include/mpn.h mpn_frcnn_train_*): the ROI
+// head with the trunk frozen, or with the trunk's last conv layers (MPN_TRAIN_CONV(k), MPN_TRAIN_TRUNK(k)).  Host code only: the
+// kernels are train.hip's (train.h) and the detect path's (dense.h); the handle and what is shared with pipeline.hip: pipeline.h.
+#include <cmath>
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "pipeline.h"
+#include "train.h"
+
+// The training state of a handle: exists between train_begin and train_end
+struct TrainState {
+  float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
+  // The Linear layers.  w, b: the handle's packed weights (creation alone allocates them: no entry point replaces p->w6 .. p->bh while this exists).
+  // x: the layer's input, g: the gradient at its output, C8 matrices at row pitch Mp; v, vb: momentum, in the layout of the weight it goes with
+  // (g, v, vb: trained layers only).  The x are the minibatch's own activations — not detect's buffers, so a detect between two training
+  // calls disturbs nothing: fc6's operand (the ROI-pooled rows of the pending images), fc6's / fc7's outputs.
+  struct LinT { float *w, *b; int K, N, inner, relu; float *x, *g, *v, *vb; };
+  LinT fc[3] = {};                     // fc6, fc7, the fused cls + bbox head
+  int n_fc = 1;                        // how many of them, counted from the head down, are trained
+  float *head = nullptr;               // the head's output, row-major [B, 5C]
+  float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
+  int *labels = nullptr;
+  int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
+  // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
+  // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
+  struct ConvT {
+    float *v = nullptr, *vb = nullptr;       // momentum: `wpk` layout, [CoutP]
+    float *dw = nullptr, *db = nullptr;      // the step's gradients, summed over the images in train_add order
+    float *wpk_t = nullptr, *wino_t = nullptr, *zero_b = nullptr;  // the input gradient's convolution (pack_conv_weights_dgrad); wino_t where Cout >= 16
+  };
+  int kconv = 0, first = 0;
+  std::vector<ConvT> cl;               // [kconv], cl[j] goes with conv[first + j]
+  float *dx6 = nullptr;                // gradient at the pooled features, fc[0].x's layout
+  int32_t *argmax = nullptr;           // [max_rois, C, PH, PW] of the pending rows
+  float *prois = nullptr;              // [max_rois, 5] the pending rows' projected ROIs (the bins' windows)
+  float *acts = nullptr;               // per image: the block's input map and the kconv trained layers' outputs (before the pool where pooled), whole C8P planes,
+                                       // then the pooled map of every pooled trained layer but the last (the next trained layer's input)
+  size_t act_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, pool_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, act_img = 0; // floats: map j / pooled map j inside an image's slot; between two images' slots
+  float *gmap[2] = {nullptr, nullptr}; // the gradient maps of the image being worked on (ping-pong through the layers)
+  size_t gmap_bytes = 0;
+  float *wtmp = nullptr, *part = nullptr;  // a layer's weights in Torch layout (x 2: W, W'); conv3x3_wgrad's partial sums
+  int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
+  int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // final map size, row range
+  int img_nh[MPN_TRAIN_MAX_IMAGES] = {}, img_nw[MPN_TRAIN_MAX_IMAGES] = {};  // network-input size (every layer's map size follows from it)
+  DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
+};
+using LinT = TrainState::LinT;
+using ConvT = TrainState::ConvT;
+
+void mpn::free_train_state(mpn_frcnn *p) {
+  delete p->train;  // (its DeviceOwner gives the buffers back)
+  p->train = nullptr;
+}
+
+// the handle kinds and states that cannot train, each named (as refuse_multi_pass does for the throughput forms)
+static int refuse_train(const mpn_frcnn *p, const char *fn) {
+  if (p->is_mpnet || p->rn) {
+    set_error("%s: a %s handle cannot be trained: only mpn_frcnn_create's VGG Fast R-CNN head (fc6, fc7, cls + bbox) has a backward pass", fn, handle_kind_name(p));
+    return MPN_ESTATE;
+  }
+  if (p->cfg.fc_arith != MPN_FC_FP32) {
+    set_error("%s: an MPN_FC_SPLIT3 handle cannot be trained (its bf16 weight planes would go stale): create it with MPN_FC_FP32", fn);
+    return MPN_ESTATE;
+  }
+  if (p->n_scales > 1) {
+    set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales): restore a single scale first", fn, p->n_scales);
+    return MPN_ESTATE;
+  }
+  if (p->augment) {
+    set_error("%s: not supported with horizontal-flip augmentation (mpn_frcnn_set_augment): switch it off; flip training images with mpn_image_hflip / mpn_flip_boxes", fn);
+    return MPN_ESTATE;
+  }
+  if (p->tail_pending[0] || p->tail_pending[1]) {
+    set_error("%s: a pipelined call's tail is still pending on this handle: call mpn_frcnn_flush first", fn);
+    return MPN_ESTATE;
+  }
+  return MPN_OK;
+}
+
+// The forms of a conv layer that are derived from its master `wpk`: (forward) the Winograd and K = 36 packs detect's kernels read, rebuilt
+// IN PLACE by the packers creation used from the layer unpacked to Torch layout — bit-identical to what creation would build from the
+// exported weights; and, where the layer hands a gradient down (T.wpk_t), the input gradient's packs.  d_wtmp: 2 x Cout * Cin * 9 floats.
+static int refresh_conv_forms(const ConvLayer &L, const ConvT &T, float *d_wtmp, bool forward, hipStream_t s) {
+  int rc = unpack_conv_weights(L.wpk, nullptr, L.Cin, L.Cout, d_wtmp, nullptr, s);
+  if (rc == MPN_OK && forward && L.wino) rc = pack_conv_weights_wino(d_wtmp, L.Cin, L.Cout, L.wino, s);
+  if (rc == MPN_OK && forward && L.w36) rc = pack_conv_weights_first(d_wtmp, L.Cin, L.Cout, L.w36, s);
+  if (rc == MPN_OK && T.wpk_t) rc = pack_conv_weights_dgrad(d_wtmp, L.Cin, L.Cout, d_wtmp + (size_t)L.Cout * L.Cin * 9, T.wpk_t, T.zero_b, T.wino_t, s);
+  return rc;
+}
+
+// the size of conv[l]'s input and output maps for an H x W network input: halved (rounding up) at every pooling layer below it
+static void layer_map_size(const mpn_frcnn *p, int l, int H, int W, int *h, int *w) {
+  for (int i = 0; i < l; ++i) if (p->conv[i].pool) { H = (H + 1) / 2; W = (W + 1) / 2; }
+  *h = H; *w = W;
+}
+// Saved map j of the trained block for an H x W network input, at `base` (an image's slot): j = 0 the input of conv[first], j = 1..k the
+// post-ReLU output of conv[first + j - 1] before its pool; pooled: the pooled output of that layer (1 <= j < k, the layer pooled)
+static Act train_map(const mpn_frcnn *p, const TrainState *t, float *base, int j, bool pooled, int H, int W) {
+  const int l = j == 0 ? t->first : t->first + j - 1;
+  int h, w;
+  layer_map_size(p, pooled ? l + 1 : l, H, W, &h, &w);
+  return make_act(base ? base + (pooled ? t->pool_off[j] : t->act_off[j]) : nullptr, j == 0 ? p->conv[l].Cin : p->conv[l].Cout, h, w);  // (no base: the geometry alone)
+}
+// the input map of trained layer j (1..k): saved map j - 1, or its pooled form where the layer below is pooled
+static Act train_in_map(const mpn_frcnn *p, const TrainState *t, float *base, int j, int H, int W) {
+  return train_map(p, t, base, j - 1, j > 1 && p->conv[t->first + j - 2].pool, H, W);
+}
+
+// MPN_TRAIN_* -> the trained layers: the last n_fc Linear layers and, below fc6, the conv layers conv[first] .. conv[first + kconv - 1]
+// (kconv == 0: none) — or a refusal
+static int parse_train_depth(const mpn_frcnn *p, int depth, TrainState *t) {
+  const int n_conv = (int)p->conv.size();
+  int Kmax = 0;  // conv layers behind the trunk's last pooling layer (none when the trunk has no pooling layer: the block's input would be the image)
+  while (Kmax < n_conv && !p->conv[n_conv - 1 - Kmax].pool) ++Kmax;
+  if (Kmax == n_conv) Kmax = 0;
+  if (Kmax > MPN_TRAIN_MAX_CONV) Kmax = MPN_TRAIN_MAX_CONV;
+  int k = depth > MPN_TRAIN_FC6 ? depth - MPN_TRAIN_FC6 : 0;
+  if (depth >= MPN_TRAIN_TRUNK(0)) {  // k <= K: no pooling layer among them, MPN_TRAIN_CONV(k) — the same code, the same bits; k > K: pooling layers among the trained ones
+    const int lim = std::min(n_conv - 1, (int)MPN_TRAIN_MAX_TRUNK);
+    k = depth - MPN_TRAIN_TRUNK(0);
+    if (k < 1 || k > lim) {
+      set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_TRUNK(%d), but k runs from 1 to %d on this trunk of %d conv layers: min(n_conv - 1, MPN_TRAIN_MAX_TRUNK = %d) — the first conv layer is never trained (its input is the image)",
+                depth, k, lim, n_conv, (int)MPN_TRAIN_MAX_TRUNK);
+      return MPN_EINVAL;
+    }
+  } else if (depth > MPN_TRAIN_CONV(Kmax)) {
+    set_error("mpn_frcnn_train_begin: depth %d = MPN_TRAIN_CONV(%d), but only K = %d conv layers lie above the trunk's last pooling layer: a pooling layer is in the way (it has no backward pass)",
+              depth, depth - MPN_TRAIN_FC6, Kmax);
+    return MPN_EINVAL;
+  }
+  t->n_fc = 1 + (depth >= MPN_TRAIN_FC7) + (depth >= MPN_TRAIN_FC6);
+  t->kconv = k; t->first = n_conv - k;
+  return MPN_OK;
+}
+
+// Where the conv block's saved maps lie in an image's slot of `acts` (act_off, pool_off, act_img), each at its own layer's size for a
+// max_h x max_w input, and the size of a gradient map: the largest of the saved maps' sizes (and the final map's)
+static void layout_train_maps(const mpn_frcnn *p, TrainState *t) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int k = t->kconv;
+  int mh = c.max_h, mw = c.max_w;
+  final_map_size(p, &mh, &mw);
+  size_t off = 0;
+  t->gmap_bytes = act_bytes(p->feat_c, mh, mw);
+  auto slot = [&](const Act &a) { const size_t b = act_bytes(a.C, a.H, a.W); off += b / sizeof(float); t->gmap_bytes = std::max(t->gmap_bytes, b); };
+  for (int j = 0; j <= k; ++j) {  // map 0: the block's input; map j: the output of conv[first + j - 1], each at its own layer's size
+    t->act_off[j] = off;
+    slot(train_map(p, t, nullptr, j, false, c.max_h, c.max_w));
+  }
+  for (int j = 1; j < k; ++j) {   // MPN_TRAIN_TRUNK: the pooled map of a pooled layer is the next trained layer's input
+    if (!p->conv[t->first + j - 1].pool) continue;
+    t->pool_off[j] = off;
+    slot(train_map(p, t, nullptr, j, true, c.max_h, c.max_w));
+  }
+  t->act_img = off;
+}
+
+// The Linear layers' table, every buffer of the state and (kconv > 1, on the NULL stream) the input gradient's weight forms.
+// false: something failed (t's DeviceOwner holds what was made)
+static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int F = c.fc_dim, C = c.n_classes, k = t->kconv, PP = c.pooled_h * c.pooled_w;
+  const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
+  t->fc[0] = LinT{p->w6, p->b6, p->K6, F, PP, 1};
+  t->fc[1] = LinT{p->w7, p->b7, F, F, 1, 1};
+  t->fc[2] = LinT{p->wh, p->bh, F, 5 * C, 1, 0};
+  auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
+  auto trained = [&](LinT &L) {  // momentum and the gradient at the output
+    return alloc0(&L.v, lin_wpk_elems(round_up(L.K, 64), L.N) * sizeof(float)) && alloc0(&L.vb, (size_t)lin_np(L.N) * sizeof(float)) &&
+           alloc0(&L.g, (size_t)(lin_np(L.N) / 8) * rec);
+  };
+  bool ok = trained(t->fc[2]);
+  ok = ok && alloc0(&t->fc[0].x, (size_t)(round_up(p->K6, 64) / 8) * rec);
+  for (int i = 1; i < 3; ++i) ok = ok && alloc0(&t->fc[i].x, (size_t)(lin_np(t->fc[i - 1].N) / 8) * rec);  // the output of the layer below
+  ok = ok && alloc0(&t->head, M * 5 * C * sizeof(float));
+  for (int i = 1; i >= 3 - t->n_fc; --i) ok = ok && trained(t->fc[i]);
+  ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
+  ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
+  if (!k) return ok;
+  ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
+  ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
+  layout_train_maps(p, t);
+  ok = ok && alloc0(&t->acts, t->act_img * MPN_TRAIN_MAX_IMAGES * sizeof(float));
+  ok = ok && alloc0(&t->gmap[0], t->gmap_bytes) && alloc0(&t->gmap[1], t->gmap_bytes);
+  size_t wmax = 0, pmax = 0;
+  t->cl.resize(k);
+  for (int j = 0; j < k && ok; ++j) {
+    const ConvLayer &L = p->conv[t->first + j];
+    ConvT &T = t->cl[j];
+    const size_t we = conv_wpk_elems(L.Cin, L.Cout) * sizeof(float), be = (size_t)conv_coutp(L.Cout) * sizeof(float);
+    ok = alloc0(&T.v, we) && alloc0(&T.vb, be) && alloc0(&T.dw, we) && alloc0(&T.db, be);
+    if (j > 0) {  // a trained layer lies below: this layer hands a gradient down
+      ok = ok && alloc0(&T.wpk_t, conv_wpk_elems(L.Cout, L.Cin) * sizeof(float)) && alloc0(&T.zero_b, (size_t)conv_coutp(L.Cin) * sizeof(float));
+      if (L.Cout >= 16) ok = ok && alloc0(&T.wino_t, conv_wino_elems(L.Cout, L.Cin) * sizeof(float));
+    }
+    wmax = std::max(wmax, (size_t)L.Cout * L.Cin * 9);
+    int lh, lw;
+    layer_map_size(p, t->first + j, c.max_h, c.max_w, &lh, &lw);
+    pmax = std::max(pmax, conv_wgrad_part_elems(L.Cin, L.Cout, lh, lw));
+  }
+  ok = ok && alloc0(&t->wtmp, 2 * wmax * sizeof(float)) && alloc0(&t->part, pmax * sizeof(float));
+  for (int j = 1; j < k && ok; ++j) ok = refresh_conv_forms(p->conv[t->first + j], t->cl[j], t->wtmp, false, nullptr) == MPN_OK;
+  return ok;
+}
+
+extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, "mpn_frcnn_train_begin");
+  if (rc) return rc;
+  if (p->train) { set_error("mpn_frcnn_train_begin: training has already begun on this handle (mpn_frcnn_train_end first)"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(depth >= MPN_TRAIN_HEADS);
+  std::unique_ptr<TrainState> t(new TrainState());  // (its DeviceOwner gives back what a failed attempt made)
+  rc = parse_train_depth(p, depth, t.get());
+  if (rc) return rc;
+  MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
+  if (!alloc_train_state(p, t.get()) || hipDeviceSynchronize() != hipSuccess) {
+    set_error("mpn_frcnn_train_begin: allocating the momentum / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
+    return MPN_ENOMEM;
+  }
+  p->train = t.release();  // all or nothing, as in mpn_frcnn_set_augment: published last, its presence says that every buffer exists
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_end(mpn_frcnn *p) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (!p->train) { set_error("mpn_frcnn_train_end: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  free_train_state(p);
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
+                                   const int *d_labels, int n, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, "mpn_frcnn_train_add");
+  if (rc) return rc;
+  TrainState *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_add: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
+  const mpn_frcnn_config &c = p->cfg;
+  if (t->pending + n > c.max_rois) {
+    set_error("mpn_frcnn_train_add: %d pending rows + %d exceed the handle's max_rois (%d)", t->pending, n, c.max_rois);
+    return MPN_EINVAL;
+  }
+  double sc = 1.0;
+  int H = H0, W = W0;
+  if (c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
+  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
+    set_error("mpn_frcnn_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
+    return MPN_EINVAL;
+  }
+  if (t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
+    set_error("mpn_frcnn_train_add: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", t->n_img, MPN_TRAIN_MAX_IMAGES);
+    return MPN_EINVAL;
+  }
+  ScratchScope scratch_scope(&p->scratch);
+  hipStream_t s = as_stream(stream);
+  p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers and the ROI table are rewritten: the next head segment runs for real
+  Act feat;
+  bool pools = false;  // a pooled layer among the trained ones (MPN_TRAIN_TRUNK): this trunk pass also writes their pre-pool maps
+  for (int j = 0; j < t->kconv; ++j) pools = pools || p->conv[t->first + j].pool;
+  if (pools) p->keep_prepool_from = t->first;
+  rc = obtain_features(p, d_image, H0, W0, H, W, sc, &p->up, s, &feat);  // getImages' rescale + the frozen trunk, exactly as detect
+  p->keep_prepool_from = -1;
+  // the map now belongs to a training image: nothing a detect on cached features may pool from
+  p->up.invalidate(); p->mir.invalidate();
+  if (rc) return rc;
+  rc = mpn_project_im_rois(d_rois, n, sc, p->rois, s);
+  if (rc) return rc;
+  // this image's rows behind the pending ones: a shifted base pointer with the buffer's row pitch
+  rc = roi_pool_c8(feat, p->rois, n, c.pooled_h, c.pooled_w, c.spatial_scale, RoiRule{1.0f, 0, c.roi_bin_rule}, t->fc[0].x + (size_t)t->pending * 8,
+                   t->kconv ? t->argmax + (size_t)t->pending * p->feat_c * c.pooled_h * c.pooled_w : nullptr, s, 5, p->Mp);
+  if (rc) return rc;
+  if (t->kconv) {  // what the conv block's backward pass reads: the block's input, every trained layer's output, the rows' windows
+    const int i = t->n_img, h = feat.H, w = feat.W, k = t->kconv;
+    float *slot = t->acts + (size_t)i * t->act_img;
+    for (int j = 0; j <= k; ++j) {
+      const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones
+      // j == 0: what conv[first] read; j >= 1: the layer's output before its pool (the last layer's unpooled output is the final map)
+      const float *src = j == 0 ? (L.pool ? L.pooled : L.out) : ((j == k && !L.pool) ? feat.p : L.out);
+      const Act a = train_map(p, t, slot, j, false, H, W);
+      MPN_CHECK_HIP(hipMemcpyAsync(a.p, src, act_bytes(a.C, a.H, a.W), hipMemcpyDeviceToDevice, s));
+      if (j >= 1 && j < k && L.pool) {
+        const Act ap = train_map(p, t, slot, j, true, H, W);
+        MPN_CHECK_HIP(hipMemcpyAsync(ap.p, L.pooled, act_bytes(ap.C, ap.H, ap.W), hipMemcpyDeviceToDevice, s));
+      }
+    }
+    MPN_CHECK_HIP(hipMemcpyAsync(t->prois + (size_t)t->pending * 5, p->rois, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    t->img_h[i] = h; t->img_w[i] = w; t->img_nh[i] = H; t->img_nw[i] = W; t->img_row0[i] = t->pending; t->img_rows[i] = n;
+    ++t->n_img;
+  }
+  MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  t->pending += n;
+  return MPN_OK;
+}
+
+// The backward pass below fc6 (depth MPN_TRAIN_CONV(k)): the gradient at the pooled features, then per image — in train_add order — the
+// ROI-pooling backward into a zero-haloed gradient map and, last trained layer to first, the bias and weight gradients (added to the
+// step's sums) and the input gradient masked with the ReLU of the layer below.  No weight is touched: the caller updates afterwards.
+// MPN_TRAIN_TRUNK(k): every layer at its own size; at a pooled layer the gradient at its pooled output first goes through
+// maxpool2x2_backward_c8p (fused with the ReLU mask of the pre-pool map, so the input gradient handed to a pooled layer is not masked
+// on its own) into the other gradient map, whose halo is laid for the larger size first — as is every map written after it.
+static int train_conv_backward(mpn_frcnn *p, TrainState *t, int B, hipStream_t s) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp, k = t->kconv;
+  // dx6 = (g6 W6) .* [x6 > 0]: fc6's packed chunk order is x6's.  The mask is the last conv layer's ReLU mask (pooled values are map values)
+  const LinT &L6 = t->fc[0];
+  int rc = linear_dgrad_c8(L6.g, Mp, B, L6.N, L6.w, L6.K, L6.x, t->dx6, Mp, s);
+  for (int i = 0; i < t->n_img && rc == MPN_OK; ++i) {
+    const int h = t->img_h[i], w = t->img_w[i], nh = t->img_nh[i], nw = t->img_nw[i];
+    float *slot = t->acts + (size_t)i * t->act_img;
+    bool relaid = false;  // a pooling layer has been crossed: the memset below no longer is the halo of the maps' sizes
+    for (float *gm : t->gmap) MPN_CHECK_HIP(hipMemsetAsync(gm, 0, t->gmap_bytes, s));  // the halo is the input gradient's padding
+    int cur = 0;
+    Act G = make_act(t->gmap[cur], p->feat_c, h, w);
+    RoiBwd a{};
+    a.g = t->dx6; a.argmax = t->argmax; a.rois = t->prois; a.by_batch = 0; a.n0 = t->img_row0[i]; a.n1 = a.n0 + t->img_rows[i];
+    a.B = 1; a.C = p->feat_c; a.H = h; a.W = w; a.PH = c.pooled_h; a.PW = c.pooled_w; a.windows = (c.pooled_h <= 32 && c.pooled_w <= 32) ? 1 : 0;
+    a.g_n = 8; a.g_cb = (long)PP * Mp * 8; a.g_c = 1; a.g_bin = (long)Mp * 8;
+    a.o_b = 0; a.o_cb = (long)G.plane(); a.o_c = 1; a.o_y = (long)G.Wp * 8; a.o_x = 8;
+    a.scale = c.spatial_scale; a.rr = RoiRule{1.0f, 0, c.roi_bin_rule};
+    a.out = G.p + ((size_t)G.Wp + 1) * 8;
+    rc = roi_pool_backward(a, s);
+    for (int j = k; j >= 1 && rc == MPN_OK; --j) {
+      const ConvLayer &L = p->conv[t->first + j - 1];
+      const ConvT &T = t->cl[j - 1];
+      const Act X = train_in_map(p, t, slot, j, nh, nw);
+      if (L.pool) {  // G is the gradient at the pooled output: route it to the pre-pool map's maxima, masked with that map's ReLU
+        const Act Y = train_map(p, t, slot, j, false, nh, nw);
+        Act Gl = make_act(t->gmap[cur ^ 1], L.Cout, Y.H, Y.W);
+        rc = c8p_zero_halos(&Gl, 1, s);
+        if (rc == MPN_OK) rc = maxpool2x2_backward_c8p(Y, G, Gl, 1, s);
+        if (rc != MPN_OK) break;
+        G = Gl; cur ^= 1; relaid = true;
+      }
+      rc = conv_bias_grad(G, T.db, i > 0, s);
+      if (rc == MPN_OK) rc = conv3x3_wgrad(X, G, t->part, T.dw, i > 0, s);
+      if (rc != MPN_OK || j == 1) break;
+      Act dX = make_act(t->gmap[cur ^ 1], L.Cin, X.H, X.W);
+      if (relaid) rc = c8p_zero_halos(&dX, 1, s);
+      if (rc == MPN_OK) rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
+      if (rc == MPN_OK && !p->conv[t->first + j - 2].pool) rc = relu_mask_c8p(dX, X, s);  // (a pooled layer below: its pool's backward masks)
+      G = dX; cur ^= 1;
+    }
+  }
+  return rc;
+}
+
+extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, "mpn_frcnn_train_step");
+  if (rc) return rc;
+  TrainState *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_step: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  if (t->pending <= 0) { set_error("mpn_frcnn_train_step: no pending rows (mpn_frcnn_train_add first)"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(std::isfinite(lr));
+  const mpn_frcnn_config &c = p->cfg;
+  const int B = t->pending, Mp = p->Mp, lowest = 3 - t->n_fc;  // fc[lowest]: the lowest trained Linear layer
+  ScratchScope scratch_scope(&p->scratch);
+  hipStream_t s = as_stream(stream);
+  // forward: detect's GEMMs on the pending rows (row pitch Mp); no dropout (opt.train_remove_dropouts).  The last layer writes the row-major head
+  for (int i = 0; i < 3 && rc == MPN_OK; ++i) {
+    const LinT &L = t->fc[i];
+    rc = linear_c8(L.x, B, L.K, L.w, L.b, L.N, L.relu, i < 2 ? t->fc[i + 1].x : nullptr, i < 2 ? nullptr : t->head, s, Mp, nullptr, 1);
+  }
+  if (rc) return rc;
+  LossCfg lc{};
+  for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
+  lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
+  lc.bbox_weight = t->bbox_weight;
+  rc = train_loss(t->head, B, c.n_classes, t->rois, t->gt, t->labels, lc, t->fc[2].g, Mp, d_loss ? d_loss : t->loss, s);
+  // backward: every input gradient before the update of the weights it was computed with
+  for (int i = 2; i > lowest && rc == MPN_OK; --i) {
+    const LinT &L = t->fc[i];
+    rc = linear_dgrad_c8(L.g, Mp, B, L.N, L.w, L.K, L.x, t->fc[i - 1].g, Mp, s);
+  }
+  if (rc == MPN_OK && t->kconv) rc = train_conv_backward(p, t, B, s);
+  for (int i = 2; i >= lowest && rc == MPN_OK; --i) {  // head, fc7, fc6
+    const LinT &L = t->fc[i];
+    rc = sgd_wgrad_c8(L.g, Mp, L.x, Mp, B, L.N, L.K, L.inner, L.w, L.v, lr, t->momentum, t->weight_decay, s);
+    if (rc == MPN_OK) rc = sgd_bias_c8(L.g, Mp, B, L.N, L.b, L.vb, lr, t->momentum, s);
+  }
+  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {  // the conv block: the master `wpk` in place, then every form derived from it
+    const ConvLayer &L = p->conv[t->first + j];
+    const ConvT &T = t->cl[j];
+    rc = conv_sgd(L.wpk, T.v, T.dw, L.Cin, L.Cout, lr, t->momentum, t->weight_decay, s);
+    if (rc == MPN_OK) rc = vec_sgd(L.bpk, T.vb, T.db, L.Cout, lr, t->momentum, s);
+    if (rc == MPN_OK) rc = refresh_conv_forms(L, T, t->wtmp, true, s);
+  }
+  t->last_img = t->n_img; t->n_img = 0;
+  t->last_rows = B;
+  t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
+  return rc;
+}
+
+extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b, float *d_cls_w,
+                                          float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (p->is_mpnet || p->rn) {
+    set_error("mpn_frcnn_get_head_weights: a %s handle has no fc6 / fc7 / fused cls + bbox head to unpack", handle_kind_name(p));
+    return MPN_ESTATE;
+  }
+  const mpn_frcnn_config &c = p->cfg;
+  const int F = c.fc_dim, C = c.n_classes;
+  hipStream_t s = as_stream(stream);
+  int rc = unpack_linear_weights(p->w6, p->b6, p->K6, F, c.pooled_h * c.pooled_w, 0, F, d_fc6_w, d_fc6_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->w7, p->b7, F, F, 1, 0, F, d_fc7_w, d_fc7_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, 0, C, d_cls_w, d_cls_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, C, 5 * C, d_bbox_w, d_bbox_b, s);
+  return rc;
+}
+
+extern "C" int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w, float *d_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (p->is_mpnet || p->rn) {
+    set_error("mpn_frcnn_get_trunk_weights: a %s handle is not supported: only mpn_frcnn_create's VGG trunk is unpacked", handle_kind_name(p));
+    return MPN_ESTATE;
+  }
+  if (layer < 0 || layer >= (int)p->conv.size()) { set_error("mpn_frcnn_get_trunk_weights: layer %d of a %d-layer trunk", layer, (int)p->conv.size()); return MPN_EINVAL; }
+  const ConvLayer &L = p->conv[layer];
+  return unpack_conv_weights(L.wpk, L.bpk, L.Cin, L.Cout, d_w, d_b, as_stream(stream));
+}
+
+#ifdef MPN_DEBUG_HOOKS
+
+// tools/bench_train.py (debug flavour only): fc6's fused weight-gradient + SGD kernel issued `iters` times BACK TO BACK on the operands the
+// last mpn_frcnn_train_step left (depth MPN_TRAIN_FC6), with lr = momentum = wd = 0 — the weights keep their values, the momentum
+// buffer ends as the plain gradient; the traffic is the real step's: w and v read and written once.
+extern "C" int mpn_debug_bench_train_fc6(mpn_frcnn *p, int iters, float *ms_out) {
+  MPN_CHECK_ARG(p && iters > 0 && ms_out);
+  TrainState *t = p->train;
+  if (!t || t->n_fc < 3 || t->last_rows <= 0) { set_error("mpn_debug_bench_train_fc6: needs a mpn_frcnn_train_step at depth MPN_TRAIN_FC6"); return MPN_ESTATE; }
+  const LinT &L = t->fc[0];
+  return time_back_to_back(iters, ms_out, [&] { return sgd_wgrad_c8(L.g, p->Mp, L.x, p->Mp, t->last_rows, L.N, L.K, L.inner, L.w, L.v, 0.f, 0.f, 0.f, nullptr); });
+}
+
+// tools/bench_train.py (debug flavour only): conv3x3_wgrad (the MFMA kernel + its segment reduce) of the LAST trained conv layer issued
+// `iters` times back to back on image 0 of the last mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1); the gradient map holds whatever
+// that step left (the kernel's time does not depend on values).  Overwrites that layer's dW sum: take a step afterwards before reading it.
+extern "C" int mpn_debug_bench_train_wgrad(mpn_frcnn *p, int iters, float *ms_out) {
+  MPN_CHECK_ARG(p && iters > 0 && ms_out);
+  TrainState *t = p->train;
+  if (!t || !t->kconv || t->last_img <= 0) { set_error("mpn_debug_bench_train_wgrad: needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)"); return MPN_ESTATE; }
+  const int k = t->kconv;
+  const ConvLayer &L = p->conv[t->first + k - 1];
+  const Act X = train_in_map(p, t, t->acts, k, t->img_nh[0], t->img_nw[0]), G = make_act(t->gmap[0], L.Cout, X.H, X.W);
+  return time_back_to_back(iters, ms_out, [&] { return conv3x3_wgrad(X, G, t->part, t->cl[k - 1].dw, 0, nullptr); });
+}
+
+// tools/bench_train.py (debug flavour only): maxpool2x2_backward_c8p in its fused form issued `iters` times back to back on the LARGEST
+// pooled trained layer of the last mpn_frcnn_train_step at depth MPN_TRAIN_TRUNK(k), k > K (image 0's saved pre-pool map; dY and dX are
+// the two gradient maps with whatever that step left: the kernel's time does not depend on values).  *layer_out: that layer's index.
+extern "C" int mpn_debug_bench_train_poolbwd(mpn_frcnn *p, int iters, float *ms_out, int *layer_out) {
+  MPN_CHECK_ARG(p && iters > 0 && ms_out);
+  TrainState *t = p->train;
+  int jb = 0;
+  for (int j = 1; t && j <= t->kconv; ++j) if (p->conv[t->first + j - 1].pool && !jb) jb = j;  // the lowest pooled layer has the largest map
+  if (!t || !jb || t->last_img <= 0) { set_error("mpn_debug_bench_train_poolbwd: needs a mpn_frcnn_train_step at a depth MPN_TRAIN_TRUNK(k) that crosses a pooling layer"); return MPN_ESTATE; }
+  const Act Y = train_map(p, t, t->acts, jb, false, t->img_nh[0], t->img_nw[0]);
+  const Act dY = make_act(t->gmap[0], Y.C, (Y.H + 1) / 2, (Y.W + 1) / 2), dX = make_act(t->gmap[1], Y.C, Y.H, Y.W);
+  if (layer_out) *layer_out = t->first + jb - 1;
+  return time_back_to_back(iters, ms_out, [&] { return maxpool2x2_backward_c8p(Y, dY, dX, 1, nullptr); });
+}
+
+#endif
+
+// mpn_frcnn_debug_tensor's training tensors (pipeline.h): "train_pooled", "train_dx6", "train_act.<i>.<j>"
+int mpn::train_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems, bool *known) {
+  const TrainState *t = p->train;
+  const int PP = p->cfg.pooled_h * p->cfg.pooled_w;
+  const bool pooled = !strcmp(name, "train_pooled"), dx6 = !strcmp(name, "train_dx6");
+  *known = pooled || dx6 || !strncmp(name, "train_act.", 10);
+  if (!*known) return MPN_OK;
+  size_t nt = 0;
+  if (pooled) {  // fc6's operand of the last mpn_frcnn_train_step, [rows, C, PH, PW]: rows at pitch Mp, valid until the next train_add
+    if (!t || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: 'train_pooled' needs a mpn_frcnn_train_step"); return MPN_ESTATE; }
+  } else if (!t || !t->kconv || t->last_rows <= 0) {  // the conv block's saved maps [C,h,w] / the gradient at the pooled features
+    set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_frcnn_train_step at depth >= MPN_TRAIN_CONV(1)", name);
+    return MPN_ESTATE;
+  }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  if (pooled || dx6) {
+    nt = (size_t)t->last_rows * p->feat_c * PP;
+    if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+    if (int rcl = launch_unpack_pooled(pooled ? t->fc[0].x : t->dx6, t->last_rows, p->feat_c, PP, p->Mp, p->dbg)) return rcl;
+  } else {
+    int i = -1, j = -1;
+    if (sscanf(name + 10, "%d.%d", &i, &j) != 2 || i < 0 || i >= t->last_img || j < 0 || j > t->kconv) {
+      set_error("mpn_frcnn_debug_tensor: '%s': the last step had %d images and maps 0..%d", name, t->last_img, t->kconv);
+      return MPN_EINVAL;
+    }
+    const Act a = train_map(p, t, t->acts + (size_t)i * t->act_img, j, false, t->img_nh[i], t->img_nw[i]);
+    nt = (size_t)a.C * a.H * a.W;
+    if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+    if (int rcc = c8p_to_nchw(a, p->dbg, nullptr)) return rcc;
+  }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  *d_ptr = p->dbg; *n_elems = nt;
+  return MPN_OK;
+}
