@@ -647,8 +647,9 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
  * Only a plain VGG Fast R-CNN handle (mpn_frcnn_create, fc_arith == MPN_FC_FP32) trains: fc6, fc7 and the fused cls + bbox head.
  * MultiPathNet, ResNet and op-list handles, MPN_FC_SPLIT3 handles, a handle with an image pyramid or augmentation on, and a handle
  * whose pipelined tail is still pending (until mpn_frcnn_flush) answer MPN_ESTATE with a message naming what refused.
- * What is built is the reference's opt.train_remove_dropouts = true configuration: NO dropout, so a step is deterministic — the
- * same calls on the same inputs give the same bits (fixed summation orders, no atomics).
+ * After mpn_frcnn_train_begin there is NO dropout (the reference's opt.train_remove_dropouts = true); mpn_frcnn_train_set_dropout
+ * switches on the reference's default, the two nn.Dropout(0.5) of models/vgg.lua:21 (below).  Either way a step is deterministic — the
+ * same calls on the same inputs, seed and step counter give the same bits (fixed summation orders, no atomics, a counter-based mask).
  *
  *   mpn_frcnn_train_begin  allocates one zeroed momentum buffer per trained tensor, in the packed layout of its weight (fc6's, as
  *                          large as fc6's weights, only at depth MPN_TRAIN_FC6), and the gradient scratch.  A second begin without an
@@ -706,12 +707,44 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
  * in its relu_mask form (X = the saved pre-pool map) into a zero-haloed map of the larger size — one pass instead of the [X > 0]
  * mask; the input gradient handed to a pooled layer is therefore not masked on its own.  Everything else — the summation orders,
  * every gradient before any update, optim.sgd, the re-pack of the derived forms — is as above.  MPN_TRAIN_MAX_IMAGES applies.
- * Still not trained: the first conv layer, MultiPathNet / ResNet / op-list handles, dropout.
+ * Still not trained: the first conv layer, MultiPathNet / ResNet / op-list handles.
  * Debug tensors after such a step, until the next mpn_frcnn_train_add: "train_act.<i>.<j>" (image i; j = 0 the block's input map,
  * j = 1..k the trained layers' outputs — before the pool where the layer is pooled; [C,h,w], each map its own h x w) and "train_dx6"
  * ([B, C, PH, PW]).
  *   mpn_frcnn_get_trunk_weights  conv layer `layer`'s current weights [Cout,Cin,3,3] and bias [Cout] in Torch layout (either may be
- *                          NULL); any mpn_frcnn_create handle, with or without training.  The exact inverse of creation. */
+ *                          NULL); any mpn_frcnn_create handle, with or without training.  The exact inverse of creation.
+ *
+ * Dropout and resumable runs.  Between mpn_frcnn_train_begin and mpn_frcnn_train_end:
+ *   mpn_frcnn_train_set_dropout  nn.Dropout(rate) (v2) in place behind fc6 + ReLU and behind fc7 + ReLU from the next mpn_frcnn_train_step
+ *                          on, at EVERY depth (at MPN_TRAIN_HEADS fc6 and fc7 are frozen, but the model is in training mode: the heads see
+ *                          the dropped y7).  rate finite in [0, 1), MPN_EINVAL otherwise; 0 switches it off (no kernel is launched, every
+ *                          bit is what it is without the call); without a train_begin MPN_ESTATE.  mpn_frcnn_train_begin starts at rate 0.
+ *                          No mask is stored; the mask of an element is a function of five integers.  Philox4x32-10 with
+ *                            key     = (seed & 0xffffffff, seed >> 32)   (seed taken as 64 bits)
+ *                            counter = (row, col >> 2, layer, step & 0xffffffff)
+ *                          gives four words; word col & 3 is the element's.  row: the row's index in the pending minibatch (train_add order
+ *                          across images); col: the layer's output column; layer: 0 behind fc6, 1 behind fc7; step: the handle's step
+ *                          counter — 0 at train_begin, incremented by every mpn_frcnn_train_step that reaches the forward pass, whatever
+ *                          the rate (also when a launch then fails); a step's masks use the value before the increment.  With
+ *                          T = floor(rate * 2^32) (in double, rate being the float passed; 0.5 -> 0x80000000) the element is KEPT iff
+ *                          word >= T.  Kept: fl(x * s), s = 1.0f / (1.0f - rate) in fp32 (rate 0.5: exactly x 2); dropped: +0.0f.
+ *                          Backward: the saved activations are the dropped ones, so [x > 0] is keep mask x ReLU mask and the two input
+ *                          gradients that cross a dropout (head -> y7, fc7 -> y6) are scaled by s; the weight gradients contract against
+ *                          the dropped activations as they are.  Inference (detect, test_one) never sees dropout.
+ *   mpn_frcnn_train_get_state  the momentum buffers in Torch layout — the shapes of mpn_frcnn_get_head_weights, cls and bbox split out of
+ *                          the fused head — and the step counter (*h_step, a HOST pointer; may be NULL).  A tensor the current depth
+ *                          trains may be NULL (not wanted); one it does NOT train has no momentum and MUST be NULL: MPN_EINVAL naming it.
+ *   mpn_frcnn_train_set_state  the inverse: packs the momentum as creation packs the weights (pad lanes +0.0; get -> set -> get is exact)
+ *                          and sets the step counter (>= 0).  EVERY tensor the depth trains must be given, every other one NULL:
+ *                          MPN_EINVAL naming the tensor.  With rows pending (a train_add without its step): MPN_ESTATE.
+ *   mpn_frcnn_train_get_trunk_state / _set_trunk_state  the same for one TRAINED conv layer ([Cout,Cin,3,3], [Cout]; the shapes of
+ *                          mpn_frcnn_get_trunk_weights); a layer the depth does not train: MPN_EINVAL naming the trained range.  get: either
+ *                          pointer may be NULL; set: both are needed, and rows pending answer MPN_ESTATE.
+ * The weights (mpn_frcnn_get_head_weights / _get_trunk_weights), this state, the rate and the seed are everything a run continues
+ * from: a new handle created from the weights, train_begin, set_dropout, set_state gives the bits of the uninterrupted run (the
+ * reference's model_<epoch>.t7 + optimState_<epoch>.t7, train.lua:188-198).
+ * Debug tensors "train_y6" / "train_y7": fc6's / fc7's output of the last step as the next layer read it (behind the dropout),
+ * [B, fc_dim] row-major, valid until the next mpn_frcnn_train_step. */
 #define MPN_TRAIN_HEADS 0   /* cls + bbox linear only          */
 #define MPN_TRAIN_FC7   1   /* + fc7                           */
 #define MPN_TRAIN_FC6   2   /* + fc6 (the whole ROI head)      */
@@ -725,6 +758,13 @@ int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const 
                         const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);
 int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss /*[2]: cls, bbox*/, void *stream);
 int mpn_frcnn_train_end(mpn_frcnn *p);
+int mpn_frcnn_train_set_dropout(mpn_frcnn *p, float rate, long seed);
+int mpn_frcnn_train_get_state(mpn_frcnn *p, float *d_fc6_v, float *d_fc6_vb, float *d_fc7_v, float *d_fc7_vb, float *d_cls_v, float *d_cls_vb,
+                              float *d_bbox_v, float *d_bbox_vb, long *h_step, void *stream);
+int mpn_frcnn_train_set_state(mpn_frcnn *p, const float *d_fc6_v, const float *d_fc6_vb, const float *d_fc7_v, const float *d_fc7_vb,
+                              const float *d_cls_v, const float *d_cls_vb, const float *d_bbox_v, const float *d_bbox_vb, long step, void *stream);
+int mpn_frcnn_train_get_trunk_state(mpn_frcnn *p, int layer, float *d_v /*[Cout,Cin,3,3]*/, float *d_vb /*[Cout]*/, void *stream);
+int mpn_frcnn_train_set_trunk_state(mpn_frcnn *p, int layer, const float *d_v, const float *d_vb, void *stream);
 int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b,
                                float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
 int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w /*[Cout,Cin,3,3]*/, float *d_b /*[Cout]*/, void *stream);

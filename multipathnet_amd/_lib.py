@@ -107,6 +107,12 @@ def load(flavour=None):
     lib.mpn_gather_rows.argtypes = [C.c_void_p, f32p, C.c_size_t, f32p, C.c_void_p]
     lib.mpn_comm_destroy.restype = None
     lib.mpn_frcnn_destroy.restype = None
+    # training state (include/mpn.h): `long` seed / step, a host `long *`, NULL for the tensors a depth does not train
+    lib.mpn_frcnn_train_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_long]
+    lib.mpn_frcnn_train_get_state.argtypes = [C.c_void_p] + [f32p] * 8 + [C.POINTER(C.c_long), C.c_void_p]
+    lib.mpn_frcnn_train_set_state.argtypes = [C.c_void_p] + [f32p] * 8 + [C.c_long, C.c_void_p]
+    lib.mpn_frcnn_train_get_trunk_state.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
+    lib.mpn_frcnn_train_set_trunk_state.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
     _libs[fl] = lib
     return lib
 

@@ -28,11 +28,20 @@ int sgd_wgrad_c8(const float *d_g_c8, int g_Mp, const float *d_x_c8, int x_Mp, i
                  float lr, float momentum, float wd, hipStream_t s);
 // Bias: db[n] = sum_{m < B} g[m,n] (a fixed pairwise-style order), v = momentum * v + db, b = b - lr * v (biases never decay, Optim.lua:66-68)
 int sgd_bias_c8(const float *d_g_c8, int g_Mp, int B, int N, float *d_bpk, float *d_vb, float lr, float momentum, hipStream_t s);
-// Input gradient through y = relu(x W^T + b): dx[m,k] = (sum_{n < N} g[m,n] W[n,k]) * [act[m,k] > 0], reading the packed W with the roles
-// of its two dimensions swapped (the contraction runs over NP, n ascending in pairs).  d_act_c8 = the forward activation x (post-ReLU)
-// and d_dx_c8, both [>= ceil(K/8)][x_Mp][8]; rows < B are written.
+// Input gradient through y = relu(x W^T + b): dx[m,k] = (sum_{n < N} g[m,n] W[n,k]) * [act[m,k] > 0] * scale, reading the packed W with the
+// roles of its two dimensions swapped (the contraction runs over NP, n ascending in pairs).  d_act_c8 = the forward activation x (post-ReLU)
+// and d_dx_c8, both [>= ceil(K/8)][x_Mp][8]; rows < B are written.  scale: 1 / (1 - rate) where act is what dropout_c8 left (a dropped
+// element is +0.0, so [act > 0] already is keep mask x ReLU mask); with 1.0f the product is exact: the bits of the unscaled gradient.
 int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_wpk, int K, const float *d_act_c8, float *d_dx_c8, int x_Mp,
-                    hipStream_t s);
+                    hipStream_t s, float scale = 1.0f);
+// nn.Dropout (v2) in place on the C8 matrix [>= ceil(N/8)][Mp][8] linear_c8 has just written, rows < B only (rows >= B are neither read nor
+// written).  The mask is stored nowhere: element (row, col) is KEPT iff word col & 3 of Philox4x32-10(counter = (row, col >> 2, layer,
+// step), key = (seed_lo, seed_hi)) is >= threshold = floor(rate * 2^32); kept: fl(x * scale), scale = 1.0f / (1.0f - rate); dropped: +0.0f.
+// Lanes col >= N of the last record are written +0.0.  One thread per 32-byte record.  DESIGN.md section 13.6.
+struct DropoutCfg { uint32_t threshold, seed_lo, seed_hi, layer, step; float scale; };
+int dropout_c8(float *d_y_c8, int Mp, int B, int N, const DropoutCfg &cfg, hipStream_t s);
+// rows < M of a C8 matrix at row pitch Mp -> row-major [M, N] (c8_to_rowmajor with the pitch given)
+int c8_rows_to_rowmajor(const float *d_c8, int Mp, int M, int N, float *d_y, hipStream_t s);
 // The inverse of pack_linear_weights for output rows [n0, n1): d_w [n1 - n0, K] Torch layout, d_b [n1 - n0]; either may be null.
 int unpack_linear_weights(const float *d_wpk, const float *d_bpk, int K, int N, int inner, int n0, int n1, float *d_w, float *d_b, hipStream_t s);
 

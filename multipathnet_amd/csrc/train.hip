@@ -1,7 +1,8 @@
 // train.hip — training the Fast R-CNN head on the device with the trunk frozen (train.lua:154-158, BBoxRegressionCriterion.lua,
 // BatchProviderROI.lua:125-131, engines/Optim.lua).  gfx950 only.
 //
-// What is built is the reference's opt.train_remove_dropouts = true configuration: no dropout, so a step is deterministic.
+// A step is deterministic: without dropout (the reference's opt.train_remove_dropouts = true) and with it (its default; dropout_c8 below,
+// whose mask is a counter-based function of seed, step, layer, row and column).
 //
 // The three Linear layers behind the ROI pooling keep their weights in the packed MFMA order [K64/8][NP][8] that the forward GEMM
 // reads (dense.h), and training updates them IN PLACE in that order.  The contraction of a weight gradient runs over the B ~ 128 ROI
@@ -209,19 +210,20 @@ int sgd_bias_c8(const float *d_g_c8, int g_Mp, int B, int N, float *d_bpk, float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Input gradient: dx = (g W) .* [act > 0]
+// Input gradient: dx = scale * (g W) .* [act > 0]
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct DgradArgs {
   const float *g, *w, *act;
   float *dx;
   int g_Mp, x_Mp, B, N, NP, nchunks, n_per_wave;
+  float scale = 1.0f;  // of the masked value: 1 / (1 - rate) where a dropout sits behind the activation (x * 1.0f is x: the plain mask's bits)
 };
 constexpr int kDgradLds = 3 * 128 * 64 * 4;  // the partial sums of waves 1..3
 
 // Block = 32 k-chunks (256 k) x 32 rows m; its 4 waves split the contraction over n into four contiguous ranges (n ascending in pairs
 // inside a range) and wave 0 adds the four partial sums in wave order: ((s0 + s1) + s2) + s3, the same in every run.  A = packed-weight
 // records (i = chunk; the record of (chunk, n) holds W[n][chunk * 8 .. + 8]), B = g[m][n] (j = m).  A lane of wave 0 ends with whole
-// records of dx — chunk ck0 + 8 (r / 4) + 4 (lane / 32) + r % 4, row m0 + lane % 32 —, masks them with the forward activation and stores.
+// records of dx — chunk ck0 + 8 (r / 4) + 4 (lane / 32) + r % 4, row m0 + lane % 32 —, masks them with the forward activation, scales and stores.
 __global__ __launch_bounds__(256) void linear_dgrad_kernel(DgradArgs a) {
   extern __shared__ float part[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
@@ -281,21 +283,79 @@ __global__ __launch_bounds__(256) void linear_dgrad_kernel(DgradArgs a) {
     const f32x4 a0 = *reinterpret_cast<const f32x4 *>(a.act + off), a1 = *reinterpret_cast<const f32x4 *>(a.act + off + 4);
     f32x4 d0, d1;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { d0[e] = a0[e] > 0.0f ? acc[e][r] : 0.0f; d1[e] = a1[e] > 0.0f ? acc[4 + e][r] : 0.0f; }
+    for (int e = 0; e < 4; ++e) { d0[e] = a0[e] > 0.0f ? acc[e][r] * a.scale : 0.0f; d1[e] = a1[e] > 0.0f ? acc[4 + e][r] * a.scale : 0.0f; }
     *reinterpret_cast<f32x4 *>(a.dx + off) = d0; *reinterpret_cast<f32x4 *>(a.dx + off + 4) = d1;
   }
 }
 
 int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_wpk, int K, const float *d_act_c8, float *d_dx_c8, int x_Mp,
-                    hipStream_t s) {
+                    hipStream_t s, float scale) {
   MPN_CHECK_ARG(d_g_c8 && d_wpk && d_act_c8 && d_dx_c8 && B > 0 && N > 0 && K > 0 && g_Mp >= B && x_Mp >= B);
   DgradArgs a{};
+  a.scale = scale;
   a.g = d_g_c8; a.w = d_wpk; a.act = d_act_c8; a.dx = d_dx_c8; a.g_Mp = g_Mp; a.x_Mp = x_Mp; a.B = B; a.N = N;
   a.NP = lin_np(N); a.nchunks = cdiv(K, 8);
   a.n_per_wave = round_up(cdiv(N, 4), 2);
   int rc = set_max_dyn_lds(reinterpret_cast<const void *>(linear_dgrad_kernel), kDgradLds);
   if (rc) return rc;
   hipLaunchKernelGGL(linear_dgrad_kernel, dim3((unsigned)cdiv(a.nchunks, 32), (unsigned)cdiv(B, 32)), dim3(256), kDgradLds, s, a);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Dropout behind fc6 / fc7 (the reference's default, train.lua:53 train_remove_dropouts = false)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11; Random123's known answers): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped between rounds
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += W0; k1 += W1;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// One thread = one record: row m < B of chunk q < ceil(N/8), i.e. columns 8q .. 8q + 7 = the Philox column groups 2q and 2q + 1.
+// Threads run along m first: a wave reads and writes 2 KiB contiguous.
+__global__ __launch_bounds__(256) void dropout_c8_kernel(float *__restrict__ y, int Mp, int B, int N, int nq, DropoutCfg c) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)nq * B) return;
+  const int q = (int)(t / B), m = (int)(t % B);
+  float *rec = y + ((size_t)q * Mp + m) * 8;
+  uint32_t w[8];
+  philox4x32_10((uint32_t)m, (uint32_t)(2 * q), c.layer, c.step, c.seed_lo, c.seed_hi, w);
+  philox4x32_10((uint32_t)m, (uint32_t)(2 * q + 1), c.layer, c.step, c.seed_lo, c.seed_hi, w + 4);
+  const f32x4 x0 = *reinterpret_cast<const f32x4 *>(rec), x1 = *reinterpret_cast<const f32x4 *>(rec + 4);
+  f32x4 d0, d1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    d0[e] = (w[e] >= c.threshold && q * 8 + e < N) ? x0[e] * c.scale : 0.0f;
+    d1[e] = (w[4 + e] >= c.threshold && q * 8 + 4 + e < N) ? x1[e] * c.scale : 0.0f;
+  }
+  *reinterpret_cast<f32x4 *>(rec) = d0; *reinterpret_cast<f32x4 *>(rec + 4) = d1;
+}
+
+int dropout_c8(float *d_y_c8, int Mp, int B, int N, const DropoutCfg &cfg, hipStream_t s) {
+  MPN_CHECK_ARG(d_y_c8 && B > 0 && N > 0 && Mp >= B);
+  const int nq = cdiv(N, 8);
+  hipLaunchKernelGGL(dropout_c8_kernel, dim3((unsigned)cdiv_sz((size_t)nq * B, 256)), dim3(256), 0, s, d_y_c8, Mp, B, N, nq, cfg);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+__global__ void c8_rows_to_rowmajor_kernel(const float *__restrict__ c8, int Mp, int M, int N, float *__restrict__ y) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)M * N) return;
+  const int n = (int)(t % N), m = (int)(t / N);
+  y[t] = c8[((size_t)(n >> 3) * Mp + m) * 8 + (n & 7)];
+}
+
+int c8_rows_to_rowmajor(const float *d_c8, int Mp, int M, int N, float *d_y, hipStream_t s) {
+  MPN_CHECK_ARG(d_c8 && d_y && M > 0 && N > 0 && Mp >= M);
+  hipLaunchKernelGGL(c8_rows_to_rowmajor_kernel, dim3((unsigned)cdiv_sz((size_t)M * N, 256)), dim3(256), 0, s, d_c8, Mp, M, N, d_y);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }

@@ -22,7 +22,13 @@ struct TrainState {
   float *head = nullptr;               // the head's output, row-major [B, 5C]
   float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
   int *labels = nullptr;
-  int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensor "train_pooled")
+  int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensors "train_pooled", "train_y6", "train_y7")
+  // nn.Dropout(rate) behind fc6 + ReLU and fc7 + ReLU (mpn_frcnn_train_set_dropout; 0: none, no kernel).  The mask is a function of
+  // (seed, step, layer, row, column) — train.h dropout_c8 —, so the stream's whole state is `seed` and `step`
+  float drop_rate = 0.f, drop_scale = 1.f;   // scale = 1.0f / (1.0f - rate)
+  uint32_t drop_threshold = 0;         // floor(rate * 2^32): an element is kept iff its word >= this
+  long seed = 0, step = 0;             // step: the train_steps that reached the forward pass (mpn_frcnn_train_get_state / _set_state)
+  float *vtmp = nullptr;               // mpn_frcnn_train_set_state: cls and bbox momentum joined as creation joins the weights, [5C, F] + [5C]
   // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
   // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
   struct ConvT {
@@ -364,10 +370,18 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   const int B = t->pending, Mp = p->Mp, lowest = 3 - t->n_fc;  // fc[lowest]: the lowest trained Linear layer
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
-  // forward: detect's GEMMs on the pending rows (row pitch Mp); no dropout (opt.train_remove_dropouts).  The last layer writes the row-major head
+  // forward: detect's GEMMs on the pending rows (row pitch Mp), at a rate > 0 each of fc6's and fc7's outputs dropped in place (the
+  // model is in training mode at every depth: frozen layers drop too).  The last layer writes the row-major head
+  const bool drop = t->drop_rate > 0.0f;
+  const long step = t->step++;  // this step's masks; counted whatever the rate, also when a launch below fails
   for (int i = 0; i < 3 && rc == MPN_OK; ++i) {
     const LinT &L = t->fc[i];
     rc = linear_c8(L.x, B, L.K, L.w, L.b, L.N, L.relu, i < 2 ? t->fc[i + 1].x : nullptr, i < 2 ? nullptr : t->head, s, Mp, nullptr, 1);
+    if (rc == MPN_OK && drop && i < 2) {
+      const DropoutCfg dc{t->drop_threshold, (uint32_t)((uint64_t)t->seed & 0xffffffffu), (uint32_t)((uint64_t)t->seed >> 32), (uint32_t)i,
+                          (uint32_t)((uint64_t)step & 0xffffffffu), t->drop_scale};
+      rc = dropout_c8(t->fc[i + 1].x, Mp, B, L.N, dc, s);
+    }
   }
   if (rc) return rc;
   LossCfg lc{};
@@ -375,10 +389,11 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
   lc.bbox_weight = t->bbox_weight;
   rc = train_loss(t->head, B, c.n_classes, t->rois, t->gt, t->labels, lc, t->fc[2].g, Mp, d_loss ? d_loss : t->loss, s);
-  // backward: every input gradient before the update of the weights it was computed with
+  // backward: every input gradient before the update of the weights it was computed with.  L.x is what the dropout left: a dropped
+  // element is +0.0, so the kernel's [x > 0] is keep mask x ReLU mask and the dropout's backward is the factor 1 / (1 - rate) alone
   for (int i = 2; i > lowest && rc == MPN_OK; --i) {
     const LinT &L = t->fc[i];
-    rc = linear_dgrad_c8(L.g, Mp, B, L.N, L.w, L.K, L.x, t->fc[i - 1].g, Mp, s);
+    rc = linear_dgrad_c8(L.g, Mp, B, L.N, L.w, L.K, L.x, t->fc[i - 1].g, Mp, s, drop ? t->drop_scale : 1.0f);
   }
   if (rc == MPN_OK && t->kconv) rc = train_conv_backward(p, t, B, s);
   for (int i = 2; i >= lowest && rc == MPN_OK; --i) {  // head, fc7, fc6
@@ -397,6 +412,130 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   t->last_rows = B;
   t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
   return rc;
+}
+
+extern "C" int mpn_frcnn_train_set_dropout(mpn_frcnn *p, float rate, long seed) {
+  MPN_CHECK_ARG(p != nullptr);
+  TrainState *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_set_dropout: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  if (!(std::isfinite(rate) && rate >= 0.0f && rate < 1.0f)) {
+    set_error("mpn_frcnn_train_set_dropout: rate %g is outside [0, 1)", (double)rate);
+    return MPN_EINVAL;
+  }
+  t->drop_rate = rate;
+  t->drop_threshold = (uint32_t)std::floor((double)rate * 4294967296.0);
+  t->drop_scale = 1.0f / (1.0f - rate);
+  t->seed = seed;
+  return MPN_OK;
+}
+
+// The eight tensors of mpn_frcnn_train_get_state / _set_state in their order, each with the Linear layer whose momentum holds it
+namespace {
+struct StateTensor { const char *name; int fc; };
+const StateTensor kStateTensors[8] = {{"d_fc6_v", 0}, {"d_fc6_vb", 0}, {"d_fc7_v", 1}, {"d_fc7_vb", 1}, {"d_cls_v", 2}, {"d_cls_vb", 2}, {"d_bbox_v", 2}, {"d_bbox_vb", 2}};
+}
+// a tensor of a layer the depth does not train has no momentum: it must be NULL
+static int check_state_tensors(const TrainState *t, const char *fn, const float *const q[8], bool need_all) {
+  for (int i = 0; i < 8; ++i) {
+    const bool trained = kStateTensors[i].fc >= 3 - t->n_fc;
+    if (q[i] && !trained) {
+      set_error("%s: %s must be NULL: this training depth does not train that tensor (it has no momentum)", fn, kStateTensors[i].name);
+      return MPN_EINVAL;
+    }
+    if (!q[i] && trained && need_all) {
+      set_error("%s: %s is NULL, but this training depth trains that tensor: its momentum is part of the state", fn, kStateTensors[i].name);
+      return MPN_EINVAL;
+    }
+  }
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_get_state(mpn_frcnn *p, float *d_fc6_v, float *d_fc6_vb, float *d_fc7_v, float *d_fc7_vb, float *d_cls_v,
+                                         float *d_cls_vb, float *d_bbox_v, float *d_bbox_vb, long *h_step, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  const TrainState *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_get_state: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  const float *const q[8] = {d_fc6_v, d_fc6_vb, d_fc7_v, d_fc7_vb, d_cls_v, d_cls_vb, d_bbox_v, d_bbox_vb};
+  int rc = check_state_tensors(t, "mpn_frcnn_train_get_state", q, false);
+  if (rc) return rc;
+  const int C = p->cfg.n_classes;
+  hipStream_t s = as_stream(stream);
+  for (int i = 3 - t->n_fc; i < 2 && rc == MPN_OK; ++i) {
+    const LinT &L = t->fc[i];
+    rc = unpack_linear_weights(L.v, L.vb, L.K, L.N, L.inner, 0, L.N, i ? d_fc7_v : d_fc6_v, i ? d_fc7_vb : d_fc6_vb, s);
+  }
+  const LinT &Lh = t->fc[2];
+  if (rc == MPN_OK) rc = unpack_linear_weights(Lh.v, Lh.vb, Lh.K, Lh.N, 1, 0, C, d_cls_v, d_cls_vb, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(Lh.v, Lh.vb, Lh.K, Lh.N, 1, C, 5 * C, d_bbox_v, d_bbox_vb, s);
+  if (rc == MPN_OK && h_step) *h_step = t->step;
+  return rc;
+}
+
+extern "C" int mpn_frcnn_train_set_state(mpn_frcnn *p, const float *d_fc6_v, const float *d_fc6_vb, const float *d_fc7_v, const float *d_fc7_vb,
+                                         const float *d_cls_v, const float *d_cls_vb, const float *d_bbox_v, const float *d_bbox_vb, long step,
+                                         void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TrainState *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_set_state: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  if (t->pending > 0) { set_error("mpn_frcnn_train_set_state: %d rows are pending: take the step (mpn_frcnn_train_step) first", t->pending); return MPN_ESTATE; }
+  const float *const q[8] = {d_fc6_v, d_fc6_vb, d_fc7_v, d_fc7_vb, d_cls_v, d_cls_vb, d_bbox_v, d_bbox_vb};
+  int rc = check_state_tensors(t, "mpn_frcnn_train_set_state", q, true);
+  if (rc) return rc;
+  if (step < 0) { set_error("mpn_frcnn_train_set_state: step %ld is negative", step); return MPN_EINVAL; }
+  const int C = p->cfg.n_classes, F = p->cfg.fc_dim;
+  hipStream_t s = as_stream(stream);
+  if (!t->vtmp && t->own.alloc(&t->vtmp, ((size_t)5 * C * F + 5 * C) * sizeof(float), true) != MPN_OK) {
+    set_error("mpn_frcnn_train_set_state: allocating the joined head momentum failed: %s", hipGetErrorString(hipGetLastError()));
+    return MPN_ENOMEM;
+  }
+  for (int i = 3 - t->n_fc; i < 2 && rc == MPN_OK; ++i) {
+    const LinT &L = t->fc[i];
+    rc = pack_linear_weights(i ? d_fc7_v : d_fc6_v, i ? d_fc7_vb : d_fc6_vb, L.K, L.N, L.inner, L.v, L.vb, s);
+  }
+  if (rc) return rc;
+  // cls and bbox joined into the fused head's [5C, F] as creation joins the weights, then the same packer
+  float *jw = t->vtmp, *jb = t->vtmp + (size_t)5 * C * F;
+  MPN_CHECK_HIP(hipMemcpyAsync(jw, d_cls_v, (size_t)C * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(jw + (size_t)C * F, d_bbox_v, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(jb, d_cls_vb, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(jb + C, d_bbox_vb, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const LinT &Lh = t->fc[2];
+  rc = pack_linear_weights(jw, jb, Lh.K, Lh.N, 1, Lh.v, Lh.vb, s);
+  if (rc == MPN_OK) t->step = step;
+  return rc;
+}
+
+// conv[layer] as a trained layer of the state: its ConvT, or a refusal naming the trained range
+static int trained_conv(mpn_frcnn *p, const char *fn, int layer, TrainState **t_out, ConvT **T_out) {
+  TrainState *t = p->train;
+  if (!t) { set_error("%s: no mpn_frcnn_train_begin on this handle", fn); return MPN_ESTATE; }
+  if (layer < t->first || layer >= t->first + t->kconv || !t->kconv) {
+    if (t->kconv) set_error("%s: conv layer %d is not trained at this depth (layers %d .. %d are): it has no momentum", fn, layer, t->first, t->first + t->kconv - 1);
+    else set_error("%s: conv layer %d is not trained at this depth (no conv layer is): it has no momentum", fn, layer);
+    return MPN_EINVAL;
+  }
+  *t_out = t; *T_out = &t->cl[layer - t->first];
+  return MPN_OK;
+}
+
+extern "C" int mpn_frcnn_train_get_trunk_state(mpn_frcnn *p, int layer, float *d_v, float *d_vb, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TrainState *t; ConvT *T;
+  int rc = trained_conv(p, "mpn_frcnn_train_get_trunk_state", layer, &t, &T);
+  if (rc) return rc;
+  const ConvLayer &L = p->conv[layer];
+  return unpack_conv_weights(T->v, T->vb, L.Cin, L.Cout, d_v, d_vb, as_stream(stream));
+}
+
+extern "C" int mpn_frcnn_train_set_trunk_state(mpn_frcnn *p, int layer, const float *d_v, const float *d_vb, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TrainState *t; ConvT *T;
+  int rc = trained_conv(p, "mpn_frcnn_train_set_trunk_state", layer, &t, &T);
+  if (rc) return rc;
+  if (t->pending > 0) { set_error("mpn_frcnn_train_set_trunk_state: %d rows are pending: take the step (mpn_frcnn_train_step) first", t->pending); return MPN_ESTATE; }
+  if (!d_v || !d_vb) { set_error("mpn_frcnn_train_set_trunk_state: %s is NULL: a trained layer's state is its weight and its bias momentum", d_v ? "d_vb" : "d_v"); return MPN_EINVAL; }
+  const ConvLayer &L = p->conv[layer];
+  return pack_conv_weights(d_v, d_vb, L.Cin, L.Cout, T->v, T->vb, as_stream(stream));
 }
 
 extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b, float *d_cls_w,
@@ -470,14 +609,25 @@ extern "C" int mpn_debug_bench_train_poolbwd(mpn_frcnn *p, int iters, float *ms_
 
 #endif
 
-// mpn_frcnn_debug_tensor's training tensors (pipeline.h): "train_pooled", "train_dx6", "train_act.<i>.<j>"
+// mpn_frcnn_debug_tensor's training tensors (pipeline.h): "train_pooled", "train_y6", "train_y7", "train_dx6", "train_act.<i>.<j>"
 int mpn::train_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems, bool *known) {
   const TrainState *t = p->train;
   const int PP = p->cfg.pooled_h * p->cfg.pooled_w;
   const bool pooled = !strcmp(name, "train_pooled"), dx6 = !strcmp(name, "train_dx6");
-  *known = pooled || dx6 || !strncmp(name, "train_act.", 10);
+  const int yi = !strcmp(name, "train_y6") ? 1 : (!strcmp(name, "train_y7") ? 2 : 0);
+  *known = pooled || dx6 || yi || !strncmp(name, "train_act.", 10);
   if (!*known) return MPN_OK;
   size_t nt = 0;
+  if (yi) {  // fc6's / fc7's output of the last mpn_frcnn_train_step as the layer above read it (behind the dropout), [rows, fc_dim]: valid until the next step
+    if (!t || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_frcnn_train_step", name); return MPN_ESTATE; }
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    nt = (size_t)t->last_rows * p->cfg.fc_dim;
+    if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+    if (int rcy = c8_rows_to_rowmajor(t->fc[yi].x, p->Mp, t->last_rows, p->cfg.fc_dim, p->dbg, nullptr)) return rcy;
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    *d_ptr = p->dbg; *n_elems = nt;
+    return MPN_OK;
+  }
   if (pooled) {  // fc6's operand of the last mpn_frcnn_train_step, [rows, C, PH, PW]: rows at pitch Mp, valid until the next train_add
     if (!t || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: 'train_pooled' needs a mpn_frcnn_train_step"); return MPN_ESTATE; }
   } else if (!t || !t->kconv || t->last_rows <= 0) {  // the conv block's saved maps [C,h,w] / the gradient at the pooled features

@@ -800,7 +800,7 @@ class FastRCNN(object):
         return keep, idx, n
 
     # ---- fine-tuning the head on the device, trunk frozen (mpn_frcnn_train_*, include/mpn.h) ----
-    def train_begin(self, depth=None, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0, trunk_layers=None):
+    def train_begin(self, depth=None, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0, trunk_layers=None, dropout=0.0, seed=555):
         """Start training: depth 0 = cls + bbox linear only, 1 = + fc7, 2 = + fc6 (the whole ROI head, the default), 2 + k = + the last k
         conv layers of the trunk, k = 1..K with K the number of conv layers above the trunk's last pooling layer (VGG-16: 3 = + conv5_3,
         4 = + conv5_2, 5 = + conv5_1; beyond K a pooling layer is in the way: MpnError).  trunk_layers = k instead of depth (both:
@@ -808,13 +808,73 @@ class FastRCNN(object):
         backward pass routes each gradient to its window's first maximum; k = 1..min(n_conv - 1, 12) — the first conv layer is never
         trained — and VGG-16 at k = 9 (conv3_1 and up) is the reference's configuration; k <= K gives the bits of depth 2 + k.  With conv
         layers trained a step takes at most 8 images.  optim.sgd's momentum and weight decay (engines/Optim.lua; biases never decay),
-        the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN handles in fp32 only; no dropout (the reference's
-        opt.train_remove_dropouts configuration)."""
+        the box loss's weight (train.lua:154-158).  Plain VGG Fast R-CNN handles in fp32 only.  dropout = 0.0: none (the reference's
+        opt.train_remove_dropouts configuration); dropout = 0.5 is the reference's default, see train_set_dropout."""
         if depth is not None and trunk_layers is not None:
             raise ValueError("train_begin: give depth or trunk_layers, not both")
         d = 32 + int(trunk_layers) if trunk_layers is not None else (2 if depth is None else int(depth))   # MPN_TRAIN_TRUNK(k)
         check(self._lib.mpn_frcnn_train_begin(self._h, d, C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)),
               "mpn_frcnn_train_begin")
+        self._train_depth, self._dropout = d, (0.0, int(seed))
+        if dropout:
+            self.train_set_dropout(dropout, seed)
+
+    def train_set_dropout(self, rate, seed=555):
+        """nn.Dropout(rate) behind fc6 + ReLU and fc7 + ReLU from the next train_step on, at every depth (models/vgg.lua:21; 0.5 is the
+        reference's default, 0 switches it off).  The mask is a pure function of (seed, step counter, layer, row, column) — Philox4x32-10,
+        include/mpn.h mpn_frcnn_train_set_dropout —, so a run is reproduced or continued from (weights, train_state(), rate, seed)."""
+        check(self._lib.mpn_frcnn_train_set_dropout(self._h, float(rate), int(seed)), "mpn_frcnn_train_set_dropout")
+        self._dropout = (float(rate), int(seed))
+
+    def _trained(self):
+        """(names of the head tensors the current depth trains, indices of the conv layers it trains)"""
+        d, n = getattr(self, "_train_depth", 2), len(self._cout)   # (no train_begin yet: the library refuses the call that follows)
+        k = d - 32 if d >= 32 else max(d - 2, 0)
+        names = ("cls_w", "cls_b", "bbox_w", "bbox_b") + (("fc7_w", "fc7_b") if d >= 1 else ()) + (("fc6_w", "fc6_b") if d >= 2 else ())
+        return names, list(range(n - k, n))
+
+    _STATE_ORDER = ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")
+
+    def _conv_cin(self, l):
+        return 3 if l == 0 else self._cout[l - 1]
+
+    def train_state(self):
+        """The optimiser's state between train_begin and train_end: {"step": the step counter, "fc6_w": ..., "bbox_b": ..., "conv_w": [...],
+        "conv_b": [...]} — the keys of head_weights() / trunk_weights(), the values the MOMENTUM of that tensor in Torch layout (device
+        tensors), None for a tensor the current depth does not train.  With the weights, the dropout rate and the seed it is what
+        train_load_state continues a run from, bit for bit (the reference's optimState_<epoch>.t7, train.lua:188-198)."""
+        names, convs = self._trained()
+        F, Cn = self.fc_dim, self.n_classes
+        k6 = self._cout[len(self._cout) - 1] * self._cfg.pooled_h * self._cfg.pooled_w
+        shapes = {"fc6_w": (F, k6), "fc6_b": (F,), "fc7_w": (F, F), "fc7_b": (F,), "cls_w": (Cn, F), "cls_b": (Cn,), "bbox_w": (4 * Cn, F), "bbox_b": (4 * Cn,)}
+        S = {k: (torch.empty(shapes[k], dtype=torch.float32, device=self.device) if k in names else None) for k in self._STATE_ORDER}
+        step = C.c_long()
+        check(self._lib.mpn_frcnn_train_get_state(self._h, *[None if S[k] is None else _f(S[k]) for k in self._STATE_ORDER], C.byref(step), _stream()),
+              "mpn_frcnn_train_get_state")
+        S["step"] = int(step.value)
+        S["conv_w"], S["conv_b"] = [None] * len(self._cout), [None] * len(self._cout)
+        for l in convs:
+            w = torch.empty((self._cout[l], self._conv_cin(l), 3, 3), dtype=torch.float32, device=self.device)
+            b = torch.empty(self._cout[l], dtype=torch.float32, device=self.device)
+            check(self._lib.mpn_frcnn_train_get_trunk_state(self._h, l, _f(w), _f(b), _stream()), "mpn_frcnn_train_get_trunk_state")
+            S["conv_w"][l], S["conv_b"][l] = w, b
+        return S
+
+    def train_load_state(self, state):
+        """Restore what train_state() returned (momentum tensors on any device; numpy arrays are taken too) into a handle that has begun
+        training at the same depth: every tensor the depth trains must be there, every other one None.  No rows may be pending."""
+        dev = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).to(self.device).contiguous()
+        T = [dev(state.get(k)) for k in self._STATE_ORDER]
+        check(self._lib.mpn_frcnn_train_set_state(self._h, *[None if t is None else _f(t) for t in T], int(state["step"]), _stream()),
+              "mpn_frcnn_train_set_state")
+        cw, cb = state.get("conv_w") or [], state.get("conv_b") or []
+        for l in range(len(cw)):
+            if cw[l] is None and cb[l] is None:
+                continue
+            w, b = dev(cw[l]), dev(cb[l])
+            check(self._lib.mpn_frcnn_train_set_trunk_state(self._h, l, None if w is None else _f(w), None if b is None else _f(b), _stream()),
+                  "mpn_frcnn_train_set_trunk_state")
+        torch.cuda.current_stream().synchronize()   # the packers have read the (possibly temporary) device copies
 
     def train_add(self, image, rois, gt_boxes, labels):
         """Append one image's rows to the pending minibatch: image [3,H,W] fp32 in [0,1], rois / gt_boxes [n,4] in the image's own

@@ -5,11 +5,12 @@ pooling, head forward, loss, backward, SGD — is models.FastRCNN.train_add / tr
   attach_proposals        DataSetJSON.lua:280-390  (DataSetCOCO:attachProposals, without the crowd and the sample-around-GT branches)
   RoiSampler              BatchProviderROI.lua:39-49 (setupOne), BatchProviderBase.lua:54-107 (takeSubset, selectBBoxesOne)
   bbox_regression_stats   BatchProviderROI.lua:53-69 (setupData)
+  save_checkpoint / load_checkpoint / resume   train.lua:188-198 (model_<epoch>.t7 + optimState_<epoch>.t7, here one table), opt.resume
 """
 import numpy as np
 import torch
 
-from . import utils
+from . import t7, utils
 
 
 def _boxoverlap_host(a, b):
@@ -104,3 +105,54 @@ def bbox_regression_stats(records, fg_threshold=0.5):
     assert vals, "no foreground rows"
     v = torch.cat(vals, 0)
     return v.mean(0).numpy(), v.std(0).numpy()
+
+
+_HEAD_KEYS = ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")
+
+
+def save_checkpoint(path, net):
+    """Everything a training run of a models.FastRCNN continues from, as ONE Torch7 table (t7.py) — the reference writes the pair
+    model_<epoch>.t7 + optimState_<epoch>.t7 (train.lua:188-198).  Between train_begin and train_end.  Flat keys:
+      "fc6_w" .. "bbox_b", "conv_w.<l>", "conv_b.<l>"       the weights (net.head_weights() + net.trunk_weights())
+      "v.fc6_w" .. "v.bbox_b", "v.conv_w.<l>", "v.conv_b.<l>"  the momentum of every TRAINED tensor (net.train_state(); the others are absent)
+      "step", "n_conv", "dropout", "seed"                   the step counter, the trunk's depth, the dropout rate and its seed (a decimal
+                                                            string: a Torch7 number is a double, a seed has 64 bits)"""
+    torch.cuda.synchronize()
+    host = lambda t: t.detach().cpu().numpy()
+    Wt, St = dict(net.head_weights()), net.train_state()
+    Wt.update(net.trunk_weights())
+    tab = {k: host(Wt[k]) for k in _HEAD_KEYS}
+    n_conv = len(Wt["conv_w"])
+    for l in range(n_conv):
+        tab["conv_w.%d" % l], tab["conv_b.%d" % l] = host(Wt["conv_w"][l]), host(Wt["conv_b"][l])
+    for k in _HEAD_KEYS:
+        if St[k] is not None:
+            tab["v." + k] = host(St[k])
+    for l in range(n_conv):
+        if St["conv_w"][l] is not None:
+            tab["v.conv_w.%d" % l], tab["v.conv_b.%d" % l] = host(St["conv_w"][l]), host(St["conv_b"][l])
+    rate, seed = net._dropout
+    tab.update({"step": St["step"], "n_conv": n_conv, "dropout": float(rate), "seed": str(int(seed))})
+    t7.save(path, tab)
+
+
+def load_checkpoint(path):
+    """-> {"weights": {...head_weights() keys, "conv_w": [...], "conv_b": [...]}, "state": what FastRCNN.train_load_state takes,
+    "dropout": rate, "seed": int} with host torch tensors.  Update a parameter dict with "weights" to create the FastRCNN, then
+    train_begin (the same depth), train_set_dropout(dropout, seed), train_load_state(state) — or `resume`."""
+    tab = t7.load(path)
+    n_conv = int(tab["n_conv"])
+    ten = lambda k: torch.from_numpy(np.array(tab[k])) if k in tab else None
+    weights = {k: ten(k) for k in _HEAD_KEYS}
+    weights["conv_w"], weights["conv_b"] = [ten("conv_w.%d" % l) for l in range(n_conv)], [ten("conv_b.%d" % l) for l in range(n_conv)]
+    state = {k: ten("v." + k) for k in _HEAD_KEYS}
+    state["conv_w"], state["conv_b"] = [ten("v.conv_w.%d" % l) for l in range(n_conv)], [ten("v.conv_b.%d" % l) for l in range(n_conv)]
+    state["step"] = int(tab["step"])
+    return {"weights": weights, "state": state, "dropout": float(tab["dropout"]), "seed": int(tab["seed"])}
+
+
+def resume(net, ckpt):
+    """opt.resume: restore load_checkpoint's dropout stream and optimiser state into `net` — a FastRCNN created from ckpt["weights"] on
+    which train_begin (the same depth, momentum, weight decay) has been called."""
+    net.train_set_dropout(ckpt["dropout"], ckpt["seed"])
+    net.train_load_state(ckpt["state"])

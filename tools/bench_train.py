@@ -9,9 +9,11 @@ weights and their momentum, each read and written once — and, at depth 3, the 
 and up, through two pooling layers — with the same two numbers, and the max-pool backward kernel alone on the largest pooled trained layer
 (k = 9: conv3_3, 256 x 150 x 250; mpn_debug_bench_train_poolbwd) against the bytes it must move: X and dX once each, dY once, at the
 6.3 TB/s a float4 copy reaches.
+--dropout RATE runs every step with nn.Dropout(RATE) behind fc6 and fc7 (0.5: the reference's default; two
+more small kernels per step and a scale in two input gradients); 0, the default, launches nothing more than a run without the option.
 One JSON line per measurement.
 
-    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9]
+    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5]
 """
 import argparse
 import ctypes as C
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trunk-layers", type=int, default=0, help="also measure MPN_TRAIN_TRUNK(k) (9: conv3_1 and up, the reference's configuration)")
+    ap.add_argument("--dropout", type=float, default=0.0, help="dropout rate behind fc6 / fc7 (0.5: the reference's default; 0: none)")
     a = ap.parse_args()
     import torch
     from multipathnet_amd import _lib, models
@@ -57,9 +60,9 @@ def main():
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         for depth in (0, 1, 2, 3, 4, 5) + (("trunk",) if a.trunk_layers > 0 else ()):
             if depth == "trunk":
-                net.train_begin(trunk_layers=a.trunk_layers, momentum=0.9, weight_decay=5e-4)
+                net.train_begin(trunk_layers=a.trunk_layers, momentum=0.9, weight_decay=5e-4, dropout=a.dropout)
             else:
-                net.train_begin(depth=depth, momentum=0.9, weight_decay=5e-4)
+                net.train_begin(depth=depth, momentum=0.9, weight_decay=5e-4, dropout=a.dropout)
             step_ms, iter_ms = [], []
             for i in range(a.warmup + a.steps):
                 e[0].record()
@@ -72,7 +75,7 @@ def main():
                 if i >= a.warmup:
                     step_ms.append(e[1].elapsed_time(e[2]))
                     iter_ms.append(e[0].elapsed_time(e[2]))
-            print(json.dumps({"what": "train_step", "depth": "MPN_TRAIN_TRUNK(%d)" % a.trunk_layers if depth == "trunk" else depth, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
+            print(json.dumps({"what": "train_step", "depth": "MPN_TRAIN_TRUNK(%d)" % a.trunk_layers if depth == "trunk" else depth, "dropout": a.dropout, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
                               "ms_step_min": round(float(np.min(step_ms)), 3), "ms_iteration_median": round(float(np.median(iter_ms)), 3),
                               "steps": a.steps, "device": name}), flush=True)
             if depth == 2:
