@@ -357,6 +357,23 @@ int mpn_frcnn_create(const mpn_frcnn_config *cfg, const float *const *d_conv_w, 
                      const float *d_fc6_w, const float *d_fc6_b, const float *d_fc7_w, const float *d_fc7_b,
                      const float *d_cls_w, const float *d_cls_b, const float *d_bbox_w, const float *d_bbox_b,
                      mpn_frcnn **out);
+/* The same handle with the integral loss's K classifiers (model_utils.lua:275-317, opt.integral on models/vgg.lua): d_cls_w
+ * [K*C, F] and d_cls_b [K*C] are the K clones of the classifier stacked in head order, n_integral = K in 1..MPN_MAX_INTEGRAL
+ * (the reference's scripts use 6).  The fused head becomes ONE Linear of (K+4)*C rows [cls_0 | .. | cls_{K-1} | bbox]; the scores
+ * every form returns (detect, test_one, the pipelined and host-fed forms, iterative localisation, the pyramid, flip augmentation,
+ * captured graphs) are the mean over k of softmax(cls_k) — summed in k order, then * (1/K), as nn.Mean —, the boxes are decoded
+ * from the one bbox regressor.  n_integral == 1 IS mpn_frcnn_create (which calls this with 1): the same code, the same bits.
+ * K > 1 with n_classes > 256 answers MPN_EINVAL (the integral score kernel's limit, as for the tower models); NULL pointers and K
+ * out of range answer MPN_EINVAL before any device work.  On a K > 1 handle the proposal-sharded forms (mpn_frcnn_shard_head /
+ * _shard_nms / _shard_finish, mpn_frcnn_test_one_sharded) answer MPN_ESTATE: sharding K classifiers is not supported.
+ * Training such a handle: mpn_frcnn_train_set_head below. */
+#define MPN_MAX_INTEGRAL 8
+int mpn_frcnn_create_integral(const mpn_frcnn_config *cfg, const float *const *d_conv_w, const float *const *d_conv_b,
+                              const float *d_fc6_w, const float *d_fc6_b, const float *d_fc7_w, const float *d_fc7_b,
+                              const float *d_cls_w /*[K*C, F]*/, const float *d_cls_b /*[K*C]*/, const float *d_bbox_w,
+                              const float *d_bbox_b, int n_integral, mpn_frcnn **out);
+/* K of the handle: mpn_frcnn_create_integral's n_integral, the towers' K for a tower model, 1 for every other handle. */
+int mpn_frcnn_n_integral(const mpn_frcnn *p);
 void mpn_frcnn_destroy(mpn_frcnn *p);
 
 /* MultiPathNet head (models/multipathnet.lua:64-120): nn.Foveal -> n_towers region towers, each
@@ -744,7 +761,24 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
  * from: a new handle created from the weights, train_begin, set_dropout, set_state gives the bits of the uninterrupted run (the
  * reference's model_<epoch>.t7 + optimState_<epoch>.t7, train.lua:188-198).
  * Debug tensors "train_y6" / "train_y7": fc6's / fc7's output of the last step as the next layer read it (behind the dropout),
- * [B, fc_dim] row-major, valid until the next mpn_frcnn_train_step. */
+ * [B, fc_dim] row-major, valid until the next mpn_frcnn_train_step.
+ *
+ * The integral loss (model_utils.lua:275-317, train.lua:288-294).  A K > 1 handle of
+ * mpn_frcnn_create_integral trains ONE of its K classifiers per minibatch:
+ *   mpn_frcnn_train_set_head  chooses the classifier k in [0, K) whose logits the loss of the NEXT mpn_frcnn_train_step reads — the
+ *                          reference's integral_selector.index, which it sets from the donkey index; the caller's schedule decides it.
+ *                          mpn_frcnn_train_begin starts at 0.  k outside [0, K): MPN_EINVAL naming K; without a train_begin: MPN_ESTATE.
+ *                          It may be called with rows pending (the head is read at the step) and is NOT part of the optimiser state
+ *                          (get_state / set_state do not carry it).  A K == 1 handle takes k = 0 only.
+ *   mpn_frcnn_train_step   on such a handle: the cross-entropy and its gradient read and write columns [k*C, (k+1)*C) of the fused
+ *                          head's row, the box columns are K*C + 4 y + j, and every other classifier's gradient columns are exactly
+ *                          +0.0.  The K - 1 unselected classifiers ARE stepped with that zero gradient, as engines/Optim.lua steps every
+ *                          module on every call: weight decay and momentum act on them; with momentum 0 and weight decay 0 their bits
+ *                          do not change.
+ *   mpn_frcnn_get_head_weights, mpn_frcnn_train_get_state / _set_state  on a K > 1 handle d_cls_w / d_cls_v are [K*C, F] and
+ *                          d_cls_b / d_cls_vb [K*C], the K classifiers stacked in head order as creation takes them.
+ * Debug tensor "cls_k" on a K > 1 plain handle: the K classifiers' logits of the last detect, [N, K*C]; "cls" there answers MPN_EINVAL
+ * naming "cls_k". */
 #define MPN_TRAIN_HEADS 0   /* cls + bbox linear only          */
 #define MPN_TRAIN_FC7   1   /* + fc7                           */
 #define MPN_TRAIN_FC6   2   /* + fc6 (the whole ROI head)      */
@@ -759,6 +793,7 @@ int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const 
 int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss /*[2]: cls, bbox*/, void *stream);
 int mpn_frcnn_train_end(mpn_frcnn *p);
 int mpn_frcnn_train_set_dropout(mpn_frcnn *p, float rate, long seed);
+int mpn_frcnn_train_set_head(mpn_frcnn *p, int k);
 int mpn_frcnn_train_get_state(mpn_frcnn *p, float *d_fc6_v, float *d_fc6_vb, float *d_fc7_v, float *d_fc7_vb, float *d_cls_v, float *d_cls_vb,
                               float *d_bbox_v, float *d_bbox_vb, long *h_step, void *stream);
 int mpn_frcnn_train_set_state(mpn_frcnn *p, const float *d_fc6_v, const float *d_fc6_vb, const float *d_fc7_v, const float *d_fc7_vb,
@@ -794,7 +829,8 @@ int mpn_frcnn_get_profile(mpn_frcnn *p, double *ms, long *counts, int n_tags, in
 /* Intermediate activations for parity tests: name in {"conv5","pooled","fc7","cls","bbox_raw"}; tower models (MultiPathNet, the
  * ResNet / op-list tower forms) keep "bbox_raw", "cls_k" (the K integral classifiers' pre-softmax logits, [N, K * C] row-major) and
  * "cat" (the towers' outputs side by side, [N, towers * fc_dim]); plain ResNet / op-list models keep "cls", "fc7" (the head's
- * average-pooled features) and "bbox_raw". */
+ * average-pooled features) and "bbox_raw"; a plain handle with K > 1 integral classifiers (mpn_frcnn_create_integral) keeps "cls_k"
+ * ([N, K * C]) in place of "cls". */
 int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems);
 
 #ifdef __cplusplus

@@ -113,6 +113,10 @@ def load(flavour=None):
     lib.mpn_frcnn_train_set_state.argtypes = [C.c_void_p] + [f32p] * 8 + [C.c_long, C.c_void_p]
     lib.mpn_frcnn_train_get_trunk_state.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
     lib.mpn_frcnn_train_set_trunk_state.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
+    # the integral loss on the plain handle (include/mpn.h): K classifiers stacked in cls_w / cls_b, the head the next step trains
+    lib.mpn_frcnn_create_integral.argtypes = [C.c_void_p] * 11 + [C.c_int, C.c_void_p]
+    lib.mpn_frcnn_n_integral.argtypes = [C.c_void_p]
+    lib.mpn_frcnn_train_set_head.argtypes = [C.c_void_p, C.c_int]
     _libs[fl] = lib
     return lib
 

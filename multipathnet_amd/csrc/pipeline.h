@@ -177,6 +177,12 @@ struct mpn_frcnn {
 };
 
 namespace mpn {
+// The fused head of a plain Fast R-CNN handle is one Linear of (K + 4) * C rows [cls_0 | .. | cls_{K-1} | bbox]: K = 1 for
+// mpn_frcnn_create and the plain ResNet / op-list handles (5C, as ever), mpn_frcnn_create_integral's n_integral otherwise
+inline int plain_head_width(const mpn_frcnn *p) { return (p->n_integral + 4) * p->cfg.n_classes; }
+// a plain VGG handle that holds K > 1 integral classifiers (tower models keep theirs behind the towers: cls_rm)
+inline bool plain_integral(const mpn_frcnn *p) { return !p->is_mpnet && !p->rn && p->n_integral > 1; }
+
 // ---- what the training driver needs from the pipeline (pipeline.hip)
 int obtain_features(mpn_frcnn *p, const float *d_image, int H0, int W0, int H, int W, double sc, mpn_frcnn::CachedMap *m, hipStream_t s, Act *feat);
 double getimages_size(int H0, int W0, double target, double cap, int *H, int *W);

@@ -103,8 +103,9 @@ __global__ void augment_merge_kernel(const float *__restrict__ sA, const float *
 }
 
 // integral eval head (model_utils.lua:296-313): K classifiers -> softmax each -> mean over K.
-// logits [M, K*C] row-major; one wave per row; sum over k in k order, then * (1/K) like nn.Mean.
-__global__ __launch_bounds__(256) void integral_softmax_mean_kernel(const float *__restrict__ logits, int M, int K, int C,
+// logits: row i's K * C values at logits + i * ld (ld == K * C: the tower models' contiguous [M, K*C]; the plain K-head handle's fused
+// head has the box columns behind them); one wave per row; sum over k in k order, then * (1/K) like nn.Mean.
+__global__ __launch_bounds__(256) void integral_softmax_mean_kernel(const float *__restrict__ logits, int ld, int M, int K, int C,
                                                                     float *__restrict__ scores) {
   int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void integral_softmax_mean_kernel(const float 
   // per k: max and sum over all C columns (wave reductions), then accumulate this lane's columns
   float accv[4] = {0.f, 0.f, 0.f, 0.f};  // supports C <= 256
   for (int k = 0; k < K; ++k) {
-    const float *r = logits + ((size_t)row * K + k) * C;
+    const float *r = logits + (size_t)row * ld + (size_t)k * C;
     float mx = -INFINITY;
     for (int c = lane; c < C; c += 64) mx = fmaxf(mx, r[c]);
 #pragma unroll
@@ -134,8 +135,8 @@ static int launch_head_softmax(const float *head, int ld, int M, int C, float *s
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
-static int launch_integral_softmax_mean(const float *logits, int M, int K, int C, float *scores, hipStream_t s) {
-  hipLaunchKernelGGL(integral_softmax_mean_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, logits, M, K, C, scores);
+static int launch_integral_softmax_mean(const float *logits, int ld, int M, int K, int C, float *scores, hipStream_t s) {
+  hipLaunchKernelGGL(integral_softmax_mean_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, logits, ld, M, K, C, scores);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
@@ -372,6 +373,7 @@ struct CreateArgs {
   const float *const *conv_w, *const *conv_b;
   const float *fc6_w, *fc6_b, *fc7_w, *fc7_b, *cls_w, *cls_b, *bbox_w, *bbox_b;
   const mpn_mpnet_weights *mw; const mpn_resnet_weights *rw; const mpn_graph_weights *gw;  // at most one of them
+  int n_integral = 1;  // none of them (mpn_frcnn_create_integral): the K classifiers stacked in cls_w / cls_b
   bool graph_net() const { return rw || gw; }  // the trunk / per-ROI stage live in a ResNetGraph object
   int tower_heads() const { return rw ? rw->n_heads : (gw ? gw->n_heads : 0); }  // > 1: MultiPathNet towers on a ResNet / op-list backbone
 };
@@ -403,6 +405,14 @@ static int check_config(const CreateArgs &a) {
   if (cfg->roi_bin_rule != MPN_ROI_BINS_CAFFE && cfg->roi_bin_rule != MPN_ROI_BINS_ADAPTIVE) { set_error("mpn_frcnn_config.roi_bin_rule: %d is not an MPN_ROI_BINS_* value", cfg->roi_bin_rule); return MPN_EINVAL; }
   for (int l = 0; !graph_net && l < cfg->n_conv; ++l) MPN_CHECK_ARG(a.conv_w[l] != nullptr);
   const int C = cfg->n_classes;
+  if (a.n_integral < 1 || a.n_integral > MPN_MAX_INTEGRAL) {
+    set_error("mpn_frcnn_create_integral: invalid argument: n_integral %d is outside 1..MPN_MAX_INTEGRAL (%d)", a.n_integral, MPN_MAX_INTEGRAL);
+    return MPN_EINVAL;
+  }
+  if (a.n_integral > 1 && C > 256) {
+    set_error("mpn_frcnn_create_integral: invalid argument: %d integral classifiers need n_classes <= 256 (the integral score kernel's limit), not %d", a.n_integral, C);
+    return MPN_EINVAL;
+  }
   if (const mpn_mpnet_weights *mw = a.mw) {
     MPN_CHECK_ARG(mw->n_towers >= 2 && mw->n_towers <= 8 && mw->tap_conv3 >= 0 && mw->tap_conv4 > mw->tap_conv3 && mw->tap_conv4 < cfg->n_conv - 1);
     MPN_CHECK_ARG(C <= 256 && cfg->fc_dim % 128 == 0);
@@ -556,6 +566,7 @@ static int build_integral_classifier(mpn_frcnn *p, const CreateArgs &a, int n_to
 static int build_plain_head(mpn_frcnn *p, const CreateArgs &a, float **tmp_w, float **tmp_b) {
   const bool graph_net = a.graph_net(), split3 = p->cfg.fc_arith == MPN_FC_SPLIT3;
   const int PP = p->cfg.pooled_h * p->cfg.pooled_w, C = p->cfg.n_classes, F = p->cfg.fc_dim;
+  const int KC = p->n_integral * C, NH = plain_head_width(p);  // the K classifiers' rows (K = 1 but for mpn_frcnn_create_integral); the fused head's
   const size_t M = p->cfg.max_rois, y_bytes = (size_t)(lin_np(F) / 8) * p->Mp * 8 * sizeof(float);
   if (!graph_net) {
     TRY(pack_linear(p, a.fc6_w, a.fc6_b, p->K6, F, PP, &p->w6, &p->b6));
@@ -569,15 +580,15 @@ static int build_plain_head(mpn_frcnn *p, const CreateArgs &a, float **tmp_w, fl
       TRY(p->own.alloc(&p->y6_s3, split3_plane_elems(F, p->Mp) * sizeof(unsigned short), true));
     }
   }
-  // cls and bbox heads share their input -> one [5C, F] GEMM (model_utils.lua:105-119 ConcatTable)
-  TRY(p->own.alloc(tmp_w, (size_t)5 * C * F * sizeof(float)));
-  TRY(p->own.alloc(tmp_b, (size_t)5 * C * sizeof(float), true));
-  hipError_t e = hipMemcpy(*tmp_w, a.cls_w, (size_t)C * F * sizeof(float), hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipMemcpy(*tmp_w + (size_t)C * F, a.bbox_w, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice);
-  if (e == hipSuccess && a.cls_b) e = hipMemcpy(*tmp_b, a.cls_b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice);
-  if (e == hipSuccess && a.bbox_b) e = hipMemcpy(*tmp_b + C, a.bbox_b, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice);
+  // cls (the K integral classifiers stacked) and bbox heads share their input -> one [(K+4)C, F] GEMM (model_utils.lua:105-119 ConcatTable)
+  TRY(p->own.alloc(tmp_w, (size_t)NH * F * sizeof(float)));
+  TRY(p->own.alloc(tmp_b, (size_t)NH * sizeof(float), true));
+  hipError_t e = hipMemcpy(*tmp_w, a.cls_w, (size_t)KC * F * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(*tmp_w + (size_t)KC * F, a.bbox_w, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && a.cls_b) e = hipMemcpy(*tmp_b, a.cls_b, (size_t)KC * sizeof(float), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess && a.bbox_b) e = hipMemcpy(*tmp_b + KC, a.bbox_b, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice);
   if (e != hipSuccess) { set_error("mpn_frcnn_create: head weight copy failed: %s", hipGetErrorString(e)); return MPN_EHIP; }
-  TRY(pack_linear(p, *tmp_w, *tmp_b, F, 5 * C, 1, &p->wh, &p->bh));
+  TRY(pack_linear(p, *tmp_w, *tmp_b, F, NH, 1, &p->wh, &p->bh));
   if (!graph_net) {
     int fh = p->cfg.max_h, fw = p->cfg.max_w;  // pixel-major copy of the final map at its largest size
     final_map_size(p, &fh, &fw);
@@ -586,7 +597,7 @@ static int build_plain_head(mpn_frcnn *p, const CreateArgs &a, float **tmp_w, fl
     TRY(p->own.alloc(&p->y6, y_bytes, true));
   }
   TRY(p->own.alloc(&p->y7, y_bytes, true));
-  return p->own.alloc(&p->head, M * 5 * C * sizeof(float), true);
+  return p->own.alloc(&p->head, M * NH * sizeof(float), true);
 }
 
 // rois, score / box tables, the iterative-localisation tables, the two NMS buffer sets
@@ -652,6 +663,7 @@ static int create_handle(const CreateArgs &a, mpn_frcnn **out) {
   const int tower_heads = a.tower_heads();
   if (tower_heads > 1) p->n_integral = (a.rw ? a.rw->n_integral : a.gw->n_integral) > 0 ? (a.rw ? a.rw->n_integral : a.gw->n_integral) : 1;
   if (const mpn_mpnet_weights *mw = a.mw) { p->is_mpnet = true; p->tap3 = mw->tap_conv3; p->tap4 = mw->tap_conv4; p->n_integral = mw->n_integral > 0 ? mw->n_integral : 1; p->conv345_norm = !mw->conv345_unnormalized; }
+  if (!a.mw && !graph_net) p->n_integral = a.n_integral;  // mpn_frcnn_create_integral: K classifiers in the plain head
   const int n_conv = graph_net ? 0 : cfg->n_conv;
   p->cfg.n_conv = n_conv;
   if (n_conv) { p->cout.assign(cfg->conv_cout, cfg->conv_cout + n_conv); p->pool_after.assign(cfg->pool_after, cfg->pool_after + n_conv); }
@@ -956,7 +968,7 @@ static int run_integral_heads(mpn_frcnn *p, const float *d_boxes, int N, int H, 
     if (rc == MPN_OK) rc = linear_c8(p->cat + (size_t)n_fov * Fcb * Mp * 8, N, F, p->wbbox, p->bbbox, 4 * C, 0, nullptr, p->bbox_rm, s, Mp, nullptr, 1); }
   if (rc) return rc;
   ProfScope ps_post(p, MPN_PROF_POST, s);
-  rc = launch_integral_softmax_mean(p->cls_rm, N, K, C, p->scores, s);
+  rc = launch_integral_softmax_mean(p->cls_rm, K * C, N, K, C, p->scores, s);
   if (rc) return rc;
   return launch_head_decode(p->bbox_rm, 4 * C, 0, N, C, d_boxes, c.bbox_mean, c.bbox_std, clamp, (float)W, (float)H, p->bbox_raw, p->bbox, s);
 }
@@ -1097,16 +1109,17 @@ static int run_resnet_towers_head(mpn_frcnn *p, const float *d_boxes, int N, int
 // (model_utils.lua:105-119), softmax, decode (+ clamp).  `s`: the launch stream (hs != s: the side stream took the heads over).
 static int run_plain_heads(mpn_frcnn *p, const float *y7, const float *dec_boxes, int N, int H, int W, hipStream_t hs, hipStream_t s, int clamp) {
   const mpn_frcnn_config &c = p->cfg;
-  const int C = c.n_classes, F = c.fc_dim;
+  const int C = c.n_classes, F = c.fc_dim, K = p->n_integral, NH = plain_head_width(p);
   int rc;
   { ProfScope ps(p, MPN_PROF_HEADS, hs);
     SplitkSlotScope sk(hs != s ? SCR_GEMM_SPLITK_SIDE : SCR_GEMM_SPLITK);  // its partial sums must not share a buffer with fc6 / fc7 of the next image
-    rc = linear_c8(y7, N, F, p->wh, p->bh, 5 * C, 0, nullptr, p->head, hs, 0, nullptr, 1); }
+    rc = linear_c8(y7, N, F, p->wh, p->bh, NH, 0, nullptr, p->head, hs, 0, nullptr, 1); }
   if (rc) return rc;
   ProfScope ps_post(p, MPN_PROF_POST, hs);
-  rc = launch_head_softmax(p->head, 5 * C, N, C, p->scores, hs);
+  // K integral classifiers (model_utils.lua:296-313): the mean of their softmaxes, read at the fused head's row pitch
+  rc = K > 1 ? launch_integral_softmax_mean(p->head, NH, N, K, C, p->scores, hs) : launch_head_softmax(p->head, NH, N, C, p->scores, hs);
   if (rc) return rc;
-  rc = launch_head_decode(p->head, 5 * C, C, N, C, dec_boxes, c.bbox_mean, c.bbox_std, clamp, (float)W, (float)H, p->bbox_raw, p->bbox, hs);
+  rc = launch_head_decode(p->head, NH, K * C, N, C, dec_boxes, c.bbox_mean, c.bbox_std, clamp, (float)W, (float)H, p->bbox_raw, p->bbox, hs);
   if (rc) return rc;
   p->last_n = N;
   return MPN_OK;
@@ -1459,6 +1472,12 @@ extern "C" int mpn_frcnn_test_one(mpn_frcnn *p, const float *d_image, int H, int
 // The three steps take caller-provided records so that the exchange between them can be any transport; mpn_frcnn_test_one_sharded
 // chains them over an mpn_comm (RCCL all-gather, comm.hip).
 static int refuse_multi_pass(const mpn_frcnn *p, const char *form);
+// the sharded forms cut the head by class into records of 5C floats per row: a plain handle with K > 1 integral classifiers has no such layout
+static int refuse_shard_integral(const mpn_frcnn *p, const char *form) {
+  if (!plain_integral(p)) return MPN_OK;
+  set_error("%s: not supported on a handle with %d integral classifiers (mpn_frcnn_create_integral): the sharded records hold one classifier; use mpn_frcnn_test_one", form, p->n_integral);
+  return MPN_ESTATE;
+}
 
 extern "C" int mpn_shard_range(int n, int world, int rank, int *lo, int *hi) {
   MPN_CHECK_ARG(n >= 0 && world >= 1 && rank >= 0 && rank < world && lo && hi);
@@ -1481,6 +1500,7 @@ extern "C" size_t mpn_frcnn_shard_class_floats(const mpn_frcnn *p, int N, int wo
 extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_boxes, int N, int rank, int world,
                                     float *d_rows_rec, void *stream) {
   MPN_CHECK_ARG(p != nullptr && d_boxes && d_rows_rec && N > 0 && N <= p->cfg.max_rois && world >= 1 && rank >= 0 && rank < world);
+  if (int ri = refuse_shard_integral(p, "mpn_frcnn_shard_head")) return ri;
   if (int rp = refuse_multi_pass(p, "mpn_frcnn_shard_head")) return rp;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
@@ -1508,6 +1528,7 @@ extern "C" int mpn_frcnn_shard_head(mpn_frcnn *p, const float *d_image, int H, i
 
 extern "C" int mpn_frcnn_shard_nms(mpn_frcnn *p, const float *d_rows_all, int N, int rank, int world, float *d_class_rec, void *stream) {
   MPN_CHECK_ARG(p != nullptr && d_rows_all && d_class_rec && N > 0 && N <= p->cfg.max_rois && world >= 1 && rank >= 0 && rank < world);
+  if (int ri = refuse_shard_integral(p, "mpn_frcnn_shard_nms")) return ri;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   int rc = mpn_frcnn_flush(p, stream);
@@ -1545,6 +1566,7 @@ extern "C" int mpn_frcnn_shard_finish(mpn_frcnn *p, const float *d_class_all, in
                                       void *stream) {
   MPN_CHECK_ARG(p != nullptr && d_class_all && N > 0 && N <= p->cfg.max_rois && world >= 1);
   MPN_CHECK_ARG(d_n_dets && (top_cap == 0 || d_dets) && top_cap >= 0);
+  if (int ri = refuse_shard_integral(p, "mpn_frcnn_shard_finish")) return ri;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
   const mpn_frcnn_config &c = p->cfg;
@@ -1565,6 +1587,7 @@ extern "C" int mpn_frcnn_shard_finish(mpn_frcnn *p, const float *d_class_all, in
 extern "C" int mpn_frcnn_test_one_sharded(mpn_frcnn *p, mpn_comm *comm, const float *d_image, int H, int W, const float *d_boxes, int N,
                                           float *d_dets, int top_cap, int *d_n_dets, void *stream) {
   MPN_CHECK_ARG(p != nullptr && comm != nullptr && N > 0);
+  if (int ri = refuse_shard_integral(p, "mpn_frcnn_test_one_sharded")) return ri;
   if (int rp = refuse_multi_pass(p, "mpn_frcnn_test_one_sharded")) return rp;
   hipStream_t s = as_stream(stream);
   const int world = mpn_comm_world(comm), rank = mpn_comm_rank(comm);
@@ -1703,8 +1726,18 @@ extern "C" int mpn_frcnn_create(const mpn_frcnn_config *cfg, const float *const 
                                 const float *d_fc6_w, const float *d_fc6_b, const float *d_fc7_w, const float *d_fc7_b,
                                 const float *d_cls_w, const float *d_cls_b, const float *d_bbox_w, const float *d_bbox_b,
                                 mpn_frcnn **out) {
-  return create_handle(CreateArgs{cfg, d_conv_w, d_conv_b, d_fc6_w, d_fc6_b, d_fc7_w, d_fc7_b, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, nullptr, nullptr}, out);
+  return mpn_frcnn_create_integral(cfg, d_conv_w, d_conv_b, d_fc6_w, d_fc6_b, d_fc7_w, d_fc7_b, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, 1, out);
 }
+
+extern "C" int mpn_frcnn_create_integral(const mpn_frcnn_config *cfg, const float *const *d_conv_w, const float *const *d_conv_b,
+                                         const float *d_fc6_w, const float *d_fc6_b, const float *d_fc7_w, const float *d_fc7_b,
+                                         const float *d_cls_w, const float *d_cls_b, const float *d_bbox_w, const float *d_bbox_b,
+                                         int n_integral, mpn_frcnn **out) {
+  return create_handle(CreateArgs{cfg, d_conv_w, d_conv_b, d_fc6_w, d_fc6_b, d_fc7_w, d_fc7_b, d_cls_w, d_cls_b, d_bbox_w, d_bbox_b, nullptr, nullptr, nullptr,
+                                  n_integral}, out);
+}
+
+extern "C" int mpn_frcnn_n_integral(const mpn_frcnn *p) { return p ? p->n_integral : 0; }
 
 extern "C" int mpn_mpnet_create(const mpn_frcnn_config *cfg, const float *const *d_conv_w, const float *const *d_conv_b,
                                 const mpn_mpnet_weights *mw, const float *d_cls_w, const float *d_cls_b,
@@ -1907,7 +1940,7 @@ extern "C" int mpn_debug_head_post(int which, const float *d_a, const float *d_b
       MPN_CHECK_ARG(C <= 256 && K >= 1);
       if (M == 0) return MPN_OK;
       MPN_CHECK_ARG(d_a && d_out);
-      return launch_integral_softmax_mean(d_a, M, K, C, d_out, s);
+      return launch_integral_softmax_mean(d_a, K * C, M, K, C, d_out, s);
     case 2:
       MPN_CHECK_ARG(col0 >= 0 && ld >= col0 + 4 * C && (h_mean4 != nullptr) == (h_std4 != nullptr));
       if (M == 0) return MPN_OK;
@@ -1938,6 +1971,10 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
     const int rct = train_debug_tensor(p, name, d_ptr, n_elems, &known);
     if (known) return rct;
   }
+  if (plain_integral(p) && !strcmp(name, "cls")) {
+    set_error("mpn_frcnn_debug_tensor: invalid argument: a handle with %d integral classifiers keeps no single 'cls': ask for \"cls_k\" ([N, K * C])", p->n_integral);
+    return MPN_EINVAL;
+  }
   if (p->last_n <= 0 || (!p->rn && p->last_h <= 0)) { set_error("mpn_frcnn_debug_tensor: run detect first"); return MPN_ESTATE; }
   const mpn_frcnn_config &c = p->cfg;
   const int N = p->last_n, C = c.n_classes, F = c.fc_dim, PP = c.pooled_h * c.pooled_w;
@@ -1961,7 +1998,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   else if (nm == "cat") n = (size_t)N * (p->is_mpnet ? p->towers.size() : p->rn_region.size()) * F;  // tower outputs side by side [N, towers * F]
   else { set_error("mpn_frcnn_debug_tensor: unknown tensor '%s'", name); return MPN_EINVAL; }
   const bool towers = p->is_mpnet || (p->rn && !p->rn_region.empty());
-  if ((nm == "cls_k" || nm == "cat") && (!towers || lin_np(F) != F)) { set_error("mpn_frcnn_debug_tensor: '%s' needs a tower model (integral heads)", name); return MPN_EINVAL; }
+  if ((nm == "cls_k" || nm == "cat") && (!towers || lin_np(F) != F) && !(nm == "cls_k" && plain_integral(p))) { set_error("mpn_frcnn_debug_tensor: '%s' needs a tower model (integral heads)", name); return MPN_EINVAL; }
   if (p->is_mpnet && nm != "conv5" && nm != "bbox_raw" && nm != "cls_k" && nm != "cat") { set_error("mpn_frcnn_debug_tensor: '%s' is not kept by the MultiPathNet head", name); return MPN_EINVAL; }
   if (p->rn && nm != "bbox_raw" && nm != "cls_k" && nm != "cat" && !((nm == "cls" || nm == "fc7") && p->rn_region.empty())) { set_error("mpn_frcnn_debug_tensor: '%s' is not kept by the op-list / ResNet pipelines", name); return MPN_EINVAL; }
   MPN_CHECK_HIP(hipDeviceSynchronize());
@@ -1979,12 +2016,15 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
     rc = launch_unpack_pooled(p->x6, N, p->feat_c, PP, lin_mp(N), p->dbg);
   } else if (nm == "fc7") {
     rc = c8_to_rowmajor(p->y7_last ? p->y7_last : p->y7, N, F, p->dbg, nullptr);  // rows at stride lin_mp(N), as linear_c8 wrote them
+  } else if (nm == "cls_k" && plain_integral(p)) {  // the first K * C columns of the fused head
+    hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, p->head, plain_head_width(p), 0, N, p->n_integral * C, p->dbg);
+    MPN_CHECK_LAUNCH();
   } else if (nm == "cls_k") {
     MPN_CHECK_HIP(hipMemcpy(p->dbg, p->cls_rm, n * sizeof(float), hipMemcpyDeviceToDevice));
   } else if (nm == "cat") {
     rc = c8_to_rowmajor(p->cat, N, (int)(n / N), p->dbg, nullptr);  // towers' [F/8][Mp][8] blocks back to back == one C8 matrix of towers * F columns
   } else if (nm == "cls") {
-    hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, p->head, 5 * C, 0, N, C, p->dbg);
+    hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, p->head, plain_head_width(p), 0, N, C, p->dbg);
     MPN_CHECK_LAUNCH();
   } else {
     MPN_CHECK_HIP(hipMemcpy(p->dbg, p->bbox_raw, n * sizeof(float), hipMemcpyDeviceToDevice));

@@ -7,15 +7,18 @@
 namespace mpn {
 
 // train.lua:154-158 + BBoxRegressionCriterion.lua on B rows, ONE launch:
-//   d_head [B, 5C] row-major = [cls logits z | raw box outputs t^] (what linear_c8 writes as y_rm for the fused head);
+//   d_head [B, (K+4)C] row-major = [cls_0 | .. | cls_{K-1} | raw box outputs t^] (what linear_c8 writes as y_rm for the fused head);
+//   z = the logits of classifier k, columns [kC, (k+1)C) — the integral loss trains one of its K classifiers per minibatch
+//   (model_utils.lua:275-317, train.lua:288-294); K = 1, k = 0: the plain head [z | t^];
 //   d_rois, d_gt [B,4] boxes of the original image, d_labels [B] (0 = background; values outside [0, C) are clamped into it);
 //   targets t = (convertTo(roi, gt) - mean) / std for labels > 0 (utils.lua:171-184; norm == 0: no normalisation);
 //   d_loss[0] = (1/B) sum_i (logsumexp(z_i) - z_i[y_i]),  d_loss[1] = (bbox_weight/B) sum_{i: y_i > 0} sum_j smoothL1(t^_{i,4y_i+j} - t_{i,j});
-//   d_g_c8 [ceil(5C/8)][Mp][8] = the gradient w.r.t. d_head as a C8 matrix, rows < B (pad lanes 5C.. of the last chunk +0):
-//     (softmax - onehot)/B on the class columns, (bbox_weight/B) clamp(d, -1, 1) on the four target columns, 0 elsewhere.
+//   d_g_c8 [ceil((K+4)C/8)][Mp][8] = the gradient w.r.t. d_head as a C8 matrix, rows < B (pad lanes (K+4)C.. of the last chunk +0):
+//     (softmax - onehot)/B on classifier k's columns, (bbox_weight/B) clamp(d, -1, 1) on the four target columns KC + 4y + j,
+//     exactly +0.0 elsewhere — the K - 1 other classifiers' columns included.
 // The two sums are reduced in a fixed order (one block: per-thread row-ascending partial sums, then a fixed LDS tree): deterministic.
 struct LossCfg { float mean[4], std[4]; int norm; float bbox_weight; };
-int train_loss(const float *d_head, int B, int C, const float *d_rois, const float *d_gt, const int *d_labels, const LossCfg &cfg,
+int train_loss(const float *d_head, int B, int C, int K, int k, const float *d_rois, const float *d_gt, const int *d_labels, const LossCfg &cfg,
                float *d_g_c8, int Mp, float *d_loss, hipStream_t s);
 
 // Weight gradient fused with optim.sgd (engines/Optim.lua: dampening 0, no Nesterov) on a packed linear weight [K64/8][NP][8]:

@@ -27,15 +27,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Loss + gradient w.r.t. the head's output
 // ---------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict__ head, int B, int C, const float *__restrict__ rois,
+// K classifiers in the row (the integral loss, model_utils.lua:275-317), of which classifier k is trained: its logits are columns
+// [c0, c0 + C), c0 = k * C; the box outputs start at column cb = K * C.  K = 1, k = 0 is the plain head (c0 = 0, cb = C).
+__global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict__ head, int B, int C, int K, int k, const float *__restrict__ rois,
                                                          const float *__restrict__ gt, const int *__restrict__ labels, LossCfg cfg,
                                                          float *__restrict__ g, int Mp, float *__restrict__ loss) {
   __shared__ float s_cls[256], s_box[256];
-  const int ld = 5 * C, nchunk = (5 * C + 7) / 8;
+  const int ld = (K + 4) * C, nchunk = (ld + 7) / 8, c0 = k * C, cb = K * C;
   const float invB = 1.0f / (float)B, gbox = cfg.bbox_weight / (float)B;
   float acc_cls = 0.0f, acc_box = 0.0f;
   for (int i = threadIdx.x; i < B; i += 256) {  // one row per thread, rows ascending
-    const float *z = head + (size_t)i * ld;
+    const float *zr = head + (size_t)i * ld, *z = zr + c0;  // the row; the selected classifier's logits
     int y = labels[i];
     y = y < 0 ? 0 : (y >= C ? C - 1 : y);
     float mx = z[0];
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (cfg.norm) tg[j] = (tg[j] - cfg.mean[j]) / cfg.std[j];
-        d[j] = z[C + 4 * y + j] - tg[j];
+        d[j] = zr[cb + 4 * y + j] - tg[j];
         const float a = fabsf(d[j]);
         row += a < 1.0f ? 0.5f * d[j] * d[j] : a - 0.5f;
       }
@@ -66,9 +68,9 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict
       for (int e = 0; e < 8; ++e) {
         const int n = q * 8 + e;
         float t = 0.0f;
-        if (n < C) t = (expf(z[n] - mx) * inv_sum - (n == y ? 1.0f : 0.0f)) * invB;
-        else if (y > 0 && n >= C + 4 * y && n < C + 4 * y + 4) {
-          const int j = n - C - 4 * y;
+        if (n >= c0 && n < c0 + C) t = (expf(z[n - c0] - mx) * inv_sum - (n - c0 == y ? 1.0f : 0.0f)) * invB;
+        else if (y > 0 && n >= cb + 4 * y && n < cb + 4 * y + 4) {  // (every other classifier's columns: exactly +0.0)
+          const int j = n - cb - 4 * y;
           const float dd = j == 0 ? d[0] : (j == 1 ? d[1] : (j == 2 ? d[2] : d[3]));
           t = gbox * (dd < -1.0f ? -1.0f : (dd > 1.0f ? 1.0f : dd));
         }
@@ -88,10 +90,10 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict
   if (threadIdx.x == 0) { loss[0] = s_cls[0] * invB; loss[1] = s_box[0] * gbox; }
 }
 
-int train_loss(const float *d_head, int B, int C, const float *d_rois, const float *d_gt, const int *d_labels, const LossCfg &cfg,
+int train_loss(const float *d_head, int B, int C, int K, int k, const float *d_rois, const float *d_gt, const int *d_labels, const LossCfg &cfg,
                float *d_g_c8, int Mp, float *d_loss, hipStream_t s) {
-  MPN_CHECK_ARG(d_head && d_rois && d_gt && d_labels && d_g_c8 && d_loss && B > 0 && C > 1 && Mp >= B);
-  hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(256), 0, s, d_head, B, C, d_rois, d_gt, d_labels, cfg, d_g_c8, Mp, d_loss);
+  MPN_CHECK_ARG(d_head && d_rois && d_gt && d_labels && d_g_c8 && d_loss && B > 0 && C > 1 && Mp >= B && K >= 1 && k >= 0 && k < K);
+  hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(256), 0, s, d_head, B, C, K, k, d_rois, d_gt, d_labels, cfg, d_g_c8, Mp, d_loss);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }

@@ -19,7 +19,8 @@ struct TrainState {
   struct LinT { float *w, *b; int K, N, inner, relu; float *x, *g, *v, *vb; };
   LinT fc[3] = {};                     // fc6, fc7, the fused cls + bbox head
   int n_fc = 1;                        // how many of them, counted from the head down, are trained
-  float *head = nullptr;               // the head's output, row-major [B, 5C]
+  float *head = nullptr;               // the head's output, row-major [B, (K+4)C]
+  int head_k = 0;                      // the integral classifier the next step's loss reads (mpn_frcnn_train_set_head); not optimiser state
   float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
   int *labels = nullptr;
   int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensors "train_pooled", "train_y6", "train_y7")
@@ -28,7 +29,7 @@ struct TrainState {
   float drop_rate = 0.f, drop_scale = 1.f;   // scale = 1.0f / (1.0f - rate)
   uint32_t drop_threshold = 0;         // floor(rate * 2^32): an element is kept iff its word >= this
   long seed = 0, step = 0;             // step: the train_steps that reached the forward pass (mpn_frcnn_train_get_state / _set_state)
-  float *vtmp = nullptr;               // mpn_frcnn_train_set_state: cls and bbox momentum joined as creation joins the weights, [5C, F] + [5C]
+  float *vtmp = nullptr;               // mpn_frcnn_train_set_state: cls and bbox momentum joined as creation joins the weights, [(K+4)C, F] + [(K+4)C]
   // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
   // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
   struct ConvT {
@@ -167,11 +168,11 @@ static void layout_train_maps(const mpn_frcnn *p, TrainState *t) {
 // false: something failed (t's DeviceOwner holds what was made)
 static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
   const mpn_frcnn_config &c = p->cfg;
-  const int F = c.fc_dim, C = c.n_classes, k = t->kconv, PP = c.pooled_h * c.pooled_w;
+  const int F = c.fc_dim, k = t->kconv, PP = c.pooled_h * c.pooled_w;
   const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
   t->fc[0] = LinT{p->w6, p->b6, p->K6, F, PP, 1};
   t->fc[1] = LinT{p->w7, p->b7, F, F, 1, 1};
-  t->fc[2] = LinT{p->wh, p->bh, F, 5 * C, 1, 0};
+  t->fc[2] = LinT{p->wh, p->bh, F, plain_head_width(p), 1, 0};
   auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
   auto trained = [&](LinT &L) {  // momentum and the gradient at the output
     return alloc0(&L.v, lin_wpk_elems(round_up(L.K, 64), L.N) * sizeof(float)) && alloc0(&L.vb, (size_t)lin_np(L.N) * sizeof(float)) &&
@@ -180,7 +181,7 @@ static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
   bool ok = trained(t->fc[2]);
   ok = ok && alloc0(&t->fc[0].x, (size_t)(round_up(p->K6, 64) / 8) * rec);
   for (int i = 1; i < 3; ++i) ok = ok && alloc0(&t->fc[i].x, (size_t)(lin_np(t->fc[i - 1].N) / 8) * rec);  // the output of the layer below
-  ok = ok && alloc0(&t->head, M * 5 * C * sizeof(float));
+  ok = ok && alloc0(&t->head, M * plain_head_width(p) * sizeof(float));
   for (int i = 1; i >= 3 - t->n_fc; --i) ok = ok && trained(t->fc[i]);
   ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
   ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
@@ -388,7 +389,7 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
   lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
   lc.bbox_weight = t->bbox_weight;
-  rc = train_loss(t->head, B, c.n_classes, t->rois, t->gt, t->labels, lc, t->fc[2].g, Mp, d_loss ? d_loss : t->loss, s);
+  rc = train_loss(t->head, B, c.n_classes, p->n_integral, t->head_k, t->rois, t->gt, t->labels, lc, t->fc[2].g, Mp, d_loss ? d_loss : t->loss, s);
   // backward: every input gradient before the update of the weights it was computed with.  L.x is what the dropout left: a dropped
   // element is +0.0, so the kernel's [x > 0] is keep mask x ReLU mask and the dropout's backward is the factor 1 / (1 - rate) alone
   for (int i = 2; i > lowest && rc == MPN_OK; --i) {
@@ -412,6 +413,18 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   t->last_rows = B;
   t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
   return rc;
+}
+
+extern "C" int mpn_frcnn_train_set_head(mpn_frcnn *p, int k) {
+  MPN_CHECK_ARG(p != nullptr);
+  TrainState *t = p->train;
+  if (!t) { set_error("mpn_frcnn_train_set_head: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
+  if (k < 0 || k >= p->n_integral) {
+    set_error("mpn_frcnn_train_set_head: invalid argument: head %d is outside [0, K) of this handle's K = %d integral classifiers", k, p->n_integral);
+    return MPN_EINVAL;
+  }
+  t->head_k = k;  // read by the next mpn_frcnn_train_step
+  return MPN_OK;
 }
 
 extern "C" int mpn_frcnn_train_set_dropout(mpn_frcnn *p, float rate, long seed) {
@@ -458,15 +471,15 @@ extern "C" int mpn_frcnn_train_get_state(mpn_frcnn *p, float *d_fc6_v, float *d_
   const float *const q[8] = {d_fc6_v, d_fc6_vb, d_fc7_v, d_fc7_vb, d_cls_v, d_cls_vb, d_bbox_v, d_bbox_vb};
   int rc = check_state_tensors(t, "mpn_frcnn_train_get_state", q, false);
   if (rc) return rc;
-  const int C = p->cfg.n_classes;
+  const int KC = p->n_integral * p->cfg.n_classes;  // the K classifiers' rows of the fused head, bbox behind them
   hipStream_t s = as_stream(stream);
   for (int i = 3 - t->n_fc; i < 2 && rc == MPN_OK; ++i) {
     const LinT &L = t->fc[i];
     rc = unpack_linear_weights(L.v, L.vb, L.K, L.N, L.inner, 0, L.N, i ? d_fc7_v : d_fc6_v, i ? d_fc7_vb : d_fc6_vb, s);
   }
   const LinT &Lh = t->fc[2];
-  if (rc == MPN_OK) rc = unpack_linear_weights(Lh.v, Lh.vb, Lh.K, Lh.N, 1, 0, C, d_cls_v, d_cls_vb, s);
-  if (rc == MPN_OK) rc = unpack_linear_weights(Lh.v, Lh.vb, Lh.K, Lh.N, 1, C, 5 * C, d_bbox_v, d_bbox_vb, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(Lh.v, Lh.vb, Lh.K, Lh.N, 1, 0, KC, d_cls_v, d_cls_vb, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(Lh.v, Lh.vb, Lh.K, Lh.N, 1, KC, Lh.N, d_bbox_v, d_bbox_vb, s);
   if (rc == MPN_OK && h_step) *h_step = t->step;
   return rc;
 }
@@ -482,9 +495,9 @@ extern "C" int mpn_frcnn_train_set_state(mpn_frcnn *p, const float *d_fc6_v, con
   int rc = check_state_tensors(t, "mpn_frcnn_train_set_state", q, true);
   if (rc) return rc;
   if (step < 0) { set_error("mpn_frcnn_train_set_state: step %ld is negative", step); return MPN_EINVAL; }
-  const int C = p->cfg.n_classes, F = p->cfg.fc_dim;
+  const int C = p->cfg.n_classes, F = p->cfg.fc_dim, KC = p->n_integral * C, NH = plain_head_width(p);
   hipStream_t s = as_stream(stream);
-  if (!t->vtmp && t->own.alloc(&t->vtmp, ((size_t)5 * C * F + 5 * C) * sizeof(float), true) != MPN_OK) {
+  if (!t->vtmp && t->own.alloc(&t->vtmp, ((size_t)NH * F + NH) * sizeof(float), true) != MPN_OK) {
     set_error("mpn_frcnn_train_set_state: allocating the joined head momentum failed: %s", hipGetErrorString(hipGetLastError()));
     return MPN_ENOMEM;
   }
@@ -493,12 +506,12 @@ extern "C" int mpn_frcnn_train_set_state(mpn_frcnn *p, const float *d_fc6_v, con
     rc = pack_linear_weights(i ? d_fc7_v : d_fc6_v, i ? d_fc7_vb : d_fc6_vb, L.K, L.N, L.inner, L.v, L.vb, s);
   }
   if (rc) return rc;
-  // cls and bbox joined into the fused head's [5C, F] as creation joins the weights, then the same packer
-  float *jw = t->vtmp, *jb = t->vtmp + (size_t)5 * C * F;
-  MPN_CHECK_HIP(hipMemcpyAsync(jw, d_cls_v, (size_t)C * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(jw + (size_t)C * F, d_bbox_v, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(jb, d_cls_vb, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(jb + C, d_bbox_vb, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // cls (the K classifiers stacked) and bbox joined into the fused head's [(K+4)C, F] as creation joins the weights, then the same packer
+  float *jw = t->vtmp, *jb = t->vtmp + (size_t)NH * F;
+  MPN_CHECK_HIP(hipMemcpyAsync(jw, d_cls_v, (size_t)KC * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(jw + (size_t)KC * F, d_bbox_v, (size_t)4 * C * F * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(jb, d_cls_vb, (size_t)KC * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(jb + KC, d_bbox_vb, (size_t)4 * C * sizeof(float), hipMemcpyDeviceToDevice, s));
   const LinT &Lh = t->fc[2];
   rc = pack_linear_weights(jw, jb, Lh.K, Lh.N, 1, Lh.v, Lh.vb, s);
   if (rc == MPN_OK) t->step = step;
@@ -546,12 +559,12 @@ extern "C" int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d
     return MPN_ESTATE;
   }
   const mpn_frcnn_config &c = p->cfg;
-  const int F = c.fc_dim, C = c.n_classes;
+  const int F = c.fc_dim, KC = p->n_integral * c.n_classes, NH = plain_head_width(p);  // cls: the K classifiers' rows [K*C, F]
   hipStream_t s = as_stream(stream);
   int rc = unpack_linear_weights(p->w6, p->b6, p->K6, F, c.pooled_h * c.pooled_w, 0, F, d_fc6_w, d_fc6_b, s);
   if (rc == MPN_OK) rc = unpack_linear_weights(p->w7, p->b7, F, F, 1, 0, F, d_fc7_w, d_fc7_b, s);
-  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, 0, C, d_cls_w, d_cls_b, s);
-  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, 5 * C, 1, C, 5 * C, d_bbox_w, d_bbox_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, NH, 1, 0, KC, d_cls_w, d_cls_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wh, p->bh, F, NH, 1, KC, NH, d_bbox_w, d_bbox_b, s);
   return rc;
 }
 

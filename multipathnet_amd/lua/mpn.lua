@@ -175,7 +175,7 @@ end
 function FastRCNN:__init(model, opt)
    local features, roipool = replica(model:get(1):get(1)), model:get(2)
    local lin = model:get(4):findModules('nn.Linear')             -- fc6, fc7
-   local cls_w, cls_b, bbox, bnorm = heads_of(model:get(5))
+   local cls_w, cls_b, bbox, bnorm, K = heads_of(model:get(5))   -- K > 1: opt.integral on models/vgg.lua (model_utils.lua:275-317)
    local convs, pool = convs_of(features)
    local n = #convs
    local cfg = ffi.new('mpn_frcnn_config')
@@ -187,11 +187,11 @@ function FastRCNN:__init(model, opt)
    end
    cfg.n_conv, cfg.conv_cout, cfg.pool_after = n, cout, pl
    cfg.pooled_h, cfg.pooled_w, cfg.spatial_scale = roipool.H, roipool.W, roipool.spatial_scale
-   cfg.fc_dim, cfg.n_classes = lin[2].weight:size(1), cls_w:size(1)
+   cfg.fc_dim, cfg.n_classes = lin[2].weight:size(1), cls_w:size(1) / K
    common_config(cfg, opt, ROSS, bnorm)
    local h = ffi.new('mpn_frcnn *[1]')
-   check(C.mpn_frcnn_create(cfg, wp, bp, lin[1].weight:data(), lin[1].bias:data(), lin[2].weight:data(), lin[2].bias:data(),
-                            cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), h), 'mpn_frcnn_create')
+   check(C.mpn_frcnn_create_integral(cfg, wp, bp, lin[1].weight:data(), lin[1].bias:data(), lin[2].weight:data(), lin[2].bias:data(),
+                                     cls_w:data(), cls_b:data(), bbox.weight:data(), bbox.bias:data(), K, h), 'mpn_frcnn_create_integral')
    finish(self, h, cfg, {cout, pl, cls_w, cls_b})
    set_pyramid(self, opt)
    set_augment(self, opt)

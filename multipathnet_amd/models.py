@@ -439,6 +439,20 @@ MPN_TOWERS = [dict(region=0, use4=1, use3=1), dict(region=1, use4=1, use3=0), di
               dict(region=3, use4=0, use3=0), dict(region=1, use4=1, use3=1)]
 
 
+def integral_params(params, K):
+    """model_utils.integral (model_utils.lua:275-317) on a plain Fast R-CNN parameter dict: the classifier cloned K times — cls_w
+    [K*C, F] and cls_b [K*C], the clones stacked in head order — and "n_integral" = K; everything else is shared with `params`.
+    FastRCNN(integral_params(P, K), ...) holds K classifiers: it scores with the mean of their softmaxes and trains the one
+    train_set_head selects."""
+    K = int(K)
+    assert K >= 1 and "towers" not in params and "cls_w" in params
+    out = dict(params)
+    out["cls_w"] = torch.cat([torch.as_tensor(params["cls_w"]).clone() for _ in range(K)], 0)
+    out["cls_b"] = torch.cat([torch.as_tensor(params["cls_b"]).clone() for _ in range(K)], 0)
+    out["n_integral"] = K
+    return out
+
+
 def conv_tap_indices(cfg):
     """0-based conv-layer indices of the last conv before the 3rd and 4th pools (VGG-16: conv3_3 = 6, conv4_3 = 9)."""
     convs, pools = -1, []
@@ -505,7 +519,14 @@ class FastRCNN(object):
         self.is_graph = "trunk_ops" in params
         cout, pool = ([], []) if (self.is_resnet or self.is_graph) else cfg_layers(cfg)
         self.is_mpnet = "towers" in params
-        self.n_classes = params["n_classes"] if (self.is_mpnet or "head_towers" in params) else params["cls_w"].shape[0]
+        plain = not (self.is_resnet or self.is_graph or self.is_mpnet)
+        # a plain handle with "n_integral" in its parameters (integral_params): cls_w / cls_b hold the K classifiers stacked
+        self.n_integral = int(params["n_integral"]) if ("n_integral" in params and (plain or self.is_mpnet or "head_towers" in params)) else 1
+        if plain and "n_integral" in params:
+            assert params["cls_w"].shape[0] % self.n_integral == 0, "cls_w holds n_integral classifiers stacked: [K*C, F]"
+            self.n_classes = params["cls_w"].shape[0] // self.n_integral
+        else:
+            self.n_classes = params["n_classes"] if (self.is_mpnet or "head_towers" in params) else params["cls_w"].shape[0]
         if self.is_resnet or self.is_graph:
             self.fc_dim = params["bbox_w"].shape[1]
         else:
@@ -650,7 +671,12 @@ class FastRCNN(object):
             check(lib.mpn_mpnet_create(C.byref(c), wp, bp, C.byref(mw), *[_f(t) for t in heads], C.byref(self._h)), "mpn_mpnet_create")
         else:
             keep = [d(params[k]) for k in ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")]
-            check(lib.mpn_frcnn_create(C.byref(c), wp, bp, *[_f(t) for t in keep], C.byref(self._h)), "mpn_frcnn_create")
+            if "n_integral" in params:   # opt.integral on models/vgg.lua (model_utils.lua:275-317); K = 1 is mpn_frcnn_create's handle
+                check(lib.mpn_frcnn_create_integral(C.byref(c), wp, bp, *[_f(t) for t in keep], self.n_integral, C.byref(self._h)),
+                      "mpn_frcnn_create_integral")
+                self.noSoftMax = self.n_integral > 1   # model_utils.lua:314
+            else:
+                check(lib.mpn_frcnn_create(C.byref(c), wp, bp, *[_f(t) for t in keep], C.byref(self._h)), "mpn_frcnn_create")
         torch.cuda.synchronize()
         self._finish_init(lib, dev, top_k)
 
@@ -826,6 +852,12 @@ class FastRCNN(object):
         check(self._lib.mpn_frcnn_train_set_dropout(self._h, float(rate), int(seed)), "mpn_frcnn_train_set_dropout")
         self._dropout = (float(rate), int(seed))
 
+    def train_set_head(self, k):
+        """The integral loss's selector (integral_selector.index, train.lua:288-294): the next train_step's loss reads classifier k of
+        the handle's n_integral, 0-based; train_begin starts at 0.  The other classifiers get a zero gradient and are still stepped
+        (weight decay, momentum).  The schedule is the caller's: it is not part of train_state()."""
+        check(self._lib.mpn_frcnn_train_set_head(self._h, int(k)), "mpn_frcnn_train_set_head")
+
     def _trained(self):
         """(names of the head tensors the current depth trains, indices of the conv layers it trains)"""
         d, n = getattr(self, "_train_depth", 2), len(self._cout)   # (no train_begin yet: the library refuses the call that follows)
@@ -844,9 +876,9 @@ class FastRCNN(object):
         tensors), None for a tensor the current depth does not train.  With the weights, the dropout rate and the seed it is what
         train_load_state continues a run from, bit for bit (the reference's optimState_<epoch>.t7, train.lua:188-198)."""
         names, convs = self._trained()
-        F, Cn = self.fc_dim, self.n_classes
+        F, Cn, KC = self.fc_dim, self.n_classes, self.n_integral * self.n_classes   # cls: the K integral classifiers stacked
         k6 = self._cout[len(self._cout) - 1] * self._cfg.pooled_h * self._cfg.pooled_w
-        shapes = {"fc6_w": (F, k6), "fc6_b": (F,), "fc7_w": (F, F), "fc7_b": (F,), "cls_w": (Cn, F), "cls_b": (Cn,), "bbox_w": (4 * Cn, F), "bbox_b": (4 * Cn,)}
+        shapes = {"fc6_w": (F, k6), "fc6_b": (F,), "fc7_w": (F, F), "fc7_b": (F,), "cls_w": (KC, F), "cls_b": (KC,), "bbox_w": (4 * Cn, F), "bbox_b": (4 * Cn,)}
         S = {k: (torch.empty(shapes[k], dtype=torch.float32, device=self.device) if k in names else None) for k in self._STATE_ORDER}
         step = C.c_long()
         check(self._lib.mpn_frcnn_train_get_state(self._h, *[None if S[k] is None else _f(S[k]) for k in self._STATE_ORDER], C.byref(step), _stream()),
@@ -897,10 +929,10 @@ class FastRCNN(object):
     def head_weights(self):
         """The handle's current fc6 / fc7 / cls / bbox weights and biases in Torch layout, under synthetic_params' keys (device tensors):
         update a parameter dict with it to build a new FastRCNN, or write it with t7.py."""
-        F, Cn = self.fc_dim, self.n_classes
+        F, Cn, KC = self.fc_dim, self.n_classes, self.n_integral * self.n_classes   # cls: [K*C, F] on a handle with K integral classifiers
         k6 = self._cout[len(self._cout) - 1] * self._cfg.pooled_h * self._cfg.pooled_w if len(self._cout) else 0
         z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
-        P = {"fc6_w": z(F, k6), "fc6_b": z(F), "fc7_w": z(F, F), "fc7_b": z(F), "cls_w": z(Cn, F), "cls_b": z(Cn), "bbox_w": z(4 * Cn, F), "bbox_b": z(4 * Cn)}
+        P = {"fc6_w": z(F, k6), "fc6_b": z(F), "fc7_w": z(F, F), "fc7_b": z(F), "cls_w": z(KC, F), "cls_b": z(KC), "bbox_w": z(4 * Cn, F), "bbox_b": z(4 * Cn)}
         check(self._lib.mpn_frcnn_get_head_weights(self._h, *[_f(P[k]) for k in ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")],
                                                    _stream()), "mpn_frcnn_get_head_weights")
         return P

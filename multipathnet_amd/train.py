@@ -4,6 +4,7 @@ pooling, head forward, loss, backward, SGD — is models.FastRCNN.train_add / tr
 
   attach_proposals        DataSetJSON.lua:280-390  (DataSetCOCO:attachProposals, without the crowd and the sample-around-GT branches)
   RoiSampler              BatchProviderROI.lua:39-49 (setupOne), BatchProviderBase.lua:54-107 (takeSubset, selectBBoxesOne)
+  IntegralSampler         donkey.lua:38-41 (the integral loss: one RoiSampler per classifier, each with its own foreground threshold)
   bbox_regression_stats   BatchProviderROI.lua:53-69 (setupData)
   save_checkpoint / load_checkpoint / resume   train.lua:188-198 (model_<epoch>.t7 + optimState_<epoch>.t7, here one table), opt.resume
 """
@@ -91,6 +92,24 @@ class RoiSampler(object):
         return rois, gtb, labels
 
 
+class IntegralSampler(object):
+    """The integral loss's K samplers (donkey.lua:38-41): donkey k, 0-based, draws its ROIs with the foreground threshold
+    t_k = bg_threshold_max + k / 20 — foreground = overlap >= t_k, background = bg_threshold_min <= overlap < t_k — and its minibatch
+    trains classifier k (FastRCNN.train_set_head(k), train.lua:288-294).  K = 6 at the default 0.5: 0.5, 0.55, ..., 0.75.  The K
+    samplers share one generator."""
+
+    def __init__(self, K, batch_size=128, fg_fraction=0.25, bg_threshold_min=0.1, bg_threshold_max=0.5, rng=None):
+        self.K = int(K)
+        assert self.K >= 1
+        rng = rng if rng is not None else np.random.default_rng()
+        self.thresholds = [float(bg_threshold_max) + k / 20.0 for k in range(self.K)]
+        self.samplers = [RoiSampler(batch_size, fg_fraction, fg_threshold=t, bg_threshold=(bg_threshold_min, t), rng=rng) for t in self.thresholds]
+
+    def sample(self, rec, k):
+        """one image's rows for head k: RoiSampler.sample at head k's threshold"""
+        return self.samplers[int(k)].sample(rec)
+
+
 def bbox_regression_stats(records, fg_threshold=0.5):
     """BatchProviderROI:setupData over attach_proposals records: mean and (unbiased, as torch's std) standard deviation of
     utils.convertTo(roi, gt box) over every foreground row -> (mean [4], std [4]) float32 numpy, what FastRCNN takes as
@@ -116,7 +135,9 @@ def save_checkpoint(path, net):
       "fc6_w" .. "bbox_b", "conv_w.<l>", "conv_b.<l>"       the weights (net.head_weights() + net.trunk_weights())
       "v.fc6_w" .. "v.bbox_b", "v.conv_w.<l>", "v.conv_b.<l>"  the momentum of every TRAINED tensor (net.train_state(); the others are absent)
       "step", "n_conv", "dropout", "seed"                   the step counter, the trunk's depth, the dropout rate and its seed (a decimal
-                                                            string: a Torch7 number is a double, a seed has 64 bits)"""
+                                                            string: a Torch7 number is a double, a seed has 64 bits)
+      "n_integral"                                          K, only where net holds K > 1 integral classifiers ("cls_w" [K*C, F], "cls_b"
+                                                            [K*C] and their momentum stacked in head order): a K = 1 file has no such key"""
     torch.cuda.synchronize()
     host = lambda t: t.detach().cpu().numpy()
     Wt, St = dict(net.head_weights()), net.train_state()
@@ -133,18 +154,23 @@ def save_checkpoint(path, net):
             tab["v.conv_w.%d" % l], tab["v.conv_b.%d" % l] = host(St["conv_w"][l]), host(St["conv_b"][l])
     rate, seed = net._dropout
     tab.update({"step": St["step"], "n_conv": n_conv, "dropout": float(rate), "seed": str(int(seed))})
+    if getattr(net, "n_integral", 1) > 1:
+        tab["n_integral"] = int(net.n_integral)
     t7.save(path, tab)
 
 
 def load_checkpoint(path):
     """-> {"weights": {...head_weights() keys, "conv_w": [...], "conv_b": [...]}, "state": what FastRCNN.train_load_state takes,
-    "dropout": rate, "seed": int} with host torch tensors.  Update a parameter dict with "weights" to create the FastRCNN, then
+    "dropout": rate, "seed": int} with host torch tensors ("weights" also carries "n_integral" where the file does: K > 1 integral
+    classifiers).  Update a parameter dict with "weights" to create the FastRCNN, then
     train_begin (the same depth), train_set_dropout(dropout, seed), train_load_state(state) — or `resume`."""
     tab = t7.load(path)
     n_conv = int(tab["n_conv"])
     ten = lambda k: torch.from_numpy(np.array(tab[k])) if k in tab else None
     weights = {k: ten(k) for k in _HEAD_KEYS}
     weights["conv_w"], weights["conv_b"] = [ten("conv_w.%d" % l) for l in range(n_conv)], [ten("conv_b.%d" % l) for l in range(n_conv)]
+    if "n_integral" in tab:
+        weights["n_integral"] = int(tab["n_integral"])
     state = {k: ten("v." + k) for k in _HEAD_KEYS}
     state["conv_w"], state["conv_b"] = [ten("v.conv_w.%d" % l) for l in range(n_conv)], [ten("v.conv_b.%d" % l) for l in range(n_conv)]
     state["step"] = int(tab["step"])

@@ -11,9 +11,11 @@ and up, through two pooling layers — with the same two numbers, and the max-po
 6.3 TB/s a float4 copy reaches.
 --dropout RATE runs every step with nn.Dropout(RATE) behind fc6 and fc7 (0.5: the reference's default; two
 more small kernels per step and a scale in two input gradients); 0, the default, launches nothing more than a run without the option.
+--integral K trains a handle with the integral loss's K classifiers (models.integral_params: a fused head of
+(K + 4) C rows instead of 5 C), step i on head i mod K as the reference's K donkeys take turns; 1, the default, is the plain handle.
 One JSON line per measurement.
 
-    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5]
+    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6]
 """
 import argparse
 import ctypes as C
@@ -46,12 +48,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trunk-layers", type=int, default=0, help="also measure MPN_TRAIN_TRUNK(k) (9: conv3_1 and up, the reference's configuration)")
     ap.add_argument("--dropout", type=float, default=0.0, help="dropout rate behind fc6 / fc7 (0.5: the reference's default; 0: none)")
+    ap.add_argument("--integral", type=int, default=1, help="K classifiers of the integral loss, trained in turn (6: the reference's scripts; 1: the plain head)")
     a = ap.parse_args()
     import torch
     from multipathnet_amd import _lib, models
     assert torch.cuda.is_available(), "bench_train needs a HIP device"
     P = models.synthetic_params(seed=557)
     C_ = P["cls_w"].shape[0]
+    if a.integral > 1:
+        P = models.integral_params(P, a.integral)
     rng = np.random.default_rng(5)
     dev_batches = [[torch.from_numpy(x).cuda() for x in batch(rng, C_)] for _ in range(IMAGES)]
     name = torch.cuda.get_device_name(0)
@@ -69,13 +74,15 @@ def main():
                 for b in dev_batches:
                     net.train_add(*b)
                 e[1].record()
+                if a.integral > 1:
+                    net.train_set_head(i % a.integral)
                 net.train_step(1e-6)   # a tiny step: the weights stay in their range over the run
                 e[2].record()
                 e[2].synchronize()
                 if i >= a.warmup:
                     step_ms.append(e[1].elapsed_time(e[2]))
                     iter_ms.append(e[0].elapsed_time(e[2]))
-            print(json.dumps({"what": "train_step", "depth": "MPN_TRAIN_TRUNK(%d)" % a.trunk_layers if depth == "trunk" else depth, "dropout": a.dropout, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
+            print(json.dumps({"what": "train_step", "depth": "MPN_TRAIN_TRUNK(%d)" % a.trunk_layers if depth == "trunk" else depth, "dropout": a.dropout, "integral": a.integral, "rows": IMAGES * ROWS, "ms_step_median": round(float(np.median(step_ms)), 3),
                               "ms_step_min": round(float(np.min(step_ms)), 3), "ms_iteration_median": round(float(np.median(iter_ms)), 3),
                               "steps": a.steps, "device": name}), flush=True)
             if depth == 2:
