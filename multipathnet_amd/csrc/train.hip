@@ -379,6 +379,7 @@ __global__ void unpack_lin_w_kernel(const float *__restrict__ wpk, const float *
 
 int unpack_linear_weights(const float *d_wpk, const float *d_bpk, int K, int N, int inner, int n0, int n1, float *d_w, float *d_b, hipStream_t s) {
   MPN_CHECK_ARG(d_wpk && d_bpk && K > 0 && N > 0 && inner > 0 && n0 >= 0 && n1 > n0 && n1 <= N);
+  MPN_CHECK_ARG(inner == 1 || (K % (8 * inner)) == 0);  // pack_linear_weights' rule: otherwise a k < K maps to a chunk past K64 / 8
   if (!d_w && !d_b) return MPN_OK;
   const size_t total = d_w ? (size_t)(n1 - n0) * K : (size_t)(n1 - n0);
   hipLaunchKernelGGL(unpack_lin_w_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, d_wpk, d_bpk, K, lin_np(N), inner, n0, n1, d_w, d_b);
