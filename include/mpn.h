@@ -724,7 +724,7 @@ int mpn_frcnn_set_augment(mpn_frcnn *p, int enable);
  * in its relu_mask form (X = the saved pre-pool map) into a zero-haloed map of the larger size — one pass instead of the [X > 0]
  * mask; the input gradient handed to a pooled layer is therefore not masked on its own.  Everything else — the summation orders,
  * every gradient before any update, optim.sgd, the re-pack of the derived forms — is as above.  MPN_TRAIN_MAX_IMAGES applies.
- * Still not trained: the first conv layer, MultiPathNet / ResNet / op-list handles.
+ * Still not trained: the first conv layer, ResNet / op-list handles (a MultiPathNet handle's towers: mpn_mpnet_train_* below).
  * Debug tensors after such a step, until the next mpn_frcnn_train_add: "train_act.<i>.<j>" (image i; j = 0 the block's input map,
  * j = 1..k the trained layers' outputs — before the pool where the layer is pooled; [C,h,w], each map its own h x w) and "train_dx6"
  * ([B, C, PH, PW]).
@@ -803,6 +803,45 @@ int mpn_frcnn_train_set_trunk_state(mpn_frcnn *p, int layer, const float *d_v, c
 int mpn_frcnn_get_head_weights(mpn_frcnn *p, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w, float *d_fc7_b,
                                float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
 int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w /*[Cout,Cin,3,3]*/, float *d_b /*[Cout]*/, void *stream);
+
+/* Training the towers of a MultiPathNet handle on the device, trunk frozen: models/multipathnet.lua phase 1 —
+ * the whole trunk inside nn.NoBackprop, everything trainable behind the ROI pooling.  Trained: per tower the 1x1 conv_mix, fc6 and fc7,
+ * the K classifiers on the Foveal towers' concat and the box regressor on the het tower.  Only an mpn_mpnet_create handle with
+ * fc_arith == MPN_FC_FP32; every other handle kind, MPN_FC_SPLIT3, an image pyramid, augmentation switched on, a pending pipelined
+ * tail and calls out of order answer MPN_ESTATE with a message naming the cause, and leave the handle usable.  (mpn_frcnn_train_*
+ * above keeps refusing MultiPathNet handles: the two families do not mix.)  The protocol is mpn_frcnn_train_*'s:
+ *   mpn_mpnet_train_begin  allocates momentum, the step's activations and gradients (its own buffers: a detect between two training
+ *                          calls disturbs nothing); no dropout, classifier 0 selected.
+ *   mpn_mpnet_train_add    one image's n rows behind the pending ones (total <= max_rois): the frozen trunk as detect runs it, then per
+ *                          tower t the operand x_t[(bin, roi), Kcat_t] = the ROI max-pools of conv5 [+ conv4] [+ conv3] at scales s, 2s, 4s
+ *                          over Foveal region r_t, each map's slab nn.Normalize(2)-ed per ROI, x 1000 (conv345_unnormalized:
+ *                          MulConstant(1, 1/30, 1/200) and no x 1000).  Cached features of the handle are invalidated.
+ *   mpn_mpnet_train_step   forward m_t = x_t Wmix^T + bmix (NO ReLU), y6_t = drop(relu(fc6(m_t))), y7_t = drop(relu(fc7(y6_t))) = slice t of
+ *                          cat; z = cat[:, 0:(T-1)F] Wcls^T + bcls [B, K*C], t^ = cat[:, (T-1)F:TF] Wbbox^T + bbbox [B, 4C]; loss and its
+ *                          gradient exactly mpn_frcnn_train_step's (classifier k's columns of z, smooth-L1 on t^, 1/B and bbox_weight/B);
+ *                          every input gradient is taken before the layer it passes through is updated; optim.sgd in place on the packed
+ *                          weights detect and captured graphs read (weight decay on weights only, momentum, dampening 0).  The K - 1
+ *                          classifiers not selected get an exactly zero gradient and are still stepped.  d_loss [2] may be NULL.
+ *                          Deterministic: fixed summation orders that depend on the shapes and B alone, no atomics.
+ *   mpn_mpnet_train_end    frees the state; the weights stay as trained.
+ *   mpn_mpnet_train_set_dropout  nn.Dropout(rate) behind fc6 + ReLU and fc7 + ReLU of every tower: mpn_frcnn_train_set_dropout's mask
+ *                          with layer = 2 t + i (i = 0 behind fc6, 1 behind fc7), so two towers never share a mask; rate 0 launches nothing.
+ *   mpn_mpnet_train_set_head  the classifier k in [0, K) the next step's loss reads.
+ *   mpn_mpnet_get_tower_weights / _get_head_weights  the weights in Torch layout, the shapes mpn_mpnet_create takes (any pointer may be
+ *                          NULL); with or without a train_begin: the exact inverse of creation.
+ * Debug tensors of the last step (mpn_frcnn_debug_tensor), row-major: "tower_train_x.<t>" [rows, Kcat_t, PH, PW], "tower_train_y6.<t>"
+ * [rows, fc_dim], "tower_train_cat" [rows, T * fc_dim], "tower_train_cls" [rows, K*C], "tower_train_bbox" [rows, 4C], "tower_train_g_cls"
+ * [rows, K*C] (the gradient at z).  Not here: phase 2 (conv layers through the skip pooling), ResNet / op-list towers, momentum export. */
+int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight);
+int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_rois /*[n,4]*/,
+                        const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);
+int mpn_mpnet_train_step(mpn_frcnn *p, float lr, float *d_loss /*[2]: cls, bbox*/, void *stream);
+int mpn_mpnet_train_end(mpn_frcnn *p);
+int mpn_mpnet_train_set_dropout(mpn_frcnn *p, float rate, long seed);
+int mpn_mpnet_train_set_head(mpn_frcnn *p, int k);
+int mpn_mpnet_get_tower_weights(mpn_frcnn *p, int t, float *d_mix_w, float *d_mix_b, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w,
+                                float *d_fc7_b, void *stream);
+int mpn_mpnet_get_head_weights(mpn_frcnn *p, float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
 
 /* Captured launch graphs.  The kernel chains of the per-image path — the head (transform .. decode) and the tail (per-class NMS,
  * voting, top-k) of mpn_frcnn_test_one / _pipelined / _pipelined_host, and the bodies of mpn_frcnn_shard_head / _shard_nms /

@@ -117,6 +117,8 @@ def load(flavour=None):
     lib.mpn_frcnn_create_integral.argtypes = [C.c_void_p] * 11 + [C.c_int, C.c_void_p]
     lib.mpn_frcnn_n_integral.argtypes = [C.c_void_p]
     lib.mpn_frcnn_train_set_head.argtypes = [C.c_void_p, C.c_int]
+    lib.mpn_mpnet_train_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_long]
+    lib.mpn_mpnet_train_set_head.argtypes = [C.c_void_p, C.c_int]
     _libs[fl] = lib
     return lib
 

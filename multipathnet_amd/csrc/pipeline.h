@@ -12,6 +12,7 @@
 using namespace mpn;  // (as both translation units do: the structs below name Act, DeviceOwner, ... as pipeline.hip always has)
 
 struct TrainState;  // the training state of a handle: defined in train_driver.hip, private to it
+struct TowerTrainState;  // ... of a MultiPathNet handle's towers (mpn_mpnet_train_*): likewise
 
 struct ConvLayer {
   int Cin, Cout, pool;
@@ -167,6 +168,7 @@ struct mpn_frcnn {
   float *aug_boxes = nullptr, *aug_scores = nullptr, *aug_bbox = nullptr;  // flipped boxes [M,4]; the upright half's tables kept aside [M,C], [M,4C]
   // ---- training the head (mpn_frcnn_train_*): exists between train_begin and train_end
   struct TrainState *train = nullptr;  // (train_driver.hip)
+  struct TowerTrainState *tower_train = nullptr;  // mpn_mpnet_train_* (DESIGN.md section 13.9): between mpn_mpnet_train_begin and _end
   // optional per-kernel-group timing with HIP events recorded on the launch stream
   bool prof = false;
   std::vector<hipEvent_t> ev_pool;
@@ -195,6 +197,8 @@ int launch_unpack_pooled(const float *xc8, int N, int C, int PP, int Mp, float *
 void free_train_state(mpn_frcnn *p);
 // mpn_frcnn_debug_tensor's "train_*" names.  *known = false: none of them (nothing done, the caller goes on to its own refusal)
 int train_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems, bool *known);
+// the "tower_train_*" names (mpn_mpnet_train_*'s state); an unknown one is refused there
+int tower_train_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems);
 
 #ifdef MPN_DEBUG_HOOKS
 // the mpn_debug_bench_* hooks' clock: two warm-up calls, then `iters` calls back to back on the NULL stream between two events of its own

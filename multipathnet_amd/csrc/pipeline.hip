@@ -1971,6 +1971,7 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
     const int rct = train_debug_tensor(p, name, d_ptr, n_elems, &known);
     if (known) return rct;
   }
+  if (!strncmp(name, "tower_train_", 12)) return tower_train_debug_tensor(p, name, d_ptr, n_elems);
   if (plain_integral(p) && !strcmp(name, "cls")) {
     set_error("mpn_frcnn_debug_tensor: invalid argument: a handle with %d integral classifiers keeps no single 'cls': ask for \"cls_k\" ([N, K * C])", p->n_integral);
     return MPN_EINVAL;

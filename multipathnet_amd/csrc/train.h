@@ -21,6 +21,13 @@ struct LossCfg { float mean[4], std[4]; int norm; float bbox_weight; };
 int train_loss(const float *d_head, int B, int C, int K, int k, const float *d_rois, const float *d_gt, const int *d_labels, const LossCfg &cfg,
                float *d_g_c8, int Mp, float *d_loss, hipStream_t s);
 
+// The same loss for a head of TWO GEMMs (the tower models: K classifiers on the Foveal towers' concat, the box regressor on the het
+// tower): d_cls [B, K*C] and d_bbox [B, 4C] row-major, the gradient in two C8 matrices d_g_cls_c8 [ceil(KC/8)][Mp][8] and d_g_bbox_c8
+// [ceil(4C/8)][Mp][8] (pad lanes +0.0) — K*C is in general no multiple of 8, so the fused matrix cannot be cut by a pointer offset.
+// The same kernel (one template): every value and both sums are train_loss's.
+int train_loss_split(const float *d_cls, const float *d_bbox, int B, int C, int K, int k, const float *d_rois, const float *d_gt, const int *d_labels,
+                     const LossCfg &cfg, float *d_g_cls_c8, float *d_g_bbox_c8, int Mp, float *d_loss, hipStream_t s);
+
 // Weight gradient fused with optim.sgd (engines/Optim.lua: dampening 0, no Nesterov) on a packed linear weight [K64/8][NP][8]:
 //   dW[n,k] = sum_{m < B} g[m,n] x[m,k]   (v_mfma_f32_32x32x2_f32, rows ascending in pairs: one fixed order, no split, no atomics)
 //   g' = dW + wd * w;  v = momentum * v + g';  w = w - lr * v        (each operation rounded on its own)
@@ -31,10 +38,25 @@ int sgd_wgrad_c8(const float *d_g_c8, int g_Mp, const float *d_x_c8, int x_Mp, i
                  float lr, float momentum, float wd, hipStream_t s);
 // Bias: db[n] = sum_{m < B} g[m,n] (a fixed pairwise-style order), v = momentum * v + db, b = b - lr * v (biases never decay, Optim.lua:66-68)
 int sgd_bias_c8(const float *d_g_c8, int g_Mp, int B, int N, float *d_bpk, float *d_vb, float lr, float momentum, hipStream_t s);
+// The two gradients of a layer whose valid rows are SEGMENTS (MultiPathNet's 1x1 mix: rows = (bin, roi) pairs): both operands are C8
+// matrices at row pitch nseg * Mp, the valid rows are seg * Mp + m, m < B, seg < nseg; every other row is stale, may be NaN and is never read.
+//   dW[n,k] = sum_seg sum_{m < B} g[seg * Mp + m, n] x[seg * Mp + m, k]
+// One block per (32 k-chunks x 32 n tile, segment) — sgd_wgrad_c8's record mapping; the block's four waves take a quarter of the B rows each
+// (round_up(ceil(B / 4), 2) rows, ascending in pairs from zero) and add their sums pairwise, (q0 + q1) + (q2 + q3) — writes its tile to slab
+// seg of d_part (seg_wgrad_part_elems floats); a second launch adds the slabs in ascending order in groups of kWgradSegGroup, the group
+// sums in ascending order, and takes the optim.sgd step on the packed weight [K64/8][NP][8] (inner = 1) in registers.  No atomics: the
+// order depends on (nseg, B) alone.  d_x_c8 [K64/8][nseg * Mp][8], d_g_c8 [>= ceil(N/8)][nseg * Mp][8].  Pad lanes of the packing stay +0.0.
+size_t seg_wgrad_part_elems(int K, int N, int nseg);
+int sgd_wgrad_seg_c8(const float *d_g_c8, const float *d_x_c8, int Mp, int nseg, int B, int N, int K, float *d_part, float *d_wpk, float *d_vpk,
+                     float lr, float momentum, float wd, hipStream_t s);
+// db[n] = the column sums over the same rows: per segment sgd_bias_c8's order, the segment sums through a fixed tree of 64 leaves (more
+// segments: the trees' roots in ascending order); fused with the bias step
+int sgd_bias_seg_c8(const float *d_g_c8, int Mp, int nseg, int B, int N, float *d_bpk, float *d_vb, float lr, float momentum, hipStream_t s);
 // Input gradient through y = relu(x W^T + b): dx[m,k] = (sum_{n < N} g[m,n] W[n,k]) * [act[m,k] > 0] * scale, reading the packed W with the
 // roles of its two dimensions swapped (the contraction runs over NP, n ascending in pairs).  d_act_c8 = the forward activation x (post-ReLU)
 // and d_dx_c8, both [>= ceil(K/8)][x_Mp][8]; rows < B are written.  scale: 1 / (1 - rate) where act is what dropout_c8 left (a dropped
 // element is +0.0, so [act > 0] already is keep mask x ReLU mask); with 1.0f the product is exact: the bits of the unscaled gradient.
+// d_act_c8 == nullptr: no activation behind the layer, every element passes (dx = scale * g W).
 int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_wpk, int K, const float *d_act_c8, float *d_dx_c8, int x_Mp,
                     hipStream_t s, float scale = 1.0f);
 // nn.Dropout (v2) in place on the C8 matrix [>= ceil(N/8)][Mp][8] linear_c8 has just written, rows < B only (rows >= B are neither read nor

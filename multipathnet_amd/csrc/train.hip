@@ -29,15 +29,20 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------------------------------------------------
 // K classifiers in the row (the integral loss, model_utils.lua:275-317), of which classifier k is trained: its logits are columns
 // [c0, c0 + C), c0 = k * C; the box outputs start at column cb = K * C.  K = 1, k = 0 is the plain head (c0 = 0, cb = C).
-__global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict__ head, int B, int C, int K, int k, const float *__restrict__ rois,
-                                                         const float *__restrict__ gt, const int *__restrict__ labels, LossCfg cfg,
-                                                         float *__restrict__ g, int Mp, float *__restrict__ loss) {
+// SPLIT (the tower models' head: two GEMMs, two outputs): the logits are rows of `cls` [B, K * C], the box outputs rows of `box` [B, 4C],
+// and the gradient goes to two C8 matrices, g [ceil(KC/8)][Mp][8] and g_box [ceil(4C/8)][Mp][8] — K * C is in general no multiple of 8,
+// so the fused matrix cannot be cut by a pointer.  Otherwise cls = the fused row, box = cls + K * C, one matrix g over all (K+4)C columns.
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict__ cls, int ld_cls, const float *__restrict__ box, int ld_box, int B, int C,
+                                                         int K, int k, const float *__restrict__ rois, const float *__restrict__ gt,
+                                                         const int *__restrict__ labels, LossCfg cfg, float *__restrict__ g, float *__restrict__ g_box,
+                                                         int Mp, float *__restrict__ loss) {
   __shared__ float s_cls[256], s_box[256];
-  const int ld = (K + 4) * C, nchunk = (ld + 7) / 8, c0 = k * C, cb = K * C;
+  const int c0 = k * C, cb = K * C;
   const float invB = 1.0f / (float)B, gbox = cfg.bbox_weight / (float)B;
   float acc_cls = 0.0f, acc_box = 0.0f;
   for (int i = threadIdx.x; i < B; i += 256) {  // one row per thread, rows ascending
-    const float *zr = head + (size_t)i * ld, *z = zr + c0;  // the row; the selected classifier's logits
+    const float *z = cls + (size_t)i * ld_cls + c0, *tb = box + (size_t)i * ld_box;  // the selected classifier's logits; the row's box outputs
     int y = labels[i];
     y = y < 0 ? 0 : (y >= C ? C - 1 : y);
     float mx = z[0];
@@ -55,30 +60,48 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (cfg.norm) tg[j] = (tg[j] - cfg.mean[j]) / cfg.std[j];
-        d[j] = zr[cb + 4 * y + j] - tg[j];
+        d[j] = tb[4 * y + j] - tg[j];
         const float a = fabsf(d[j]);
         row += a < 1.0f ? 0.5f * d[j] * d[j] : a - 0.5f;
       }
       acc_box += row;
     }
     const float inv_sum = 1.0f / sum;
-    for (int q = 0; q < nchunk; ++q) {
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int n = q * 8 + e;
-        float t = 0.0f;
-        if (n >= c0 && n < c0 + C) t = (expf(z[n - c0] - mx) * inv_sum - (n - c0 == y ? 1.0f : 0.0f)) * invB;
-        else if (y > 0 && n >= cb + 4 * y && n < cb + 4 * y + 4) {  // (every other classifier's columns: exactly +0.0)
-          const int j = n - cb - 4 * y;
-          const float dd = j == 0 ? d[0] : (j == 1 ? d[1] : (j == 2 ? d[2] : d[3]));
-          t = gbox * (dd < -1.0f ? -1.0f : (dd > 1.0f ? 1.0f : dd));
-        }
-        v[e] = t;
-      }
-      float *o = g + ((size_t)q * Mp + i) * 8;
+    // column n of the K classifiers' block / of the box block: every other classifier's columns, every other class's four: exactly +0.0
+    auto cls_val = [&](int n) -> float {
+      return (n >= c0 && n < c0 + C) ? (expf(z[n - c0] - mx) * inv_sum - (n - c0 == y ? 1.0f : 0.0f)) * invB : 0.0f;
+    };
+    auto box_val = [&](int n) -> float {
+      if (!(y > 0 && n >= 4 * y && n < 4 * y + 4)) return 0.0f;
+      const int j = n - 4 * y;
+      const float dd = j == 0 ? d[0] : (j == 1 ? d[1] : (j == 2 ? d[2] : d[3]));
+      return gbox * (dd < -1.0f ? -1.0f : (dd > 1.0f ? 1.0f : dd));
+    };
+    auto store = [&](float *gm, int q, const float *v) {
+      float *o = gm + ((size_t)q * Mp + i) * 8;
       *reinterpret_cast<f32x4 *>(o) = f32x4{v[0], v[1], v[2], v[3]};
       *reinterpret_cast<f32x4 *>(o + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    };
+    if (SPLIT) {
+      for (int q = 0; q < (cb + 7) / 8; ++q) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = q * 8 + e < cb ? cls_val(q * 8 + e) : 0.0f;
+        store(g, q, v);
+      }
+      for (int q = 0; q < (4 * C + 7) / 8; ++q) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = box_val(q * 8 + e);
+        store(g_box, q, v);
+      }
+    } else {
+      for (int q = 0; q < ((K + 4) * C + 7) / 8; ++q) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const int n = q * 8 + e; v[e] = n < cb ? cls_val(n) : box_val(n - cb); }
+        store(g, q, v);
+      }
     }
   }
   s_cls[threadIdx.x] = acc_cls; s_box[threadIdx.x] = acc_box;
@@ -93,7 +116,18 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float *__restrict
 int train_loss(const float *d_head, int B, int C, int K, int k, const float *d_rois, const float *d_gt, const int *d_labels, const LossCfg &cfg,
                float *d_g_c8, int Mp, float *d_loss, hipStream_t s) {
   MPN_CHECK_ARG(d_head && d_rois && d_gt && d_labels && d_g_c8 && d_loss && B > 0 && C > 1 && Mp >= B && K >= 1 && k >= 0 && k < K);
-  hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(256), 0, s, d_head, B, C, K, k, d_rois, d_gt, d_labels, cfg, d_g_c8, Mp, d_loss);
+  const int ld = (K + 4) * C;
+  hipLaunchKernelGGL(train_loss_kernel<false>, dim3(1), dim3(256), 0, s, d_head, ld, d_head + K * C, ld, B, C, K, k, d_rois, d_gt, d_labels, cfg, d_g_c8,
+                     static_cast<float *>(nullptr), Mp, d_loss);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+int train_loss_split(const float *d_cls, const float *d_bbox, int B, int C, int K, int k, const float *d_rois, const float *d_gt, const int *d_labels,
+                     const LossCfg &cfg, float *d_g_cls_c8, float *d_g_bbox_c8, int Mp, float *d_loss, hipStream_t s) {
+  MPN_CHECK_ARG(d_cls && d_bbox && d_rois && d_gt && d_labels && d_g_cls_c8 && d_g_bbox_c8 && d_loss && B > 0 && C > 1 && Mp >= B && K >= 1 && k >= 0 && k < K);
+  hipLaunchKernelGGL(train_loss_kernel<true>, dim3(1), dim3(256), 0, s, d_cls, K * C, d_bbox, 4 * C, B, C, K, k, d_rois, d_gt, d_labels, cfg, d_g_cls_c8,
+                     d_g_bbox_c8, Mp, d_loss);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }
@@ -212,6 +246,203 @@ int sgd_bias_c8(const float *d_g_c8, int g_Mp, int B, int N, float *d_bpk, float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The same two gradients over SEGMENTED rows: MultiPathNet's 1x1 mix layer, whose rows are (bin, roi) pairs
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct SegWgradArgs {
+  const float *g, *x;
+  int Mp, B, N, NP, nchunks, rows_per_wave;
+  size_t pitch;        // rows between two chunks of both operands: nseg * Mp
+  float *part;
+  size_t part_stride;  // floats between two segments' partial sums: nchunks * NP * 8
+};
+
+constexpr int kSegWgradLds = 2 * 128 * 64 * 4;  // two waves' accumulators
+
+// sgd_wgrad_kernel's record mapping, one block per (32 k-chunks x 32 n tile, SEGMENT on grid.z).  The block's 4 waves cut the segment's B
+// rows into four contiguous quarters (rows_per_wave, even): each accumulates its rows seg * Mp + m ascending in pairs from zero — rows
+// >= B (stale, maybe NaN) contribute exact zeros on both sides — and the four sums are added pairwise through LDS, (q0 + q1) + (q2 + q3):
+// chains of B / 8 MFMA steps instead of B / 2 (with one chain per bin the B = 128 gradient sat at 1.4 x the rms error of a blocked CPU
+// sum, 2.3 x at its worst element).  The tile goes to the segment's slab of `part` in the packed layout; seg_wgrad_sgd_kernel adds the
+// slabs.  A slab is written in full (all NP columns, all nchunks chunks), so the sum reads nothing stale.
+__global__ __launch_bounds__(256, 2) void seg_wgrad_kernel(SegWgradArgs a) {
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
+  const int n = blockIdx.x * 32 + l31;   // < NP: the grid covers NP exactly
+  const int ck0 = blockIdx.y * 32, ck = ck0 + l31;
+  const bool ck_ok = ck < a.nchunks, n_ok = n < a.N;
+  const size_t row0 = (size_t)blockIdx.z * a.Mp;
+  const int mb = wave * a.rows_per_wave, me = min(a.B, mb + a.rows_per_wave);
+  f32x16 acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[e][r] = 0.0f;
+  const float *xp = a.x + ((size_t)(ck_ok ? ck : 0) * a.pitch + row0) * 8;
+  const float *gp = a.g + ((size_t)((n_ok ? n : 0) >> 3) * a.pitch + row0) * 8 + (n & 7);
+  auto load = [&](int m0, f32x4 &lo, f32x4 &hi, float &b) {
+    const int m = m0 + half;
+    lo = f32x4{0.f, 0.f, 0.f, 0.f}; hi = lo; b = 0.0f;
+    if (m < me) {
+      if (ck_ok) { lo = *reinterpret_cast<const f32x4 *>(xp + (size_t)m * 8); hi = *reinterpret_cast<const f32x4 *>(xp + (size_t)m * 8 + 4); }
+      if (n_ok) b = gp[(size_t)m * 8];
+    }
+  };
+  f32x4 lo, hi; float b;
+  load(mb, lo, hi, b);
+  for (int m0 = mb; m0 < me; m0 += 2) {
+    f32x4 nlo, nhi; float nb;
+    load(m0 + 2, nlo, nhi, nb);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(lo[e], b, acc[e], 0, 0, 0);
+      acc[4 + e] = __builtin_amdgcn_mfma_f32_32x32x2f32(hi[e], b, acc[4 + e], 0, 0, 0);
+    }
+    lo = nlo; hi = nhi; b = nb;
+  }
+  // (q0 + q1) and (q2 + q3): the odd waves hand their sums over, one 32 KiB slot each (lane-contiguous: no bank conflicts)
+  auto put = [&](int slot) {
+    float *o = lds + (size_t)slot * 128 * 64 + lane;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[(e * 16 + r) * 64] = acc[e][r];
+  };
+  auto add = [&](int slot) {
+    const float *o = lds + (size_t)slot * 128 * 64 + lane;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[e][r] += o[(e * 16 + r) * 64];
+  };
+  if (wave & 1) put(wave >> 1);
+  __syncthreads();
+  if (!(wave & 1)) add(wave >> 1);
+  __syncthreads();
+  if (wave == 2) put(0);
+  __syncthreads();
+  if (wave != 0) return;
+  add(0);
+  float *out = a.part + (size_t)blockIdx.z * a.part_stride;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int kc = ck0 + 8 * (r >> 2) + 4 * half + (r & 3);
+    if (kc >= a.nchunks) continue;
+    const size_t off = ((size_t)kc * a.NP + n) * 8;
+    *reinterpret_cast<f32x4 *>(out + off) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+    *reinterpret_cast<f32x4 *>(out + off + 4) = f32x4{acc[4][r], acc[5][r], acc[6][r], acc[7][r]};
+  }
+}
+
+// One thread per record (chunk kc, row n < N) of the packed weight: the segments' partial sums added in ascending order in groups of
+// kWgradSegGroup, the group sums in ascending order (conv_wgrad_reduce_kernel's order), then optim.sgd on the record (inner = 1: float
+// e is k = kc * 8 + e; lanes k >= K and rows n >= N keep the packing's +0.0).
+__global__ __launch_bounds__(256) void seg_wgrad_sgd_kernel(const float *__restrict__ part, size_t stride, int nseg, int N, int NP, int K, int nchunks,
+                                                            float *__restrict__ w, float *__restrict__ v, float lr, float mom, float wd) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)nchunks * NP) return;
+  const int n = (int)(t % NP), kc = (int)(t / NP);
+  if (n >= N || kc * 8 >= K) return;
+  const size_t off = t * 8;
+  f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
+  for (int g0 = 0; g0 < nseg; g0 += kWgradSegGroup) {
+    const int g1 = min(g0 + kWgradSegGroup, nseg);
+    f32x4 q0 = f32x4{0.f, 0.f, 0.f, 0.f}, q1 = q0;
+    for (int sg = g0; sg < g1; ++sg) {
+      const float *pp = part + (size_t)sg * stride + off;
+      q0 += *reinterpret_cast<const f32x4 *>(pp); q1 += *reinterpret_cast<const f32x4 *>(pp + 4);
+    }
+    if (g0 == 0) { s0 = q0; s1 = q1; } else { s0 += q0; s1 += q1; }
+  }
+  f32x4 w0 = *reinterpret_cast<const f32x4 *>(w + off), w1 = *reinterpret_cast<const f32x4 *>(w + off + 4);
+  f32x4 v0 = *reinterpret_cast<const f32x4 *>(v + off), v1 = *reinterpret_cast<const f32x4 *>(v + off + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (kc * 8 + e < K) {
+      const float gr = s0[e] + wd * w0[e];
+      v0[e] = mom * v0[e] + gr;
+      w0[e] = w0[e] - lr * v0[e];
+    }
+    if (kc * 8 + 4 + e < K) {
+      const float gr = s1[e] + wd * w1[e];
+      v1[e] = mom * v1[e] + gr;
+      w1[e] = w1[e] - lr * v1[e];
+    }
+  }
+  *reinterpret_cast<f32x4 *>(w + off) = w0; *reinterpret_cast<f32x4 *>(w + off + 4) = w1;
+  *reinterpret_cast<f32x4 *>(v + off) = v0; *reinterpret_cast<f32x4 *>(v + off + 4) = v1;
+}
+
+size_t seg_wgrad_part_elems(int K, int N, int nseg) { return (size_t)nseg * (round_up(K, 64) / 8) * lin_np(N) * 8; }
+
+int sgd_wgrad_seg_c8(const float *d_g_c8, const float *d_x_c8, int Mp, int nseg, int B, int N, int K, float *d_part, float *d_wpk, float *d_vpk,
+                     float lr, float momentum, float wd, hipStream_t s) {
+  MPN_CHECK_ARG(d_g_c8 && d_x_c8 && d_part && d_wpk && d_vpk && B > 0 && N > 0 && K > 0 && Mp >= B && nseg > 0 && nseg <= 65535);
+  SegWgradArgs a{};
+  a.g = d_g_c8; a.x = d_x_c8; a.Mp = Mp; a.B = B; a.N = N; a.NP = lin_np(N); a.nchunks = round_up(K, 64) / 8;
+  a.rows_per_wave = round_up(cdiv(B, 4), 2);
+  a.pitch = (size_t)nseg * Mp; a.part = d_part; a.part_stride = (size_t)a.nchunks * a.NP * 8;
+  int rc = set_max_dyn_lds(reinterpret_cast<const void *>(seg_wgrad_kernel), kSegWgradLds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(seg_wgrad_kernel, dim3((unsigned)(a.NP / 32), (unsigned)cdiv(a.nchunks, 32), (unsigned)nseg), dim3(256), kSegWgradLds, s, a);
+  MPN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(seg_wgrad_sgd_kernel, dim3((unsigned)cdiv_sz((size_t)a.nchunks * a.NP, 256)), dim3(256), 0, s, d_part, a.part_stride, nseg, N, a.NP, K,
+                     a.nchunks, d_wpk, d_vpk, lr, momentum, wd);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+constexpr int kSegBiasLds = 64 * 32 * 8 * 4;  // the slot sums of a block of 64 segments
+
+// Block = one 8-column chunk of g.  Per segment sgd_bias_kernel's sum (thread t: column t % 8 over the rows seg * Mp + m, m = t / 8 mod 32,
+// ascending, then the fixed LDS tree over the 32 partial sums); the segment sums then go through a second fixed tree (segments in
+// blocks of 64 leaves, missing ones +0.0; the blocks' roots added in ascending order — one block for the 49 bins of a 7 x 7 pooling),
+// and the one thread per column that holds the result takes the bias step.  The slot sums of a block of segments are all taken first
+// and their trees run side by side: ten barriers per 64 segments.
+__global__ __launch_bounds__(256) void seg_bias_sgd_kernel(const float *__restrict__ g, int Mp, int nseg, int B, int N, float *__restrict__ b,
+                                                           float *__restrict__ vb, float lr, float mom) {
+  extern __shared__ float sb[];  // [64 segments][32 slots][8]
+  const int e = threadIdx.x & 7, slot = threadIdx.x >> 3, n = blockIdx.x * 8 + e;
+  const float *gc = g + (size_t)blockIdx.x * nseg * Mp * 8 + e;
+  float total = 0.0f;
+  for (int s0 = 0; s0 < nseg; s0 += 64) {
+    const int ns = min(64, nseg - s0);
+    for (int sg = 0; sg < 64; ++sg) {
+      float sum = 0.0f;
+      if (sg < ns) {
+        const float *gp = gc + (size_t)(s0 + sg) * Mp * 8;
+        for (int m = slot; m < B; m += 32) sum += gp[(size_t)m * 8];
+      }
+      sb[(sg * 32 + slot) * 8 + e] = sum;
+    }
+    __syncthreads();
+    for (int w = 16; w > 0; w >>= 1) {
+      if (slot < w)
+        for (int sg = 0; sg < ns; ++sg) sb[(sg * 32 + slot) * 8 + e] += sb[(sg * 32 + slot + w) * 8 + e];
+      __syncthreads();
+    }
+    for (int w = 32; w > 0; w >>= 1) {  // the segment sums sb[sg][0]: leaves slot and slot + w
+      if (slot < w) sb[slot * 32 * 8 + e] += sb[(slot + w) * 32 * 8 + e];
+      __syncthreads();
+    }
+    if (slot == 0) total = s0 == 0 ? sb[e] : total + sb[e];
+    __syncthreads();
+  }
+  if (slot != 0 || n >= N) return;
+  const float v = mom * vb[n] + total;
+  vb[n] = v;
+  b[n] = b[n] - lr * v;
+}
+
+int sgd_bias_seg_c8(const float *d_g_c8, int Mp, int nseg, int B, int N, float *d_bpk, float *d_vb, float lr, float momentum, hipStream_t s) {
+  MPN_CHECK_ARG(d_g_c8 && d_bpk && d_vb && B > 0 && N > 0 && Mp >= B && nseg > 0);
+  int rc = set_max_dyn_lds(reinterpret_cast<const void *>(seg_bias_sgd_kernel), kSegBiasLds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(seg_bias_sgd_kernel, dim3((unsigned)cdiv(N, 8)), dim3(256), kSegBiasLds, s, d_g_c8, Mp, nseg, B, N, d_bpk, d_vb, lr, momentum);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Input gradient: dx = scale * (g W) .* [act > 0]
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct DgradArgs {
@@ -282,17 +513,22 @@ __global__ __launch_bounds__(256) void linear_dgrad_kernel(DgradArgs a) {
     const int kc = ck0 + 8 * (r >> 2) + 4 * half + (r & 3);
     if (kc >= a.nchunks) continue;
     const size_t off = ((size_t)kc * a.x_Mp + m) * 8;
-    const f32x4 a0 = *reinterpret_cast<const f32x4 *>(a.act + off), a1 = *reinterpret_cast<const f32x4 *>(a.act + off + 4);
     f32x4 d0, d1;
+    if (a.act) {
+      const f32x4 a0 = *reinterpret_cast<const f32x4 *>(a.act + off), a1 = *reinterpret_cast<const f32x4 *>(a.act + off + 4);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { d0[e] = a0[e] > 0.0f ? acc[e][r] * a.scale : 0.0f; d1[e] = a1[e] > 0.0f ? acc[4 + e][r] * a.scale : 0.0f; }
+      for (int e = 0; e < 4; ++e) { d0[e] = a0[e] > 0.0f ? acc[e][r] * a.scale : 0.0f; d1[e] = a1[e] > 0.0f ? acc[4 + e][r] * a.scale : 0.0f; }
+    } else {  // no activation behind the layer (MultiPathNet's 1x1 mix feeds fc6 directly): every element passes
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { d0[e] = acc[e][r] * a.scale; d1[e] = acc[4 + e][r] * a.scale; }
+    }
     *reinterpret_cast<f32x4 *>(a.dx + off) = d0; *reinterpret_cast<f32x4 *>(a.dx + off + 4) = d1;
   }
 }
 
 int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_wpk, int K, const float *d_act_c8, float *d_dx_c8, int x_Mp,
                     hipStream_t s, float scale) {
-  MPN_CHECK_ARG(d_g_c8 && d_wpk && d_act_c8 && d_dx_c8 && B > 0 && N > 0 && K > 0 && g_Mp >= B && x_Mp >= B);
+  MPN_CHECK_ARG(d_g_c8 && d_wpk && d_dx_c8 && B > 0 && N > 0 && K > 0 && g_Mp >= B && x_Mp >= B);  // (d_act_c8 null: unmasked)
   DgradArgs a{};
   a.scale = scale;
   a.g = d_g_c8; a.w = d_wpk; a.act = d_act_c8; a.dx = d_dx_c8; a.g_Mp = g_Mp; a.x_Mp = x_Mp; a.B = B; a.N = N;

@@ -1,5 +1,6 @@
 // train_driver.hip — training a VGG Fast R-CNN handle on the device (include/mpn.h mpn_frcnn_train_*): the ROI
-// head with the trunk frozen, or with the trunk's last conv layers (MPN_TRAIN_CONV(k), MPN_TRAIN_TRUNK(k)).  Host code only: the
+// head with the trunk frozen, or with the trunk's last conv layers (MPN_TRAIN_CONV(k), MPN_TRAIN_TRUNK(k)); and the towers of a
+// MultiPathNet handle with the trunk frozen (mpn_mpnet_train_*; section 13.9).  Host code only: the
 // kernels are train.hip's (train.h) and the detect path's (dense.h); the handle and what is shared with pipeline.hip: pipeline.h.
 #include <cmath>
 #include <algorithm>
@@ -56,15 +57,47 @@ struct TrainState {
 using LinT = TrainState::LinT;
 using ConvT = TrainState::ConvT;
 
+// The training state of a MultiPathNet handle's towers (mpn_mpnet_train_*): exists between mpn_mpnet_train_begin
+// and mpn_mpnet_train_end.  Every activation and gradient of a step lives here, none in detect's buffers.  C8 matrices at row pitch Mp
+// unless said otherwise; momentum in the layout of the weight it goes with.
+struct TowerTrainState {
+  float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
+  struct TowT {
+    int Kcat = 0;                        // the tower's concat width (conv5 [+ conv4] [+ conv3])
+    float *x = nullptr;                  // the mix layer's operand [Kcat64/8][PP * Mp][8]: rows (bin, roi), the normalised ROI pools side by side
+    float *m = nullptr;                  // the mix layer's output [c5P/8][PP * Mp][8] == fc6's operand [.. >= K6_64/8][Mp][8]
+    float *y6 = nullptr;                 // fc6's output as fc7 read it (behind the dropout)
+    float *gm = nullptr, *g6 = nullptr;  // the gradients at m (m's layout) and at fc6's output
+    float *v_mix = nullptr, *vb_mix = nullptr, *v6 = nullptr, *vb6 = nullptr, *v7 = nullptr, *vb7 = nullptr;
+  };
+  std::vector<TowT> tw;
+  float *cat = nullptr, *dcat = nullptr;         // the towers' fc7 outputs side by side [T * F/8][Mp][8] (behind the dropout); the gradient there
+  float *cls_rm = nullptr, *bbox_rm = nullptr;   // the two heads' outputs, row-major [B, K*C], [B, 4C]
+  float *g_cls = nullptr, *g_bbox = nullptr;     // train_loss_split's two gradient matrices
+  float *v_cls = nullptr, *vb_cls = nullptr, *v_bbox = nullptr, *vb_bbox = nullptr;
+  float *part = nullptr;                         // sgd_wgrad_seg_c8's partial sums (the widest tower's)
+  float *rois = nullptr, *gt = nullptr, *loss = nullptr;
+  int *labels = nullptr;
+  int head_k = 0, pending = 0, last_rows = 0;
+  float drop_rate = 0.f, drop_scale = 1.f;       // as TrainState's; the layer word of tower t is 2 t (behind fc6), 2 t + 1 (behind fc7)
+  uint32_t drop_threshold = 0;
+  long seed = 0, step = 0;
+  DeviceOwner own;
+};
+using TowT = TowerTrainState::TowT;
+
 void mpn::free_train_state(mpn_frcnn *p) {
   delete p->train;  // (its DeviceOwner gives the buffers back)
   p->train = nullptr;
+  delete p->tower_train;
+  p->tower_train = nullptr;
 }
 
 // the handle kinds and states that cannot train, each named (as refuse_multi_pass does for the throughput forms)
 static int refuse_train(const mpn_frcnn *p, const char *fn) {
   if (p->is_mpnet || p->rn) {
-    set_error("%s: a %s handle cannot be trained: only mpn_frcnn_create's VGG Fast R-CNN head (fc6, fc7, cls + bbox) has a backward pass", fn, handle_kind_name(p));
+    set_error("%s: a %s handle cannot be trained: only mpn_frcnn_create's VGG Fast R-CNN head (fc6, fc7, cls + bbox) has a backward pass%s", fn, handle_kind_name(p),
+              p->is_mpnet ? " here (its towers train through mpn_mpnet_train_begin)" : "");
     return MPN_ESTATE;
   }
   if (p->cfg.fc_arith != MPN_FC_FP32) {
@@ -579,6 +612,329 @@ extern "C" int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w, 
   return unpack_conv_weights(L.wpk, L.bpk, L.Cin, L.Cout, d_w, d_b, as_stream(stream));
 }
 
+// =================================================================================================================================
+// MultiPathNet's towers with the trunk frozen (include/mpn.h mpn_mpnet_train_*): models/multipathnet.lua
+// phase 1 — the trunk inside nn.NoBackprop, everything trainable behind the ROI pooling: per tower the 1x1 mix, fc6, fc7, on top
+// the K classifiers on the Foveal towers' concat and the box regressor on the het tower.  mpn_frcnn_train_* keeps refusing these
+// handles (refuse_train); these entry points refuse every other kind.
+// =================================================================================================================================
+static int refuse_tower_train(const mpn_frcnn *p, const char *fn) {
+  if (p->n_scales > 1) {  // (only a plain handle can hold one)
+    set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales), which only a plain Fast R-CNN handle holds: this entry point trains mpn_mpnet_create handles", fn, p->n_scales);
+    return MPN_ESTATE;
+  }
+  if (!p->is_mpnet) {
+    set_error("%s: not an mpn_mpnet_create handle: a %s handle has no towers to train%s", fn, handle_kind_name(p), p->rn ? "" : " (mpn_frcnn_train_begin trains its head)");
+    return MPN_ESTATE;
+  }
+  if (p->cfg.fc_arith != MPN_FC_FP32) {
+    set_error("%s: an MPN_FC_SPLIT3 handle cannot be trained (its bf16 weight planes would go stale): create it with MPN_FC_FP32", fn);
+    return MPN_ESTATE;
+  }
+  if (p->augment) {
+    set_error("%s: not supported with horizontal-flip augmentation (mpn_frcnn_set_augment): switch it off; flip training images with mpn_image_hflip / mpn_flip_boxes", fn);
+    return MPN_ESTATE;
+  }
+  if (p->tail_pending[0] || p->tail_pending[1]) {
+    set_error("%s: a pipelined call's tail is still pending on this handle: call mpn_frcnn_flush first", fn);
+    return MPN_ESTATE;
+  }
+  return MPN_OK;
+}
+
+// every buffer of the state; false: something failed (t's DeviceOwner holds what was made)
+static bool alloc_tower_train_state(const mpn_frcnn *p, TowerTrainState *t) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int F = c.fc_dim, PP = c.pooled_h * c.pooled_w, C = c.n_classes, KC = p->n_integral * C, c5 = p->feat_c;
+  const int T = (int)p->towers.size(), Fcb = lin_np(F) / 8;
+  const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
+  auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
+  auto momentum = [&](float **v, float **vb, int K, int N) {
+    return alloc0(v, lin_wpk_elems(round_up(K, 64), N) * sizeof(float)) && alloc0(vb, (size_t)lin_np(N) * sizeof(float));
+  };
+  bool ok = true;
+  size_t part = 0;
+  t->tw.resize(T);
+  for (int i = 0; i < T && ok; ++i) {
+    TowT &W = t->tw[i];
+    W.Kcat = p->towers[i].total_feat;
+    const size_t k6_rec = (size_t)(round_up(p->K6, 64) / 8) * rec;
+    ok = alloc0(&W.x, (size_t)(round_up(W.Kcat, 64) / 8) * PP * rec) && alloc0(&W.m, std::max((size_t)(lin_np(c5) / 8) * PP * rec, k6_rec)) &&
+         alloc0(&W.y6, (size_t)Fcb * rec) && alloc0(&W.gm, k6_rec) && alloc0(&W.g6, (size_t)Fcb * rec) &&
+         momentum(&W.v_mix, &W.vb_mix, W.Kcat, c5) && momentum(&W.v6, &W.vb6, p->K6, F) && momentum(&W.v7, &W.vb7, F, F);
+    part = std::max(part, seg_wgrad_part_elems(W.Kcat, c5, PP));
+  }
+  ok = ok && alloc0(&t->cat, (size_t)T * Fcb * rec) && alloc0(&t->dcat, (size_t)T * Fcb * rec);
+  ok = ok && alloc0(&t->cls_rm, M * KC * sizeof(float)) && alloc0(&t->bbox_rm, M * 4 * C * sizeof(float));
+  ok = ok && alloc0(&t->g_cls, (size_t)(lin_np(KC) / 8) * rec) && alloc0(&t->g_bbox, (size_t)(lin_np(4 * C) / 8) * rec);
+  ok = ok && momentum(&t->v_cls, &t->vb_cls, (T - 1) * F, KC) && momentum(&t->v_bbox, &t->vb_bbox, F, 4 * C);
+  ok = ok && alloc0(&t->part, part * sizeof(float));
+  ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
+  return ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
+}
+
+extern "C" int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_tower_train(p, "mpn_mpnet_train_begin");
+  if (rc) return rc;
+  if (p->tower_train) { set_error("mpn_mpnet_train_begin: training has already begun on this handle (mpn_mpnet_train_end first)"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  std::unique_ptr<TowerTrainState> t(new TowerTrainState());
+  t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
+  if (!alloc_tower_train_state(p, t.get()) || hipDeviceSynchronize() != hipSuccess) {
+    set_error("mpn_mpnet_train_begin: allocating the momentum / activation / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
+    return MPN_ENOMEM;
+  }
+  p->tower_train = t.release();  // all or nothing: published last
+  return MPN_OK;
+}
+
+extern "C" int mpn_mpnet_train_end(mpn_frcnn *p) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (!p->tower_train) { set_error("mpn_mpnet_train_end: no mpn_mpnet_train_begin on this handle"); return MPN_ESTATE; }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  delete p->tower_train;
+  p->tower_train = nullptr;
+  return MPN_OK;
+}
+
+// the state of a call between begin and end, or a refusal
+static int tower_state(mpn_frcnn *p, const char *fn, TowerTrainState **t) {
+  *t = p->tower_train;
+  if (*t) return MPN_OK;
+  set_error("%s: no mpn_mpnet_train_begin on this handle", fn);
+  return MPN_ESTATE;
+}
+
+extern "C" int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt, const int *d_labels,
+                                   int n, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_tower_train(p, "mpn_mpnet_train_add");
+  if (rc) return rc;
+  TowerTrainState *t;
+  if ((rc = tower_state(p, "mpn_mpnet_train_add", &t)) != MPN_OK) return rc;
+  MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
+  const mpn_frcnn_config &c = p->cfg;
+  if (t->pending + n > c.max_rois) {
+    set_error("mpn_mpnet_train_add: %d pending rows + %d exceed the handle's max_rois (%d)", t->pending, n, c.max_rois);
+    return MPN_EINVAL;
+  }
+  double sc = 1.0;
+  int H = H0, W = W0;
+  if (c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
+  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
+    set_error("mpn_mpnet_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
+    return MPN_EINVAL;
+  }
+  ScratchScope scratch_scope(&p->scratch);
+  hipStream_t s = as_stream(stream);
+  p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers, the ROI and Foveal tables are rewritten: the next head segment runs for real
+  Act feat;
+  rc = obtain_features(p, d_image, H0, W0, H, W, sc, &p->up, s, &feat);  // getImages' rescale + the frozen trunk, exactly as detect
+  // the maps now belong to a training image: nothing a detect on cached features may pool from, and no range-max table goes with them
+  p->up.invalidate(); p->mir.invalidate();
+  p->vmax_built[0] = p->vmax_built[1] = p->vmax_built[2] = false;
+  if (rc) return rc;
+  rc = mpn_project_im_rois(d_rois, n, sc, p->rois, s);
+  if (rc == MPN_OK) rc = mpn_foveal_forward(p->rois, n, p->fov, s);
+  if (rc) return rc;
+  // conv345Combine in detect's in-place form (run_mpnet_head without the scale fold), one stream: per tower the ROI max-pools of its maps
+  // over its Foveal region side by side, each map's slab normalised per ROI — the same launches, so the same bits: the pooling from the
+  // pixel-major range-max tables with the sum of squares fused in (roi_pool_c8 + l2norm_scale_c8 pool the same values but add the squares
+  // in another order: the norm's last bit differs).  The tables are detect's buffers, rebuilt here for this image's maps and left marked
+  // unbuilt.  This image's rows go behind the pending ones: a shifted base pointer with the buffer's row pitch
+  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp;
+  const Act maps[3] = {feat, p->tap_act[1], p->tap_act[2]};
+  const float scales[3] = {c.spatial_scale, c.spatial_scale * 2.0f, c.spatial_scale * 4.0f};
+  const float kConv345Factor[3] = {1.0f, (float)(1.0 / 30), (float)(1.0 / 200)};  // model_utils.lua:231-237 (run_mpnet_head's)
+  bool used_any[3] = {true, false, false};
+  for (const mpn_frcnn::Tower &T : p->towers) { used_any[1] = used_any[1] || T.use4; used_any[2] = used_any[2] || T.use3; }
+  for (int m = 0; m < 3 && rc == MPN_OK; ++m) if (used_any[m]) rc = build_vmax_tables_pm(maps[m], p->vmax_tab[m], s);
+  if (rc) return rc;
+  for (size_t i = 0; i < p->towers.size(); ++i) {
+    const mpn_frcnn::Tower &T = p->towers[i];
+    const int used[3] = {1, T.use4, T.use3};
+    int cb_off = 0;
+    for (int m = 0; m < 3; ++m) {
+      if (!used[m]) continue;
+      float *dst = t->tw[i].x + ((size_t)cb_off * PP * Mp + t->pending) * 8;
+      rc = roi_pool_pm_rmq(maps[m], p->vmax_tab[m], p->fov + 5 * T.region, n, c.pooled_h, c.pooled_w, scales[m], RoiRule{1.0f, 0, c.roi_bin_rule}, dst, s, 20, Mp,
+                           p->conv345_norm ? 1 : 0, p->conv345_norm ? 1000.0f : kConv345Factor[m]);
+      if (rc) return rc;
+      cb_off += maps[m].Cb();
+    }
+  }
+  MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  t->pending += n;
+  return MPN_OK;
+}
+
+extern "C" int mpn_mpnet_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_tower_train(p, "mpn_mpnet_train_step");
+  if (rc) return rc;
+  TowerTrainState *t;
+  if ((rc = tower_state(p, "mpn_mpnet_train_step", &t)) != MPN_OK) return rc;
+  if (t->pending <= 0) { set_error("mpn_mpnet_train_step: no pending rows (mpn_mpnet_train_add first)"); return MPN_ESTATE; }
+  MPN_CHECK_ARG(std::isfinite(lr));
+  const mpn_frcnn_config &c = p->cfg;
+  const int B = t->pending, Mp = p->Mp, PP = c.pooled_h * c.pooled_w, F = c.fc_dim, C = c.n_classes, KC = p->n_integral * C, c5 = p->feat_c;
+  const int T = (int)p->towers.size(), nf = T - 1, Fcb = lin_np(F) / 8;
+  const size_t slice = (size_t)Fcb * Mp * 8;  // a tower's columns of cat / dcat
+  ScratchScope scratch_scope(&p->scratch);
+  hipStream_t s = as_stream(stream);
+  const bool drop = t->drop_rate > 0.0f;
+  const float gscale = drop ? t->drop_scale : 1.0f;
+  const long step = t->step++;  // this step's masks; counted whatever the rate, also when a launch below fails
+  auto dropout = [&](float *y, int layer) {
+    const DropoutCfg dc{t->drop_threshold, (uint32_t)((uint64_t)t->seed & 0xffffffffu), (uint32_t)((uint64_t)t->seed >> 32), (uint32_t)layer,
+                        (uint32_t)((uint64_t)step & 0xffffffffu), t->drop_scale};
+    return dropout_c8(y, Mp, B, F, dc, s);
+  };
+  // forward: detect's GEMMs, one stream, tower after tower.  The mix runs over all PP * Mp rows of the operand (the valid ones are PP
+  // segments of B; a row's result depends on that row alone) and there is no ReLU between it and fc6 (multipathnet.lua: View, Linear)
+  for (int i = 0; i < T && rc == MPN_OK; ++i) {
+    const mpn_frcnn::Tower &W = p->towers[i];
+    const TowT &A = t->tw[i];
+    float *y7 = t->cat + (size_t)i * slice;
+    rc = linear_c8(A.x, PP * Mp, A.Kcat, W.mix_w, W.mix_b, c5, 0, A.m, nullptr, s, PP * Mp, nullptr, 2);
+    if (rc == MPN_OK) rc = linear_c8(A.m, B, p->K6, W.w6, W.b6, F, 1, A.y6, nullptr, s, Mp, nullptr, 1);
+    if (rc == MPN_OK && drop) rc = dropout(A.y6, 2 * i);
+    if (rc == MPN_OK) rc = linear_c8(A.y6, B, F, W.w7, W.b7, F, 1, y7, nullptr, s, Mp, nullptr, 1);
+    if (rc == MPN_OK && drop) rc = dropout(y7, 2 * i + 1);
+  }
+  if (rc == MPN_OK) rc = linear_c8(t->cat, B, nf * F, p->wcls, p->bcls, KC, 0, nullptr, t->cls_rm, s, Mp, nullptr, 1);
+  if (rc == MPN_OK) rc = linear_c8(t->cat + (size_t)nf * slice, B, F, p->wbbox, p->bbbox, 4 * C, 0, nullptr, t->bbox_rm, s, Mp, nullptr, 1);
+  if (rc) return rc;
+  LossCfg lc{};
+  for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
+  lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
+  lc.bbox_weight = t->bbox_weight;
+  rc = train_loss_split(t->cls_rm, t->bbox_rm, B, C, p->n_integral, t->head_k, t->rois, t->gt, t->labels, lc, t->g_cls, t->g_bbox, Mp, d_loss ? d_loss : t->loss, s);
+  // backward: every input gradient before any update.  cat and y6 are what the dropout left, so [x > 0] is keep mask x ReLU mask
+  if (rc == MPN_OK) rc = linear_dgrad_c8(t->g_cls, Mp, B, KC, p->wcls, nf * F, t->cat, t->dcat, Mp, s, gscale);
+  if (rc == MPN_OK) rc = linear_dgrad_c8(t->g_bbox, Mp, B, 4 * C, p->wbbox, F, t->cat + (size_t)nf * slice, t->dcat + (size_t)nf * slice, Mp, s, gscale);
+  for (int i = 0; i < T && rc == MPN_OK; ++i) {
+    const mpn_frcnn::Tower &W = p->towers[i];
+    const TowT &A = t->tw[i];
+    rc = linear_dgrad_c8(t->dcat + (size_t)i * slice, Mp, B, F, W.w7, F, A.y6, A.g6, Mp, s, gscale);
+    if (rc == MPN_OK) rc = linear_dgrad_c8(A.g6, Mp, B, F, W.w6, p->K6, nullptr, A.gm, Mp, s);  // unmasked, fc6's (cb, bin) chunk order == m's layout
+  }
+  // the updates, in place on the packed weights detect reads: the heads, then per tower fc7, fc6, mix
+  const float mom = t->momentum, wd = t->weight_decay;
+  if (rc == MPN_OK) rc = sgd_wgrad_c8(t->g_cls, Mp, t->cat, Mp, B, KC, nf * F, 1, p->wcls, t->v_cls, lr, mom, wd, s);
+  if (rc == MPN_OK) rc = sgd_bias_c8(t->g_cls, Mp, B, KC, p->bcls, t->vb_cls, lr, mom, s);
+  if (rc == MPN_OK) rc = sgd_wgrad_c8(t->g_bbox, Mp, t->cat + (size_t)nf * slice, Mp, B, 4 * C, F, 1, p->wbbox, t->v_bbox, lr, mom, wd, s);
+  if (rc == MPN_OK) rc = sgd_bias_c8(t->g_bbox, Mp, B, 4 * C, p->bbbox, t->vb_bbox, lr, mom, s);
+  for (int i = 0; i < T && rc == MPN_OK; ++i) {
+    const mpn_frcnn::Tower &W = p->towers[i];
+    const TowT &A = t->tw[i];
+    const float *g7 = t->dcat + (size_t)i * slice;
+    rc = sgd_wgrad_c8(g7, Mp, A.y6, Mp, B, F, F, 1, W.w7, A.v7, lr, mom, wd, s);
+    if (rc == MPN_OK) rc = sgd_bias_c8(g7, Mp, B, F, W.b7, A.vb7, lr, mom, s);
+    if (rc == MPN_OK) rc = sgd_wgrad_c8(A.g6, Mp, A.m, Mp, B, F, p->K6, PP, W.w6, A.v6, lr, mom, wd, s);
+    if (rc == MPN_OK) rc = sgd_bias_c8(A.g6, Mp, B, F, W.b6, A.vb6, lr, mom, s);
+    if (rc == MPN_OK) rc = sgd_wgrad_seg_c8(A.gm, A.x, Mp, PP, B, c5, A.Kcat, t->part, W.mix_w, A.v_mix, lr, mom, wd, s);
+    if (rc == MPN_OK) rc = sgd_bias_seg_c8(A.gm, Mp, PP, B, c5, W.mix_b, A.vb_mix, lr, mom, s);
+  }
+  t->last_rows = B;
+  t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
+  return rc;
+}
+
+extern "C" int mpn_mpnet_train_set_head(mpn_frcnn *p, int k) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t;
+  if (int rc = tower_state(p, "mpn_mpnet_train_set_head", &t)) return rc;
+  if (k < 0 || k >= p->n_integral) {
+    set_error("mpn_mpnet_train_set_head: invalid argument: head %d is outside [0, K) of this handle's K = %d integral classifiers", k, p->n_integral);
+    return MPN_EINVAL;
+  }
+  t->head_k = k;  // read by the next mpn_mpnet_train_step
+  return MPN_OK;
+}
+
+extern "C" int mpn_mpnet_train_set_dropout(mpn_frcnn *p, float rate, long seed) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t;
+  if (int rc = tower_state(p, "mpn_mpnet_train_set_dropout", &t)) return rc;
+  if (!(std::isfinite(rate) && rate >= 0.0f && rate < 1.0f)) {
+    set_error("mpn_mpnet_train_set_dropout: rate %g is outside [0, 1)", (double)rate);
+    return MPN_EINVAL;
+  }
+  t->drop_rate = rate;
+  t->drop_threshold = (uint32_t)std::floor((double)rate * 4294967296.0);
+  t->drop_scale = 1.0f / (1.0f - rate);
+  t->seed = seed;
+  return MPN_OK;
+}
+
+static int refuse_not_mpnet(const mpn_frcnn *p, const char *fn) {
+  if (p->is_mpnet) return MPN_OK;
+  set_error("%s: not an mpn_mpnet_create handle: a %s handle has no towers to unpack", fn, handle_kind_name(p));
+  return MPN_ESTATE;
+}
+
+extern "C" int mpn_mpnet_get_tower_weights(mpn_frcnn *p, int tower, float *d_mix_w, float *d_mix_b, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w,
+                                           float *d_fc7_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (int rc = refuse_not_mpnet(p, "mpn_mpnet_get_tower_weights")) return rc;
+  if (tower < 0 || tower >= (int)p->towers.size()) { set_error("mpn_mpnet_get_tower_weights: tower %d of %d", tower, (int)p->towers.size()); return MPN_EINVAL; }
+  const mpn_frcnn::Tower &W = p->towers[tower];
+  const int F = p->cfg.fc_dim, c5 = p->feat_c;
+  hipStream_t s = as_stream(stream);
+  int rc = unpack_linear_weights(W.mix_w, W.mix_b, W.total_feat, c5, 1, 0, c5, d_mix_w, d_mix_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(W.w6, W.b6, p->K6, F, p->cfg.pooled_h * p->cfg.pooled_w, 0, F, d_fc6_w, d_fc6_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(W.w7, W.b7, F, F, 1, 0, F, d_fc7_w, d_fc7_b, s);
+  return rc;
+}
+
+extern "C" int mpn_mpnet_get_head_weights(mpn_frcnn *p, float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (int rc = refuse_not_mpnet(p, "mpn_mpnet_get_head_weights")) return rc;
+  const int F = p->cfg.fc_dim, C = p->cfg.n_classes, KC = p->n_integral * C, nf = (int)p->towers.size() - 1;
+  hipStream_t s = as_stream(stream);
+  int rc = unpack_linear_weights(p->wcls, p->bcls, nf * F, KC, 1, 0, KC, d_cls_w, d_cls_b, s);
+  if (rc == MPN_OK) rc = unpack_linear_weights(p->wbbox, p->bbbox, F, 4 * C, 1, 0, 4 * C, d_bbox_w, d_bbox_b, s);
+  return rc;
+}
+
+// mpn_frcnn_debug_tensor's "tower_train_*" names, all of the last mpn_mpnet_train_step, row-major: "tower_train_x.<t>" the mix operand
+// [rows, Kcat_t, PH, PW] (valid until the next mpn_mpnet_train_add), "tower_train_y6.<t>" fc6's output behind the dropout [rows, F],
+// "tower_train_cat" [rows, T * F], "tower_train_cls" [rows, K * C], "tower_train_bbox" [rows, 4C], "tower_train_g_cls" [rows, K * C]
+int mpn::tower_train_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems) {
+  const TowerTrainState *t = p->tower_train;
+  if (!t || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_mpnet_train_step", name); return MPN_ESTATE; }
+  const mpn_frcnn_config &c = p->cfg;
+  const int R = t->last_rows, F = c.fc_dim, C = c.n_classes, KC = p->n_integral * C, T = (int)p->towers.size(), PP = c.pooled_h * c.pooled_w, Mp = p->Mp;
+  const char *tail = name + 12;
+  int ti = -1;
+  const bool is_x = sscanf(tail, "x.%d", &ti) == 1, is_y6 = !is_x && sscanf(tail, "y6.%d", &ti) == 1;
+  if ((is_x || is_y6) && (ti < 0 || ti >= T)) { set_error("mpn_frcnn_debug_tensor: '%s': the handle has towers 0..%d", name, T - 1); return MPN_EINVAL; }
+  size_t n = 0;
+  if (is_x) n = (size_t)R * t->tw[ti].Kcat * PP;
+  else if (is_y6) n = (size_t)R * F;
+  else if (!strcmp(tail, "cat")) n = (size_t)R * T * F;
+  else if (!strcmp(tail, "cls") || !strcmp(tail, "g_cls")) n = (size_t)R * KC;
+  else if (!strcmp(tail, "bbox")) n = (size_t)R * 4 * C;
+  else { set_error("mpn_frcnn_debug_tensor: unknown tensor '%s'", name); return MPN_EINVAL; }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  if (int rcd = grow_dbg(p, n * sizeof(float))) return rcd;
+  int rc = MPN_OK;
+  if (is_x) rc = launch_unpack_pooled(t->tw[ti].x, R, t->tw[ti].Kcat, PP, Mp, p->dbg);
+  else if (is_y6) rc = c8_rows_to_rowmajor(t->tw[ti].y6, Mp, R, F, p->dbg, nullptr);
+  else if (!strcmp(tail, "cat")) rc = c8_rows_to_rowmajor(t->cat, Mp, R, T * F, p->dbg, nullptr);  // the towers' blocks back to back == one C8 matrix
+  else if (!strcmp(tail, "g_cls")) rc = c8_rows_to_rowmajor(t->g_cls, Mp, R, KC, p->dbg, nullptr);
+  else MPN_CHECK_HIP(hipMemcpy(p->dbg, !strcmp(tail, "cls") ? t->cls_rm : t->bbox_rm, n * sizeof(float), hipMemcpyDeviceToDevice));
+  if (rc) return rc;
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  *d_ptr = p->dbg; *n_elems = n;
+  return MPN_OK;
+}
+
 #ifdef MPN_DEBUG_HOOKS
 
 // tools/bench_train.py (debug flavour only): fc6's fused weight-gradient + SGD kernel issued `iters` times BACK TO BACK on the operands the
@@ -679,10 +1035,33 @@ extern "C" int mpn_debug_linear_dgrad_c8(const float *d_g_c8, size_t n_g, int g_
   if (B > 0 && N > 0 && K > 0 && g_Mp >= B && x_Mp >= B) {
     DBG_NEED(d_g_c8, n_g, dbg_c8(N, g_Mp));
     DBG_NEED(d_wpk, n_w, dbg_lin_pack(K, N));
-    DBG_NEED(d_act_c8, n_act, dbg_c8(K, x_Mp));
+    if (d_act_c8) DBG_NEED(d_act_c8, n_act, dbg_c8(K, x_Mp));  // (null: the unmasked form)
     DBG_NEED(d_dx_c8, n_dx, dbg_c8(K, x_Mp));
   }
   return linear_dgrad_c8(d_g_c8, g_Mp, B, N, d_wpk, K, d_act_c8, d_dx_c8, x_Mp, nullptr, scale);
+}
+
+// the segmented forms (MultiPathNet's mix layer): operands at row pitch nseg * Mp
+extern "C" int mpn_debug_sgd_wgrad_seg_c8(const float *d_g_c8, size_t n_g, const float *d_x_c8, size_t n_x, int Mp, int nseg, int B, int N, int K, float *d_part,
+                                          size_t n_part, float *d_wpk, size_t n_w, float *d_vpk, size_t n_v, float lr, float momentum, float wd) {
+  if (B > 0 && N > 0 && K > 0 && Mp >= B && nseg > 0 && nseg <= 65535) {
+    DBG_NEED(d_g_c8, n_g, dbg_c8(N, nseg * Mp));
+    DBG_NEED(d_x_c8, n_x, dbg_c8(round_up(K, 64), nseg * Mp));
+    DBG_NEED(d_part, n_part, seg_wgrad_part_elems(K, N, nseg));
+    DBG_NEED(d_wpk, n_w, dbg_lin_pack(K, N));
+    DBG_NEED(d_vpk, n_v, dbg_lin_pack(K, N));
+  }
+  return sgd_wgrad_seg_c8(d_g_c8, d_x_c8, Mp, nseg, B, N, K, d_part, d_wpk, d_vpk, lr, momentum, wd, nullptr);
+}
+
+extern "C" int mpn_debug_sgd_bias_seg_c8(const float *d_g_c8, size_t n_g, int Mp, int nseg, int B, int N, float *d_bpk, size_t n_b, float *d_vb, size_t n_vb,
+                                         float lr, float momentum) {
+  if (B > 0 && N > 0 && Mp >= B && nseg > 0) {
+    DBG_NEED(d_g_c8, n_g, dbg_c8(N, nseg * Mp));
+    DBG_NEED(d_bpk, n_b, (size_t)N);
+    DBG_NEED(d_vb, n_vb, (size_t)N);
+  }
+  return sgd_bias_seg_c8(d_g_c8, Mp, nseg, B, N, d_bpk, d_vb, lr, momentum, nullptr);
 }
 
 extern "C" int mpn_debug_dropout_c8(float *d_y_c8, size_t n_y, int Mp, int B, int N, uint32_t threshold, uint32_t seed_lo, uint32_t seed_hi, uint32_t layer,

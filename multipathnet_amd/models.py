@@ -667,6 +667,10 @@ class FastRCNN(object):
                     dt = d(T[name])
                     keep.append(dt)
                     getattr(mw, name)[t] = _f(dt)
+            # what tower_weights() needs beside the device's tensors: the towers' geometry and the (frozen) trunk as creation took it
+            self._towers = [dict(region=T["region"], use4=T["use4"], use3=T["use3"], total_feat=int(T["mix_w"].shape[1])) for T in tow]
+            self._mpnet_fixed = dict(conv_w=cw, conv_b=cb, bbox_mean=params.get("bbox_mean"), bbox_std=params.get("bbox_std"),
+                                     conv345_norm=params.get("conv345_norm", True))
             heads = [d(params[k]) for k in ("cls_w", "cls_b", "bbox_w", "bbox_b")]
             check(lib.mpn_mpnet_create(C.byref(c), wp, bp, C.byref(mw), *[_f(t) for t in heads], C.byref(self._h)), "mpn_mpnet_create")
         else:
@@ -947,6 +951,63 @@ class FastRCNN(object):
             check(self._lib.mpn_frcnn_get_trunk_weights(self._h, l, _f(w), _f(b), _stream()), "mpn_frcnn_get_trunk_weights")
             ws.append(w); bs.append(b); cin = co
         return {"conv_w": ws, "conv_b": bs}
+
+    # ---- training a MultiPathNet handle's towers, trunk frozen (mpn_mpnet_train_*, include/mpn.h) ----
+    def tower_train_begin(self, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0, dropout=0.0, seed=555):
+        """Start training the towers of a MultiPathNet handle (models/multipathnet.lua phase 1: the trunk frozen): every tower's 1x1 mix,
+        fc6 and fc7, the K integral classifiers and the box regressor.  fp32 handles only; train_begin keeps refusing these handles.
+        dropout = 0.0: none; see tower_train_set_dropout."""
+        check(self._lib.mpn_mpnet_train_begin(self._h, C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)), "mpn_mpnet_train_begin")
+        if dropout:
+            self.tower_train_set_dropout(dropout, seed)
+
+    def tower_train_set_dropout(self, rate, seed=555):
+        """nn.Dropout(rate) behind fc6 + ReLU and fc7 + ReLU of every tower from the next tower_train_step on: train_set_dropout's mask
+        with layer = 2 * tower + (0 behind fc6, 1 behind fc7), so two towers never share one."""
+        check(self._lib.mpn_mpnet_train_set_dropout(self._h, float(rate), int(seed)), "mpn_mpnet_train_set_dropout")
+
+    def tower_train_set_head(self, k):
+        """The integral loss's selector: the next tower_train_step's loss reads classifier k of n_integral (train_set_head's rule)."""
+        check(self._lib.mpn_mpnet_train_set_head(self._h, int(k)), "mpn_mpnet_train_set_head")
+
+    def tower_train_add(self, image, rois, gt_boxes, labels):
+        """train_add for the towers: one image's rows behind the pending ones (the same arguments)."""
+        H, W = image.shape[1:]
+        n = rois.size(0)
+        assert gt_boxes.shape == rois.shape and labels.numel() == n and labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
+        check(self._lib.mpn_mpnet_train_add(self._h, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream()),
+              "mpn_mpnet_train_add")
+
+    def tower_train_step(self, lr):
+        """Forward, loss, backward and the SGD update of every tower and both heads on the pending rows -> device tensor [2] = (cls, bbox)."""
+        loss = torch.empty(2, dtype=torch.float32, device=self.device)
+        check(self._lib.mpn_mpnet_train_step(self._h, C.c_float(lr), _f(loss), _stream()), "mpn_mpnet_train_step")
+        return loss
+
+    def tower_train_end(self):
+        check(self._lib.mpn_mpnet_train_end(self._h), "mpn_mpnet_train_end")
+
+    def tower_weights(self):
+        """The MultiPathNet handle's parameters as synthetic_mpnet_params shapes them (device tensors): the towers' and heads' current
+        weights in Torch layout, the frozen trunk as creation took it.  MultiPathNet(net.tower_weights(), ...) rebuilds the same network."""
+        if not self.is_mpnet:
+            check(self._lib.mpn_mpnet_get_head_weights(self._h, None, None, None, None, _stream()), "mpn_mpnet_get_head_weights")  # (names the cause)
+        F, Cn, KC, PP = self.fc_dim, self.n_classes, self.n_integral * self.n_classes, self._cfg.pooled_h * self._cfg.pooled_w
+        c5, nf = self._cout[len(self._cout) - 1], len(self._towers) - 1
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        P = dict(self._mpnet_fixed)
+        P = {k: v for k, v in P.items() if v is not None}
+        P["towers"] = []
+        for t, T in enumerate(self._towers):
+            W = dict(T, mix_w=z(c5, T["total_feat"]), mix_b=z(c5), fc6_w=z(F, c5 * PP), fc6_b=z(F), fc7_w=z(F, F), fc7_b=z(F))
+            check(self._lib.mpn_mpnet_get_tower_weights(self._h, t, *[_f(W[k]) for k in ("mix_w", "mix_b", "fc6_w", "fc6_b", "fc7_w", "fc7_b")], _stream()),
+                  "mpn_mpnet_get_tower_weights")
+            P["towers"].append(W)
+        P.update(cls_w=z(KC, nf * F), cls_b=z(KC), bbox_w=z(4 * Cn, F), bbox_b=z(4 * Cn))
+        check(self._lib.mpn_mpnet_get_head_weights(self._h, *[_f(P[k]) for k in ("cls_w", "cls_b", "bbox_w", "bbox_b")], _stream()),
+              "mpn_mpnet_get_head_weights")
+        P["n_integral"], P["n_classes"] = self.n_integral, self.n_classes
+        return P
 
     def set_graphs(self, on):
         """captured launch graphs (mpn_frcnn_set_graphs): replay the per-image kernel chains with hipGraphLaunch.

@@ -13,9 +13,12 @@ and up, through two pooling layers — with the same two numbers, and the max-po
 more small kernels per step and a scale in two input gradients); 0, the default, launches nothing more than a run without the option.
 --integral K trains a handle with the integral loss's K classifiers (models.integral_params: a fused head of
 (K + 4) C rows instead of 5 C), step i on head i mod K as the reference's K donkeys take turns; 1, the default, is the plain handle.
+--model mpnet measures instead the tower training of a MultiPathNet handle (models.synthetic_mpnet_params: VGG-16,
+the five MPN_TOWERS, fc_dim 4096, C 81, K 6; mpn_mpnet_train_*): ms of mpn_mpnet_train_step alone and of the whole iteration on the same
+2 x 64 rows, step i on classifier i mod K, beside the step's derived floor — every trained weight and its momentum read and written once.
 One JSON line per measurement.
 
-    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6]
+    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6] [--model mpnet]
 """
 import argparse
 import ctypes as C
@@ -42,6 +45,42 @@ def batch(rng, n_classes):
     return im, rois, gt, labels
 
 
+def bench_mpnet(a):
+    """mpn_mpnet_train_step and the whole iteration (two tower_train_add + the step) on the product library"""
+    import torch
+    from multipathnet_amd import models
+    P = models.synthetic_mpnet_params(seed=557)
+    K, C_ = P["n_integral"], P["n_classes"]
+    rng = np.random.default_rng(5)
+    dev_batches = [[torch.from_numpy(x).cuda() for x in batch(rng, C_)] for _ in range(IMAGES)]
+    net = models.MultiPathNet(P, max_h=H, max_w=W, max_rois=IMAGES * ROWS)
+    trained = sum(int(T[k].numel()) for T in P["towers"] for k in ("mix_w", "mix_b", "fc6_w", "fc6_b", "fc7_w", "fc7_b")) + \
+        sum(int(P[k].numel()) for k in ("cls_w", "cls_b", "bbox_w", "bbox_b"))
+    gb = 4 * trained * 4 / 1e9   # w read + w write + v read + v write
+    del P
+    net.tower_train_begin(momentum=0.9, weight_decay=5e-4, dropout=a.dropout)
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    step_ms, iter_ms = [], []
+    for i in range(a.warmup + a.steps):
+        e[0].record()
+        for b in dev_batches:
+            net.tower_train_add(*b)
+        e[1].record()
+        net.tower_train_set_head(i % K)
+        net.tower_train_step(1e-6)   # a tiny step: the weights stay in their range over the run
+        e[2].record()
+        e[2].synchronize()
+        if i >= a.warmup:
+            step_ms.append(e[1].elapsed_time(e[2]))
+            iter_ms.append(e[0].elapsed_time(e[2]))
+    net.tower_train_end()
+    net.close()
+    print(json.dumps({"what": "mpnet_train_step", "towers": 5, "dropout": a.dropout, "integral": K, "rows": IMAGES * ROWS,
+                      "ms_step_median": round(float(np.median(step_ms)), 3), "ms_step_min": round(float(np.min(step_ms)), 3),
+                      "ms_iteration_median": round(float(np.median(iter_ms)), 3), "gbytes_weights_and_momentum": round(gb, 2),
+                      "floor_ms_at_6.3TBps": round(gb / 6.3e3 * 1e3, 3), "steps": a.steps, "device": torch.cuda.get_device_name(0)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -49,10 +88,13 @@ def main():
     ap.add_argument("--trunk-layers", type=int, default=0, help="also measure MPN_TRAIN_TRUNK(k) (9: conv3_1 and up, the reference's configuration)")
     ap.add_argument("--dropout", type=float, default=0.0, help="dropout rate behind fc6 / fc7 (0.5: the reference's default; 0: none)")
     ap.add_argument("--integral", type=int, default=1, help="K classifiers of the integral loss, trained in turn (6: the reference's scripts; 1: the plain head)")
+    ap.add_argument("--model", choices=("vgg", "mpnet"), default="vgg", help="mpnet: the tower training of a MultiPathNet handle (mpn_mpnet_train_*)")
     a = ap.parse_args()
     import torch
     from multipathnet_amd import _lib, models
     assert torch.cuda.is_available(), "bench_train needs a HIP device"
+    if a.model == "mpnet":
+        return bench_mpnet(a)
     P = models.synthetic_params(seed=557)
     C_ = P["cls_w"].shape[0]
     if a.integral > 1:
