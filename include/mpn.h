@@ -449,7 +449,9 @@ int mpn_resnet_create(const mpn_frcnn_config *cfg, const mpn_resnet_weights *rw,
  * layer follows its rule in every launch: the tiles a split-K or tail-split launch finishes in the reduce kernel give 0 as well.
  * The trunk's ceil-mode 2x2 max-pool, fused into a convolution or on its own: the NaNs of a window are ignored, a window holding only
  * NaN gives -inf (v > m from -inf, the CPU oracle's rule) in every kernel that pools: the graph's max-pools and the ROI poolings of both
- * dtypes follow the same rule (the bf16 ROI pooling on the order-preserving int16 image of the map encodes a NaN as -inf).  An EMPTY ROI bin
+ * dtypes follow the same rule (the bf16 ROI pooling on the order-preserving int16 image of the map encodes a NaN as -inf; the range-max
+ * tables the MultiPathNet towers pool through drop a NaN on either side of every comparison, so they give what the direct kernel gives; a bin
+ * that holds nothing above -inf reports arg-max -1, as an empty one does).  An EMPTY ROI bin
  * gives 0.  The sign of a zero maximum is not specified: a window holding both zeros gives the zero met first (row-major) in the kernels that
  * compare floats and +0 in the bf16 ROI pooling on the int16 image and its fused max-pool. */
 typedef struct mpn_graph_op {

@@ -144,7 +144,11 @@ int c8p_to_pixel_major(Act feat, float *d_pm, hipStream_t s);
 int roi_pool_pm(Act feat, const float *d_pm, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr,
                 float *d_x_c8, hipStream_t s, int roi_stride = 5, int Mp = 0, LevelStack lv = LevelStack{0, 0});
 // vertical range-max tables of a C8P map (levels 1..vmax_levels_for(H), each feat.elems() floats) and the ROI max-pool that
-// reads them: identical output to roi_pool_c8 (no argmax), cost 2 x bin-width reads per bin instead of bin-height x bin-width
+// reads them: identical output to roi_pool_c8 (no argmax), cost 2 x bin-width reads per bin instead of bin-height x bin-width.
+// On maps that hold NaN too: the builders' select drops a NaN on either side ((b > a || a != a) ? b : a), so a table entry is NaN only
+// when its whole row range is, and the readers compare each of their two table values with the running maximum (`v > m`, as the direct
+// kernel), so a bin ignores its NaNs.  (A plain b > a ? b : a kept a NaN `a`: a NaN at the head of a row range then hid the rest of it.)
+// NaN-free maps pool to the same bits either way, the sign of a zero maximum included.
 int vmax_levels_for(int H);
 int build_vmax_tables(Act feat, float *d_tables, hipStream_t s);
 int roi_pool_c8_rmq(Act feat, const float *d_tables, const float *d_rois, int N, int PH, int PW, float scale, RoiRule rr, float *d_x_c8, hipStream_t s, int roi_stride = 5, int Mp = 0);

@@ -2433,7 +2433,7 @@ __global__ void vmax_level_kernel(const float *__restrict__ prev, float *__restr
   if (y + step < H) {
     const f32x4 b = *reinterpret_cast<const f32x4 *>(prev + base + ((size_t)(y + step + 1) * Wp + x + 1) * 8);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] = b[e] > a[e] ? b[e] : a[e];
+    for (int e = 0; e < 4; ++e) a[e] = (b[e] > a[e] || a[e] != a[e]) ? b[e] : a[e];  // a NaN on either side loses
   }
   *reinterpret_cast<f32x4 *>(out + o) = a;
 }
@@ -2492,8 +2492,8 @@ __global__ __launch_bounds__(256) void roi_pool_c8_rmq_kernel(const float *__res
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = b[j][e] > a[j][e] ? b[j][e] : a[j][e];
-          if (v > m[e]) m[e] = v;
+          if (a[j][e] > m[e]) m[e] = a[j][e];  // (each against m: a NaN on either side loses, as in the direct kernel)
+          if (b[j][e] > m[e]) m[e] = b[j][e];
         }
     }
   }
@@ -2623,7 +2623,7 @@ __global__ void vmax_level_pm_kernel(const f32x4 *__restrict__ prev, f32x4 *__re
   if (y + step < H) {
     const f32x4 b = prev[t + (size_t)step * row];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] = b[e] > a[e] ? b[e] : a[e];
+    for (int e = 0; e < 4; ++e) a[e] = (b[e] > a[e] || a[e] != a[e]) ? b[e] : a[e];  // a NaN on either side loses
   }
   out[t] = a;
 }
@@ -2690,8 +2690,8 @@ __global__ __launch_bounds__(256) void roi_pool_pm_rmq_kernel(const float *__res
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float v = b[j][e] > a[j][e] ? b[j][e] : a[j][e];
-            if (v > m[e]) m[e] = v;
+            if (a[j][e] > m[e]) m[e] = a[j][e];  // (each against m: a NaN on either side loses, as in the direct kernel)
+            if (b[j][e] > m[e]) m[e] = b[j][e];
           }
       }
     }
@@ -3144,6 +3144,113 @@ extern "C" int mpn_debug_conv3x3_form(const float *d_x, int Cin, int H, int W, c
   if (wpk) (void)hipFree(wpk);
   if (bpk) (void)hipFree(bpk);
   if (wx) (void)hipFree(wx);
+  return rc;
+}
+
+// tests/test_gpu_roi_pool_numerics.py (debug flavour only): the trunk-side ROI poolings and the L2 normalisation one form at a time, on raw
+// device pointers in the kernels' own layouts, through the product's host wrappers on the null stream.  Every caller-owned buffer comes with
+// its element count, and one smaller than its layout's footprint is refused before anything is launched (MPN_EINVAL).  Footprints: a C8P map
+// mpn_debug_act_elems(C, H, W) floats (with levels: (n_levels - 1) * level_stride more); the ROI table (N - 1) * roi_stride + 5; the C8 matrix
+// Cb * PH * PW * mp * 8 with mp = Mp, or lin_mp(N) for Mp = 0; the arg-max N * C * PH * PW; the scale vector mp.  The entries write into no
+// caller-owned buffer themselves: what the caller filled them with survives wherever the kernels do not store.  Range-max tables and
+// pixel-major copies are the entry's own.  Each sits between one map row of slack in front and one level plus a row and four pixels behind,
+// all of it holding FLT_MAX: a reader that leaves its window by a row, a few columns, a level or a 256-channel slice stays inside the
+// allocation and meets a value that wins.  Synchronous.
+static bool dbg_pool_short(const char *fn, const char *name, size_t have, size_t want) {
+  if (have >= want) return false;
+  set_error("%s: %s holds %zu elements, the launch's footprint is %zu", fn, name, have, want);
+  return true;
+}
+#define DBG_POOL_NEED(buf, have, want) do { if (dbg_pool_short(__func__, #buf, (size_t)(have), (size_t)(want))) return MPN_EINVAL; } while (0)
+
+// `levels` levels of `level` floats behind `front` floats of slack; *base = the first level
+static int dbg_pool_slab(size_t front, size_t level, int levels, size_t row, float **raw, float **base) {
+  const size_t n = front + level * (size_t)(levels + 1) + row;
+  MPN_CHECK_HIP(hipMalloc(raw, n * sizeof(float)));
+  hipLaunchKernelGGL(dbg_fill_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, *raw, n, 3.402823466e+38f);
+  MPN_CHECK_LAUNCH();
+  *base = *raw + front;
+  return MPN_OK;
+}
+
+// form 0: roi_pool_c8 (d_argmax optional; n_levels > 0: a LevelStack of maps level_stride floats apart)
+// form 1: build_vmax_tables + roi_pool_c8_rmq
+// form 2: c8p_to_pixel_major (of every level) + roi_pool_pm (n_levels as form 0)
+// form 3: build_vmax_tables_pm + roi_pool_pm_rmq: normalize 0 (then mul_const_c8 by mul), normalize 1 in place, or normalize 1 with d_scale_out
+extern "C" int mpn_debug_roi_pool_form(int form, const float *d_feat_c8p, size_t feat_elems, int C, int H, int W, int n_levels, size_t level_stride,
+                                       const float *d_rois, size_t rois_elems, int roi_stride, int N, int PH, int PW, float scale, int bin_rule, int Mp,
+                                       int normalize, float mul, float *d_x_c8, size_t x_elems, int32_t *d_argmax, size_t argmax_elems,
+                                       float *d_scale_out, size_t scale_elems) {
+  MPN_CHECK_ARG(form >= 0 && form <= 3 && d_feat_c8p && d_rois && d_x_c8 && C > 0 && H > 0 && W > 0 && N > 0 && PH > 0 && PW > 0);
+  MPN_CHECK_ARG(roi_stride >= 5 && n_levels >= 0 && (bin_rule == 0 || bin_rule == 1) && (Mp == 0 || Mp >= N));
+  MPN_CHECK_ARG(n_levels == 0 || form == 0 || form == 2);
+  MPN_CHECK_ARG(!d_argmax || form == 0);
+  MPN_CHECK_ARG(form == 3 ? ((normalize == 0 || normalize == 1) && (!d_scale_out || normalize == 1)) : (normalize == 0 && mul == 1.0f && !d_scale_out));
+  const size_t ae = act_bytes(C, H, W) / sizeof(float);
+  MPN_CHECK_ARG(n_levels == 0 || (level_stride >= ae && level_stride % 4 == 0));
+  const int mp = Mp > 0 ? Mp : lin_mp(N), Cb = (C + 7) / 8, PP = PH * PW;
+  DBG_POOL_NEED(d_feat_c8p, feat_elems, ae + (n_levels > 0 ? (size_t)(n_levels - 1) * level_stride : 0));
+  DBG_POOL_NEED(d_rois, rois_elems, (size_t)(N - 1) * roi_stride + 5);
+  DBG_POOL_NEED(d_x_c8, x_elems, (size_t)Cb * PP * mp * 8);
+  if (d_argmax) DBG_POOL_NEED(d_argmax, argmax_elems, (size_t)N * C * PP);
+  if (d_scale_out) DBG_POOL_NEED(d_scale_out, scale_elems, (size_t)mp);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  const RoiRule rr{1.0f, 0, bin_rule};
+  const Act a = make_act(const_cast<float *>(d_feat_c8p), C, H, W);
+  const LevelStack lv{level_stride, n_levels};
+  const int L = vmax_levels_for(H);
+  const size_t pe = pixel_major_elems(a), pm_row = (size_t)W * Cb * 8;
+  float *raw = nullptr, *own = nullptr;
+  int rc = MPN_OK;
+  if (form == 0) {
+    rc = roi_pool_c8(a, d_rois, N, PH, PW, scale, rr, d_x_c8, d_argmax, nullptr, roi_stride, Mp, lv);
+  } else if (form == 1) {
+    rc = dbg_pool_slab((size_t)a.Wp * 8, ae, L, (size_t)a.Wp * 8, &raw, &own);
+    if (rc == MPN_OK) rc = build_vmax_tables(a, own, nullptr);
+    if (rc == MPN_OK) rc = roi_pool_c8_rmq(a, own, d_rois, N, PH, PW, scale, rr, d_x_c8, nullptr, roi_stride, Mp);
+  } else if (form == 2) {
+    const int nl = n_levels > 0 ? n_levels : 1;
+    rc = dbg_pool_slab(pm_row, pe, nl, pm_row + (size_t)32 * Cb, &raw, &own);
+    for (int l = 0; l < nl && rc == MPN_OK; ++l)
+      rc = c8p_to_pixel_major(make_act(const_cast<float *>(d_feat_c8p) + (size_t)l * level_stride, C, H, W), own + (size_t)l * pe, nullptr);
+    if (rc == MPN_OK) rc = roi_pool_pm(a, own, d_rois, N, PH, PW, scale, rr, d_x_c8, nullptr, roi_stride, Mp, LevelStack{pe, n_levels});
+  } else {
+    rc = dbg_pool_slab(pm_row, pe, L + 1, pm_row + (size_t)32 * Cb, &raw, &own);
+    if (rc == MPN_OK) rc = build_vmax_tables_pm(a, own, nullptr);
+    if (rc == MPN_OK) rc = roi_pool_pm_rmq(a, own, d_rois, N, PH, PW, scale, rr, d_x_c8, nullptr, roi_stride, Mp, normalize, mul, d_scale_out);
+  }
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  if (raw) (void)hipFree(raw);
+  return rc;
+}
+
+// the range-max levels as the builders write them: pm = 0 the C8P levels 1 .. L (mpn_debug_act_elems floats each), pm = 1 the pixel-major
+// levels 0 .. L (H * W * Cb * 8 floats each), L = the number of k >= 1 with 2^k <= H
+extern "C" int mpn_debug_vmax_tables(int pm, const float *d_feat_c8p, size_t feat_elems, int C, int H, int W, float *d_tables_out, size_t tables_elems) {
+  MPN_CHECK_ARG((pm == 0 || pm == 1) && d_feat_c8p && d_tables_out && C > 0 && H > 0 && W > 0);
+  const size_t ae = act_bytes(C, H, W) / sizeof(float);
+  const Act a = make_act(const_cast<float *>(d_feat_c8p), C, H, W);
+  const int L = vmax_levels_for(H), Cb = (C + 7) / 8;
+  const size_t pe = pixel_major_elems(a), pm_row = (size_t)W * Cb * 8, n_out = pm ? pe * (size_t)(L + 1) : ae * (size_t)L;
+  DBG_POOL_NEED(d_feat_c8p, feat_elems, ae);
+  DBG_POOL_NEED(d_tables_out, tables_elems, n_out);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  float *raw = nullptr, *own = nullptr;
+  int rc = pm ? dbg_pool_slab(pm_row, pe, L + 1, pm_row + (size_t)32 * Cb, &raw, &own) : dbg_pool_slab((size_t)a.Wp * 8, ae, L, (size_t)a.Wp * 8, &raw, &own);
+  if (rc == MPN_OK) rc = pm ? build_vmax_tables_pm(a, own, nullptr) : build_vmax_tables(a, own, nullptr);
+  if (rc == MPN_OK && n_out) MPN_CHECK_HIP(hipMemcpy(d_tables_out, own, n_out * sizeof(float), hipMemcpyDeviceToDevice));
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  if (raw) (void)hipFree(raw);
+  return rc;
+}
+
+// l2norm_scale_c8 (normalize = 1) or mul_const_c8 (normalize = 0) in place on n_records records of a C8 matrix of row pitch Mp
+extern "C" int mpn_debug_l2norm_c8(float *d_x_c8, size_t x_elems, int n_records, int Mp, int N, float mul, int normalize) {
+  MPN_CHECK_ARG(d_x_c8 && n_records > 0 && N > 0 && Mp >= N && (normalize == 0 || normalize == 1));
+  DBG_POOL_NEED(d_x_c8, x_elems, (size_t)n_records * Mp * 8);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
+  const int rc = normalize ? l2norm_scale_c8(d_x_c8, n_records, Mp, N, mul, nullptr) : mul_const_c8(d_x_c8, n_records, Mp, N, mul, nullptr);
+  MPN_CHECK_HIP(hipDeviceSynchronize());
   return rc;
 }
 
