@@ -845,6 +845,55 @@ int mpn_mpnet_get_tower_weights(mpn_frcnn *p, int t, float *d_mix_w, float *d_mi
                                 float *d_fc7_b, void *stream);
 int mpn_mpnet_get_head_weights(mpn_frcnn *p, float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
 
+/* Drawing a training minibatch's rows on the device: DataSetCOCO:attachProposals with its crowd branch
+ * (DataSetJSON.lua:280-390) and BatchProviderROI's setupOne + selectBBoxesOne (BatchProviderROI.lua:39-49, 98-101) for ONE image — what
+ * lies between an image's proposals and mpn_frcnn_train_add / mpn_mpnet_train_add.  One launch each, no atomics, every order fixed:
+ * the same inputs, seed and draw give the same bits.  Boxes are (x1, y1, x2, y2) in the image's own coordinates; inputs are NaN-free.
+ *   mpn_attach_proposals   rows = [gt ; proposals], m = g + n.  Per row, over the g GT boxes in order, utils.boxoverlap in fp32 in the
+ *                          reference's operation order (w = x2 - x1 + 1, h = y2 - y1 + 1, inter = w * h, o = inter / (aarea + barea - inter),
+ *                          o = 0 where w < 0 or h < 0): d_overlap = the maximum, d_corr = the FIRST maximum's 1-based index (0 where the
+ *                          maximum is 0), d_label = d_gt_labels[corr - 1] (0 without one).  Then the crowd branch: utils.intersection =
+ *                          inter / aarea over the n_crowd crowd boxes — WITHOUT the w < 0 / h < 0 zeroing, as utils.lua:131-148 writes it,
+ *                          so a box off a crowd's corner (both negative) has a positive value —; a row >= g whose maximum over the crowds
+ *                          is > 0.7f gets d_overlap = -1 (neither foreground nor background); GT rows are never masked; d_corr and
+ *                          d_label stay as they are.  Outputs d_boxes [m,4], d_overlap [m], d_corr [m], d_label [m].  g == 0 is legal
+ *                          (every overlap 0); a pointer may be NULL only where its count is 0; g + n <= 2^28.
+ *   mpn_sample_rois        foreground = overlap >= fg_threshold, background = bg_lo <= overlap < bg_hi, each list in ascending row order;
+ *                          d_counts[2] = (n_bg, n_fg).  fg_num = (int)(fg_fraction * batch_size) in double, bg_num = batch_size - fg_num;
+ *                          r_bg = min(bg_num, n_bg) and r_fg = min(fg_num, n_fg) draws WITH replacement.  Draw i of set s (0 background,
+ *                          1 foreground): word 0 of Philox4x32-10 with
+ *                            key     = (seed & 0xffffffff, seed >> 32)
+ *                            counter = (i, draw & 0xffffffff, 0x80000000 + s, draw >> 32)
+ *                          (the high bit of counter word 2 keeps the stream apart from the dropout masks' under the same seed), mapped to
+ *                          list index (uint64(word) * count) >> 32.  Rows 0 .. r_bg - 1 are the background draws, then r_fg foreground
+ *                          ones: d_rois = the row's box, d_gt = zeros on background rows and d_boxes[corr - 1] on foreground ones,
+ *                          d_labels = 0 / the row's label.  flip_width > 0: both tables through mpn_flip_boxes' formula at that width
+ *                          (zeros included).  Nothing past row r = r_bg + r_fg <= batch_size is written.  m > 0.
+ *   mpn_frcnn_train_add_sampled / mpn_mpnet_train_add_sampled   attach + sample into buffers of the training state, read the two counts
+ *                          back into h_counts (a HOST pointer; one stream synchronisation), then: n_bg == 0 or n_fg == 0 adds NOTHING and
+ *                          returns MPN_OK — the caller draws another image —; pending + r > max_rois returns MPN_EINVAL and changes nothing;
+ *                          otherwise exactly mpn_frcnn_train_add / mpn_mpnet_train_add of the r rows, with flip != 0 on the mirrored image
+ *                          (mpn_image_hflip) and the boxes flipped at width W.  The flip decision is the caller's.
+ * MPN_EINVAL, named in mpn_last_error, before any launch: a NULL required pointer or a NULL pointer with a positive count; n, g or
+ * n_crowd < 0; g + n == 0; batch_size <= 0; fg_fraction not a finite number in [0, 1]; a threshold that is not finite; bg_lo > bg_hi.
+ * Not here: dataset / JSON loading, sampleAroundGTBoxes, the scale / aspect jitter of getImages, bbox regression statistics, and the
+ * choice of the images of a minibatch. */
+typedef struct { int batch_size; double fg_fraction; float fg_threshold, bg_lo, bg_hi; } mpn_roi_sampler;
+int mpn_attach_proposals(const float *d_proposals /*[n,4]*/, int n, const float *d_gt /*[g,4]*/, const int *d_gt_labels /*[g]*/, int g,
+                         const float *d_crowds /*[n_crowd,4]*/, int n_crowd,
+                         float *d_boxes /*[g+n,4]*/, float *d_overlap /*[g+n]*/, int *d_corr /*[g+n]*/, int *d_label /*[g+n]*/, void *stream);
+int mpn_sample_rois(const float *d_boxes, const float *d_overlap, const int *d_corr, const int *d_label, int m,
+                    const mpn_roi_sampler *cfg, uint64_t seed, uint64_t draw, int flip_width,
+                    float *d_rois /*[batch_size,4]*/, float *d_gt /*[batch_size,4]*/, int *d_labels /*[batch_size]*/, int *d_counts /*[2]: n_bg, n_fg*/, void *stream);
+int mpn_frcnn_train_add_sampled(mpn_frcnn *p, const float *d_image, int H, int W,
+                                const float *d_proposals, int n, const float *d_gt, const int *d_gt_labels, int g,
+                                const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                                uint64_t seed, uint64_t draw, int flip, int *h_counts /*[2]: n_bg, n_fg*/, void *stream);
+int mpn_mpnet_train_add_sampled(mpn_frcnn *p, const float *d_image, int H, int W,
+                                const float *d_proposals, int n, const float *d_gt, const int *d_gt_labels, int g,
+                                const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                                uint64_t seed, uint64_t draw, int flip, int *h_counts /*[2]: n_bg, n_fg*/, void *stream);
+
 /* Captured launch graphs.  The kernel chains of the per-image path — the head (transform .. decode) and the tail (per-class NMS,
  * voting, top-k) of mpn_frcnn_test_one / _pipelined / _pipelined_host, and the bodies of mpn_frcnn_shard_head / _shard_nms /
  * _shard_finish — are captured with hipStreamBeginCapture once per (buffer pointers, H, W, N) and replayed with hipGraphLaunch: one host

@@ -72,6 +72,11 @@ class GraphWeights(C.Structure):
                 ("out_tensor", C.c_int), ("bf16", C.c_int), ("n_heads", C.c_int), ("head_region", C.c_int * 8), ("n_integral", C.c_int)]
 
 
+class RoiSamplerCfg(C.Structure):
+    """mirror of mpn_roi_sampler (include/mpn.h)"""
+    _fields_ = [("batch_size", C.c_int), ("fg_fraction", C.c_double), ("fg_threshold", C.c_float), ("bg_lo", C.c_float), ("bg_hi", C.c_float)]
+
+
 def lib_path():
     return _LIB_PATH
 
@@ -119,6 +124,13 @@ def load(flavour=None):
     lib.mpn_frcnn_train_set_head.argtypes = [C.c_void_p, C.c_int]
     lib.mpn_mpnet_train_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_long]
     lib.mpn_mpnet_train_set_head.argtypes = [C.c_void_p, C.c_int]
+    # the minibatch sampler (include/mpn.h): 64-bit seed / draw, the configuration by pointer, the two counts through a HOST int[2]
+    vp, cfgp = C.c_void_p, C.POINTER(RoiSamplerCfg)
+    lib.mpn_attach_proposals.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.mpn_sample_rois.argtypes = [vp, vp, vp, vp, C.c_int, cfgp, C.c_uint64, C.c_uint64, C.c_int, vp, vp, vp, vp, vp]
+    for fn in (lib.mpn_frcnn_train_add_sampled, lib.mpn_mpnet_train_add_sampled):
+        fn.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, cfgp, C.c_uint64, C.c_uint64, C.c_int,
+                       C.POINTER(C.c_int), vp]
     _libs[fl] = lib
     return lib
 

@@ -651,9 +651,7 @@ __global__ void image_hflip_kernel(const float *__restrict__ in, size_t rows, in
   out[t] = in[r * W + (W - 1 - x)];
 }
 
-// utils.flipBoxes (utils.lua:151-155) in its operation order, each step rounded to fp32: x1' = ((-x2) + W) + 1, x2' = ((-x1) + W) + 1
-__device__ __forceinline__ float flip_x(float x, float im_w) { return __fadd_rn(__fadd_rn(-x, im_w), 1.0f); }
-
+// utils.flipBoxes (utils.lua:151-155): flip_x (mpn_internal.h) on both corners
 __global__ void flip_boxes_kernel(const float *__restrict__ boxes, int n, float im_w, float *__restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

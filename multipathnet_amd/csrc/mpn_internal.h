@@ -165,6 +165,10 @@ __device__ __forceinline__ float iou_plus1(float ax1, float ay1, float ax2, floa
   return (w <= 0.0f || h <= 0.0f) ? 0.0f : iou;
 }
 
+// utils.flipBoxes (utils.lua:151-155) in its operation order, each step rounded to fp32: x1' = ((-x2) + W) + 1, x2' = ((-x1) + W) + 1
+// (mpn_flip_boxes and the ROI sampler's flipped gather)
+__device__ __forceinline__ float flip_x(float x, float im_w) { return __fadd_rn(__fadd_rn(-x, im_w), 1.0f); }
+
 // ---- inn.ROIPooling's window and bins, both conventions (include/mpn.h: MPN_ROI_BINS_*; the oracle's orc_roi_pool) -------------------
 // bins = 0, the CUDA kernel's rule (Fast R-CNN):  start = round((x1 - off) * scale), end = round((x2 - off) * scale) + end_adjust, window forced
 //   >= 1 x 1, bin p = [floor(p * size / P), ceil((p + 1) * size / P)) with the fp32 bin size, offset by the start, THEN clipped to the map

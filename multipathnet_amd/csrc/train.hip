@@ -18,6 +18,7 @@
 #include "train.h"
 
 #include "dense.h"
+#include "philox.h"
 
 namespace mpn {
 
@@ -544,18 +545,7 @@ int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Dropout behind fc6 / fc7 (the reference's default, train.lua:53 train_remove_dropouts = false)
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11; Random123's known answers): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped between rounds
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += W0; k1 += W1;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// (Philox4x32-10: philox.h, shared with the ROI sampler's draws)
 // One thread = one record: row m < B of chunk q < ceil(N/8), i.e. columns 8q .. 8q + 7 = the Philox column groups 2q and 2q + 1.
 // Threads run along m first: a wave reads and writes 2 KiB contiguous.
 __global__ __launch_bounds__(256) void dropout_c8_kernel(float *__restrict__ y, int Mp, int B, int N, int nq, DropoutCfg c) {

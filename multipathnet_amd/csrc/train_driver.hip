@@ -8,7 +8,30 @@
 #include <vector>
 
 #include "pipeline.h"
+#include "sampler.h"
 #include "train.h"
+
+// What *_train_add_sampled draws an image's rows into (sampler.h): the attach_proposals record of the image
+// ([m] rows, regrown for the largest image seen), the sampler's two row lists, and the sampled rows the add then reads — sized at
+// train_begin for max_rois rows and regrown for a larger batch_size (the overflow is refused only once the counts are known).  The
+// mirrored image of a flipped add lives here too.  All slots of the training state's DeviceOwner.
+struct SampleBufs {
+  float *boxes = nullptr, *overlap = nullptr;      // the record
+  int *corr = nullptr, *label = nullptr, *lists = nullptr;
+  size_t boxes_b = 0, overlap_b = 0, corr_b = 0, label_b = 0, lists_b = 0;
+  float *rois = nullptr, *gt = nullptr;            // the sampled rows
+  int *labels = nullptr, *counts = nullptr;
+  size_t rois_b = 0, gt_b = 0, labels_b = 0, counts_b = 0;
+  float *flipped = nullptr;                        // the mirrored image [3, H, W]
+  size_t flipped_b = 0;
+};
+// train_begin's part: the sampled-row buffers for max_rois rows and the two counts.  Plain allocations — the allocation generation is
+// not bumped, so a launch graph captured before training is still replayed after it.
+static bool alloc_sample_rows(SampleBufs &b, DeviceOwner &own, size_t rows) {
+  b.rois_b = b.gt_b = rows * 4 * sizeof(float); b.labels_b = rows * sizeof(int); b.counts_b = 2 * sizeof(int);
+  return own.alloc_slot(&b.rois, b.rois_b) == MPN_OK && own.alloc_slot(&b.gt, b.gt_b) == MPN_OK &&
+         own.alloc_slot(&b.labels, b.labels_b) == MPN_OK && own.alloc_slot(&b.counts, b.counts_b) == MPN_OK;
+}
 
 // The training state of a handle: exists between train_begin and train_end
 struct TrainState {
@@ -52,6 +75,7 @@ struct TrainState {
   int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
   int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // final map size, row range
   int img_nh[MPN_TRAIN_MAX_IMAGES] = {}, img_nw[MPN_TRAIN_MAX_IMAGES] = {};  // network-input size (every layer's map size follows from it)
+  SampleBufs smp;                      // mpn_frcnn_train_add_sampled's record and sampled rows
   DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
 };
 using LinT = TrainState::LinT;
@@ -82,6 +106,7 @@ struct TowerTrainState {
   float drop_rate = 0.f, drop_scale = 1.f;       // as TrainState's; the layer word of tower t is 2 t (behind fc6), 2 t + 1 (behind fc7)
   uint32_t drop_threshold = 0;
   long seed = 0, step = 0;
+  SampleBufs smp;                                // mpn_mpnet_train_add_sampled's record and sampled rows
   DeviceOwner own;
 };
 using TowT = TowerTrainState::TowT;
@@ -218,6 +243,7 @@ static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
   for (int i = 1; i >= 3 - t->n_fc; --i) ok = ok && trained(t->fc[i]);
   ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
   ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
+  ok = ok && alloc_sample_rows(t->smp, t->own, M);
   if (!k) return ok;
   ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
   ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
@@ -273,6 +299,90 @@ extern "C" int mpn_frcnn_train_end(mpn_frcnn *p) {
   return MPN_OK;
 }
 
+// ---- drawing an image's rows on the device (*_train_add_sampled; sampler.h) ----
+// the sampled-row buffers for `rows` rows (train_begin made them for max_rois rows; a larger batch_size regrows them)
+static int grow_sample_rows(SampleBufs &b, DeviceOwner &own, size_t rows, hipStream_t s) {
+  int rc = own.grow(&b.rois, &b.rois_b, rows * 4 * sizeof(float), s);
+  if (rc == MPN_OK) rc = own.grow(&b.gt, &b.gt_b, rows * 4 * sizeof(float), s);
+  if (rc == MPN_OK) rc = own.grow(&b.labels, &b.labels_b, rows * sizeof(int), s);
+  return rc;
+}
+
+// The refusals of the sampled entry points' own arguments (the handle's state has been checked), before any launch
+static int check_sampled_args(const char *fn, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
+                              const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg, const int *h_counts) {
+  if (!d_image || !h_counts || H0 <= 0 || W0 <= 0) {
+    set_error("%s: invalid argument: %s", fn, !d_image ? "d_image is NULL" : !h_counts ? "h_counts is NULL" : "H <= 0 or W <= 0");
+    return MPN_EINVAL;
+  }
+  int rc = check_attach_args(fn, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd);
+  if (rc == MPN_OK) rc = check_sampler_cfg(fn, cfg, 0);
+  return rc;
+}
+
+// Attach and sample one image into b (both launches on s), then the two counts back into h_counts: one stream synchronisation, after
+// which the caller knows how many rows the image gives before the trunk runs.  flip_width > 0: the sampled boxes flipped at that width.
+static int sample_image(SampleBufs &b, DeviceOwner &own, const float *d_proposals, int n, const float *d_gt, const int *d_gt_labels, int g,
+                        const float *d_crowds, int n_crowd, const mpn_roi_sampler &cfg, uint64_t seed, uint64_t draw, int flip_width,
+                        int *h_counts, hipStream_t s) {
+  const size_t m = (size_t)g + n;
+  int rc = grow_sample_rows(b, own, std::min((size_t)cfg.batch_size, 2 * m), s);  // r_bg <= n_bg <= m, r_fg <= n_fg <= m
+  if (rc == MPN_OK) rc = own.grow(&b.boxes, &b.boxes_b, m * 4 * sizeof(float), s);
+  if (rc == MPN_OK) rc = own.grow(&b.overlap, &b.overlap_b, m * sizeof(float), s);
+  if (rc == MPN_OK) rc = own.grow(&b.corr, &b.corr_b, m * sizeof(int), s);
+  if (rc == MPN_OK) rc = own.grow(&b.label, &b.label_b, m * sizeof(int), s);
+  if (rc == MPN_OK) rc = own.grow(&b.lists, &b.lists_b, 2 * m * sizeof(int), s);
+  if (rc == MPN_OK) rc = attach_proposals(d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, b.boxes, b.overlap, b.corr, b.label, s);
+  if (rc == MPN_OK) rc = roi_sample(b.boxes, b.overlap, b.corr, b.label, (int)m, cfg, seed, draw, flip_width, b.lists, b.rois, b.gt, b.labels, b.counts, s);
+  if (rc) return rc;
+  MPN_CHECK_HIP(hipMemcpyAsync(h_counts, b.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+  MPN_CHECK_HIP(hipStreamSynchronize(s));
+  return MPN_OK;
+}
+
+// rows the sampler wrote for these counts, both >= 1: r_bg + r_fg >= 1, as batch_size >= 1 gives one of the two sets a quota
+static int sampled_rows(const mpn_roi_sampler &cfg, const int *counts) {
+  const int fg_num = sampler_fg_num(cfg);
+  return std::min(cfg.batch_size - fg_num, counts[0]) + std::min(fg_num, counts[1]);
+}
+
+// the image of a flipped add: mpn_image_hflip's kernel into the state's own buffer
+static int flip_train_image(SampleBufs &b, DeviceOwner &own, const float *d_image, int H0, int W0, hipStream_t s, const float **d_out) {
+  int rc = own.grow(&b.flipped, &b.flipped_b, (size_t)3 * H0 * W0 * sizeof(float), s);
+  if (rc == MPN_OK) rc = mpn_image_hflip(d_image, 3, H0, W0, b.flipped, s);
+  *d_out = b.flipped;
+  return rc;
+}
+
+// What one more image of n rows behind `pending` must satisfy (the four *_train_add* entry points, under the caller's name `fn`), and
+// getImages' size
+static int add_check(const mpn_frcnn *p, int pending, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
+  const mpn_frcnn_config &c = p->cfg;
+  if (pending + n > c.max_rois) {
+    set_error("%s: %d pending rows + %d exceed the handle's max_rois (%d)", fn, pending, n, c.max_rois);
+    return MPN_EINVAL;
+  }
+  *sc = 1.0; *H = H0; *W = W0;
+  if (c.scale_target > 0.0) *sc = getimages_size(H0, W0, c.scale_target, c.scale_max, H, W);
+  if (*H <= 0 || *W <= 0 || *H > c.max_h || *W > c.max_w) {
+    set_error("%s: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", fn, H0, W0, *H, *W, c.max_h, c.max_w);
+    return MPN_EINVAL;
+  }
+  return MPN_OK;
+}
+static int frcnn_add_check(const mpn_frcnn *p, const TrainState *t, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
+  const int rc = add_check(p, t->pending, fn, H0, W0, n, sc, H, W);
+  if (rc) return rc;
+  if (t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
+    set_error("%s: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", fn, t->n_img, MPN_TRAIN_MAX_IMAGES);
+    return MPN_EINVAL;
+  }
+  return MPN_OK;
+}
+
+static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
+                          const float *d_gt, const int *d_labels, int n, hipStream_t s);
+
 extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
                                    const int *d_labels, int n, void *stream) {
   MPN_CHECK_ARG(p != nullptr);
@@ -281,24 +391,42 @@ extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, i
   TrainState *t = p->train;
   if (!t) { set_error("mpn_frcnn_train_add: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
   MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
-  const mpn_frcnn_config &c = p->cfg;
-  if (t->pending + n > c.max_rois) {
-    set_error("mpn_frcnn_train_add: %d pending rows + %d exceed the handle's max_rois (%d)", t->pending, n, c.max_rois);
-    return MPN_EINVAL;
-  }
-  double sc = 1.0;
-  int H = H0, W = W0;
-  if (c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
-  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
-    set_error("mpn_frcnn_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
-    return MPN_EINVAL;
-  }
-  if (t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
-    set_error("mpn_frcnn_train_add: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", t->n_img, MPN_TRAIN_MAX_IMAGES);
-    return MPN_EINVAL;
-  }
+  double sc;
+  int H, W;
+  if ((rc = frcnn_add_check(p, t, "mpn_frcnn_train_add", H0, W0, n, &sc, &H, &W)) != MPN_OK) return rc;
+  ScratchScope scratch_scope(&p->scratch);
+  return frcnn_add_rows(p, t, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, as_stream(stream));
+}
+
+extern "C" int mpn_frcnn_train_add_sampled(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
+                                           const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                                           uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
+  const char *fn = "mpn_frcnn_train_add_sampled";
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_train(p, fn);
+  if (rc) return rc;
+  TrainState *t = p->train;
+  if (!t) { set_error("%s: no mpn_frcnn_train_begin on this handle", fn); return MPN_ESTATE; }
+  if ((rc = check_sampled_args(fn, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, h_counts)) != MPN_OK) return rc;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
+  rc = sample_image(t->smp, t->own, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, *cfg, seed, draw, flip ? W0 : 0, h_counts, s);
+  if (rc) return rc;
+  if (h_counts[0] == 0 || h_counts[1] == 0) return MPN_OK;  // no background or no foreground: nothing is added, the caller draws another image
+  const int r = sampled_rows(*cfg, h_counts);
+  double sc;
+  int H, W;
+  if ((rc = frcnn_add_check(p, t, fn, H0, W0, r, &sc, &H, &W)) != MPN_OK) return rc;
+  if (flip && (rc = flip_train_image(t->smp, t->own, d_image, H0, W0, s, &d_image)) != MPN_OK) return rc;
+  return frcnn_add_rows(p, t, d_image, H0, W0, H, W, sc, t->smp.rois, t->smp.gt, t->smp.labels, r, s);
+}
+
+// The body of mpn_frcnn_train_add on device row pointers, everything checked: the frozen trunk, the ROI pooling of these rows behind the
+// pending ones, what the conv block's backward pass reads, the rows' copies
+static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
+                          const float *d_gt, const int *d_labels, int n, hipStream_t s) {
+  const mpn_frcnn_config &c = p->cfg;
+  int rc = MPN_OK;
   p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers and the ROI table are rewritten: the next head segment runs for real
   Act feat;
   bool pools = false;  // a pooled layer among the trained ones (MPN_TRAIN_TRUNK): this trunk pass also writes their pre-pool maps
@@ -670,6 +798,7 @@ static bool alloc_tower_train_state(const mpn_frcnn *p, TowerTrainState *t) {
   ok = ok && momentum(&t->v_cls, &t->vb_cls, (T - 1) * F, KC) && momentum(&t->v_bbox, &t->vb_bbox, F, 4 * C);
   ok = ok && alloc0(&t->part, part * sizeof(float));
   ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
+  ok = ok && alloc_sample_rows(t->smp, t->own, M);
   return ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
 }
 
@@ -707,6 +836,13 @@ static int tower_state(mpn_frcnn *p, const char *fn, TowerTrainState **t) {
   return MPN_ESTATE;
 }
 
+static int mpnet_add_check(const mpn_frcnn *p, const TowerTrainState *t, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
+  return add_check(p, t->pending, fn, H0, W0, n, sc, H, W);
+}
+
+static int mpnet_add_rows(mpn_frcnn *p, TowerTrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
+                          const float *d_gt, const int *d_labels, int n, hipStream_t s);
+
 extern "C" int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt, const int *d_labels,
                                    int n, void *stream) {
   MPN_CHECK_ARG(p != nullptr);
@@ -715,20 +851,41 @@ extern "C" int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H0, i
   TowerTrainState *t;
   if ((rc = tower_state(p, "mpn_mpnet_train_add", &t)) != MPN_OK) return rc;
   MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
-  const mpn_frcnn_config &c = p->cfg;
-  if (t->pending + n > c.max_rois) {
-    set_error("mpn_mpnet_train_add: %d pending rows + %d exceed the handle's max_rois (%d)", t->pending, n, c.max_rois);
-    return MPN_EINVAL;
-  }
-  double sc = 1.0;
-  int H = H0, W = W0;
-  if (c.scale_target > 0.0) sc = getimages_size(H0, W0, c.scale_target, c.scale_max, &H, &W);
-  if (H <= 0 || W <= 0 || H > c.max_h || W > c.max_w) {
-    set_error("mpn_mpnet_train_add: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", H0, W0, H, W, c.max_h, c.max_w);
-    return MPN_EINVAL;
-  }
+  double sc;
+  int H, W;
+  if ((rc = mpnet_add_check(p, t, "mpn_mpnet_train_add", H0, W0, n, &sc, &H, &W)) != MPN_OK) return rc;
+  ScratchScope scratch_scope(&p->scratch);
+  return mpnet_add_rows(p, t, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, as_stream(stream));
+}
+
+extern "C" int mpn_mpnet_train_add_sampled(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
+                                           const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                                           uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
+  const char *fn = "mpn_mpnet_train_add_sampled";
+  MPN_CHECK_ARG(p != nullptr);
+  int rc = refuse_tower_train(p, fn);
+  if (rc) return rc;
+  TowerTrainState *t;
+  if ((rc = tower_state(p, fn, &t)) != MPN_OK) return rc;
+  if ((rc = check_sampled_args(fn, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, h_counts)) != MPN_OK) return rc;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
+  rc = sample_image(t->smp, t->own, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, *cfg, seed, draw, flip ? W0 : 0, h_counts, s);
+  if (rc) return rc;
+  if (h_counts[0] == 0 || h_counts[1] == 0) return MPN_OK;  // no background or no foreground: nothing is added, the caller draws another image
+  const int r = sampled_rows(*cfg, h_counts);
+  double sc;
+  int H, W;
+  if ((rc = mpnet_add_check(p, t, fn, H0, W0, r, &sc, &H, &W)) != MPN_OK) return rc;
+  if (flip && (rc = flip_train_image(t->smp, t->own, d_image, H0, W0, s, &d_image)) != MPN_OK) return rc;
+  return mpnet_add_rows(p, t, d_image, H0, W0, H, W, sc, t->smp.rois, t->smp.gt, t->smp.labels, r, s);
+}
+
+// The body of mpn_mpnet_train_add on device row pointers, everything checked
+static int mpnet_add_rows(mpn_frcnn *p, TowerTrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
+                          const float *d_gt, const int *d_labels, int n, hipStream_t s) {
+  const mpn_frcnn_config &c = p->cfg;
+  int rc = MPN_OK;
   p->seg_shape[0][0] = -1;  // (as run_detect) the trunk's buffers, the ROI and Foveal tables are rewritten: the next head segment runs for real
   Act feat;
   rc = obtain_features(p, d_image, H0, W0, H, W, sc, &p->up, s, &feat);  // getImages' rescale + the frozen trunk, exactly as detect

@@ -921,6 +921,25 @@ class FastRCNN(object):
         check(self._lib.mpn_frcnn_train_add(self._h, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream()),
               "mpn_frcnn_train_add")
 
+    def _add_sampled(self, entry, image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes, flip):
+        from .train import _dev_f32, _dev_i32, _ptr
+        H, W = image.shape[1:]
+        prop, gtb, gtl = _dev_f32(proposals, (-1, 4)), _dev_f32(gt_boxes, (-1, 4)), _dev_i32(gt_labels)
+        crowds = None if crowd_boxes is None else _dev_f32(crowd_boxes, (-1, 4))
+        assert gtl.numel() == gtb.size(0)
+        cfg, counts = sampler.cfg(), (C.c_int * 2)()
+        check(getattr(self._lib, entry)(self._h, _f(image, "image"), H, W, _ptr(prop), prop.size(0), _ptr(gtb), _ptr(gtl), gtb.size(0), _ptr(crowds),
+                                        0 if crowds is None else crowds.size(0), C.byref(cfg), sampler.seed, int(draw) & 0xFFFFFFFFFFFFFFFF,
+                                        1 if flip else 0, counts, _stream()), entry)
+        return int(counts[0]), int(counts[1])
+
+    def train_add_sampled(self, image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes=None, flip=False):
+        """train_add with the rows drawn on the device (mpn_frcnn_train_add_sampled): attach_proposals (crowd_boxes:
+        the image's `iscrowd` regions) and `sampler` (a train.DeviceRoiSampler) under its seed and the caller's counter `draw`, then
+        train_add of those rows — with `flip` on the mirrored image and boxes.  image [3,H,W] on the device; the boxes may be numpy
+        arrays or tensors.  -> (n_bg, n_fg); where either is 0 NOTHING was added: draw another image."""
+        return self._add_sampled("mpn_frcnn_train_add_sampled", image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes, flip)
+
     def train_step(self, lr):
         """Head forward, loss, backward and the SGD update on the pending rows -> device tensor [2] = (cls loss, bbox loss)."""
         loss = torch.empty(2, dtype=torch.float32, device=self.device)
@@ -977,6 +996,10 @@ class FastRCNN(object):
         assert gt_boxes.shape == rois.shape and labels.numel() == n and labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
         check(self._lib.mpn_mpnet_train_add(self._h, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream()),
               "mpn_mpnet_train_add")
+
+    def tower_train_add_sampled(self, image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes=None, flip=False):
+        """train_add_sampled for the towers (mpn_mpnet_train_add_sampled): the same arguments -> (n_bg, n_fg)."""
+        return self._add_sampled("mpn_mpnet_train_add_sampled", image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes, flip)
 
     def tower_train_step(self, lr):
         """Forward, loss, backward and the SGD update of every tower and both heads on the pending rows -> device tensor [2] = (cls, bbox)."""

@@ -2,12 +2,16 @@
 statistics of their regression targets.  numpy / torch on the host, not on the per-image path; the per-step work — frozen trunk, ROI
 pooling, head forward, loss, backward, SGD — is models.FastRCNN.train_add / train_step on the device.
 
-  attach_proposals        DataSetJSON.lua:280-390  (DataSetCOCO:attachProposals, without the crowd and the sample-around-GT branches)
+  attach_proposals        DataSetJSON.lua:280-390  (DataSetCOCO:attachProposals with its crowd branch, without the sample-around-GT one)
   RoiSampler              BatchProviderROI.lua:39-49 (setupOne), BatchProviderBase.lua:54-107 (takeSubset, selectBBoxesOne)
+  attach_proposals_device, DeviceRoiSampler   the same two on the device (mpn_attach_proposals / mpn_sample_rois, DESIGN.md section
+                          13.11): what FastRCNN.train_add_sampled / tower_train_add_sampled run per image, with a counter-based draw
   IntegralSampler         donkey.lua:38-41 (the integral loss: one RoiSampler per classifier, each with its own foreground threshold)
   bbox_regression_stats   BatchProviderROI.lua:53-69 (setupData)
   save_checkpoint / load_checkpoint / resume   train.lua:188-198 (model_<epoch>.t7 + optimState_<epoch>.t7, here one table), opt.resume
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -25,20 +29,40 @@ def _boxoverlap_host(a, b):
     inter = w * h
     aarea = (a[:, 2] - a[:, 0] + np.float32(1)) * (a[:, 3] - a[:, 1] + np.float32(1))
     barea = (b[2] - b[0] + np.float32(1)) * (b[3] - b[1] + np.float32(1))
-    o = inter / (aarea + barea - inter)
+    with np.errstate(divide="ignore", invalid="ignore"):   # a zero union only meets a negative w or h, zeroed below
+        o = inter / (aarea + barea - inter)
     o[(w < 0) | (h < 0)] = 0
     return o.astype(np.float32)
 
 
-def attach_proposals(proposals, gt_boxes, gt_labels):
+def _intersection_host(a, b):
+    """utils.intersection (utils.lua:131-148) in fp32 on the host: the share of each box of a [N,4] that lies inside the one box b,
+    inter / aarea — WITHOUT boxoverlap's zeroing of negative widths and heights, as the reference writes it: a box off b's corner
+    (w < 0 and h < 0) has a positive inter."""
+    a = np.asarray(a, np.float32).reshape(-1, 4)
+    b = np.asarray(b, np.float32).reshape(4)
+    x1, y1 = np.maximum(a[:, 0], b[0]), np.maximum(a[:, 1], b[1])
+    x2, y2 = np.minimum(a[:, 2], b[2]), np.minimum(a[:, 3], b[3])
+    w, h = x2 - x1 + np.float32(1), y2 - y1 + np.float32(1)
+    aarea = (a[:, 2] - a[:, 0] + np.float32(1)) * (a[:, 3] - a[:, 1] + np.float32(1))
+    with np.errstate(divide="ignore", invalid="ignore"):   # (a degenerate box of zero area)
+        return ((w * h) / aarea).astype(np.float32)
+
+
+def _to_np(t, dt):
+    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
+
+
+def attach_proposals(proposals, gt_boxes, gt_labels, crowd_boxes=None):
     """DataSetCOCO:attachProposals for one image: the GT boxes FIRST, then the proposals (DataSetJSON.lua:291-299); per row the maximum IoU
     with a GT box (`overlap`), the 1-based index of that GT box (`correspondance`, the reference's spelling; the first maximum, 0 where the
-    overlap is 0) and its class (`label`, 0 where there is none).  gt_labels are class ids >= 1.  Returns a dict of numpy arrays:
+    overlap is 0) and its class (`label`, 0 where there is none).  gt_labels are class ids >= 1.  crowd_boxes [k,4] (the image's
+    `iscrowd` regions; None or empty: none): a proposal row more than 0.7 inside one of them gets overlap -1 — neither foreground nor
+    background —, GT rows never; correspondance and label stay (DataSetJSON.lua:345-363).  Returns a dict of numpy arrays:
     boxes [n,4] float32, gt [n] uint8 (1 on the GT rows), overlap [n] float32, correspondance [n] int64, label [n] int32."""
-    to_np = lambda t, dt: (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
-    prop = to_np(proposals, np.float32).reshape(-1, 4)
-    gtb = to_np(gt_boxes, np.float32).reshape(-1, 4)
-    gtl = to_np(gt_labels, np.int32).reshape(-1)
+    prop = _to_np(proposals, np.float32).reshape(-1, 4)
+    gtb = _to_np(gt_boxes, np.float32).reshape(-1, 4)
+    gtl = _to_np(gt_labels, np.int32).reshape(-1)
     assert gtb.shape[0] == gtl.shape[0]
     ng, n = gtb.shape[0], gtb.shape[0] + prop.shape[0]
     boxes = np.concatenate([gtb, prop], 0)
@@ -55,7 +79,90 @@ def attach_proposals(proposals, gt_boxes, gt_labels):
     label = np.zeros(n, np.int32)
     label[corr > 0] = gtl[corr[corr > 0] - 1]
     rec["label"] = label
+    crowds = None if crowd_boxes is None else _to_np(crowd_boxes, np.float32).reshape(-1, 4)
+    if crowds is not None and crowds.shape[0] and n:
+        mask = np.stack([_intersection_host(boxes, c) for c in crowds], 0).max(0) > np.float32(0.7)
+        mask[:ng] = False   # "don't want to exclude ground truth boxes"
+        rec["overlap"] = np.where(mask, np.float32(-1), rec["overlap"]).astype(np.float32)
     return rec
+
+
+def _dev_f32(t, shape=None):
+    """a contiguous fp32 device tensor of `t` (numpy, host or device tensor)"""
+    t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, np.float32)))
+    t = t.to(device="cuda", dtype=torch.float32)
+    if shape is not None:
+        t = t.reshape((0,) + tuple(shape[1:])) if t.numel() == 0 else t.reshape(shape)   # (-1 cannot be inferred for no elements)
+    return t.contiguous()
+
+
+def _dev_i32(t):
+    t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, np.int32)))
+    return t.to(device="cuda", dtype=torch.int32).reshape(-1).contiguous()
+
+
+def _ptr(t):
+    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def attach_proposals_device(proposals, gt_boxes, gt_labels, crowd_boxes=None):
+    """attach_proposals on the device (include/mpn.h mpn_attach_proposals: one launch, the crowd branch included): a record of DEVICE
+    tensors boxes [m,4] float32, overlap [m] float32, correspondance [m] int32, label [m] int32, m = g + n, the GT rows first — bit for
+    bit what attach_proposals gives.  The inputs may be numpy arrays or tensors on either side."""
+    from . import _lib
+    lib = _lib.load()
+    prop, gtb, gtl = _dev_f32(proposals, (-1, 4)), _dev_f32(gt_boxes, (-1, 4)), _dev_i32(gt_labels)
+    crowds = None if crowd_boxes is None else _dev_f32(crowd_boxes, (-1, 4))
+    n, g, nc = prop.size(0), gtb.size(0), 0 if crowds is None else crowds.size(0)
+    assert gtl.numel() == g
+    m, dev = g + n, prop.device
+    rec = {"boxes": torch.empty((m, 4), dtype=torch.float32, device=dev), "overlap": torch.empty(m, dtype=torch.float32, device=dev),
+           "correspondance": torch.empty(m, dtype=torch.int32, device=dev), "label": torch.empty(m, dtype=torch.int32, device=dev)}
+    _lib.check(lib.mpn_attach_proposals(_ptr(prop), n, _ptr(gtb), _ptr(gtl), g, _ptr(crowds), nc, _ptr(rec["boxes"]), _ptr(rec["overlap"]),
+                                        _ptr(rec["correspondance"]), _ptr(rec["label"]), _stream()), "mpn_attach_proposals")
+    return rec
+
+
+class DeviceRoiSampler(object):
+    """RoiSampler on the device (include/mpn.h mpn_sample_rois): the same two sets and quotas, the draws from
+    Philox4x32-10 under (seed, draw) — draw is the caller's counter, one value per (image, minibatch) —, so any host of the C ABI
+    reproduces a run's rows.  The integral loss's sampler k is DeviceRoiSampler(batch_size, fg_fraction, t_k, (bg_threshold_min, t_k), seed)
+    with IntegralSampler's t_k.  models.FastRCNN.train_add_sampled / tower_train_add_sampled take one of these."""
+
+    def __init__(self, batch_size=128, fg_fraction=0.25, fg_threshold=0.5, bg_threshold=(0.1, 0.5), seed=555):
+        self.batch_size, self.fg_fraction = int(batch_size), float(fg_fraction)
+        self.fg_threshold, self.bg_threshold = float(fg_threshold), (float(bg_threshold[0]), float(bg_threshold[1]))
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.counts = None   # (n_bg, n_fg) of the last sample()
+
+    def cfg(self):
+        """the mpn_roi_sampler this sampler stands for"""
+        from . import _lib
+        return _lib.RoiSamplerCfg(self.batch_size, self.fg_fraction, self.fg_threshold, self.bg_threshold[0], self.bg_threshold[1])
+
+    def sample(self, rec, draw, flip_width=0):
+        """-> (rois [r,4], gt_boxes [r,4], labels [r] int32) device tensors, background rows first (RoiSampler.sample's layout), of an
+        attach_proposals_device record; flip_width > 0: both box tables flipped at that image width.  self.counts = (n_bg, n_fg).
+        Reads the two counts back (one synchronisation) to cut the tensors to r rows."""
+        from . import _lib
+        lib = _lib.load()
+        boxes, m = rec["boxes"], rec["boxes"].size(0)
+        B, dev = self.batch_size, boxes.device
+        rois, gt = torch.empty((B, 4), dtype=torch.float32, device=dev), torch.empty((B, 4), dtype=torch.float32, device=dev)
+        labels, counts = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
+        cfg = self.cfg()
+        _lib.check(lib.mpn_sample_rois(_ptr(boxes), _ptr(rec["overlap"]), _ptr(rec["correspondance"]), _ptr(rec["label"]), m, C.byref(cfg),
+                                       self.seed, int(draw) & 0xFFFFFFFFFFFFFFFF, int(flip_width), _ptr(rois), _ptr(gt), _ptr(labels),
+                                       _ptr(counts), _stream()), "mpn_sample_rois")
+        n_bg, n_fg = (int(v) for v in counts.cpu())
+        self.counts = (n_bg, n_fg)
+        fg_num = int(self.fg_fraction * self.batch_size)
+        r = min(self.batch_size - fg_num, n_bg) + min(fg_num, n_fg)
+        return rois[:r], gt[:r], labels[:r]
 
 
 class RoiSampler(object):

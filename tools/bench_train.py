@@ -16,9 +16,11 @@ more small kernels per step and a scale in two input gradients); 0, the default,
 --model mpnet measures instead the tower training of a MultiPathNet handle (models.synthetic_mpnet_params: VGG-16,
 the five MPN_TOWERS, fc_dim 4096, C 81, K 6; mpn_mpnet_train_*): ms of mpn_mpnet_train_step alone and of the whole iteration on the same
 2 x 64 rows, step i on classifier i mod K, beside the step's derived floor — every trained weight and its momentum read and written once.
+--device-sampler measures instead the whole iteration at depth 2 with each image's rows chosen from 2000
+proposals, drawn on the device (train_add_sampled) and, alternating in the same run, on the host (numpy + uploads + train_add).
 One JSON line per measurement.
 
-    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6] [--model mpnet]
+    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6] [--model mpnet] [--device-sampler]
 """
 import argparse
 import ctypes as C
@@ -81,8 +83,65 @@ def bench_mpnet(a):
                       "floor_ms_at_6.3TBps": round(gb / 6.3e3 * 1e3, 3), "steps": a.steps, "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
+def bench_sampled(a):
+    """--device-sampler: the whole iteration at depth 2 with each image's rows chosen from 2000 proposals x 20 GT boxes x 2 crowds
+    (tools/bench_sampler.py's image), batch 64 per image — drawn on the device by train_add_sampled, against the host-sampled run of
+    the same build (train.attach_proposals + RoiSampler.sample in numpy, three uploads, train_add).  Host clock around iterations that
+    end in a synchronise: the host's work is what differs."""
+    import time
+    import torch
+    from multipathnet_amd import models, train
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bench_sampler import image_case
+    P = models.synthetic_params(seed=557)
+    C_ = P["cls_w"].shape[0]
+    rng = np.random.default_rng(5)
+    images = []
+    for _ in range(IMAGES):
+        prop, gt, gl, crowds = image_case(rng, n_classes=C_)
+        images.append(dict(im=torch.from_numpy(rng.random((3, H, W), dtype=np.float32)).cuda(), host=(prop, gt, gl, crowds),
+                           dev=[torch.from_numpy(x).cuda() for x in (prop, gt, gl, crowds)]))
+    net = models.FastRCNN(P, max_h=H, max_w=W, max_rois=IMAGES * ROWS)
+    del P
+    dev_smp = train.DeviceRoiSampler(ROWS, 0.25, 0.5, (0.1, 0.5), seed=555)
+    host_smp = train.RoiSampler(ROWS, 0.25, 0.5, (0.1, 0.5), rng=np.random.default_rng(555))
+
+    def host_iter(i):
+        for im in images:
+            prop, gt, gl, crowds = im["host"]
+            rows = host_smp.sample(train.attach_proposals(prop, gt, gl, crowd_boxes=crowds))
+            net.train_add(im["im"], *[torch.from_numpy(x).cuda() for x in rows])
+
+    def dev_iter(i):
+        for j, im in enumerate(images):
+            prop, gt, gl, crowds = im["dev"]
+            n_bg, n_fg = net.train_add_sampled(im["im"], prop, gt, gl, dev_smp, draw=i * IMAGES + j, crowd_boxes=crowds)
+            assert n_bg and n_fg
+
+    net.train_begin(depth=2, momentum=0.9, weight_decay=5e-4, dropout=a.dropout)
+    ms = {"host": [], "device": []}
+    for i in range(a.warmup + a.steps):
+        for which, fn in (("host", host_iter), ("device", dev_iter)):   # alternating: both see the same machine state
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(i)
+            net.train_step(1e-6)
+            torch.cuda.synchronize()
+            if i >= a.warmup:
+                ms[which].append((time.perf_counter() - t0) * 1e3)
+    net.train_end()
+    net.close()
+    for which in ("host", "device"):
+        v = ms[which]
+        print(json.dumps({"what": "train_iteration_%s_sampler" % which, "depth": 2, "dropout": a.dropout, "images": IMAGES, "rows_per_image": ROWS,
+                          "proposals": 2000, "gt": 20, "crowds": 2, "ms_iteration_median": round(float(np.median(v)), 3),
+                          "ms_iteration_min": round(float(np.min(v)), 3), "ms_iteration_max": round(float(np.max(v)), 3), "steps": a.steps,
+                          "host_threads": torch.get_num_threads(), "device": torch.cuda.get_device_name(0)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device-sampler", action="store_true", help="instead: the iteration with the rows drawn on the device (train_add_sampled) against the host-sampled one")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trunk-layers", type=int, default=0, help="also measure MPN_TRAIN_TRUNK(k) (9: conv3_1 and up, the reference's configuration)")
@@ -93,6 +152,8 @@ def main():
     import torch
     from multipathnet_amd import _lib, models
     assert torch.cuda.is_available(), "bench_train needs a HIP device"
+    if a.device_sampler:
+        return bench_sampled(a)
     if a.model == "mpnet":
         return bench_mpnet(a)
     P = models.synthetic_params(seed=557)
