@@ -12,7 +12,7 @@
 using namespace mpn;  // (as both translation units do: the structs below name Act, DeviceOwner, ... as pipeline.hip always has)
 
 struct TrainState;  // the training state of a handle: defined in train_driver.hip, private to it
-struct TowerTrainState;  // ... of a MultiPathNet handle's towers (mpn_mpnet_train_*): likewise
+struct TowerTrainState;  // ... of a MultiPathNet handle's towers (mpn_mpnet_train_*): likewise; a handle holds the one of its kind
 
 struct ConvLayer {
   int Cin, Cout, pool;

@@ -1,7 +1,8 @@
 // train_driver.hip — training a VGG Fast R-CNN handle on the device (include/mpn.h mpn_frcnn_train_*): the ROI
 // head with the trunk frozen, or with the trunk's last conv layers (MPN_TRAIN_CONV(k), MPN_TRAIN_TRUNK(k)); and the towers of a
-// MultiPathNet handle with the trunk frozen (mpn_mpnet_train_*; section 13.9).  Host code only: the
-// kernels are train.hip's (train.h) and the detect path's (dense.h); the handle and what is shared with pipeline.hip: pipeline.h.
+// MultiPathNet handle with the trunk frozen (mpn_mpnet_train_*; section 13.9) — two trainers over one core and one layer table
+// (section 13.12).  Host code only: the kernels are train.hip's (train.h) and the detect path's (dense.h); the handle and what is
+// shared with pipeline.hip: pipeline.h.  The state-free debug pass-throughs to the kernels: train_debug.hip.
 #include <cmath>
 #include <algorithm>
 #include <memory>
@@ -33,26 +34,40 @@ static bool alloc_sample_rows(SampleBufs &b, DeviceOwner &own, size_t rows) {
          own.alloc_slot(&b.labels, b.labels_b) == MPN_OK && own.alloc_slot(&b.counts, b.counts_b) == MPN_OK;
 }
 
-// The training state of a handle: exists between train_begin and train_end
-struct TrainState {
+// What both trainers keep between *_train_begin and *_train_end: the optimiser's settings, the pending minibatch, the dropout stream
+struct TrainCore {
   float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
-  // The Linear layers.  w, b: the handle's packed weights (creation alone allocates them: no entry point replaces p->w6 .. p->bh while this exists).
-  // x: the layer's input, g: the gradient at its output, C8 matrices at row pitch Mp; v, vb: momentum, in the layout of the weight it goes with
-  // (g, v, vb: trained layers only).  The x are the minibatch's own activations — not detect's buffers, so a detect between two training
-  // calls disturbs nothing: fc6's operand (the ROI-pooled rows of the pending images), fc6's / fc7's outputs.
-  struct LinT { float *w, *b; int K, N, inner, relu; float *x, *g, *v, *vb; };
-  LinT fc[3] = {};                     // fc6, fc7, the fused cls + bbox head
-  int n_fc = 1;                        // how many of them, counted from the head down, are trained
-  float *head = nullptr;               // the head's output, row-major [B, (K+4)C]
-  int head_k = 0;                      // the integral classifier the next step's loss reads (mpn_frcnn_train_set_head); not optimiser state
+  int head_k = 0;                      // the integral classifier the next step's loss reads (*_train_set_head); not optimiser state
   float *rois = nullptr, *gt = nullptr, *loss = nullptr;   // the pending minibatch's boxes [max_rois,4] x 2; the two loss terms
   int *labels = nullptr;
-  int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensors "train_pooled", "train_y6", "train_y7")
-  // nn.Dropout(rate) behind fc6 + ReLU and fc7 + ReLU (mpn_frcnn_train_set_dropout; 0: none, no kernel).  The mask is a function of
+  int pending = 0, last_rows = 0;      // rows added since the last step; rows of the last step (debug tensors "train_pooled", "train_y6", "tower_train_cat", ...)
+  // nn.Dropout(rate) behind every fc6 + ReLU and fc7 + ReLU (*_train_set_dropout; 0: none, no kernel).  The mask is a function of
   // (seed, step, layer, row, column) — train.h dropout_c8 —, so the stream's whole state is `seed` and `step`
   float drop_rate = 0.f, drop_scale = 1.f;   // scale = 1.0f / (1.0f - rate)
   uint32_t drop_threshold = 0;         // floor(rate * 2^32): an element is kept iff its word >= this
   long seed = 0, step = 0;             // step: the train_steps that reached the forward pass (mpn_frcnn_train_get_state / _set_state)
+  SampleBufs smp;                      // *_train_add_sampled's record and sampled rows
+  DeviceOwner own;                     // of every buffer of the state: *_train_end gives them back at once, not at handle destruction
+};
+
+// A Linear layer of a step.  w, b: the handle's packed weights (creation alone allocates them: no entry point replaces them while a state
+// exists).  x: the layer's input, g: the gradient at its output, C8 matrices at row pitch nseg * Mp; v, vb: momentum, in the layout of the
+// weight it goes with (trained layers only).  The x are the minibatch's own activations — not detect's buffers, so a detect between
+// two training calls disturbs nothing.
+struct LinT {
+  float *w, *b; int K, N, inner, relu; float *x, *g, *v, *vb;
+  float *y = nullptr, *y_rm = nullptr; // the output: a C8 matrix (the x of the layer above) or row-major (a head)
+  int drop = -1;                       // >= 0: y goes through the dropout under this layer word
+  float *dx = nullptr;                 // where lin_dgrad puts the gradient at x (null: not its business)
+  int masked = 1;                      // x is a ReLU output behind the dropout: dx is masked with [x > 0] and scaled by 1 / (1 - rate)
+  int nseg = 1;                        // > 1 (MultiPathNet's mix, PP): the valid rows are nseg segments of B at pitch Mp — the forward runs over all
+};                                     // nseg * Mp rows, the update is sgd_wgrad_seg_c8 / sgd_bias_seg_c8
+
+// The training state of a plain handle: exists between train_begin and train_end
+struct TrainState : TrainCore {
+  LinT fc[3] = {};                     // fc6 (x: the ROI-pooled rows of the pending images), fc7, the fused cls + bbox head
+  int n_fc = 1;                        // how many of them, counted from the head down, are trained
+  float *head = nullptr;               // the head's output, row-major [B, (K+4)C]
   float *vtmp = nullptr;               // mpn_frcnn_train_set_state: cls and bbox momentum joined as creation joins the weights, [(K+4)C, F] + [(K+4)C]
   // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
   // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
@@ -75,41 +90,26 @@ struct TrainState {
   int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
   int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // final map size, row range
   int img_nh[MPN_TRAIN_MAX_IMAGES] = {}, img_nw[MPN_TRAIN_MAX_IMAGES] = {};  // network-input size (every layer's map size follows from it)
-  SampleBufs smp;                      // mpn_frcnn_train_add_sampled's record and sampled rows
-  DeviceOwner own;                     // of the buffers above: mpn_frcnn_train_end gives them back at once, not at handle destruction
 };
-using LinT = TrainState::LinT;
 using ConvT = TrainState::ConvT;
 
 // The training state of a MultiPathNet handle's towers (mpn_mpnet_train_*): exists between mpn_mpnet_train_begin
-// and mpn_mpnet_train_end.  Every activation and gradient of a step lives here, none in detect's buffers.  C8 matrices at row pitch Mp
-// unless said otherwise; momentum in the layout of the weight it goes with.
-struct TowerTrainState {
-  float momentum = 0.f, weight_decay = 0.f, bbox_weight = 1.f;
-  struct TowT {
-    int Kcat = 0;                        // the tower's concat width (conv5 [+ conv4] [+ conv3])
-    float *x = nullptr;                  // the mix layer's operand [Kcat64/8][PP * Mp][8]: rows (bin, roi), the normalised ROI pools side by side
-    float *m = nullptr;                  // the mix layer's output [c5P/8][PP * Mp][8] == fc6's operand [.. >= K6_64/8][Mp][8]
-    float *y6 = nullptr;                 // fc6's output as fc7 read it (behind the dropout)
-    float *gm = nullptr, *g6 = nullptr;  // the gradients at m (m's layout) and at fc6's output
-    float *v_mix = nullptr, *vb_mix = nullptr, *v6 = nullptr, *vb6 = nullptr, *v7 = nullptr, *vb7 = nullptr;
-  };
-  std::vector<TowT> tw;
+// and mpn_mpnet_train_end.  Every activation and gradient of a step lives here, none in detect's buffers.
+struct TowerTrainState : TrainCore {
+  // The layers in forward order: per tower t its mix, fc6, fc7 (rows 3 t ..), then the K classifiers and the box regressor.
+  //   mix: x the operand [Kcat64/8][PP * Mp][8], rows (bin, roi), the normalised ROI pools side by side; K = Kcat, the tower's concat width
+  //        (conv5 [+ conv4] [+ conv3]); y [c5P/8][PP * Mp][8] == fc6's operand [.. >= K6_64/8][Mp][8]; no ReLU between the two
+  //        (multipathnet.lua: View, Linear), so fc6's dx — the mix's g, in y's layout — is unmasked
+  //   fc6: y as fc7 read it, behind the dropout under the layer word 2 t;  fc7: y the tower's columns of `cat`, word 2 t + 1, g those of `dcat`
+  std::vector<LinT> lin;
+  std::vector<int> bwd;                          // the rows in the backward pass's order: the heads, then per tower fc7, fc6, mix
   float *cat = nullptr, *dcat = nullptr;         // the towers' fc7 outputs side by side [T * F/8][Mp][8] (behind the dropout); the gradient there
-  float *cls_rm = nullptr, *bbox_rm = nullptr;   // the two heads' outputs, row-major [B, K*C], [B, 4C]
-  float *g_cls = nullptr, *g_bbox = nullptr;     // train_loss_split's two gradient matrices
-  float *v_cls = nullptr, *vb_cls = nullptr, *v_bbox = nullptr, *vb_bbox = nullptr;
-  float *part = nullptr;                         // sgd_wgrad_seg_c8's partial sums (the widest tower's)
-  float *rois = nullptr, *gt = nullptr, *loss = nullptr;
-  int *labels = nullptr;
-  int head_k = 0, pending = 0, last_rows = 0;
-  float drop_rate = 0.f, drop_scale = 1.f;       // as TrainState's; the layer word of tower t is 2 t (behind fc6), 2 t + 1 (behind fc7)
-  uint32_t drop_threshold = 0;
-  long seed = 0, step = 0;
-  SampleBufs smp;                                // mpn_mpnet_train_add_sampled's record and sampled rows
-  DeviceOwner own;
+  float *seg_part = nullptr;                     // sgd_wgrad_seg_c8's partial sums (the widest tower's)
+  LinT &mix(int t) { return lin[3 * t]; }
+  LinT &fc6(int t) { return lin[3 * t + 1]; }
+  LinT &cls() { return lin[lin.size() - 2]; }    // y_rm [B, K*C], g: train_loss_split's two gradient matrices
+  LinT &bbox() { return lin[lin.size() - 1]; }   // y_rm [B, 4C]
 };
-using TowT = TowerTrainState::TowT;
 
 void mpn::free_train_state(mpn_frcnn *p) {
   delete p->train;  // (its DeviceOwner gives the buffers back)
@@ -118,9 +118,27 @@ void mpn::free_train_state(mpn_frcnn *p) {
   p->tower_train = nullptr;
 }
 
-// the handle kinds and states that cannot train, each named (as refuse_multi_pass does for the throughput forms)
-static int refuse_train(const mpn_frcnn *p, const char *fn) {
-  if (p->is_mpnet || p->rn) {
+// MPN_CHECK_ARG / MPN_CHECK_HIP in a body that two entry points share: reported under the entry point's name `fn`
+#define CHECK_ARG_AS(fn, cond) do { if (!(cond)) { set_error("%s: invalid argument: %s", fn, #cond); return MPN_EINVAL; } } while (0)
+#define CHECK_HIP_AS(fn, expr) \
+  do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s: %s failed: %s", fn, #expr, hipGetErrorString(_e)); return MPN_EHIP; } } while (0)
+
+// The two kinds of trainer, told apart by `mpnet` in everything they share: mpn_frcnn_train_* on a plain handle's TrainState,
+// mpn_mpnet_train_* on a MultiPathNet handle's TowerTrainState
+static const char *kind_prefix(bool mpnet) { return mpnet ? "mpn_mpnet" : "mpn_frcnn"; }
+
+// The handle kinds and states that cannot train, each named (as refuse_multi_pass does for the throughput forms).  Each kind refuses
+// the other's handles; the order of the refusals is each kind's own.
+static int refuse_train(const mpn_frcnn *p, bool mpnet, const char *fn) {
+  if (mpnet && p->n_scales > 1) {  // (only a plain handle can hold one)
+    set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales), which only a plain Fast R-CNN handle holds: this entry point trains mpn_mpnet_create handles", fn, p->n_scales);
+    return MPN_ESTATE;
+  }
+  if (mpnet && !p->is_mpnet) {
+    set_error("%s: not an mpn_mpnet_create handle: a %s handle has no towers to train%s", fn, handle_kind_name(p), p->rn ? "" : " (mpn_frcnn_train_begin trains its head)");
+    return MPN_ESTATE;
+  }
+  if (!mpnet && (p->is_mpnet || p->rn)) {
     set_error("%s: a %s handle cannot be trained: only mpn_frcnn_create's VGG Fast R-CNN head (fc6, fc7, cls + bbox) has a backward pass%s", fn, handle_kind_name(p),
               p->is_mpnet ? " here (its towers train through mpn_mpnet_train_begin)" : "");
     return MPN_ESTATE;
@@ -142,6 +160,130 @@ static int refuse_train(const mpn_frcnn *p, const char *fn) {
     return MPN_ESTATE;
   }
   return MPN_OK;
+}
+
+// the core of the kind's state (null outside begin .. end); need_core: or a refusal
+static TrainCore *core_of(mpn_frcnn *p, bool mpnet) { return mpnet ? static_cast<TrainCore *>(p->tower_train) : p->train; }
+static int need_core(mpn_frcnn *p, bool mpnet, const char *fn, TrainCore **c) {
+  *c = core_of(p, mpnet);
+  if (*c) return MPN_OK;
+  set_error("%s: no %s_train_begin on this handle", fn, kind_prefix(mpnet));
+  return MPN_ESTATE;
+}
+
+// *_train_begin up to its own arguments: the handle can train and has not begun
+static int begin_refusals(mpn_frcnn *p, bool mpnet, const char *fn) {
+  if (int rc = refuse_train(p, mpnet, fn)) return rc;
+  if (!core_of(p, mpnet)) return MPN_OK;
+  set_error("%s: training has already begun on this handle (%s_train_end first)", fn, kind_prefix(mpnet));
+  return MPN_ESTATE;
+}
+// ... and from its optimiser arguments on: checked, the device idle, taken into the new state
+static int begin_core(TrainCore &c, const char *fn, float momentum, float weight_decay, float bbox_weight) {
+  CHECK_ARG_AS(fn, std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
+  CHECK_HIP_AS(fn, hipDeviceSynchronize());
+  c.momentum = momentum; c.weight_decay = weight_decay; c.bbox_weight = bbox_weight;
+  return MPN_OK;
+}
+
+// The core's buffers: the pending rows and, for *_train_add_sampled, the sampled rows.  Plain allocations — the allocation generation is
+// not bumped, so a launch graph captured before training is still replayed after it.
+static bool alloc_core(const mpn_frcnn *p, TrainCore &c) {
+  const size_t M = (size_t)p->cfg.max_rois;
+  return c.own.alloc(&c.rois, M * 4 * sizeof(float), true) == MPN_OK && c.own.alloc(&c.gt, M * 4 * sizeof(float), true) == MPN_OK &&
+         c.own.alloc(&c.loss, 16, true) == MPN_OK && c.own.alloc(&c.labels, M * sizeof(int), true) == MPN_OK && alloc_sample_rows(c.smp, c.own, M);
+}
+// a trained layer's momentum
+static bool alloc_momentum(DeviceOwner &own, LinT &L) {
+  return own.alloc(&L.v, lin_wpk_elems(round_up(L.K, 64), L.N) * sizeof(float), true) == MPN_OK && own.alloc(&L.vb, (size_t)lin_np(L.N) * sizeof(float), true) == MPN_OK;
+}
+
+static int train_end(mpn_frcnn *p, bool mpnet, const char *fn) {
+  TrainCore *c;
+  if (int rc = need_core(p, mpnet, fn, &c)) return rc;
+  CHECK_HIP_AS(fn, hipDeviceSynchronize());
+  free_train_state(p);
+  return MPN_OK;
+}
+
+static int train_set_head(mpn_frcnn *p, bool mpnet, const char *fn, int k) {
+  TrainCore *c;
+  if (int rc = need_core(p, mpnet, fn, &c)) return rc;
+  if (k < 0 || k >= p->n_integral) {
+    set_error("%s: invalid argument: head %d is outside [0, K) of this handle's K = %d integral classifiers", fn, k, p->n_integral);
+    return MPN_EINVAL;
+  }
+  c->head_k = k;  // read by the next *_train_step
+  return MPN_OK;
+}
+
+static int train_set_dropout(mpn_frcnn *p, bool mpnet, const char *fn, float rate, long seed) {
+  TrainCore *c;
+  if (int rc = need_core(p, mpnet, fn, &c)) return rc;
+  if (!(std::isfinite(rate) && rate >= 0.0f && rate < 1.0f)) {
+    set_error("%s: rate %g is outside [0, 1)", fn, (double)rate);
+    return MPN_EINVAL;
+  }
+  c->drop_rate = rate;
+  c->drop_threshold = (uint32_t)std::floor((double)rate * 4294967296.0);
+  c->drop_scale = 1.0f / (1.0f - rate);
+  c->seed = seed;
+  return MPN_OK;
+}
+
+static LossCfg loss_cfg(const mpn_frcnn *p, const TrainCore &c) {
+  LossCfg lc{};
+  for (int i = 0; i < 4; ++i) { lc.mean[i] = p->cfg.bbox_mean[i]; lc.std[i] = p->cfg.bbox_std[i]; }
+  lc.norm = p->cfg.bbox_std[0] != 0.0f ? 1 : 0;
+  lc.bbox_weight = c.bbox_weight;
+  return lc;
+}
+
+static DropoutCfg dropout_cfg(const TrainCore &c, int layer, long step) {
+  return DropoutCfg{c.drop_threshold, (uint32_t)((uint64_t)c.seed & 0xffffffffu), (uint32_t)((uint64_t)c.seed >> 32), (uint32_t)layer,
+                    (uint32_t)((uint64_t)step & 0xffffffffu), c.drop_scale};
+}
+
+// ---- the three passes of a step over the layer table: the launches of both kinds' Linear layers
+// Forward, rows[0 .. n) in order: detect's GEMMs on the pending rows and, at a rate > 0, the dropout of the outputs that have one (the
+// model is in training mode at every depth: frozen layers drop too).  A segmented layer runs over all nseg * Mp rows of its operand
+// (a row's result depends on that row alone) in the one-segment canonical order.
+static int lin_forward(const LinT *rows, int n, const TrainCore &c, int B, int Mp, long step, hipStream_t s) {
+  int rc = MPN_OK;
+  for (int i = 0; i < n && rc == MPN_OK; ++i) {
+    const LinT &L = rows[i];
+    rc = linear_c8(L.x, L.nseg > 1 ? L.nseg * Mp : B, L.K, L.w, L.b, L.N, L.relu, L.y, L.y_rm, s, L.nseg * Mp, nullptr, L.nseg > 1 ? 2 : 1);
+    if (rc == MPN_OK && L.drop >= 0 && c.drop_rate > 0.0f) rc = dropout_c8(L.y, Mp, B, L.N, dropout_cfg(c, L.drop, step), s);
+  }
+  return rc;
+}
+// The input gradients of the rows that hand one down (dx), in `order`: all of them run before any update of the weights they read.  A
+// masked row's x is what the dropout left: a dropped element is +0.0, so the kernel's [x > 0] is keep mask x ReLU mask and the
+// dropout's backward is the factor 1 / (1 - rate) alone
+static int lin_dgrad(const LinT *rows, const int *order, int n, const TrainCore &c, int B, int Mp, hipStream_t s) {
+  const float gscale = c.drop_rate > 0.0f ? c.drop_scale : 1.0f;
+  int rc = MPN_OK;
+  for (int i = 0; i < n && rc == MPN_OK; ++i) {
+    const LinT &L = rows[order[i]];
+    if (L.dx) rc = linear_dgrad_c8(L.g, Mp, B, L.N, L.w, L.K, L.masked ? L.x : nullptr, L.dx, Mp, s, L.masked ? gscale : 1.0f);
+  }
+  return rc;
+}
+// The weight and bias updates of the trained rows (v), in `order`, in place on the packed weights detect reads.  part: the segmented form's partial sums
+static int lin_update(const LinT *rows, const int *order, int n, const TrainCore &c, int B, int Mp, float lr, float *part, hipStream_t s) {
+  int rc = MPN_OK;
+  for (int i = 0; i < n && rc == MPN_OK; ++i) {
+    const LinT &L = rows[order[i]];
+    if (!L.v) continue;
+    if (L.nseg > 1) {
+      rc = sgd_wgrad_seg_c8(L.g, L.x, Mp, L.nseg, B, L.N, L.K, part, L.w, L.v, lr, c.momentum, c.weight_decay, s);
+      if (rc == MPN_OK) rc = sgd_bias_seg_c8(L.g, Mp, L.nseg, B, L.N, L.b, L.vb, lr, c.momentum, s);
+    } else {
+      rc = sgd_wgrad_c8(L.g, Mp, L.x, Mp, B, L.N, L.K, L.inner, L.w, L.v, lr, c.momentum, c.weight_decay, s);
+      if (rc == MPN_OK) rc = sgd_bias_c8(L.g, Mp, B, L.N, L.b, L.vb, lr, c.momentum, s);
+    }
+  }
+  return rc;
 }
 
 // The forms of a conv layer that are derived from its master `wpk`: (forward) the Winograd and K = 36 packs detect's kernels read, rebuilt
@@ -233,17 +375,16 @@ static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
   t->fc[2] = LinT{p->wh, p->bh, F, plain_head_width(p), 1, 0};
   auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
   auto trained = [&](LinT &L) {  // momentum and the gradient at the output
-    return alloc0(&L.v, lin_wpk_elems(round_up(L.K, 64), L.N) * sizeof(float)) && alloc0(&L.vb, (size_t)lin_np(L.N) * sizeof(float)) &&
-           alloc0(&L.g, (size_t)(lin_np(L.N) / 8) * rec);
+    return alloc_momentum(t->own, L) && alloc0(&L.g, (size_t)(lin_np(L.N) / 8) * rec);
   };
   bool ok = trained(t->fc[2]);
   ok = ok && alloc0(&t->fc[0].x, (size_t)(round_up(p->K6, 64) / 8) * rec);
   for (int i = 1; i < 3; ++i) ok = ok && alloc0(&t->fc[i].x, (size_t)(lin_np(t->fc[i - 1].N) / 8) * rec);  // the output of the layer below
   ok = ok && alloc0(&t->head, M * plain_head_width(p) * sizeof(float));
   for (int i = 1; i >= 3 - t->n_fc; --i) ok = ok && trained(t->fc[i]);
-  ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
-  ok = ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
-  ok = ok && alloc_sample_rows(t->smp, t->own, M);
+  for (int i = 0; i < 2; ++i) { t->fc[i].y = t->fc[i + 1].x; t->fc[i].drop = i; t->fc[i + 1].dx = t->fc[i].g; }  // (dx: null below the lowest trained layer)
+  t->fc[2].y_rm = t->head;
+  ok = ok && alloc_core(p, *t);
   if (!k) return ok;
   ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
   ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
@@ -273,16 +414,13 @@ static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
 
 extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, float weight_decay, float bbox_weight) {
   MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, "mpn_frcnn_train_begin");
+  int rc = begin_refusals(p, false, __func__);
   if (rc) return rc;
-  if (p->train) { set_error("mpn_frcnn_train_begin: training has already begun on this handle (mpn_frcnn_train_end first)"); return MPN_ESTATE; }
   MPN_CHECK_ARG(depth >= MPN_TRAIN_HEADS);
   std::unique_ptr<TrainState> t(new TrainState());  // (its DeviceOwner gives back what a failed attempt made)
   rc = parse_train_depth(p, depth, t.get());
+  if (rc == MPN_OK) rc = begin_core(*t, __func__, momentum, weight_decay, bbox_weight);
   if (rc) return rc;
-  MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
   if (!alloc_train_state(p, t.get()) || hipDeviceSynchronize() != hipSuccess) {
     set_error("mpn_frcnn_train_begin: allocating the momentum / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
     return MPN_ENOMEM;
@@ -293,10 +431,7 @@ extern "C" int mpn_frcnn_train_begin(mpn_frcnn *p, int depth, float momentum, fl
 
 extern "C" int mpn_frcnn_train_end(mpn_frcnn *p) {
   MPN_CHECK_ARG(p != nullptr);
-  if (!p->train) { set_error("mpn_frcnn_train_end: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  free_train_state(p);
-  return MPN_OK;
+  return train_end(p, false, __func__);
 }
 
 // ---- drawing an image's rows on the device (*_train_add_sampled; sampler.h) ----
@@ -354,10 +489,11 @@ static int flip_train_image(SampleBufs &b, DeviceOwner &own, const float *d_imag
   return rc;
 }
 
-// What one more image of n rows behind `pending` must satisfy (the four *_train_add* entry points, under the caller's name `fn`), and
-// getImages' size
-static int add_check(const mpn_frcnn *p, int pending, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
+// What one more image of n rows behind the pending ones must satisfy (the four *_train_add* entry points, under the caller's name `fn`),
+// and getImages' size
+static int add_check(mpn_frcnn *p, bool mpnet, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
   const mpn_frcnn_config &c = p->cfg;
+  const int pending = core_of(p, mpnet)->pending;
   if (pending + n > c.max_rois) {
     set_error("%s: %d pending rows + %d exceed the handle's max_rois (%d)", fn, pending, n, c.max_rois);
     return MPN_EINVAL;
@@ -368,45 +504,56 @@ static int add_check(const mpn_frcnn *p, int pending, const char *fn, int H0, in
     set_error("%s: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", fn, H0, W0, *H, *W, c.max_h, c.max_w);
     return MPN_EINVAL;
   }
-  return MPN_OK;
-}
-static int frcnn_add_check(const mpn_frcnn *p, const TrainState *t, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
-  const int rc = add_check(p, t->pending, fn, H0, W0, n, sc, H, W);
-  if (rc) return rc;
-  if (t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
+  const TrainState *t = mpnet ? nullptr : p->train;
+  if (t && t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
     set_error("%s: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", fn, t->n_img, MPN_TRAIN_MAX_IMAGES);
     return MPN_EINVAL;
   }
   return MPN_OK;
 }
 
+// the kinds' bodies of an add on device row pointers, everything checked (below): the frozen trunk, the kind's ROI pooling, the rows' copies
 static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
                           const float *d_gt, const int *d_labels, int n, hipStream_t s);
-
-extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
-                                   const int *d_labels, int n, void *stream) {
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, "mpn_frcnn_train_add");
-  if (rc) return rc;
-  TrainState *t = p->train;
-  if (!t) { set_error("mpn_frcnn_train_add: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
-  double sc;
-  int H, W;
-  if ((rc = frcnn_add_check(p, t, "mpn_frcnn_train_add", H0, W0, n, &sc, &H, &W)) != MPN_OK) return rc;
-  ScratchScope scratch_scope(&p->scratch);
-  return frcnn_add_rows(p, t, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, as_stream(stream));
+static int mpnet_add_rows(mpn_frcnn *p, TowerTrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
+                          const float *d_gt, const int *d_labels, int n, hipStream_t s);
+static int add_rows(mpn_frcnn *p, bool mpnet, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois, const float *d_gt,
+                    const int *d_labels, int n, hipStream_t s) {
+  return mpnet ? mpnet_add_rows(p, p->tower_train, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, s)
+               : frcnn_add_rows(p, p->train, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, s);
+}
+// ... which both end with the rows' copies behind the pending ones (fn: the kind's body)
+static int append_rows(TrainCore &c, const char *fn, const float *d_rois, const float *d_gt, const int *d_labels, int n, hipStream_t s) {
+  CHECK_HIP_AS(fn, hipMemcpyAsync(c.rois + (size_t)c.pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  CHECK_HIP_AS(fn, hipMemcpyAsync(c.gt + (size_t)c.pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  CHECK_HIP_AS(fn, hipMemcpyAsync(c.labels + c.pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+  c.pending += n;
+  return MPN_OK;
 }
 
-extern "C" int mpn_frcnn_train_add_sampled(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
-                                           const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
-                                           uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
-  const char *fn = "mpn_frcnn_train_add_sampled";
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, fn);
+// mpn_frcnn_train_add and mpn_mpnet_train_add behind their `p != nullptr`
+static int train_add(mpn_frcnn *p, bool mpnet, const char *fn, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
+                     const int *d_labels, int n, void *stream) {
+  int rc = refuse_train(p, mpnet, fn);
   if (rc) return rc;
-  TrainState *t = p->train;
-  if (!t) { set_error("%s: no mpn_frcnn_train_begin on this handle", fn); return MPN_ESTATE; }
+  TrainCore *t;
+  if ((rc = need_core(p, mpnet, fn, &t)) != MPN_OK) return rc;
+  CHECK_ARG_AS(fn, d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
+  double sc;
+  int H, W;
+  if ((rc = add_check(p, mpnet, fn, H0, W0, n, &sc, &H, &W)) != MPN_OK) return rc;
+  ScratchScope scratch_scope(&p->scratch);
+  return add_rows(p, mpnet, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, as_stream(stream));
+}
+
+// ... and the two *_train_add_sampled
+static int train_add_sampled(mpn_frcnn *p, bool mpnet, const char *fn, const float *d_image, int H0, int W0, const float *d_proposals, int n,
+                             const float *d_gt, const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                             uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
+  int rc = refuse_train(p, mpnet, fn);
+  if (rc) return rc;
+  TrainCore *t;
+  if ((rc = need_core(p, mpnet, fn, &t)) != MPN_OK) return rc;
   if ((rc = check_sampled_args(fn, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, h_counts)) != MPN_OK) return rc;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
@@ -416,13 +563,36 @@ extern "C" int mpn_frcnn_train_add_sampled(mpn_frcnn *p, const float *d_image, i
   const int r = sampled_rows(*cfg, h_counts);
   double sc;
   int H, W;
-  if ((rc = frcnn_add_check(p, t, fn, H0, W0, r, &sc, &H, &W)) != MPN_OK) return rc;
+  if ((rc = add_check(p, mpnet, fn, H0, W0, r, &sc, &H, &W)) != MPN_OK) return rc;
   if (flip && (rc = flip_train_image(t->smp, t->own, d_image, H0, W0, s, &d_image)) != MPN_OK) return rc;
-  return frcnn_add_rows(p, t, d_image, H0, W0, H, W, sc, t->smp.rois, t->smp.gt, t->smp.labels, r, s);
+  return add_rows(p, mpnet, d_image, H0, W0, H, W, sc, t->smp.rois, t->smp.gt, t->smp.labels, r, s);
 }
 
-// The body of mpn_frcnn_train_add on device row pointers, everything checked: the frozen trunk, the ROI pooling of these rows behind the
-// pending ones, what the conv block's backward pass reads, the rows' copies
+extern "C" int mpn_frcnn_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt,
+                                   const int *d_labels, int n, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_add(p, false, __func__, d_image, H0, W0, d_rois, d_gt, d_labels, n, stream);
+}
+extern "C" int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt, const int *d_labels,
+                                   int n, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_add(p, true, __func__, d_image, H0, W0, d_rois, d_gt, d_labels, n, stream);
+}
+extern "C" int mpn_frcnn_train_add_sampled(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
+                                           const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                                           uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_add_sampled(p, false, __func__, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, seed, draw, flip, h_counts, stream);
+}
+extern "C" int mpn_mpnet_train_add_sampled(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
+                                           const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
+                                           uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_add_sampled(p, true, __func__, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, seed, draw, flip, h_counts, stream);
+}
+
+// The plain handle's add: the frozen trunk, the ROI pooling of these rows behind the pending ones, what the conv block's backward pass
+// reads, the rows' copies
 static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
                           const float *d_gt, const int *d_labels, int n, hipStream_t s) {
   const mpn_frcnn_config &c = p->cfg;
@@ -461,11 +631,7 @@ static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int
     t->img_h[i] = h; t->img_w[i] = w; t->img_nh[i] = H; t->img_nw[i] = W; t->img_row0[i] = t->pending; t->img_rows[i] = n;
     ++t->n_img;
   }
-  MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
-  t->pending += n;
-  return MPN_OK;
+  return append_rows(*t, __func__, d_rois, d_gt, d_labels, n, s);
 }
 
 // The backward pass below fc6 (depth MPN_TRAIN_CONV(k)): the gradient at the pooled features, then per image — in train_add order — the
@@ -520,49 +686,41 @@ static int train_conv_backward(mpn_frcnn *p, TrainState *t, int B, hipStream_t s
   return rc;
 }
 
+// A step up to its first launch: the kind's refusals, a begun state with pending rows, a finite rate.  *step: this step's masks —
+// counted whatever the rate, also when a launch fails
+static int step_begin(mpn_frcnn *p, bool mpnet, const char *fn, float lr, TrainCore **c, long *step) {
+  int rc = refuse_train(p, mpnet, fn);
+  if (rc == MPN_OK) rc = need_core(p, mpnet, fn, c);
+  if (rc) return rc;
+  if ((*c)->pending <= 0) { set_error("%s: no pending rows (%s_train_add first)", fn, kind_prefix(mpnet)); return MPN_ESTATE; }
+  CHECK_ARG_AS(fn, std::isfinite(lr));
+  *step = (*c)->step++;
+  return MPN_OK;
+}
+// ... and behind its last one (also a failed one: the weights may be half updated, the batch is not to be replayed)
+static void step_end(TrainCore &c) {
+  c.last_rows = c.pending;
+  c.pending = 0;
+}
+
+static const int kPlainBwd[3] = {2, 1, 0};  // head, fc7, fc6
+
 extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
   MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_train(p, "mpn_frcnn_train_step");
+  TrainCore *core;
+  long step;
+  int rc = step_begin(p, false, __func__, lr, &core, &step);
   if (rc) return rc;
-  TrainState *t = p->train;
-  if (!t) { set_error("mpn_frcnn_train_step: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  if (t->pending <= 0) { set_error("mpn_frcnn_train_step: no pending rows (mpn_frcnn_train_add first)"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(std::isfinite(lr));
-  const mpn_frcnn_config &c = p->cfg;
-  const int B = t->pending, Mp = p->Mp, lowest = 3 - t->n_fc;  // fc[lowest]: the lowest trained Linear layer
+  TrainState *t = static_cast<TrainState *>(core);
+  const int B = t->pending, Mp = p->Mp;
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
-  // forward: detect's GEMMs on the pending rows (row pitch Mp), at a rate > 0 each of fc6's and fc7's outputs dropped in place (the
-  // model is in training mode at every depth: frozen layers drop too).  The last layer writes the row-major head
-  const bool drop = t->drop_rate > 0.0f;
-  const long step = t->step++;  // this step's masks; counted whatever the rate, also when a launch below fails
-  for (int i = 0; i < 3 && rc == MPN_OK; ++i) {
-    const LinT &L = t->fc[i];
-    rc = linear_c8(L.x, B, L.K, L.w, L.b, L.N, L.relu, i < 2 ? t->fc[i + 1].x : nullptr, i < 2 ? nullptr : t->head, s, Mp, nullptr, 1);
-    if (rc == MPN_OK && drop && i < 2) {
-      const DropoutCfg dc{t->drop_threshold, (uint32_t)((uint64_t)t->seed & 0xffffffffu), (uint32_t)((uint64_t)t->seed >> 32), (uint32_t)i,
-                          (uint32_t)((uint64_t)step & 0xffffffffu), t->drop_scale};
-      rc = dropout_c8(t->fc[i + 1].x, Mp, B, L.N, dc, s);
-    }
-  }
+  rc = lin_forward(t->fc, 3, *t, B, Mp, step, s);  // the last layer writes the row-major head
   if (rc) return rc;
-  LossCfg lc{};
-  for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
-  lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
-  lc.bbox_weight = t->bbox_weight;
-  rc = train_loss(t->head, B, c.n_classes, p->n_integral, t->head_k, t->rois, t->gt, t->labels, lc, t->fc[2].g, Mp, d_loss ? d_loss : t->loss, s);
-  // backward: every input gradient before the update of the weights it was computed with.  L.x is what the dropout left: a dropped
-  // element is +0.0, so the kernel's [x > 0] is keep mask x ReLU mask and the dropout's backward is the factor 1 / (1 - rate) alone
-  for (int i = 2; i > lowest && rc == MPN_OK; --i) {
-    const LinT &L = t->fc[i];
-    rc = linear_dgrad_c8(L.g, Mp, B, L.N, L.w, L.K, L.x, t->fc[i - 1].g, Mp, s, drop ? t->drop_scale : 1.0f);
-  }
+  rc = train_loss(t->head, B, p->cfg.n_classes, p->n_integral, t->head_k, t->rois, t->gt, t->labels, loss_cfg(p, *t), t->fc[2].g, Mp, d_loss ? d_loss : t->loss, s);
+  if (rc == MPN_OK) rc = lin_dgrad(t->fc, kPlainBwd, 3, *t, B, Mp, s);  // down to the lowest trained layer
   if (rc == MPN_OK && t->kconv) rc = train_conv_backward(p, t, B, s);
-  for (int i = 2; i >= lowest && rc == MPN_OK; --i) {  // head, fc7, fc6
-    const LinT &L = t->fc[i];
-    rc = sgd_wgrad_c8(L.g, Mp, L.x, Mp, B, L.N, L.K, L.inner, L.w, L.v, lr, t->momentum, t->weight_decay, s);
-    if (rc == MPN_OK) rc = sgd_bias_c8(L.g, Mp, B, L.N, L.b, L.vb, lr, t->momentum, s);
-  }
+  if (rc == MPN_OK) rc = lin_update(t->fc, kPlainBwd, 3, *t, B, Mp, lr, nullptr, s);
   for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {  // the conv block: the master `wpk` in place, then every form derived from it
     const ConvLayer &L = p->conv[t->first + j];
     const ConvT &T = t->cl[j];
@@ -571,36 +729,25 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
     if (rc == MPN_OK) rc = refresh_conv_forms(L, T, t->wtmp, true, s);
   }
   t->last_img = t->n_img; t->n_img = 0;
-  t->last_rows = B;
-  t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
+  step_end(*t);
   return rc;
 }
 
 extern "C" int mpn_frcnn_train_set_head(mpn_frcnn *p, int k) {
   MPN_CHECK_ARG(p != nullptr);
-  TrainState *t = p->train;
-  if (!t) { set_error("mpn_frcnn_train_set_head: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  if (k < 0 || k >= p->n_integral) {
-    set_error("mpn_frcnn_train_set_head: invalid argument: head %d is outside [0, K) of this handle's K = %d integral classifiers", k, p->n_integral);
-    return MPN_EINVAL;
-  }
-  t->head_k = k;  // read by the next mpn_frcnn_train_step
-  return MPN_OK;
+  return train_set_head(p, false, __func__, k);
 }
-
+extern "C" int mpn_mpnet_train_set_head(mpn_frcnn *p, int k) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_set_head(p, true, __func__, k);
+}
 extern "C" int mpn_frcnn_train_set_dropout(mpn_frcnn *p, float rate, long seed) {
   MPN_CHECK_ARG(p != nullptr);
-  TrainState *t = p->train;
-  if (!t) { set_error("mpn_frcnn_train_set_dropout: no mpn_frcnn_train_begin on this handle"); return MPN_ESTATE; }
-  if (!(std::isfinite(rate) && rate >= 0.0f && rate < 1.0f)) {
-    set_error("mpn_frcnn_train_set_dropout: rate %g is outside [0, 1)", (double)rate);
-    return MPN_EINVAL;
-  }
-  t->drop_rate = rate;
-  t->drop_threshold = (uint32_t)std::floor((double)rate * 4294967296.0);
-  t->drop_scale = 1.0f / (1.0f - rate);
-  t->seed = seed;
-  return MPN_OK;
+  return train_set_dropout(p, false, __func__, rate, seed);
+}
+extern "C" int mpn_mpnet_train_set_dropout(mpn_frcnn *p, float rate, long seed) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_set_dropout(p, true, __func__, rate, seed);
 }
 
 // The eight tensors of mpn_frcnn_train_get_state / _set_state in their order, each with the Linear layer whose momentum holds it
@@ -746,71 +893,45 @@ extern "C" int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w, 
 // the K classifiers on the Foveal towers' concat and the box regressor on the het tower.  mpn_frcnn_train_* keeps refusing these
 // handles (refuse_train); these entry points refuse every other kind.
 // =================================================================================================================================
-static int refuse_tower_train(const mpn_frcnn *p, const char *fn) {
-  if (p->n_scales > 1) {  // (only a plain handle can hold one)
-    set_error("%s: not supported with an image pyramid (mpn_frcnn_set_scales, %d scales), which only a plain Fast R-CNN handle holds: this entry point trains mpn_mpnet_create handles", fn, p->n_scales);
-    return MPN_ESTATE;
-  }
-  if (!p->is_mpnet) {
-    set_error("%s: not an mpn_mpnet_create handle: a %s handle has no towers to train%s", fn, handle_kind_name(p), p->rn ? "" : " (mpn_frcnn_train_begin trains its head)");
-    return MPN_ESTATE;
-  }
-  if (p->cfg.fc_arith != MPN_FC_FP32) {
-    set_error("%s: an MPN_FC_SPLIT3 handle cannot be trained (its bf16 weight planes would go stale): create it with MPN_FC_FP32", fn);
-    return MPN_ESTATE;
-  }
-  if (p->augment) {
-    set_error("%s: not supported with horizontal-flip augmentation (mpn_frcnn_set_augment): switch it off; flip training images with mpn_image_hflip / mpn_flip_boxes", fn);
-    return MPN_ESTATE;
-  }
-  if (p->tail_pending[0] || p->tail_pending[1]) {
-    set_error("%s: a pipelined call's tail is still pending on this handle: call mpn_frcnn_flush first", fn);
-    return MPN_ESTATE;
-  }
-  return MPN_OK;
-}
-
-// every buffer of the state; false: something failed (t's DeviceOwner holds what was made)
+// The layer table and every buffer of the state; false: something failed (t's DeviceOwner holds what was made)
 static bool alloc_tower_train_state(const mpn_frcnn *p, TowerTrainState *t) {
   const mpn_frcnn_config &c = p->cfg;
   const int F = c.fc_dim, PP = c.pooled_h * c.pooled_w, C = c.n_classes, KC = p->n_integral * C, c5 = p->feat_c;
-  const int T = (int)p->towers.size(), Fcb = lin_np(F) / 8;
-  const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float);
+  const int T = (int)p->towers.size(), nf = T - 1, Fcb = lin_np(F) / 8;
+  const size_t M = (size_t)c.max_rois, rec = (size_t)p->Mp * 8 * sizeof(float), k6_rec = (size_t)(round_up(p->K6, 64) / 8) * rec;
+  const size_t slice = (size_t)Fcb * p->Mp * 8;  // a tower's columns of cat / dcat
   auto alloc0 = [&](float **q, size_t bytes) -> bool { return t->own.alloc(q, bytes, true) == MPN_OK; };
-  auto momentum = [&](float **v, float **vb, int K, int N) {
-    return alloc0(v, lin_wpk_elems(round_up(K, 64), N) * sizeof(float)) && alloc0(vb, (size_t)lin_np(N) * sizeof(float));
-  };
-  bool ok = true;
+  bool ok = alloc0(&t->cat, (size_t)T * Fcb * rec) && alloc0(&t->dcat, (size_t)T * Fcb * rec);
   size_t part = 0;
-  t->tw.resize(T);
   for (int i = 0; i < T && ok; ++i) {
-    TowT &W = t->tw[i];
-    W.Kcat = p->towers[i].total_feat;
-    const size_t k6_rec = (size_t)(round_up(p->K6, 64) / 8) * rec;
-    ok = alloc0(&W.x, (size_t)(round_up(W.Kcat, 64) / 8) * PP * rec) && alloc0(&W.m, std::max((size_t)(lin_np(c5) / 8) * PP * rec, k6_rec)) &&
-         alloc0(&W.y6, (size_t)Fcb * rec) && alloc0(&W.gm, k6_rec) && alloc0(&W.g6, (size_t)Fcb * rec) &&
-         momentum(&W.v_mix, &W.vb_mix, W.Kcat, c5) && momentum(&W.v6, &W.vb6, p->K6, F) && momentum(&W.v7, &W.vb7, F, F);
-    part = std::max(part, seg_wgrad_part_elems(W.Kcat, c5, PP));
+    const mpn_frcnn::Tower &W = p->towers[i];
+    LinT mix{W.mix_w, W.mix_b, W.total_feat, c5, 1, 0}, fc6{W.w6, W.b6, p->K6, F, PP, 1}, fc7{W.w7, W.b7, F, F, 1, 1};
+    ok = alloc0(&mix.x, (size_t)(round_up(mix.K, 64) / 8) * PP * rec) && alloc0(&mix.y, std::max((size_t)(lin_np(c5) / 8) * PP * rec, k6_rec)) &&
+         alloc0(&fc6.y, (size_t)Fcb * rec) && alloc0(&mix.g, k6_rec) && alloc0(&fc6.g, (size_t)Fcb * rec);
+    mix.nseg = PP;
+    fc6.x = mix.y; fc6.dx = mix.g; fc6.masked = 0; fc6.drop = 2 * i;
+    fc7.x = fc6.y; fc7.dx = fc6.g; fc7.y = t->cat + (size_t)i * slice; fc7.g = t->dcat + (size_t)i * slice; fc7.drop = 2 * i + 1;
+    t->lin.insert(t->lin.end(), {mix, fc6, fc7});
+    part = std::max(part, seg_wgrad_part_elems(mix.K, c5, PP));
   }
-  ok = ok && alloc0(&t->cat, (size_t)T * Fcb * rec) && alloc0(&t->dcat, (size_t)T * Fcb * rec);
-  ok = ok && alloc0(&t->cls_rm, M * KC * sizeof(float)) && alloc0(&t->bbox_rm, M * 4 * C * sizeof(float));
-  ok = ok && alloc0(&t->g_cls, (size_t)(lin_np(KC) / 8) * rec) && alloc0(&t->g_bbox, (size_t)(lin_np(4 * C) / 8) * rec);
-  ok = ok && momentum(&t->v_cls, &t->vb_cls, (T - 1) * F, KC) && momentum(&t->v_bbox, &t->vb_bbox, F, 4 * C);
-  ok = ok && alloc0(&t->part, part * sizeof(float));
-  ok = ok && alloc0(&t->rois, M * 4 * sizeof(float)) && alloc0(&t->gt, M * 4 * sizeof(float)) && alloc0(&t->loss, 16);
-  ok = ok && alloc_sample_rows(t->smp, t->own, M);
-  return ok && t->own.alloc(&t->labels, M * sizeof(int), true) == MPN_OK;
+  LinT cls{p->wcls, p->bcls, nf * F, KC, 1, 0}, bbox{p->wbbox, p->bbbox, F, 4 * C, 1, 0};  // on the Foveal towers' concat; on the het tower
+  cls.x = t->cat; cls.dx = t->dcat;
+  bbox.x = t->cat + (size_t)nf * slice; bbox.dx = t->dcat + (size_t)nf * slice;
+  ok = ok && alloc0(&cls.y_rm, M * KC * sizeof(float)) && alloc0(&bbox.y_rm, M * 4 * C * sizeof(float));
+  ok = ok && alloc0(&cls.g, (size_t)(lin_np(KC) / 8) * rec) && alloc0(&bbox.g, (size_t)(lin_np(4 * C) / 8) * rec);
+  t->lin.insert(t->lin.end(), {cls, bbox});
+  for (LinT &L : t->lin) ok = ok && alloc_momentum(t->own, L);  // every layer is trained
+  t->bwd = {3 * T, 3 * T + 1};
+  for (int i = 0; i < T; ++i) t->bwd.insert(t->bwd.end(), {3 * i + 2, 3 * i + 1, 3 * i});
+  return ok && alloc0(&t->seg_part, part * sizeof(float)) && alloc_core(p, *t);
 }
 
 extern "C" int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight) {
   MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_tower_train(p, "mpn_mpnet_train_begin");
+  int rc = begin_refusals(p, true, __func__);
   if (rc) return rc;
-  if (p->tower_train) { set_error("mpn_mpnet_train_begin: training has already begun on this handle (mpn_mpnet_train_end first)"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(std::isfinite(momentum) && momentum >= 0.0f && std::isfinite(weight_decay) && weight_decay >= 0.0f && std::isfinite(bbox_weight));
-  MPN_CHECK_HIP(hipDeviceSynchronize());
   std::unique_ptr<TowerTrainState> t(new TowerTrainState());
-  t->momentum = momentum; t->weight_decay = weight_decay; t->bbox_weight = bbox_weight;
+  if ((rc = begin_core(*t, __func__, momentum, weight_decay, bbox_weight)) != MPN_OK) return rc;
   if (!alloc_tower_train_state(p, t.get()) || hipDeviceSynchronize() != hipSuccess) {
     set_error("mpn_mpnet_train_begin: allocating the momentum / activation / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
     return MPN_ENOMEM;
@@ -821,64 +942,7 @@ extern "C" int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_
 
 extern "C" int mpn_mpnet_train_end(mpn_frcnn *p) {
   MPN_CHECK_ARG(p != nullptr);
-  if (!p->tower_train) { set_error("mpn_mpnet_train_end: no mpn_mpnet_train_begin on this handle"); return MPN_ESTATE; }
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  delete p->tower_train;
-  p->tower_train = nullptr;
-  return MPN_OK;
-}
-
-// the state of a call between begin and end, or a refusal
-static int tower_state(mpn_frcnn *p, const char *fn, TowerTrainState **t) {
-  *t = p->tower_train;
-  if (*t) return MPN_OK;
-  set_error("%s: no mpn_mpnet_train_begin on this handle", fn);
-  return MPN_ESTATE;
-}
-
-static int mpnet_add_check(const mpn_frcnn *p, const TowerTrainState *t, const char *fn, int H0, int W0, int n, double *sc, int *H, int *W) {
-  return add_check(p, t->pending, fn, H0, W0, n, sc, H, W);
-}
-
-static int mpnet_add_rows(mpn_frcnn *p, TowerTrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
-                          const float *d_gt, const int *d_labels, int n, hipStream_t s);
-
-extern "C" int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_rois, const float *d_gt, const int *d_labels,
-                                   int n, void *stream) {
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_tower_train(p, "mpn_mpnet_train_add");
-  if (rc) return rc;
-  TowerTrainState *t;
-  if ((rc = tower_state(p, "mpn_mpnet_train_add", &t)) != MPN_OK) return rc;
-  MPN_CHECK_ARG(d_image && d_rois && d_gt && d_labels && n > 0 && H0 > 0 && W0 > 0);
-  double sc;
-  int H, W;
-  if ((rc = mpnet_add_check(p, t, "mpn_mpnet_train_add", H0, W0, n, &sc, &H, &W)) != MPN_OK) return rc;
-  ScratchScope scratch_scope(&p->scratch);
-  return mpnet_add_rows(p, t, d_image, H0, W0, H, W, sc, d_rois, d_gt, d_labels, n, as_stream(stream));
-}
-
-extern "C" int mpn_mpnet_train_add_sampled(mpn_frcnn *p, const float *d_image, int H0, int W0, const float *d_proposals, int n, const float *d_gt,
-                                           const int *d_gt_labels, int g, const float *d_crowds, int n_crowd, const mpn_roi_sampler *cfg,
-                                           uint64_t seed, uint64_t draw, int flip, int *h_counts, void *stream) {
-  const char *fn = "mpn_mpnet_train_add_sampled";
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_tower_train(p, fn);
-  if (rc) return rc;
-  TowerTrainState *t;
-  if ((rc = tower_state(p, fn, &t)) != MPN_OK) return rc;
-  if ((rc = check_sampled_args(fn, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, h_counts)) != MPN_OK) return rc;
-  ScratchScope scratch_scope(&p->scratch);
-  hipStream_t s = as_stream(stream);
-  rc = sample_image(t->smp, t->own, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, *cfg, seed, draw, flip ? W0 : 0, h_counts, s);
-  if (rc) return rc;
-  if (h_counts[0] == 0 || h_counts[1] == 0) return MPN_OK;  // no background or no foreground: nothing is added, the caller draws another image
-  const int r = sampled_rows(*cfg, h_counts);
-  double sc;
-  int H, W;
-  if ((rc = mpnet_add_check(p, t, fn, H0, W0, r, &sc, &H, &W)) != MPN_OK) return rc;
-  if (flip && (rc = flip_train_image(t->smp, t->own, d_image, H0, W0, s, &d_image)) != MPN_OK) return rc;
-  return mpnet_add_rows(p, t, d_image, H0, W0, H, W, sc, t->smp.rois, t->smp.gt, t->smp.labels, r, s);
+  return train_end(p, true, __func__);
 }
 
 // The body of mpn_mpnet_train_add on device row pointers, everything checked
@@ -915,118 +979,34 @@ static int mpnet_add_rows(mpn_frcnn *p, TowerTrainState *t, const float *d_image
     int cb_off = 0;
     for (int m = 0; m < 3; ++m) {
       if (!used[m]) continue;
-      float *dst = t->tw[i].x + ((size_t)cb_off * PP * Mp + t->pending) * 8;
+      float *dst = t->mix((int)i).x + ((size_t)cb_off * PP * Mp + t->pending) * 8;
       rc = roi_pool_pm_rmq(maps[m], p->vmax_tab[m], p->fov + 5 * T.region, n, c.pooled_h, c.pooled_w, scales[m], RoiRule{1.0f, 0, c.roi_bin_rule}, dst, s, 20, Mp,
                            p->conv345_norm ? 1 : 0, p->conv345_norm ? 1000.0f : kConv345Factor[m]);
       if (rc) return rc;
       cb_off += maps[m].Cb();
     }
   }
-  MPN_CHECK_HIP(hipMemcpyAsync(t->rois + (size_t)t->pending * 4, d_rois, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(t->gt + (size_t)t->pending * 4, d_gt, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  MPN_CHECK_HIP(hipMemcpyAsync(t->labels + t->pending, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
-  t->pending += n;
-  return MPN_OK;
+  return append_rows(*t, __func__, d_rois, d_gt, d_labels, n, s);
 }
 
 extern "C" int mpn_mpnet_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
   MPN_CHECK_ARG(p != nullptr);
-  int rc = refuse_tower_train(p, "mpn_mpnet_train_step");
+  TrainCore *core;
+  long step;
+  int rc = step_begin(p, true, __func__, lr, &core, &step);
   if (rc) return rc;
-  TowerTrainState *t;
-  if ((rc = tower_state(p, "mpn_mpnet_train_step", &t)) != MPN_OK) return rc;
-  if (t->pending <= 0) { set_error("mpn_mpnet_train_step: no pending rows (mpn_mpnet_train_add first)"); return MPN_ESTATE; }
-  MPN_CHECK_ARG(std::isfinite(lr));
-  const mpn_frcnn_config &c = p->cfg;
-  const int B = t->pending, Mp = p->Mp, PP = c.pooled_h * c.pooled_w, F = c.fc_dim, C = c.n_classes, KC = p->n_integral * C, c5 = p->feat_c;
-  const int T = (int)p->towers.size(), nf = T - 1, Fcb = lin_np(F) / 8;
-  const size_t slice = (size_t)Fcb * Mp * 8;  // a tower's columns of cat / dcat
+  TowerTrainState *t = static_cast<TowerTrainState *>(core);
+  const int B = t->pending, Mp = p->Mp, n = (int)t->lin.size();
   ScratchScope scratch_scope(&p->scratch);
   hipStream_t s = as_stream(stream);
-  const bool drop = t->drop_rate > 0.0f;
-  const float gscale = drop ? t->drop_scale : 1.0f;
-  const long step = t->step++;  // this step's masks; counted whatever the rate, also when a launch below fails
-  auto dropout = [&](float *y, int layer) {
-    const DropoutCfg dc{t->drop_threshold, (uint32_t)((uint64_t)t->seed & 0xffffffffu), (uint32_t)((uint64_t)t->seed >> 32), (uint32_t)layer,
-                        (uint32_t)((uint64_t)step & 0xffffffffu), t->drop_scale};
-    return dropout_c8(y, Mp, B, F, dc, s);
-  };
-  // forward: detect's GEMMs, one stream, tower after tower.  The mix runs over all PP * Mp rows of the operand (the valid ones are PP
-  // segments of B; a row's result depends on that row alone) and there is no ReLU between it and fc6 (multipathnet.lua: View, Linear)
-  for (int i = 0; i < T && rc == MPN_OK; ++i) {
-    const mpn_frcnn::Tower &W = p->towers[i];
-    const TowT &A = t->tw[i];
-    float *y7 = t->cat + (size_t)i * slice;
-    rc = linear_c8(A.x, PP * Mp, A.Kcat, W.mix_w, W.mix_b, c5, 0, A.m, nullptr, s, PP * Mp, nullptr, 2);
-    if (rc == MPN_OK) rc = linear_c8(A.m, B, p->K6, W.w6, W.b6, F, 1, A.y6, nullptr, s, Mp, nullptr, 1);
-    if (rc == MPN_OK && drop) rc = dropout(A.y6, 2 * i);
-    if (rc == MPN_OK) rc = linear_c8(A.y6, B, F, W.w7, W.b7, F, 1, y7, nullptr, s, Mp, nullptr, 1);
-    if (rc == MPN_OK && drop) rc = dropout(y7, 2 * i + 1);
-  }
-  if (rc == MPN_OK) rc = linear_c8(t->cat, B, nf * F, p->wcls, p->bcls, KC, 0, nullptr, t->cls_rm, s, Mp, nullptr, 1);
-  if (rc == MPN_OK) rc = linear_c8(t->cat + (size_t)nf * slice, B, F, p->wbbox, p->bbbox, 4 * C, 0, nullptr, t->bbox_rm, s, Mp, nullptr, 1);
+  rc = lin_forward(t->lin.data(), n, *t, B, Mp, step, s);  // one stream, tower after tower, then the two heads
   if (rc) return rc;
-  LossCfg lc{};
-  for (int i = 0; i < 4; ++i) { lc.mean[i] = c.bbox_mean[i]; lc.std[i] = c.bbox_std[i]; }
-  lc.norm = c.bbox_std[0] != 0.0f ? 1 : 0;
-  lc.bbox_weight = t->bbox_weight;
-  rc = train_loss_split(t->cls_rm, t->bbox_rm, B, C, p->n_integral, t->head_k, t->rois, t->gt, t->labels, lc, t->g_cls, t->g_bbox, Mp, d_loss ? d_loss : t->loss, s);
-  // backward: every input gradient before any update.  cat and y6 are what the dropout left, so [x > 0] is keep mask x ReLU mask
-  if (rc == MPN_OK) rc = linear_dgrad_c8(t->g_cls, Mp, B, KC, p->wcls, nf * F, t->cat, t->dcat, Mp, s, gscale);
-  if (rc == MPN_OK) rc = linear_dgrad_c8(t->g_bbox, Mp, B, 4 * C, p->wbbox, F, t->cat + (size_t)nf * slice, t->dcat + (size_t)nf * slice, Mp, s, gscale);
-  for (int i = 0; i < T && rc == MPN_OK; ++i) {
-    const mpn_frcnn::Tower &W = p->towers[i];
-    const TowT &A = t->tw[i];
-    rc = linear_dgrad_c8(t->dcat + (size_t)i * slice, Mp, B, F, W.w7, F, A.y6, A.g6, Mp, s, gscale);
-    if (rc == MPN_OK) rc = linear_dgrad_c8(A.g6, Mp, B, F, W.w6, p->K6, nullptr, A.gm, Mp, s);  // unmasked, fc6's (cb, bin) chunk order == m's layout
-  }
-  // the updates, in place on the packed weights detect reads: the heads, then per tower fc7, fc6, mix
-  const float mom = t->momentum, wd = t->weight_decay;
-  if (rc == MPN_OK) rc = sgd_wgrad_c8(t->g_cls, Mp, t->cat, Mp, B, KC, nf * F, 1, p->wcls, t->v_cls, lr, mom, wd, s);
-  if (rc == MPN_OK) rc = sgd_bias_c8(t->g_cls, Mp, B, KC, p->bcls, t->vb_cls, lr, mom, s);
-  if (rc == MPN_OK) rc = sgd_wgrad_c8(t->g_bbox, Mp, t->cat + (size_t)nf * slice, Mp, B, 4 * C, F, 1, p->wbbox, t->v_bbox, lr, mom, wd, s);
-  if (rc == MPN_OK) rc = sgd_bias_c8(t->g_bbox, Mp, B, 4 * C, p->bbbox, t->vb_bbox, lr, mom, s);
-  for (int i = 0; i < T && rc == MPN_OK; ++i) {
-    const mpn_frcnn::Tower &W = p->towers[i];
-    const TowT &A = t->tw[i];
-    const float *g7 = t->dcat + (size_t)i * slice;
-    rc = sgd_wgrad_c8(g7, Mp, A.y6, Mp, B, F, F, 1, W.w7, A.v7, lr, mom, wd, s);
-    if (rc == MPN_OK) rc = sgd_bias_c8(g7, Mp, B, F, W.b7, A.vb7, lr, mom, s);
-    if (rc == MPN_OK) rc = sgd_wgrad_c8(A.g6, Mp, A.m, Mp, B, F, p->K6, PP, W.w6, A.v6, lr, mom, wd, s);
-    if (rc == MPN_OK) rc = sgd_bias_c8(A.g6, Mp, B, F, W.b6, A.vb6, lr, mom, s);
-    if (rc == MPN_OK) rc = sgd_wgrad_seg_c8(A.gm, A.x, Mp, PP, B, c5, A.Kcat, t->part, W.mix_w, A.v_mix, lr, mom, wd, s);
-    if (rc == MPN_OK) rc = sgd_bias_seg_c8(A.gm, Mp, PP, B, c5, W.mix_b, A.vb_mix, lr, mom, s);
-  }
-  t->last_rows = B;
-  t->pending = 0;  // (also after a failed launch: the weights may be half updated, the batch is not to be replayed)
+  rc = train_loss_split(t->cls().y_rm, t->bbox().y_rm, B, p->cfg.n_classes, p->n_integral, t->head_k, t->rois, t->gt, t->labels, loss_cfg(p, *t), t->cls().g,
+                        t->bbox().g, Mp, d_loss ? d_loss : t->loss, s);
+  if (rc == MPN_OK) rc = lin_dgrad(t->lin.data(), t->bwd.data(), n, *t, B, Mp, s);
+  if (rc == MPN_OK) rc = lin_update(t->lin.data(), t->bwd.data(), n, *t, B, Mp, lr, t->seg_part, s);
+  step_end(*t);
   return rc;
-}
-
-extern "C" int mpn_mpnet_train_set_head(mpn_frcnn *p, int k) {
-  MPN_CHECK_ARG(p != nullptr);
-  TowerTrainState *t;
-  if (int rc = tower_state(p, "mpn_mpnet_train_set_head", &t)) return rc;
-  if (k < 0 || k >= p->n_integral) {
-    set_error("mpn_mpnet_train_set_head: invalid argument: head %d is outside [0, K) of this handle's K = %d integral classifiers", k, p->n_integral);
-    return MPN_EINVAL;
-  }
-  t->head_k = k;  // read by the next mpn_mpnet_train_step
-  return MPN_OK;
-}
-
-extern "C" int mpn_mpnet_train_set_dropout(mpn_frcnn *p, float rate, long seed) {
-  MPN_CHECK_ARG(p != nullptr);
-  TowerTrainState *t;
-  if (int rc = tower_state(p, "mpn_mpnet_train_set_dropout", &t)) return rc;
-  if (!(std::isfinite(rate) && rate >= 0.0f && rate < 1.0f)) {
-    set_error("mpn_mpnet_train_set_dropout: rate %g is outside [0, 1)", (double)rate);
-    return MPN_EINVAL;
-  }
-  t->drop_rate = rate;
-  t->drop_threshold = (uint32_t)std::floor((double)rate * 4294967296.0);
-  t->drop_scale = 1.0f / (1.0f - rate);
-  t->seed = seed;
-  return MPN_OK;
 }
 
 static int refuse_not_mpnet(const mpn_frcnn *p, const char *fn) {
@@ -1063,7 +1043,7 @@ extern "C" int mpn_mpnet_get_head_weights(mpn_frcnn *p, float *d_cls_w, float *d
 // [rows, Kcat_t, PH, PW] (valid until the next mpn_mpnet_train_add), "tower_train_y6.<t>" fc6's output behind the dropout [rows, F],
 // "tower_train_cat" [rows, T * F], "tower_train_cls" [rows, K * C], "tower_train_bbox" [rows, 4C], "tower_train_g_cls" [rows, K * C]
 int mpn::tower_train_debug_tensor(mpn_frcnn *p, const char *name, const float **d_ptr, size_t *n_elems) {
-  const TowerTrainState *t = p->tower_train;
+  TowerTrainState *t = p->tower_train;
   if (!t || t->last_rows <= 0) { set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_mpnet_train_step", name); return MPN_ESTATE; }
   const mpn_frcnn_config &c = p->cfg;
   const int R = t->last_rows, F = c.fc_dim, C = c.n_classes, KC = p->n_integral * C, T = (int)p->towers.size(), PP = c.pooled_h * c.pooled_w, Mp = p->Mp;
@@ -1072,7 +1052,7 @@ int mpn::tower_train_debug_tensor(mpn_frcnn *p, const char *name, const float **
   const bool is_x = sscanf(tail, "x.%d", &ti) == 1, is_y6 = !is_x && sscanf(tail, "y6.%d", &ti) == 1;
   if ((is_x || is_y6) && (ti < 0 || ti >= T)) { set_error("mpn_frcnn_debug_tensor: '%s': the handle has towers 0..%d", name, T - 1); return MPN_EINVAL; }
   size_t n = 0;
-  if (is_x) n = (size_t)R * t->tw[ti].Kcat * PP;
+  if (is_x) n = (size_t)R * t->mix(ti).K * PP;
   else if (is_y6) n = (size_t)R * F;
   else if (!strcmp(tail, "cat")) n = (size_t)R * T * F;
   else if (!strcmp(tail, "cls") || !strcmp(tail, "g_cls")) n = (size_t)R * KC;
@@ -1081,11 +1061,11 @@ int mpn::tower_train_debug_tensor(mpn_frcnn *p, const char *name, const float **
   MPN_CHECK_HIP(hipDeviceSynchronize());
   if (int rcd = grow_dbg(p, n * sizeof(float))) return rcd;
   int rc = MPN_OK;
-  if (is_x) rc = launch_unpack_pooled(t->tw[ti].x, R, t->tw[ti].Kcat, PP, Mp, p->dbg);
-  else if (is_y6) rc = c8_rows_to_rowmajor(t->tw[ti].y6, Mp, R, F, p->dbg, nullptr);
+  if (is_x) rc = launch_unpack_pooled(t->mix(ti).x, R, t->mix(ti).K, PP, Mp, p->dbg);
+  else if (is_y6) rc = c8_rows_to_rowmajor(t->fc6(ti).y, Mp, R, F, p->dbg, nullptr);
   else if (!strcmp(tail, "cat")) rc = c8_rows_to_rowmajor(t->cat, Mp, R, T * F, p->dbg, nullptr);  // the towers' blocks back to back == one C8 matrix
-  else if (!strcmp(tail, "g_cls")) rc = c8_rows_to_rowmajor(t->g_cls, Mp, R, KC, p->dbg, nullptr);
-  else MPN_CHECK_HIP(hipMemcpy(p->dbg, !strcmp(tail, "cls") ? t->cls_rm : t->bbox_rm, n * sizeof(float), hipMemcpyDeviceToDevice));
+  else if (!strcmp(tail, "g_cls")) rc = c8_rows_to_rowmajor(t->cls().g, Mp, R, KC, p->dbg, nullptr);
+  else MPN_CHECK_HIP(hipMemcpy(p->dbg, !strcmp(tail, "cls") ? t->cls().y_rm : t->bbox().y_rm, n * sizeof(float), hipMemcpyDeviceToDevice));
   if (rc) return rc;
   MPN_CHECK_HIP(hipDeviceSynchronize());
   *d_ptr = p->dbg; *n_elems = n;
@@ -1133,169 +1113,6 @@ extern "C" int mpn_debug_bench_train_poolbwd(mpn_frcnn *p, int iters, float *ms_
   return time_back_to_back(iters, ms_out, [&] { return maxpool2x2_backward_c8p(Y, dY, dX, 1, nullptr); });
 }
 
-// tests/test_gpu_train_kernels_numerics.py (debug flavour only): train.h's head-training kernels one launch at a time, on raw device
-// pointers in the kernels' own layouts, through the product's host wrappers (their grids, their MPN_CHECK_ARG) on the null stream.  Every
-// buffer comes with its element count and a buffer smaller than the footprint of its layout is refused before anything is launched — a
-// layout mistake of a test becomes MPN_EINVAL, never an access outside the test's allocation.  Footprints: K64 / 8 * NP * 8 for a packed
-// linear weight (K64 = K rounded up to 64), chunks * Mp * 8 for a C8 matrix, conv_wpk_elems for a packed conv weight, the whole
-// padded planes for a C8P map.  Dimensions a footprint cannot be computed from (<= 0) go to the wrapper, which refuses them.
-static bool dbg_short(const char *fn, const char *name, size_t have, size_t want) {
-  if (have >= want) return false;
-  set_error("%s: %s holds %zu elements, the launch's footprint is %zu", fn, name, have, want);
-  return true;
-}
-#define DBG_NEED(buf, have, want) do { if (dbg_short(__func__, #buf, (size_t)(have), (size_t)(want))) return MPN_EINVAL; } while (0)
-static size_t dbg_c8(int cols, int Mp) { return (size_t)cdiv(cols, 8) * Mp * 8; }
-static size_t dbg_lin_pack(int K, int N) { return (size_t)(round_up(K, 64) / 8) * lin_np(N) * 8; }
-
-extern "C" int mpn_debug_train_loss(const float *d_head, size_t n_head, int B, int C, int K, int k, const float *d_rois, size_t n_rois, const float *d_gt,
-                                    size_t n_gt, const int *d_labels, size_t n_labels, const float *mean4, const float *std4, int norm,
-                                    float bbox_weight, float *d_g_c8, size_t n_g, int Mp, float *d_loss, size_t n_loss) {
-  MPN_CHECK_ARG(mean4 && std4);
-  if (B > 0 && C > 1 && K >= 1 && Mp >= B) {
-    DBG_NEED(d_head, n_head, (size_t)B * (K + 4) * C);
-    DBG_NEED(d_rois, n_rois, (size_t)B * 4);
-    DBG_NEED(d_gt, n_gt, (size_t)B * 4);
-    DBG_NEED(d_labels, n_labels, (size_t)B);
-    DBG_NEED(d_g_c8, n_g, dbg_c8((K + 4) * C, Mp));
-    DBG_NEED(d_loss, n_loss, 2);
-  }
-  LossCfg cfg{};
-  for (int j = 0; j < 4; ++j) { cfg.mean[j] = mean4[j]; cfg.std[j] = std4[j]; }
-  cfg.norm = norm; cfg.bbox_weight = bbox_weight;
-  return train_loss(d_head, B, C, K, k, d_rois, d_gt, d_labels, cfg, d_g_c8, Mp, d_loss, nullptr);
-}
-
-extern "C" int mpn_debug_sgd_wgrad_c8(const float *d_g_c8, size_t n_g, int g_Mp, const float *d_x_c8, size_t n_x, int x_Mp, int B, int N, int K, int inner,
-                                      float *d_wpk, size_t n_w, float *d_vpk, size_t n_v, float lr, float momentum, float wd) {
-  if (B > 0 && N > 0 && K > 0 && g_Mp >= B && x_Mp >= B) {
-    DBG_NEED(d_g_c8, n_g, dbg_c8(N, g_Mp));
-    DBG_NEED(d_x_c8, n_x, dbg_c8(round_up(K, 64), x_Mp));
-    DBG_NEED(d_wpk, n_w, dbg_lin_pack(K, N));
-    DBG_NEED(d_vpk, n_v, dbg_lin_pack(K, N));
-  }
-  return sgd_wgrad_c8(d_g_c8, g_Mp, d_x_c8, x_Mp, B, N, K, inner, d_wpk, d_vpk, lr, momentum, wd, nullptr);
-}
-
-extern "C" int mpn_debug_sgd_bias_c8(const float *d_g_c8, size_t n_g, int g_Mp, int B, int N, float *d_bpk, size_t n_b, float *d_vb, size_t n_vb, float lr,
-                                     float momentum) {
-  if (B > 0 && N > 0 && g_Mp >= B) {
-    DBG_NEED(d_g_c8, n_g, dbg_c8(N, g_Mp));
-    DBG_NEED(d_bpk, n_b, (size_t)N);
-    DBG_NEED(d_vb, n_vb, (size_t)N);
-  }
-  return sgd_bias_c8(d_g_c8, g_Mp, B, N, d_bpk, d_vb, lr, momentum, nullptr);
-}
-
-extern "C" int mpn_debug_linear_dgrad_c8(const float *d_g_c8, size_t n_g, int g_Mp, int B, int N, const float *d_wpk, size_t n_w, int K, const float *d_act_c8,
-                                         size_t n_act, float *d_dx_c8, size_t n_dx, int x_Mp, float scale) {
-  if (B > 0 && N > 0 && K > 0 && g_Mp >= B && x_Mp >= B) {
-    DBG_NEED(d_g_c8, n_g, dbg_c8(N, g_Mp));
-    DBG_NEED(d_wpk, n_w, dbg_lin_pack(K, N));
-    if (d_act_c8) DBG_NEED(d_act_c8, n_act, dbg_c8(K, x_Mp));  // (null: the unmasked form)
-    DBG_NEED(d_dx_c8, n_dx, dbg_c8(K, x_Mp));
-  }
-  return linear_dgrad_c8(d_g_c8, g_Mp, B, N, d_wpk, K, d_act_c8, d_dx_c8, x_Mp, nullptr, scale);
-}
-
-// the segmented forms (MultiPathNet's mix layer): operands at row pitch nseg * Mp
-extern "C" int mpn_debug_sgd_wgrad_seg_c8(const float *d_g_c8, size_t n_g, const float *d_x_c8, size_t n_x, int Mp, int nseg, int B, int N, int K, float *d_part,
-                                          size_t n_part, float *d_wpk, size_t n_w, float *d_vpk, size_t n_v, float lr, float momentum, float wd) {
-  if (B > 0 && N > 0 && K > 0 && Mp >= B && nseg > 0 && nseg <= 65535) {
-    DBG_NEED(d_g_c8, n_g, dbg_c8(N, nseg * Mp));
-    DBG_NEED(d_x_c8, n_x, dbg_c8(round_up(K, 64), nseg * Mp));
-    DBG_NEED(d_part, n_part, seg_wgrad_part_elems(K, N, nseg));
-    DBG_NEED(d_wpk, n_w, dbg_lin_pack(K, N));
-    DBG_NEED(d_vpk, n_v, dbg_lin_pack(K, N));
-  }
-  return sgd_wgrad_seg_c8(d_g_c8, d_x_c8, Mp, nseg, B, N, K, d_part, d_wpk, d_vpk, lr, momentum, wd, nullptr);
-}
-
-extern "C" int mpn_debug_sgd_bias_seg_c8(const float *d_g_c8, size_t n_g, int Mp, int nseg, int B, int N, float *d_bpk, size_t n_b, float *d_vb, size_t n_vb,
-                                         float lr, float momentum) {
-  if (B > 0 && N > 0 && Mp >= B && nseg > 0) {
-    DBG_NEED(d_g_c8, n_g, dbg_c8(N, nseg * Mp));
-    DBG_NEED(d_bpk, n_b, (size_t)N);
-    DBG_NEED(d_vb, n_vb, (size_t)N);
-  }
-  return sgd_bias_seg_c8(d_g_c8, Mp, nseg, B, N, d_bpk, d_vb, lr, momentum, nullptr);
-}
-
-extern "C" int mpn_debug_dropout_c8(float *d_y_c8, size_t n_y, int Mp, int B, int N, uint32_t threshold, uint32_t seed_lo, uint32_t seed_hi, uint32_t layer,
-                                    uint32_t step, float scale) {
-  if (B > 0 && N > 0 && Mp >= B) DBG_NEED(d_y_c8, n_y, dbg_c8(N, Mp));
-  DropoutCfg cfg{};
-  cfg.threshold = threshold; cfg.seed_lo = seed_lo; cfg.seed_hi = seed_hi; cfg.layer = layer; cfg.step = step; cfg.scale = scale;
-  return dropout_c8(d_y_c8, Mp, B, N, cfg, nullptr);
-}
-
-extern "C" int mpn_debug_c8_rows_to_rowmajor(const float *d_c8, size_t n_c8, int Mp, int M, int N, float *d_y, size_t n_y) {
-  if (M > 0 && N > 0 && Mp >= M) {
-    DBG_NEED(d_c8, n_c8, dbg_c8(N, Mp));
-    DBG_NEED(d_y, n_y, (size_t)M * N);
-  }
-  return c8_rows_to_rowmajor(d_c8, Mp, M, N, d_y, nullptr);
-}
-
-extern "C" int mpn_debug_pack_linear_weights(const float *d_w, size_t n_w, const float *d_b, size_t n_b, int K, int N, int inner, float *d_wpk, size_t n_wpk,
-                                             float *d_bpk, size_t n_bpk) {
-  if (K > 0 && N > 0) {
-    DBG_NEED(d_w, n_w, (size_t)K * N);
-    if (d_b) DBG_NEED(d_b, n_b, (size_t)N);
-    DBG_NEED(d_wpk, n_wpk, dbg_lin_pack(K, N));
-    DBG_NEED(d_bpk, n_bpk, (size_t)lin_np(N));
-  }
-  return pack_linear_weights(d_w, d_b, K, N, inner, d_wpk, d_bpk, nullptr);
-}
-
-extern "C" int mpn_debug_unpack_linear_weights(const float *d_wpk, size_t n_wpk, const float *d_bpk, size_t n_bpk, int K, int N, int inner, int n0, int n1,
-                                               float *d_w, size_t n_w, float *d_b, size_t n_b) {
-  if (K > 0 && N > 0 && n0 >= 0 && n1 > n0 && n1 <= N) {
-    DBG_NEED(d_wpk, n_wpk, dbg_lin_pack(K, N));
-    DBG_NEED(d_bpk, n_bpk, (size_t)lin_np(N));
-    if (d_w) DBG_NEED(d_w, n_w, (size_t)(n1 - n0) * K);
-    if (d_b) DBG_NEED(d_b, n_b, (size_t)(n1 - n0));
-  }
-  return unpack_linear_weights(d_wpk, d_bpk, K, N, inner, n0, n1, d_w, d_b, nullptr);
-}
-
-extern "C" int mpn_debug_conv_sgd(float *d_wpk, size_t n_w, float *d_vpk, size_t n_v, const float *d_dw, size_t n_dw, int Cin, int Cout, float lr,
-                                  float momentum, float wd) {
-  if (Cin > 0 && Cout > 0) {
-    DBG_NEED(d_wpk, n_w, conv_wpk_elems(Cin, Cout));
-    DBG_NEED(d_vpk, n_v, conv_wpk_elems(Cin, Cout));
-    DBG_NEED(d_dw, n_dw, conv_wpk_elems(Cin, Cout));
-  }
-  return conv_sgd(d_wpk, d_vpk, d_dw, Cin, Cout, lr, momentum, wd, nullptr);
-}
-
-extern "C" int mpn_debug_vec_sgd(float *d_b, size_t n_b, float *d_vb, size_t n_vb, const float *d_db, size_t n_db, int n, float lr, float momentum) {
-  if (n > 0) {
-    DBG_NEED(d_b, n_b, (size_t)n);
-    DBG_NEED(d_vb, n_vb, (size_t)n);
-    DBG_NEED(d_db, n_db, (size_t)n);
-  }
-  return vec_sgd(d_b, d_vb, d_db, n, lr, momentum, nullptr);
-}
-
-// the two maps as make_act lays a C x H x W map out (mpn_debug_conv3x3_form's rule)
-extern "C" int mpn_debug_relu_mask_c8p(float *d_g, size_t n_g, const float *d_x, size_t n_x, int C, int H, int W) {
-  MPN_CHECK_ARG(C > 0 && H > 0 && W > 0);
-  DBG_NEED(d_g, n_g, act_bytes(C, H, W) / sizeof(float));
-  DBG_NEED(d_x, n_x, act_bytes(C, H, W) / sizeof(float));
-  return relu_mask_c8p(make_act(d_g, C, H, W), make_act(const_cast<float *>(d_x), C, H, W), nullptr);
-}
-
-extern "C" int mpn_debug_unpack_conv_weights(const float *d_wpk, size_t n_wpk, const float *d_bpk, size_t n_bpk, int Cin, int Cout, float *d_w, size_t n_w,
-                                             float *d_b, size_t n_b) {
-  if (Cin > 0 && Cout > 0) {
-    DBG_NEED(d_wpk, n_wpk, conv_wpk_elems(Cin, Cout));
-    if (d_b) { DBG_NEED(d_bpk, n_bpk, (size_t)Cout); DBG_NEED(d_b, n_b, (size_t)Cout); }
-    if (d_w) DBG_NEED(d_w, n_w, (size_t)Cout * Cin * 9);
-  }
-  return unpack_conv_weights(d_wpk, d_bpk, Cin, Cout, d_w, d_b, nullptr);
-}
-#undef DBG_NEED
 
 #endif
 

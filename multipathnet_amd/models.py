@@ -856,11 +856,26 @@ class FastRCNN(object):
         check(self._lib.mpn_frcnn_train_set_dropout(self._h, float(rate), int(seed)), "mpn_frcnn_train_set_dropout")
         self._dropout = (float(rate), int(seed))
 
+    # the entry points the two trainers (mpn_frcnn_train_*, mpn_mpnet_train_*) share the signature of, under the entry's name
+    def _train_call(self, entry, *args):
+        check(getattr(self._lib, entry)(self._h, *args), entry)
+
+    def _train_add(self, entry, image, rois, gt_boxes, labels):
+        H, W = image.shape[1:]
+        n = rois.size(0)
+        assert gt_boxes.shape == rois.shape and labels.numel() == n and labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
+        self._train_call(entry, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream())
+
+    def _train_step(self, entry, lr):
+        loss = torch.empty(2, dtype=torch.float32, device=self.device)
+        self._train_call(entry, C.c_float(lr), _f(loss), _stream())
+        return loss
+
     def train_set_head(self, k):
         """The integral loss's selector (integral_selector.index, train.lua:288-294): the next train_step's loss reads classifier k of
         the handle's n_integral, 0-based; train_begin starts at 0.  The other classifiers get a zero gradient and are still stepped
         (weight decay, momentum).  The schedule is the caller's: it is not part of train_state()."""
-        check(self._lib.mpn_frcnn_train_set_head(self._h, int(k)), "mpn_frcnn_train_set_head")
+        self._train_call("mpn_frcnn_train_set_head", int(k))
 
     def _trained(self):
         """(names of the head tensors the current depth trains, indices of the conv layers it trains)"""
@@ -915,11 +930,7 @@ class FastRCNN(object):
     def train_add(self, image, rois, gt_boxes, labels):
         """Append one image's rows to the pending minibatch: image [3,H,W] fp32 in [0,1], rois / gt_boxes [n,4] in the image's own
         coordinates (as detect takes boxes), labels [n] int32, 0 = background — all on the device.  The trunk runs frozen."""
-        H, W = image.shape[1:]
-        n = rois.size(0)
-        assert gt_boxes.shape == rois.shape and labels.numel() == n and labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
-        check(self._lib.mpn_frcnn_train_add(self._h, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream()),
-              "mpn_frcnn_train_add")
+        self._train_add("mpn_frcnn_train_add", image, rois, gt_boxes, labels)
 
     def _add_sampled(self, entry, image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes, flip):
         from .train import _dev_f32, _dev_i32, _ptr
@@ -942,12 +953,10 @@ class FastRCNN(object):
 
     def train_step(self, lr):
         """Head forward, loss, backward and the SGD update on the pending rows -> device tensor [2] = (cls loss, bbox loss)."""
-        loss = torch.empty(2, dtype=torch.float32, device=self.device)
-        check(self._lib.mpn_frcnn_train_step(self._h, C.c_float(lr), _f(loss), _stream()), "mpn_frcnn_train_step")
-        return loss
+        return self._train_step("mpn_frcnn_train_step", lr)
 
     def train_end(self):
-        check(self._lib.mpn_frcnn_train_end(self._h), "mpn_frcnn_train_end")
+        self._train_call("mpn_frcnn_train_end")
 
     def head_weights(self):
         """The handle's current fc6 / fc7 / cls / bbox weights and biases in Torch layout, under synthetic_params' keys (device tensors):
@@ -987,15 +996,11 @@ class FastRCNN(object):
 
     def tower_train_set_head(self, k):
         """The integral loss's selector: the next tower_train_step's loss reads classifier k of n_integral (train_set_head's rule)."""
-        check(self._lib.mpn_mpnet_train_set_head(self._h, int(k)), "mpn_mpnet_train_set_head")
+        self._train_call("mpn_mpnet_train_set_head", int(k))
 
     def tower_train_add(self, image, rois, gt_boxes, labels):
         """train_add for the towers: one image's rows behind the pending ones (the same arguments)."""
-        H, W = image.shape[1:]
-        n = rois.size(0)
-        assert gt_boxes.shape == rois.shape and labels.numel() == n and labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous()
-        check(self._lib.mpn_mpnet_train_add(self._h, _f(image, "image"), H, W, _f(rois, "rois"), _f(gt_boxes, "gt_boxes"), _i(labels), n, _stream()),
-              "mpn_mpnet_train_add")
+        self._train_add("mpn_mpnet_train_add", image, rois, gt_boxes, labels)
 
     def tower_train_add_sampled(self, image, proposals, gt_boxes, gt_labels, sampler, draw, crowd_boxes=None, flip=False):
         """train_add_sampled for the towers (mpn_mpnet_train_add_sampled): the same arguments -> (n_bg, n_fg)."""
@@ -1003,12 +1008,10 @@ class FastRCNN(object):
 
     def tower_train_step(self, lr):
         """Forward, loss, backward and the SGD update of every tower and both heads on the pending rows -> device tensor [2] = (cls, bbox)."""
-        loss = torch.empty(2, dtype=torch.float32, device=self.device)
-        check(self._lib.mpn_mpnet_train_step(self._h, C.c_float(lr), _f(loss), _stream()), "mpn_mpnet_train_step")
-        return loss
+        return self._train_step("mpn_mpnet_train_step", lr)
 
     def tower_train_end(self):
-        check(self._lib.mpn_mpnet_train_end(self._h), "mpn_mpnet_train_end")
+        self._train_call("mpn_mpnet_train_end")
 
     def tower_weights(self):
         """The MultiPathNet handle's parameters as synthetic_mpnet_params shapes them (device tensors): the towers' and heads' current

@@ -3,7 +3,7 @@ train.h documents operation by operation: train_loss, sgd_wgrad_c8, sgd_bias_c8,
 vec_sgd and relu_mask_c8p.  Until now they were reachable only through mpn_frcnn_train_step on one tiny network (K6 = 1568, fc_dim <= 128,
 C <= 7, B <= 200, read back through unpack_linear_weights, which skips every pad lane).
 
-The kernels are called through the mpn_debug_* pass-throughs of train_driver.hip (debug flavour only): raw device pointers in the kernels'
+The kernels are called through the mpn_debug_* pass-throughs of train_debug.hip (debug flavour only): raw device pointers in the kernels'
 own layouts, the product's host wrappers, and an element count per buffer that turns a layout mistake of this file into MPN_EINVAL.  The
 layouts and references are tests/train_kernels_np.py's (checked on the CPU in tests/test_train_kernels_ref_cpu.py).
 
