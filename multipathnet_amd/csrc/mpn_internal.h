@@ -139,9 +139,11 @@ int nms_batched_under_trunk(const float *d_scored, const int *d_counts, int n_cl
 // compile-time constant, no mpn_debug_* symbol is exported and the timing-only kernel instantiations are not built.
 #ifdef MPN_DEBUG_HOOKS
 #define MPN_KNOB(type, name, init) static type name = init
+#define MPN_KNOB_SHARED(type, name, init) inline type name = init  // a knob read by several files: defined in their shared header
 #define MPN_ABLATE(expr) (expr)
 #else
 #define MPN_KNOB(type, name, init) static constexpr type name = init
+#define MPN_KNOB_SHARED(type, name, init) inline constexpr type name = init
 #define MPN_ABLATE(expr) 0
 #endif
 

@@ -1,6 +1,7 @@
 // resnet.h — ResNet Fast R-CNN graph (models/resnet.lua:24-50): trunk conv1 / max-pool / layer1-3 on the
 // image, ROIPooling(14,14,1/16), per-ROI layer4 + global average pool.  fp32 MFMA, BN folded into the convolutions by the
-// caller.  Used by pipeline.hip (mpn_resnet_create); kernels in resnet.hip.
+// caller.  Used by pipeline.hip (mpn_resnet_create); kernels in resnet.hip (convolutions)
+// and graph_pool.hip (pooling).
 //
 // Layout "C8I": [C/8][B*H*W rows, pitch rounded up to 128][8] fp32 — a batch of channel-blocked maps WITHOUT halos: the generic
 // convolution gathers its input pixels with explicit bounds checks (7x7 pad 3, strides 1/2, 14x14 and 7x7 per-ROI maps), so a

@@ -7,31 +7,9 @@
 // the packed weights and the 4-KiB activation slice is GATHERED (one 16-byte load per thread, zero outside the map), both
 // staged through registers into double-buffered LDS; every MFMA operand fetch is then the same conflict-free ds_read_b128
 // as in dense.hip's kernels.  16 KiB of LDS per block lets several blocks share a CU, which hides the gather latency.
-#include <algorithm>
-#include <cmath>
-#include <type_traits>
-#include <utility>
-#include <vector>
-
-#include "../../include/mpn.h"
-#include "resnet.h"
+#include "graph_internal.h"
 
 namespace mpn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct ActI {  // C8I batch of maps: element (b, c, y, x) at ((c/8) * pitch + (b*H + y)*W + x) * 8 + c%8
-  float *p;
-  int B, C, H, W;
-  const float *planar = nullptr;  // the image only: the same transformed pixels as [3][H][W] planes (the im2col first layer reads these)
-  int Cb() const { return (C + 7) / 8; }
-  size_t rows() const { return (size_t)B * H * W; }
-  size_t pitch() const { return (rows() + 127) / 128 * 128; }  // rows per channel-block plane (a C8 matrix of `rows` rows)
-};
-static size_t c8i_elems(int B, int C, int H, int W) {  // allocation size: planes rounded up to the GEMM's 128-column tiles
-  return (size_t)(round_up(C, 128) / 8) * (((size_t)B * H * W + 127) / 128 * 128) * 8;
-}
 
 // ------------------------------------------------------------------------------------------------------------------------
 // packed weights: [tap = ky*KW + kx][Cin8/8][CoutP][8], CoutP = round_up(Cout, 128); bias [CoutP]
@@ -222,129 +200,6 @@ __global__ void conv_splitk_finalize_kernel(const float *__restrict__ part, int 
   *reinterpret_cast<f32x4 *>(out + off) = v;
 }
 
-// nn.SpatialMaxPooling(k,k,s,s,p,p), floor mode, on C8I
-__global__ void maxpool2d_c8i_kernel(const float *__restrict__ in, int Cb, int B, int H, int W, size_t pitch_in, int k, int stride, int pad, int OH,
-                                     int OW, size_t pitch_out, float *__restrict__ out) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)Cb * B * OH * OW * 2;
-  if (t >= total) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const int ox = (int)(r % OW); r /= OW;
-  const int oy = (int)(r % OH); r /= OH;
-  const int b = (int)(r % B); const size_t cb = r / B;
-  f32x4 m = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  for (int ky = 0; ky < k; ++ky)
-    for (int kx = 0; kx < k; ++kx) {
-      const int iy = oy * stride + ky - pad, ix = ox * stride + kx - pad;
-      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(in + (cb * pitch_in + ((size_t)b * H + iy) * W + ix) * 8 + h * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
-    }
-  *reinterpret_cast<f32x4 *>(out + (cb * pitch_out + ((size_t)b * OH + oy) * OW + ox) * 8 + h * 4) = m;
-}
-
-// image transformer (modules/ImageTransformer.lua:19-33, f64 arithmetic) into a one-map C8I image (channels 3..7 zero)
-__global__ void image_transform_c8i_kernel(const float *__restrict__ in, int H, int W, int s0, int s1, int s2, double scale, double m0,
-                                           double m1, double m2, double d0, double d1, double d2, int has_std, float *__restrict__ out,
-                                           float *__restrict__ planar) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t plane = (size_t)H * W;
-  if (t >= plane) return;
-  double v0 = (double)in[(size_t)s0 * plane + t], v1 = (double)in[(size_t)s1 * plane + t], v2 = (double)in[(size_t)s2 * plane + t];
-  if (scale != 1.0) { v0 = v0 * scale; v1 = v1 * scale; v2 = v2 * scale; }
-  v0 = v0 + (-m0); v1 = v1 + (-m1); v2 = v2 + (-m2);
-  if (has_std) { v0 = v0 / d0; v1 = v1 / d1; v2 = v2 / d2; }
-  *reinterpret_cast<f32x4 *>(out + t * 8) = f32x4{(float)v0, (float)v1, (float)v2, 0.0f};
-  *reinterpret_cast<f32x4 *>(out + t * 8 + 4) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  if (planar) { planar[t] = (float)v0; planar[plane + t] = (float)v1; planar[2 * plane + t] = (float)v2; }
-}
-
-// inn.ROIPooling on a one-map C8I feature -> [N][Cb][PH][PW][8] (the batch the per-ROI head convolves); the bin arithmetic
-// is the same as roi_pool_c8_kernel / the oracle's orc_roi_pool (coord_offset 1, end_adjust 0)
-__global__ void roi_pool_c8i_kernel(const float *__restrict__ feat, int Cb, int H, int W, size_t pitch_f, const float *__restrict__ rois, int roi_stride,
-                                    int N, int PH, int PW, float scale, float *__restrict__ out, size_t pitch_o, int roi_bins) {
-  const int PP = PH * PW;
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)N * Cb * PP * 2;
-  if (t >= total) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const int bin = (int)(r % PP); r /= PP;
-  const int cb = (int)(r % Cb); const int n = (int)(r / Cb);
-  const int ph = bin / PW, pw = bin - ph * PW;
-  const float *ro = rois + (size_t)roi_stride * n;
-  int hs, he, ws, we;
-  roi_bin_bounds(ro, scale, RoiRule{1.0f, 0, roi_bins}, H, W, PH, PW, ph, pw, hs, he, ws, we);
-  const bool empty = (he <= hs) || (we <= ws);
-  f32x4 m = empty ? f32x4{0, 0, 0, 0} : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  const float *fp = feat + (size_t)cb * pitch_f * 8 + h * 4;
-  for (int y = hs; y < he; ++y)
-    for (int x = ws; x < we; ++x) {
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(fp + ((size_t)y * W + x) * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
-    }
-  *reinterpret_cast<f32x4 *>(out + ((size_t)cb * pitch_o + ((size_t)n * PH + ph) * PW + pw) * 8 + h * 4) = m;
-}
-
-// the same pooling with the bin arithmetic done once per (roi, bin): a thread owns one output row for CBG channel blocks, reads
-// whole 32-byte records and a wave stores 64 consecutive records (the kernel above spends most of its instructions on the
-// per-thread bin arithmetic for 16 output bytes).  Same cells, same comparisons, same order: bit-identical to it.
-template <int CBG>
-__global__ __launch_bounds__(256) void roi_pool_c8i_rows_kernel(const float *__restrict__ feat, int H, int W, size_t pitch_f, const float *__restrict__ rois,
-                                                                 int roi_stride, int N, int PH, int PW, float scale, float *__restrict__ out, size_t pitch_o,
-                                                                 int fc_mp, int roi_bins) {
-  const int PP = PH * PW;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)N * PP) return;
-  const int n = (int)(t / PP), bin = (int)(t - (size_t)n * PP);
-  const int ph = bin / PW, pw = bin - ph * PW;
-  const float *ro = rois + (size_t)roi_stride * n;
-  int hs, he, ws, we;
-  roi_bin_bounds(ro, scale, RoiRule{1.0f, 0, roi_bins}, H, W, PH, PW, ph, pw, hs, he, ws, we);
-  const bool empty = (he <= hs) || (we <= ws);
-  const int cb0 = blockIdx.y * CBG;
-  const float *fp = feat + (size_t)cb0 * pitch_f * 8;
-  // fc_mp > 0: the (bin, roi)-row C8 matrix [Cb][PP][fc_mp][8] a fully-connected first layer reads as its GEMM operand
-  // (plane = (channel block, bin), row = roi — the VGG pipeline's fc6 layout), instead of the C8I batch of maps
-  float *op = fc_mp > 0 ? out + (((size_t)cb0 * PP + bin) * fc_mp + n) * 8 : out + ((size_t)cb0 * pitch_o + t) * 8;
-  const size_t plane_o = fc_mp > 0 ? (size_t)PP * fc_mp : pitch_o;
-  const float lowest = empty ? 0.0f : -INFINITY;
-  f32x4 lo[CBG], hi[CBG];
-#pragma unroll
-  for (int c = 0; c < CBG; ++c) lo[c] = hi[c] = f32x4{lowest, lowest, lowest, lowest};
-  for (int y = hs; y < he; ++y)
-    for (int x = ws; x < we; ++x) {
-      const float *px = fp + ((size_t)y * W + x) * 8;
-#pragma unroll
-      for (int c = 0; c < CBG; ++c) {
-        const f32x4 a = *reinterpret_cast<const f32x4 *>(px + (size_t)c * pitch_f * 8), b = *reinterpret_cast<const f32x4 *>(px + (size_t)c * pitch_f * 8 + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lo[c][e] = a[e] > lo[c][e] ? a[e] : lo[c][e]; hi[c][e] = b[e] > hi[c][e] ? b[e] : hi[c][e]; }
-      }
-    }
-#pragma unroll
-  for (int c = 0; c < CBG; ++c) {
-    *reinterpret_cast<f32x4 *>(op + (size_t)c * plane_o * 8) = lo[c];
-    *reinterpret_cast<f32x4 *>(op + (size_t)c * plane_o * 8 + 4) = hi[c];
-  }
-}
-
-// 7x7 global average pool of [N][Cb][H][W][8] into the C8 matrix [Cb][Mp][8] the head GEMM reads (row = roi); the sum
-// runs in row-major order like the oracle's, then * 1/(H*W)
-__global__ void avgpool_c8i_to_c8_kernel(const float *__restrict__ in, int N, int Cb, int HW, size_t pitch, float inv, float *__restrict__ out,
-                                         int Mp) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)N * Cb * 2;
-  if (t >= total) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const int n = (int)(r % N); const int cb = (int)(r / N);
-  const float *ip = in + ((size_t)cb * pitch + (size_t)n * HW) * 8 + h * 4;
-  f32x4 sacc = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int i = 0; i < HW; ++i) sacc += *reinterpret_cast<const f32x4 *>(ip + (size_t)i * 8);
-  *reinterpret_cast<f32x4 *>(out + ((size_t)cb * Mp + n) * 8 + h * 4) = sacc * inv;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // bf16 variant (SURVEY §8f rank 3 asks for the ResNet / Inception trunks in bf16): activations and weights stored as bf16
 // (round-to-nearest-even), products accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (K = 16 per instruction = two 8-channel
@@ -352,26 +207,6 @@ __global__ void avgpool_c8i_to_c8_kernel(const float *__restrict__ in, int N, in
 // the k order inside the instruction cannot matter), bias / residual / ReLU in fp32, one rounding to bf16 at the store.
 // Layout: C8I with 16-byte records [C/8][rows, pitch][8 x bf16]; channel-block count padded to even (zero planes).
 // ------------------------------------------------------------------------------------------------------------------------
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// fp32 -> bf16, round to nearest even: gfx950's own conversion (v_cvt_pk_bf16_f32, two values per instruction).  Every kernel of this
-// file rounds through these two helpers, so kernels that share a K order stay bit-identical to each other.  (The bit-arithmetic form
-// — add 0x7fff + lsb, shift — costs 4-5 VALU instructions per value; at 128 accumulators per lane that was 10-20 % of a convolution
-// launch: VALU work never overlaps the wave's MFMAs on this chip.)
-typedef __bf16 hwbf16x2 __attribute__((ext_vector_type(2)));
-typedef float cvtf32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {  // bits 0-15 = bf16(lo), bits 16-31 = bf16(hi)
-  const cvtf32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, hwbf16x2));
-}
-__device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf16x2(f, 0.0f) & 0xffffu); }
-// The ReLU of every bf16 convolution epilogue, switched by a wave-uniform flag: one v_med3_f32 (v, 0, +inf), which maps NaN to 0 (as
-// Torch's Threshold does; include/mpn.h).  Off, the value passes untouched: a med3 against -inf would turn NaN into -inf.
-__device__ __forceinline__ float relu_bf(float v, bool on) { return on ? __builtin_amdgcn_fmed3f(v, 0.0f, __builtin_inff()) : v; }
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((unsigned)h << 16); }
 
 // packed bf16 weights: [tap][nch2][CoutP][8], nch2 = Cin chunks rounded up to even
 __global__ void pack_conv_bf16_kernel(const float *__restrict__ w, int Cin, int Cout, int KK, int nch2, int CoutP, bf16_t *__restrict__ wpk) {
@@ -1933,491 +1768,6 @@ __global__ __launch_bounds__(256) void conv2d_c8i_pf_kernel(GConvArgs a) {
   }
 }
 
-// one thread = one 16-byte pixel record (8 channels)
-__global__ void maxpool2d_c8i_bf16_kernel(const bf16_t *__restrict__ in, int Cb, int B, int H, int W, size_t pitch_in, int k, int stride, int pad,
-                                          int OH, int OW, size_t pitch_out, bf16_t *__restrict__ out) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)Cb * B * OH * OW;
-  if (t >= total) return;
-  size_t r = t;
-  const int ox = (int)(r % OW); r /= OW;
-  const int oy = (int)(r % OH); r /= OH;
-  const int b = (int)(r % B); const size_t cb = r / B;
-  float m[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
-  const u32x4 *ip = reinterpret_cast<const u32x4 *>(in) + cb * pitch_in + (size_t)b * H * W;
-  for (int ky = 0; ky < k; ++ky)
-    for (int kx = 0; kx < k; ++kx) {
-      const int iy = oy * stride + ky - pad, ix = ox * stride + kx - pad;
-      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      const u32x4 v = ip[(size_t)iy * W + ix];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned w = v[e];
-        const float lo = __uint_as_float(w << 16), hi = __uint_as_float(w & 0xffff0000u);
-        m[2 * e] = lo > m[2 * e] ? lo : m[2 * e];
-        m[2 * e + 1] = hi > m[2 * e + 1] ? hi : m[2 * e + 1];
-      }
-    }
-  u32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(m[2 * e], m[2 * e + 1]);
-  reinterpret_cast<u32x4 *>(out)[cb * pitch_out + ((size_t)b * OH + oy) * OW + ox] = o;
-}
-
-// transformed image as bf16 C8I with TWO channel-block planes (channels 3..15 zero: the MFMA consumes chunk pairs)
-__global__ void image_transform_c8i_bf16_kernel(const float *__restrict__ in, int H, int W, int s0, int s1, int s2, double scale, double m0,
-                                                double m1, double m2, double d0, double d1, double d2, int has_std, bf16_t *__restrict__ out,
-                                                size_t pitch) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t plane = (size_t)H * W;
-  if (t >= plane) return;
-  double v0 = (double)in[(size_t)s0 * plane + t], v1 = (double)in[(size_t)s1 * plane + t], v2 = (double)in[(size_t)s2 * plane + t];
-  if (scale != 1.0) { v0 = v0 * scale; v1 = v1 * scale; v2 = v2 * scale; }
-  v0 = v0 + (-m0); v1 = v1 + (-m1); v2 = v2 + (-m2);
-  if (has_std) { v0 = v0 / d0; v1 = v1 / d1; v2 = v2 / d2; }
-  u16x4 lo = {f2bf((float)v0), f2bf((float)v1), f2bf((float)v2), 0}, z = {0, 0, 0, 0};
-  *reinterpret_cast<u16x4 *>(out + t * 8) = lo;
-  *reinterpret_cast<u16x4 *>(out + t * 8 + 4) = z;
-  *reinterpret_cast<u16x4 *>(out + (pitch + t) * 8) = z;
-  *reinterpret_cast<u16x4 *>(out + (pitch + t) * 8 + 4) = z;
-}
-
-__global__ void roi_pool_c8i_bf16_kernel(const bf16_t *__restrict__ feat, int Cb, int H, int W, size_t pitch_f, const float *__restrict__ rois,
-                                         int roi_stride, int N, int PH, int PW, float scale, bf16_t *__restrict__ out, size_t pitch_o, int roi_bins) {
-  const int PP = PH * PW;
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)N * Cb * PP * 2;
-  if (t >= total) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const int bin = (int)(r % PP); r /= PP;
-  const int cb = (int)(r % Cb); const int n = (int)(r / Cb);
-  const int ph = bin / PW, pw = bin - ph * PW;
-  const float *ro = rois + (size_t)roi_stride * n;
-  int hs, he, ws, we;
-  roi_bin_bounds(ro, scale, RoiRule{1.0f, 0, roi_bins}, H, W, PH, PW, ph, pw, hs, he, ws, we);
-  const bool empty = (he <= hs) || (we <= ws);
-  f32x4 m = empty ? f32x4{0, 0, 0, 0} : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  const bf16_t *fp = feat + (size_t)cb * pitch_f * 8 + h * 4;
-  for (int y = hs; y < he; ++y)
-    for (int x = ws; x < we; ++x) {
-      const u16x4 v = *reinterpret_cast<const u16x4 *>(fp + ((size_t)y * W + x) * 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float f = bf2f(v[e]); m[e] = f > m[e] ? f : m[e]; }
-    }
-  u16x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = f2bf(m[e]);
-  *reinterpret_cast<u16x4 *>(out + ((size_t)cb * pitch_o + ((size_t)n * PH + ph) * PW + pw) * 8 + h * 4) = o;
-}
-
-// ---- ROI max-pooling, bf16, fast path ---------------------------------------------------------------------------------------
-// The kernel above spends ~200 instructions per 8 output bytes (per-thread bin arithmetic, 4 channels per thread).  Here the
-// feature map is first re-coded so that bf16 order is int16 order (negative values: magnitude bits flipped — a monotone,
-// self-inverse map, so max commutes with it), and a thread owns one (roi, bin) for a run of
-// channel blocks: the bin arithmetic is done once, each pixel record (8 channels) costs one 16-byte load + 4 v_pk_max_i16, and a
-// wave's stores are 64 consecutive records.  Against roi_pool_c8i_bf16_kernel's `f > m` the result is the same VALUE everywhere and the same
-// bits except the sign of a zero: a window whose maximum is zero and that holds both zeros gives +0 here (code 0 > code -1) and the zero met
-// first there.  NaNs: the encoder below gives a NaN of either sign -inf's code, so — as `f > m` from -inf does — the maxima ignore the NaNs of
-// a window and a window of NaNs alone gives -inf (include/mpn.h); the raw order would have put +NaN above +inf.
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned bf16x2_sortable(unsigned x) { return x ^ (((x >> 15) & 0x00010001u) * 0x7fffu); }
-
-__device__ __forceinline__ unsigned bf16x2_sortable_enc(unsigned x) {  // bf16x2_sortable, NaN -> the code of -inf (0x807f)
-  unsigned c = bf16x2_sortable(x);
-  if ((x & 0x00007fffu) > 0x00007f80u) c = (c & 0xffff0000u) | 0x0000807fu;
-  if ((x & 0x7fff0000u) > 0x7f800000u) c = (c & 0x0000ffffu) | 0x807f0000u;
-  return c;
-}
-
-__global__ void bf16_sortable_kernel(const u32x4 *__restrict__ in, size_t n, u32x4 *__restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  u32x4 v = in[t];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = bf16x2_sortable_enc(v[e]);
-  out[t] = v;
-}
-
-// vertical range-max (sparse) table level of the sortable map: out[y] = max(prev[y], prev[y + step]) = max over rows y .. y + 2 * step - 1
-// (rows past H - 2 * step are never queried).  The fused ROI max-pool below then reads two rows per window column instead of all of them.
-__global__ void vmax_level_sorted_kernel(const u32x4 *__restrict__ prev, u32x4 *__restrict__ out, int H, int W, size_t pitch, int Cb, int step) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t HW = (size_t)H * W;
-  if (t >= HW * Cb) return;
-  const int cb = (int)(t / HW); const size_t px = t - (size_t)cb * HW;
-  const int y = (int)(px / W);
-  const u32x4 a = prev[(size_t)cb * pitch + px];
-  const u32x4 b = prev[(size_t)cb * pitch + px + (y + step < H ? (size_t)step * W : 0)];
-  u32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const unsigned ua = a[e], ub = b[e];
-    const i16x2 mx = __builtin_elementwise_max(__builtin_bit_cast(i16x2, ua), __builtin_bit_cast(i16x2, ub));
-    r[e] = __builtin_bit_cast(unsigned, mx);
-  }
-  out[(size_t)cb * pitch + px] = r;
-}
-
-template <int CBG, bool NT = false>  // channel blocks per thread (grid.y = Cb / CBG); NT: non-temporal stores (timing experiment, debug flavour)
-__global__ __launch_bounds__(256) void roi_pool_c8i_bf16_sorted_kernel(const u32x4 *__restrict__ feat, int H, int W, size_t pitch_f,
-                                                                        const float *__restrict__ rois, int roi_stride, int N, int PH, int PW, float scale,
-                                                                        u32x4 *__restrict__ out, size_t pitch_o, int roi_bins) {
-  const int PP = PH * PW;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // (roi, bin): the output row of the pooled batch
-  if (t >= (size_t)N * PP) return;
-  const int n = (int)(t / PP), bin = (int)(t - (size_t)n * PP);
-  const int ph = bin / PW, pw = bin - ph * PW;
-  const float *ro = rois + (size_t)roi_stride * n;
-  int hs, he, ws, we;
-  roi_bin_bounds(ro, scale, RoiRule{1.0f, 0, roi_bins}, H, W, PH, PW, ph, pw, hs, he, ws, we);
-  const bool empty = (he <= hs) || (we <= ws);
-  const int cb0 = blockIdx.y * CBG;
-  const u32x4 *fp = feat + (size_t)cb0 * pitch_f;
-  u32x4 *op = out + (size_t)cb0 * pitch_o + t;
-  const unsigned lowest = 0x80008000u;  // int16 minimum in both halves
-  u32x4 m[CBG];
-#pragma unroll
-  for (int c = 0; c < CBG; ++c) m[c] = u32x4{lowest, lowest, lowest, lowest};
-  for (int y = hs; y < he; ++y)
-    for (int x = ws; x < we; ++x) {
-      const size_t px = (size_t)y * W + x;
-#pragma unroll
-      for (int c = 0; c < CBG; ++c) {
-        const u32x4 v = fp[(size_t)c * pitch_f + px];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const unsigned cur = m[c][e], val = v[e];  // scalar copies: __builtin_bit_cast of a vector-element lvalue reads element 0
-          const i16x2 mx = __builtin_elementwise_max(__builtin_bit_cast(i16x2, cur), __builtin_bit_cast(i16x2, val));
-          m[c][e] = __builtin_bit_cast(unsigned, mx);
-        }
-      }
-    }
-#pragma unroll
-  for (int c = 0; c < CBG; ++c) {
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = empty ? 0u : bf16x2_sortable(m[c][e]);
-    if constexpr (NT) __builtin_nontemporal_store(o, &op[(size_t)c * pitch_o]);
-    else op[(size_t)c * pitch_o] = o;
-  }
-}
-
-// max-pool OF the ROI-pooled map, straight from the feature map (graph heads: Inception's Mixed_7a pools its input — the ROI-pooled
-// 17 x 17 x 768 tensor, 0.9 GB for 2000 ROIs — 3 x 3 / 2; max of maxes = one max over the union of the bins' windows).  Output pixel
-// (oy, ox) covers bins [o * stride - pad, + k) clipped to the bin grid; consecutive bins touch or overlap (ceil((b + 1) h) >= floor((b + 1) h)),
-// so the union of their windows is ONE window of the map; a bin that falls outside the map is empty and holds 0 in the pooled tensor, so 0
-// joins the max when the group has one.  Bin bounds are the pooling kernel's own expressions; max is exact: the result is the two-step
-// result bit for bit (up to the sign of a zero), and the max-pool launch that re-read the pooled tensor (210 us, 5.2 TB/s) is gone.
-template <int CBG>
-__global__ __launch_bounds__(256) void roi_maxpool_c8i_bf16_sorted_kernel(const u32x4 *__restrict__ feat, int H, int W, size_t pitch_f,
-                                                                           const float *__restrict__ rois, int roi_stride, int N, int PH, int PW, float scale,
-                                                                           int k, int stride, int pad, int OH, int OW, u32x4 *__restrict__ out, size_t pitch_o,
-                                                                           const u32x4 *__restrict__ tabs, size_t level_elems, int n_levels) {
-  const int OP = OH * OW;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // (roi, output pixel): the output row of the max-pooled batch
-  if (t >= (size_t)N * OP) return;
-  const int n = (int)(t / OP), o = (int)(t - (size_t)n * OP);
-  const int oy = o / OW, ox = o - oy * OW;
-  const float *ro = rois + (size_t)roi_stride * n;
-  const int sw = (int)roundf((ro[1] - 1.0f) * scale), sh = (int)roundf((ro[2] - 1.0f) * scale);
-  const int ew = (int)roundf((ro[3] - 1.0f) * scale), eh = (int)roundf((ro[4] - 1.0f) * scale);
-  const int rw = max(ew - sw + 1, 1), rh = max(eh - sh + 1, 1);
-  const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;
-  bool any_empty = false;
-  int hs = 0x7fffffff, he = -1, ws = 0x7fffffff, we = -1;
-  for (int ph = max(oy * stride - pad, 0); ph < min(oy * stride - pad + k, PH); ++ph) {
-    int a = (int)floorf((float)ph * bh) + sh, b = (int)ceilf((float)(ph + 1) * bh) + sh;
-    a = min(max(a, 0), H); b = min(max(b, 0), H);
-    if (b <= a) any_empty = true; else { hs = min(hs, a); he = max(he, b); }
-  }
-  for (int pw = max(ox * stride - pad, 0); pw < min(ox * stride - pad + k, PW); ++pw) {
-    int a = (int)floorf((float)pw * bw) + sw, b = (int)ceilf((float)(pw + 1) * bw) + sw;
-    a = min(max(a, 0), W); b = min(max(b, 0), W);
-    if (b <= a) any_empty = true; else { ws = min(ws, a); we = max(we, b); }
-  }
-  const int cb0 = blockIdx.y * CBG;
-  const u32x4 *fp = feat + (size_t)cb0 * pitch_f;
-  u32x4 *op = out + (size_t)cb0 * pitch_o + t;
-  const unsigned lowest = 0x80008000u;  // int16 minimum in both halves
-  u32x4 m[CBG];
-#pragma unroll
-  for (int c = 0; c < CBG; ++c) m[c] = u32x4{lowest, lowest, lowest, lowest};
-  // rows [hs, he) as ceil(h / 2^lv) blocks of 2^lv rows from table level lv (the last block pulled back to end at he: overlap is
-  // harmless for a max); lv = floor(log2 h) capped at the levels built -> two row reads per column for any window height
-  int lv = 0, bstep = 1;
-  if (tabs && he - hs > 1) {
-    lv = min(31 - __builtin_clz((unsigned)(he - hs)), n_levels);
-    bstep = 1 << lv;
-    if (lv > 0) fp = tabs + (size_t)(lv - 1) * level_elems + (size_t)cb0 * pitch_f;
-  }
-  for (int y0 = hs; y0 < he; y0 += bstep) {
-    const int y = min(y0, he - bstep);
-    for (int x = ws; x < we; ++x) {
-      const size_t px = (size_t)y * W + x;
-#pragma unroll
-      for (int c = 0; c < CBG; ++c) {
-        const u32x4 v = fp[(size_t)c * pitch_f + px];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const unsigned cur = m[c][e], val = v[e];
-          const i16x2 mx = __builtin_elementwise_max(__builtin_bit_cast(i16x2, cur), __builtin_bit_cast(i16x2, val));
-          m[c][e] = __builtin_bit_cast(unsigned, mx);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < CBG; ++c) {
-    u32x4 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      unsigned cur = m[c][e];
-      if (any_empty) {  // an empty bin's 0.0 (sortable code 0) takes part in the max
-        const i16x2 mx = __builtin_elementwise_max(__builtin_bit_cast(i16x2, cur), i16x2{0, 0});
-        cur = __builtin_bit_cast(unsigned, mx);
-      }
-      r[e] = bf16x2_sortable(cur);
-    }
-    op[(size_t)c * pitch_o] = r;
-  }
-}
-
-// average pool of the bf16 maps into the fp32 C8 matrix the (fp32) head GEMM reads.  Block = one channel block x 16 maps: the
-// 16 * HW records are read as consecutive 16-byte loads (fully coalesced) into LDS as fp32, then 128 threads (map, channel) sum
-// their HW values in pixel order (the order of the plain kernel below, so the result is bit-identical to it).
-__global__ __launch_bounds__(256) void avgpool_c8i_bf16_to_c8_lds_kernel(const bf16_t *__restrict__ in, int N, int HW, size_t pitch, float inv,
-                                                                          float *__restrict__ out, int Mp) {
-  extern __shared__ float sm[];  // [16 * HW][8 + 1]: odd row stride -> the 128 summing threads hit distinct banks
-  const int cb = blockIdx.y, n0 = blockIdx.x * 16;
-  const int nm = min(16, N - n0);
-  const int nrec = nm * HW;
-  const u32x4 *src = reinterpret_cast<const u32x4 *>(in) + (size_t)cb * pitch + (size_t)n0 * HW;
-  for (int i = threadIdx.x; i < nrec; i += 256) {
-    const u32x4 v = src[i];
-    float *d = sm + i * 9;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { d[2 * e] = __uint_as_float(v[e] << 16); d[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u); }
-  }
-  __syncthreads();
-  const int m = threadIdx.x >> 3, c = threadIdx.x & 7;
-  if (threadIdx.x < 128 && m < nm) {
-    const float *d = sm + (size_t)m * HW * 9 + c;
-    float acc = 0.0f;
-    for (int i = 0; i < HW; ++i) acc += d[i * 9];
-    out[((size_t)cb * Mp + n0 + m) * 8 + c] = acc * inv;
-  }
-}
-
-
-__global__ void avgpool_c8i_bf16_to_c8_kernel(const bf16_t *__restrict__ in, int N, int Cb, int HW, size_t pitch, float inv, float *__restrict__ out,
-                                              int Mp) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)N * Cb * 2;
-  if (t >= total) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const int n = (int)(r % N); const int cb = (int)(r / N);
-  const bf16_t *ip = in + ((size_t)cb * pitch + (size_t)n * HW) * 8 + h * 4;
-  f32x4 sacc = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int i = 0; i < HW; ++i) {
-    const u16x4 v = *reinterpret_cast<const u16x4 *>(ip + (size_t)i * 8);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sacc[e] += bf2f(v[e]);
-  }
-  *reinterpret_cast<f32x4 *>(out + ((size_t)cb * Mp + n) * 8 + h * 4) = sacc * inv;
-}
-
-// nn.SpatialAveragePooling(kw,kh,sw,sh,pw,ph), count_include_pad (torch's default): sum over the in-map cells of the window
-// in row-major order, divided by kh*kw regardless of how many cells lie in the padding.  T = float or bf16_t.
-template <typename T>
-__global__ void avgpool2d_c8i_kernel(const T *__restrict__ in, int Cb, int B, int H, int W, size_t pitch_in, int kh, int kw, int sh, int sw, int ph,
-                                     int pw, int OH, int OW, size_t pitch_out, T *__restrict__ out, const float *__restrict__ bias, int relu) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)Cb * B * OH * OW * 2;
-  if (t >= total) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const int ox = (int)(r % OW); r /= OW;
-  const int oy = (int)(r % OH); r /= OH;
-  const int b = (int)(r % B); const size_t cb = r / B;
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int ky = 0; ky < kh; ++ky)
-    for (int kx = 0; kx < kw; ++kx) {
-      const int iy = oy * sh + ky - ph, ix = ox * sw + kx - pw;
-      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      const size_t off = (cb * pitch_in + ((size_t)b * H + iy) * W + ix) * 8 + h * 4;
-      if constexpr (sizeof(T) == 2) {
-        const u16x4 v = *reinterpret_cast<const u16x4 *>(in + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += bf2f(v[e]);
-      } else {
-        acc += *reinterpret_cast<const f32x4 *>(in + off);
-      }
-    }
-  const float inv = 1.0f / (float)(kh * kw);
-  const size_t oo = (cb * pitch_out + ((size_t)b * OH + oy) * OW + ox) * 8 + h * 4;
-  acc = acc * inv;
-  if (bias) {  // a commuted pool -> pointwise-convolution pair (graph_parse): the convolution's bias and ReLU follow the pool
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { acc[e] += bias[cb * 8 + h * 4 + e]; if (relu && acc[e] < 0.0f) acc[e] = 0.0f; }
-  }
-  if constexpr (sizeof(T) == 2) {
-    u16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[e]);
-    *reinterpret_cast<u16x4 *>(out + oo) = o;
-  } else {
-    *reinterpret_cast<f32x4 *>(out + oo) = acc;
-  }
-}
-
-// bf16: one thread = one 16-byte pixel record; same summation order per channel as the template above
-__global__ void avgpool2d_c8i_bf16_kernel(const bf16_t *__restrict__ in, int Cb, int B, int H, int W, size_t pitch_in, int kh, int kw, int sh, int sw,
-                                          int ph, int pw, int OH, int OW, size_t pitch_out, bf16_t *__restrict__ out, const float *__restrict__ bias, int relu) {
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)Cb * B * OH * OW;
-  if (t >= total) return;
-  size_t r = t;
-  const int ox = (int)(r % OW); r /= OW;
-  const int oy = (int)(r % OH); r /= OH;
-  const int b = (int)(r % B); const size_t cb = r / B;
-  float acc[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
-  const u32x4 *ip = reinterpret_cast<const u32x4 *>(in) + cb * pitch_in + (size_t)b * H * W;
-  for (int ky = 0; ky < kh; ++ky)
-    for (int kx = 0; kx < kw; ++kx) {
-      const int iy = oy * sh + ky - ph, ix = ox * sw + kx - pw;
-      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      const u32x4 v = ip[(size_t)iy * W + ix];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { acc[2 * e] += __uint_as_float(v[e] << 16); acc[2 * e + 1] += __uint_as_float(v[e] & 0xffff0000u); }
-    }
-  const float inv = 1.0f / (float)(kh * kw);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc[e] *= inv;
-    if (bias) { acc[e] += bias[cb * 8 + e]; if (relu && acc[e] < 0.0f) acc[e] = 0.0f; }
-  }
-  u32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
-  reinterpret_cast<u32x4 *>(out)[cb * pitch_out + ((size_t)b * OH + oy) * OW + ox] = o;
-}
-
-// stride-1 average pooling of SMALL maps (per-ROI 8x8 in Inception's Mixed_7b/7c: H*W <= 256) through LDS: a block owns
-// 256 / (H*W) consecutive maps of one channel block, reads their records once (consecutive 16-byte loads) and takes the window
-// cells from LDS — the plain kernel issues kh*kw global loads per output.  Same cells, same order: bit-identical to it.
-__global__ __launch_bounds__(256) void avgpool2d_c8i_bf16_small_kernel(const bf16_t *__restrict__ in, int B, int H, int W, size_t pitch_in, int kh, int kw,
-                                                                        int ph, int pw, size_t pitch_out, bf16_t *__restrict__ out,
-                                                                        const float *__restrict__ bias, int relu) {
-  __shared__ u32x4 tile[256];
-  const int HW = H * W, mpb = 256 / HW;           // maps per block
-  const int cb = blockIdx.y;
-  const int b0 = blockIdx.x * mpb;
-  const int nrec = min(mpb, B - b0) * HW;
-  const int t = threadIdx.x;
-  const u32x4 *ip = reinterpret_cast<const u32x4 *>(in) + (size_t)cb * pitch_in + (size_t)b0 * HW;
-  if (t < nrec) tile[t] = ip[t];
-  __syncthreads();
-  if (t >= nrec) return;
-  const int m = t / HW, r = t - m * HW;
-  const int oy = r / W, ox = r - oy * W;
-  float acc[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
-  for (int ky = 0; ky < kh; ++ky)
-    for (int kx = 0; kx < kw; ++kx) {
-      const int iy = oy + ky - ph, ix = ox + kx - pw;
-      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      const u32x4 v = tile[m * HW + iy * W + ix];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { acc[2 * e] += __uint_as_float(v[e] << 16); acc[2 * e + 1] += __uint_as_float(v[e] & 0xffff0000u); }
-    }
-  const float inv = 1.0f / (float)(kh * kw);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc[e] *= inv;
-    if (bias) { acc[e] += bias[cb * 8 + e]; if (relu && acc[e] < 0.0f) acc[e] = 0.0f; }
-  }
-  u32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
-  reinterpret_cast<u32x4 *>(out)[(size_t)cb * pitch_out + (size_t)b0 * HW + t] = o;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// graph
-// ------------------------------------------------------------------------------------------------------------------------
-// nn.SpatialCrossMapLRN(size, alpha, beta, k) on C8I (models/alexnet.lua's trunk: norm1 / norm2): one thread per (pixel row, channel
-// block); the window spans at most one block either side (size <= 17).  fp32, squares summed in ascending channel order.
-__global__ void lrn_c8i_kernel(const float *__restrict__ in, int Cb, int C, size_t rows, size_t pitch_in, int size, float alpha, float beta, float k,
-                               size_t pitch_out, float *__restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= rows * Cb) return;
-  const size_t row = t % rows;
-  const int cb = (int)(t / rows);
-  float v[24];  // channels 8*cb - 8 .. 8*cb + 15
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int b = cb - 1 + q;
-    f32x4 lo = f32x4{0, 0, 0, 0}, hi = lo;
-    if (b >= 0 && b < Cb) {
-      const float *p = in + ((size_t)b * pitch_in + row) * 8;
-      lo = *reinterpret_cast<const f32x4 *>(p); hi = *reinterpret_cast<const f32x4 *>(p + 4);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[q * 8 + e] = lo[e]; v[q * 8 + 4 + e] = hi[e]; }
-  }
-  const int half = (size - 1) / 2;
-  const float a = alpha / (float)size;
-  float o[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = cb * 8 + j;
-    float ssum = 0.0f;
-#pragma unroll
-    for (int d = -8; d <= 8; ++d) {  // static register indices; the window is [-half, half]
-      const int cc = c + d;
-      if (d >= -half && d <= half && cc >= 0 && cc < C) { const float x = v[8 + j + d]; ssum = ssum + x * x; }
-    }
-    const float sc = k + a * ssum;
-    o[j] = c < C ? v[8 + j] * powf(sc, -beta) : 0.0f;
-  }
-  float *q = out + ((size_t)cb * pitch_out + row) * 8;
-  *reinterpret_cast<f32x4 *>(q) = f32x4{o[0], o[1], o[2], o[3]};
-  *reinterpret_cast<f32x4 *>(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
-}
-
-// C8I map (B = 1) <-> C8P map (dense.h: one zero halo row / column in front, padded behind): the trunk's 3x3 / stride-1 / pad-1
-// convolutions run on dense.hip's Winograd F(2x2,3x3) kernel, which reads its halo tiles straight from the padded layout
-__global__ void c8i_to_c8p_kernel(const float *__restrict__ in, int Cb, int H, int W, size_t pitch, int Hp, int Wp, float *__restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t HW = (size_t)H * W;
-  if (t >= HW * Cb * 2) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const size_t px = r % HW; const int cb = (int)(r / HW);
-  const int y = (int)(px / W), x = (int)(px - (size_t)y * W);
-  *reinterpret_cast<f32x4 *>(out + (((size_t)cb * Hp + y + 1) * Wp + x + 1) * 8 + h * 4) = *reinterpret_cast<const f32x4 *>(in + ((size_t)cb * pitch + px) * 8 + h * 4);
-}
-__global__ void c8p_to_c8i_kernel(const float *__restrict__ in, int Cb, int H, int W, int Hp, int Wp, size_t pitch, float *__restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t HW = (size_t)H * W;
-  if (t >= HW * Cb * 2) return;
-  const int h = (int)(t & 1); size_t r = t >> 1;
-  const size_t px = r % HW; const int cb = (int)(r / HW);
-  const int y = (int)(px / W), x = (int)(px - (size_t)y * W);
-  *reinterpret_cast<f32x4 *>(out + ((size_t)cb * pitch + px) * 8 + h * 4) = *reinterpret_cast<const f32x4 *>(in + (((size_t)cb * Hp + y + 1) * Wp + x + 1) * 8 + h * 4);
-}
-
-// one-map C8I -> pixel-major [y][x][Cb * 8] (dense.h roi_pool_pm's operand: a pixel's channels contiguous)
-__global__ void c8i_to_pixel_major_kernel(const float *__restrict__ in, int Cb, size_t HW, size_t pitch, float *__restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= HW * Cb * 2) return;
-  const int q = (int)(t % (Cb * 2)); const size_t px = t / (Cb * 2);   // q = cb * 2 + half: consecutive lanes write consecutive 16 bytes
-  *reinterpret_cast<f32x4 *>(out + px * (size_t)Cb * 8 + q * 4) = *reinterpret_cast<const f32x4 *>(in + ((size_t)(q >> 1) * pitch + px) * 8 + (q & 1) * 4);
-}
-
 // A batch of small per-ROI maps (ResNet's layer4: 1000 x 7 x 7) as ONE padded C8P image for the Winograd kernel: a mosaic of
 // (H + 1) x (W + 1) cells, mx maps per mosaic row, map b at cell (b / mx, b % mx) with its pixels in the cell's top-left H x W and
 // the cell's last row / column left ZERO — together with the C8P halo every map is surrounded by zeros, i.e. pad 1.  The
@@ -2480,85 +1830,11 @@ __global__ void permute_w3_kernel(const float *__restrict__ w, int Cout, int KK,
   o[t] = w[((size_t)n * 3 + c) * KK + tap];
 }
 
-struct RnConv {
-  int Cin = 0, Cout = 0, K = 0, stride = 1, pad = 0;  // square form (ResNet); KH/KW/sh/sw/ph/pw below are what the kernels use
-  int KH = 0, KW = 0, sh = 1, sw = 1, ph = 0, pw = 0;
-  float *wpk = nullptr, *bpk = nullptr;
-  float *lin_w = nullptr, *lin_b = nullptr;  // 1x1 / stride 1 with Cin % 64 == 0: also packed for the tuned GEMM (linear_c8)
-  float *col_w = nullptr, *col_b = nullptr;  // Cin == 3 (fp32): packed for the GEMM over im2col rows, k = tap * 3 + c
-  float *wino = nullptr;                     // graph trunks / ResNet heads (fp32), 3x3 / stride 1 / pad 1: Winograd-transformed weights (dense.h conv3x3_c8p)
-  float *mos_in = nullptr, *mos_out = nullptr;  // ResNet heads: the mosaic images (shared by the head's eligible convolutions), laid out for
-  int mos_h = 0, mos_w = 0, mos_mx = 0, mos_rows = 0, mos_cols = 0;  //   mos_rows x mos_cols px = max_rois maps of mos_h x mos_w, mos_mx per mosaic row
-  bf16_t *wpk16 = nullptr;                   // bf16 graph: [tap][nch2][CoutP][8]
-  int norelu_c0 = 0, norelu_c1 = 0;          // output channels [c0, c1) skip the ReLU (fused siblings with mixed activations; multiples of 8)
-  float *ws = nullptr;                       // the graph's split-K workspace
-  size_t ws_bytes = 0;
-};
-struct RnBlock {
-  std::vector<RnConv> convs;
-  bool has_sc = false;
-  RnConv sc;
-};
-struct GTensor {
-  int C = 0, H = 0, W = 0;
-  float *buf = nullptr;
-  float *c8p = nullptr;       // trunk tensors a Winograd convolution reads or writes: the same map in the C8P layout
-  int p_h = 0, p_w = 0;       // the dims c8p's zero halo is laid out for (re-zeroed when the image size changes)
-  int alias_of = -1, alias_c_off = 0;  // >= 0: this tensor is channels [alias_c_off, alias_c_off + C) of tensor alias_of (fused sibling convolutions)
-};
-struct GOp {
-  int kind = 0, src = 0, dst = 0, dst_c_off = 0, kh = 1, kw = 1, sh = 1, sw = 1, ph = 0, pw = 0, relu = 0;
-  int src_c_off = 0, cin = 0, ceil_mode = 0;   // the op reads channels [src_c_off, src_c_off + cin) of src
-  float lrn_alpha = 0.f, lrn_beta = 0.f, lrn_k = 1.f;
-  RnConv conv;
-  float *pool_bias = nullptr;  // average pool only: bias (+ ReLU if relu) applied after the pool (commuted pool -> pointwise convolution)
-  bool from_rois = false;      // head graphs: a max-pool of the ROI-pooled input itself -> computed from the feature map (roi_maxpool_c8i_bf16_sorted_kernel)
-  float *fc_w = nullptr, *fc_b = nullptr;  // head graphs (fp32): a convolution over the WHOLE pooled map (AlexNet's fc6) packed for the tuned GEMM, K = (channel block, bin)
-};
-struct ResNetGraph {
-  // op-list mode (graph_build): branching graphs; tensor 0 = image (trunk) / ROI-pooled map (head)
-  bool is_graph = false;
-  std::vector<GOp> g_trunk;
-  std::vector<std::vector<GOp>> g_heads;  // one op list per tower (1 for plain inceptionv3.lua), all over the same head tensors
-  std::vector<GTensor> t_trunk, t_head;
-  int feat_tensor = 0, out_tensor = 0;
-  RnConv conv1;
-  std::vector<RnBlock> trunk;
-  std::vector<std::vector<RnBlock>> heads;  // one layer4 copy per tower (1 for plain resnet.lua)
-  int feat_c = 0, out_c = 0, pooled = 14, max_rois = 0;
-  bool bf16 = false;             // activations / conv weights in bf16 (fp32 accumulate); the cls / bbox head GEMM stays fp32
-  float *img = nullptr;          // C8I image
-  float *img_planar = nullptr;   // fp32 graphs: the transformed image as [3][H][W] planes too (im2col first layer)
-  float *tb[4] = {nullptr, nullptr, nullptr, nullptr};  // trunk activations (rotating)
-  float *hb[4] = {nullptr, nullptr, nullptr, nullptr};  // per-ROI head activations (rotating)
-  size_t tb_elems = 0, hb_elems = 0;
-  float *feat = nullptr;         // points into tb[]: layer3 output of the last trunk run
-  int feat_h = 0, feat_w = 0, last_h = -1, last_w = -1;
-  float *fc_x = nullptr;         // (bin, roi)-row ROI-pooled matrix [Cb][PP][round_up(max_rois, 128)][8] for a GOp with fc_w
-  bf16_t *feat_sorted = nullptr; // order-preserving int16 re-coding of the cached feature map (bf16 ROI pooling), rebuilt per trunk run
-  size_t feat_sorted_elems = 0;
-  bool feat_sorted_valid = false;
-  bf16_t *feat_vmax = nullptr;   // vertical range-max levels 1 .. feat_vmax_levels of feat_sorted (the fused ROI max-pool reads two rows per column)
-  size_t feat_vmax_elems = 0;    // elements per level
-  int feat_vmax_levels = 0;
-  bool feat_vmax_valid = false;
-  float *splitk_ws = nullptr;    // fp32 partial slabs of split-K convolutions (bf16 graph; one stream at a time, like tb / hb)
-  int roi_bins = 0;              // MPN_ROI_BINS_* (resnet_set_roi_bins)
-  // second tower LANE (graphs with more than one head): a second set of per-ROI activation buffers, so that towers 1, 3 can run on a
-  // second stream beside towers 0, 2, 4 (resnet_head_forward's `lane`; pipeline.hip run_detect).  Weights, the feature map and its sorted /
-  // range-max images are shared (read-only while the towers run: resnet_heads_prepare builds them before the lanes fork).
-  std::vector<GTensor> t_head2;
-  float *hb2[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool has_lane2 = false;
-  DeviceOwner own;  // of every device buffer above (mpn_internal.h)
-};
-constexpr size_t SPLITK_WS_BYTES = (size_t)96 << 20;
-
-static int rn_alloc(ResNetGraph *g, float **p, size_t bytes) { return g->own.alloc(p, bytes); }
+int rn_alloc(ResNetGraph *g, float **p, size_t bytes) { return g->own.alloc(p, bytes); }
 
 // a buffer that grows with the image size (outside the steady state): the old block is released (hipFree waits for the device, so
 // kernels still reading it have finished) instead of staying with the owner until the handle dies
-static int rn_regrow(ResNetGraph *g, float **p, size_t bytes) {
+int rn_regrow(ResNetGraph *g, float **p, size_t bytes) {
   if (*p) {
     bump_alloc_generation();  // captured launch graphs (pipeline.hip) hold the old pointer: bump, THEN free
     g->own.free_now(p);
@@ -2566,8 +1842,7 @@ static int rn_regrow(ResNetGraph *g, float **p, size_t bytes) {
   return rn_alloc(g, p, bytes);
 }
 
-MPN_KNOB(int, g_graph_fuse, 511);  // mpn_debug_set_graph_fuse: bit 0 = fuse sibling pointwise convolutions, bit 1 = commute average-pool -> pointwise convolution, bit 2 = max-pools of the ROI-pooled input computed from the feature map, bit 3 = fully-connected head layers (whole-map / 1x1-map convolutions) on the tuned GEMM, bit 4 = the image layer (Cin = 3) as a GEMM over im2col rows, bit 5 = trunk 3x3 / stride-1 convolutions on dense.hip's Winograd kernel, bit 6 = the fused ROI max-pool (bit 2) reads vertical range-max tables of the map, bit 7 = ResNet heads' 3x3 / stride-1 convolutions on the Winograd kernel (mosaic image of the per-ROI maps), bit 8 = the fully-connected operand pooled by dense.hip's pixel-major kernel; 0 = run the op list as given
-static int rn_pack(ResNetGraph *g, RnConv &c, const float *d_w, const float *d_b) {
+int rn_pack(ResNetGraph *g, RnConv &c, const float *d_w, const float *d_b) {
   if (g->bf16) {
     const int nch2 = round_up((c.Cin + 7) / 8, 2), CoutP = round_up(c.Cout, 128), KK = c.KH * c.KW;
     const size_t total = (size_t)KK * nch2 * CoutP * 8;
@@ -2628,7 +1903,6 @@ static int rn_pack(ResNetGraph *g, RnConv &c, const float *d_w, const float *d_b
 
 MPN_KNOB(unsigned long long *, g_bf16_trace, nullptr);  // mpn_debug_set_bf16_trace (tools/dma_trace.py)
 MPN_KNOB(int, g_bf16_trace_kh, 3);
-MPN_KNOB(int, g_bf16_fast_pool, 3);       // bit 0: row-per-thread ROI pooling (bf16: on the int16-sortable map), bit 1: LDS average pooling (bf16) (0 = the plain kernels; mpn_debug_set_bf16_fast_pool)
 MPN_KNOB(int, g_fp32_pf, 1);              // fp32 graph: conv2d_c8i_pf_kernel for 32-channel-stage layers (0 = conv2d_c8i_kernel<4>; mpn_debug_set_fp32_pf)
 MPN_KNOB(int, g_split_max_tiles, 192);     // split-K only layers with fewer 128 x 128 tiles than this (mpn_debug_set_split_max_tiles)
 MPN_KNOB(int, g_bf16_split_target, 256);  // split-K (both dtypes) aims at this many blocks (0 = never split; mpn_debug_set_bf16_split_target)
@@ -2642,51 +1916,7 @@ MPN_KNOB(int, g_bf16_bdir, 1);  // mpn_debug_set_bf16_bdir: 1 = conv2d_c8i_bf16_
 #ifdef MPN_DEBUG_HOOKS
 MPN_KNOB(int, g_bf16_bdir_abl, 0);  // mpn_debug_set_bf16_bdir_abl: the B-direct kernel's ABL knock-outs (only in -DMPN_BF16_ABLATE builds)
 MPN_KNOB(int, g_bf16_bdir_ver, 1);  // mpn_debug_set_bf16_bdir_ver: 1 = compiler-counted form <3>, 2 / 3 = hand-counted form <3> / <4> (debug flavour only)
-// mpn_debug_set_tower_knock (tools/tower_knockout.py; timing only, garbage results): the CEILING of a first per-ROI layer that never reads a
-// materialised pooled tensor (VERDICT r5 task 1, step 1).  bit 0: the ROI pooling launch of the bf16 heads is skipped; bit 1: the convolutions
-// that read the pooled tensor (Mixed_7a's fused 1x1 768 -> 384; layer4 block 1's conv1 and shortcut) run the B-direct kernel with every pixel
-// load hitting ONE resident 1-KiB window (ABL bit 5: nothing can fetch its operand cheaper than from the CU's own cache).
-static int g_tower_knock = 0;
-static int g_pool_exp = 0;   // mpn_debug_set_pool_exp: timing experiments of the bf16 ROI pooling launch (resnet_head_forward)
-static int g_knock_arm = 0;  // the next `g_knock_arm` rn_conv calls are first-layer convolutions (armed by the caller)
-static bool knock_first() { return g_knock_arm > 0 && (g_tower_knock & 2); }
-#else
-constexpr bool knock_first() { return false; }
 #endif
-// Which launch rn_conv's call took (mpn_debug_conv_last_form: tests/test_gpu_conv_numerics.py asserts it per case)
-enum ConvForm : int {
-  CF_KC1 = 1, CF_KC2 = 2, CF_KC3 = 3, CF_KC4 = 4, CF_PF = 5,  // fp32: conv2d_c8i_kernel<KC>, conv2d_c8i_pf_kernel
-  CF_MOSAIC = 10, CF_IM2COL = 11, CF_GEMM_FC = 12,            // the Winograd mosaic, im2col + GEMM, the GEMM's split-K form on 1x1 maps
-  CF_GEMM_DIRECT = 13, CF_GEMM_RI = 14,                       // the pointwise GEMM (direct / row-invariant)
-  CF_BDIR = 20,                                               // bf16: conv2d_c8i_bf16_bdir_kernel
-  CF_DMA_256x128 = 21, CF_DMA_128x256 = 22, CF_DMA_256x256 = 23,  // the LDS-DMA kernel, couts x pixels
-  CF_B_KP1 = 26, CF_B_KP2 = 27,                               // conv2d_c8i_bf16_kernel<KP>
-  CF_DMA_NCH8 = 28, CF_DMA_W8 = 29,                           // debug flavour: the LDS-DMA kernel with 64-channel stages / in the 8-wave shape
-  CF_BDIR2_DS3 = 32, CF_BDIR2_DS4 = 33, CF_BDIR8 = 38, CF_BDPP = 39,  // debug flavour: bdir_ver 2 / 3 / 8 / 9
-  CF_SPLIT = 0x100,                                           // or-ed in: split K (the generic fp32 / the 128 x 128 bf16 kernel + a finalize kernel)
-};
-#ifdef MPN_DEBUG_HOOKS
-static int g_dbg_conv_form = 0;
-#define RN_FORM(v) (g_dbg_conv_form = (v))
-#else
-#define RN_FORM(v) ((void)0)
-#endif
-// Which pooling / LRN launch ran (mpn_debug_graph_op, mpn_debug_head_pool: tests/test_gpu_graph_pool_numerics.py asserts it per case).  An
-// id's high nibble is its stage, so one head forward records the ROI pooling, the fused max-pool and the closing average side by side.
-enum PoolKernel : int {
-  PK_MAX_F32 = 1, PK_MAX_BF16 = 2, PK_AVG_F32 = 3, PK_AVG_BF16 = 4, PK_AVG_BF16_SMALL = 5, PK_LRN = 6,  // graph_run's pool / LRN block
-  PK_ROI_F32 = 16, PK_ROI_ROWS4 = 17, PK_ROI_BF16 = 18, PK_ROI_SORTED = 19, PK_ROI_PM = 20,             // resnet_head_forward: ROI pooling
-  PK_ROI_SORTED_EXP = 21,                                                                               //   (debug flavour: the sorted kernel's mpn_debug_set_pool_exp variants)
-  PK_ROIMAX_SORTED = 32, PK_ROIMAX_SORTED_TABLES = 33,                                                  //   the fused max-pool (with range-max tables)
-  PK_GAVG_F32 = 48, PK_GAVG_BF16 = 49, PK_GAVG_BF16_LDS = 50,                                           //   the closing average
-};
-#ifdef MPN_DEBUG_HOOKS
-static int g_dbg_pool_kernel[4] = {0, 0, 0, 0};
-#define RN_POOL(v) (g_dbg_pool_kernel[(v) >> 4] = (v))
-#else
-#define RN_POOL(v) ((void)0)
-#endif
-MPN_KNOB(int, g_roi_invariant, 1);  // mpn_debug_set_roi_invariant: 0 = per-ROI layers pick kernel / split by batch size as round 3 did (tests, timing)
 // the fields GConvArgs and GConvArgsB share, from the layer and its input; *o = the output batch
 template <class Args>
 static int conv_geometry(const RnConv &c, const ActI &in, float *out, int relu, Args &a, ActI *o) {
@@ -2979,14 +2209,14 @@ static int rn_conv_fp32(const RnConv &c, ActI in, float *out, const float *res, 
 // kernel family below accumulates K = (tap, channel chunk) in ONE chain per output, and the bf16 tile shapes / the small and the
 // LDS-DMA kernel share that chain bit for bit), pointwise convolutions always on the un-split GEMM, eligible 3x3 convolutions
 // always on the Winograd mosaic with a batch-independent launch plan.  Tile shapes may still follow the batch size.
-static int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int relu, hipStream_t s, ActI *o, bool allow_gemm = true, bool per_roi = false) {
+int rn_conv(const RnConv &c, ActI in, float *out, const float *res, int relu, hipStream_t s, ActI *o, bool allow_gemm, bool per_roi) {
   const bool inv = per_roi && g_roi_invariant;
   if (c.wpk16) return rn_conv_bf16(c, in, out, res, relu, s, o, inv);  // bf16 graph
   return rn_conv_fp32(c, in, out, res, relu, s, o, allow_gemm, inv);
 }
 
 // one residual block: y = relu(conv_n(... relu(conv_1(x))) + shortcut(x)); buffers b[0..3] rotate, x may live in any of them
-static int rn_block(const RnBlock &blk, ActI x, float *const bufs[4], hipStream_t s, ActI *out, bool per_roi = false) {
+int rn_block(const RnBlock &blk, ActI x, float *const bufs[4], hipStream_t s, ActI *out, bool per_roi) {
   // pick three scratch buffers different from x.p
   float *free_b[3];
   int nf = 0;
@@ -3172,7 +2402,7 @@ static void gop_out_dims(const GOp &op, int h, int w, int &oh, int &ow) {
 }
 
 // propagate the spatial dims of one op list from tensor 0's; checks that concatenated writers agree
-static int graph_dims(const std::vector<GOp> &ops, std::vector<GTensor> &ts, int h0, int w0) {
+int graph_dims(const std::vector<GOp> &ops, std::vector<GTensor> &ts, int h0, int w0) {
   for (auto &t : ts) t.H = t.W = 0;
   ts[0].H = h0; ts[0].W = w0;
   for (const GOp &op : ops) {
@@ -3190,8 +2420,8 @@ static int graph_dims(const std::vector<GOp> &ops, std::vector<GTensor> &ts, int
   return MPN_OK;
 }
 
-static int graph_parse(ResNetGraph *g, int n_ops, const mpn_graph_op *ops_in, int n_t, const int *tc, std::vector<GOp> &out, std::vector<GTensor> &ts,
-                       bool head = false) {
+int graph_parse(ResNetGraph *g, int n_ops, const mpn_graph_op *ops_in, int n_t, const int *tc, std::vector<GOp> &out, std::vector<GTensor> &ts,
+                bool head) {
   MPN_CHECK_ARG(n_ops > 0 && ops_in && n_t > 1 && tc);
   ts.resize(n_t);
   for (int i = 0; i < n_t; ++i) { ts[i].C = tc[i]; MPN_CHECK_ARG(tc[i] > 0); }
@@ -3354,11 +2584,6 @@ static int graph_parse(ResNetGraph *g, int n_ops, const mpn_graph_op *ops_in, in
   return MPN_OK;
 }
 
-// a head op that max-pools the ROI-pooled input itself (all of tensor 0's channels, square, floor mode): GOp::from_rois.  (A macro, shared with
-// mpn_debug_head_pool: the expression expands in place, so graph_build compiles to the code it had.)
-#define MPN_GOP_POOLS_ROIS(op, c0) \
-  ((op).kind == 1 && (op).src == 0 && (op).src_c_off == 0 && (op).cin == (c0) && (op).kh == (op).kw && (op).sh == (op).sw && (op).ph == (op).pw && !(op).ceil_mode)
-
 int graph_build(const mpn_graph_weights *gw, int max_h, int max_w, int max_rois, int pooled, ResNetGraph **out) {
   MPN_CHECK_ARG(gw && out && gw->feat_tensor > 0 && gw->feat_tensor < gw->n_trunk_tensors && gw->out_tensor > 0 && gw->out_tensor < gw->n_head_tensors);
   const int n_heads = gw->n_heads > 1 ? gw->n_heads : 1;
@@ -3458,8 +2683,7 @@ int graph_build(const mpn_graph_weights *gw, int max_h, int max_w, int max_rois,
 }
 
 // run one op list on a batch of B maps; dims must have been propagated (graph_dims)
-static int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GTensor> &ts, int B, hipStream_t s, bool skip_from_rois = false,
-                     bool fc_gemm = false) {
+int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GTensor> &ts, int B, hipStream_t s, bool skip_from_rois, bool fc_gemm) {
   const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
   // layout bookkeeping for the Winograd convolutions (trunk only): which form of each tensor holds this run's values
   const bool trunk = &ts == &g->t_trunk;
@@ -3472,12 +2696,7 @@ static int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GT
   };
   auto need_c8i = [&](int id) -> int {
     if (in_i[id]) return MPN_OK;
-    GTensor &t = ts[id];
-    const ActI ti{t.buf, 1, t.C, t.H, t.W};
-    const Act tp = make_act(t.c8p, t.C, t.H, t.W);
-    hipLaunchKernelGGL(c8p_to_c8i_kernel, dim3((unsigned)cdiv_sz((size_t)t.H * t.W * ti.Cb() * 2, 256)), dim3(256), 0, s, t.c8p, ti.Cb(), t.H, t.W, tp.Hp, tp.Wp,
-                       ti.pitch(), t.buf);
-    MPN_CHECK_LAUNCH();
+    { int rc = rn_c8p_to_c8i(ts[id], s); if (rc) return rc; }
     in_i[id] = 1;
     return MPN_OK;
   };
@@ -3489,11 +2708,8 @@ static int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GT
       if (!in_p[op.src]) {
         rc = fit_halo(ps);
         if (rc) return rc;
-        const ActI ti{ps.buf, 1, ps.C, ps.H, ps.W};
-        const Act tp = make_act(ps.c8p, ps.C, ps.H, ps.W);
-        hipLaunchKernelGGL(c8i_to_c8p_kernel, dim3((unsigned)cdiv_sz((size_t)ps.H * ps.W * ti.Cb() * 2, 256)), dim3(256), 0, s, ps.buf, ti.Cb(), ps.H, ps.W, ti.pitch(),
-                           tp.Hp, tp.Wp, ps.c8p);
-        MPN_CHECK_LAUNCH();
+        rc = rn_c8i_to_c8p(ps, s);
+        if (rc) return rc;
         in_p[op.src] = 1;
       }
       if (!in_p[op.dst]) { rc = fit_halo(pd); if (rc) return rc; }
@@ -3545,42 +2761,8 @@ static int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GT
 #endif
       if (rc) return rc;
     } else {
-      const size_t total = (size_t)in.Cb() * B * dst.H * dst.W * 2;
-      const dim3 grid((unsigned)cdiv_sz(total, 256)), grid16((unsigned)cdiv_sz(total / 2, 256));  // fp32: half records, bf16: whole records per thread
-      if (op.kind == 3) {
-        const size_t rows = (size_t)B * src.H * src.W;
-        RN_POOL(PK_LRN);
-        hipLaunchKernelGGL(lrn_c8i_kernel, dim3((unsigned)cdiv_sz(rows * in.Cb(), 256)), dim3(256), 0, s, src.buf, in.Cb(), src.C, rows, in.pitch(), op.kh,
-                           op.lrn_alpha, op.lrn_beta, op.lrn_k, od.pitch(), reinterpret_cast<float *>(outp));
-      } else if (op.kind == 1) {
-        MPN_CHECK_ARG(op.kh == op.kw && op.sh == op.sw && op.ph == op.pw);
-        if (g->bf16) {
-          RN_POOL(PK_MAX_BF16);
-          hipLaunchKernelGGL(maxpool2d_c8i_bf16_kernel, grid16, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(src.buf), in.Cb(), B, src.H, src.W, in.pitch(),
-                             op.kh, op.sh, op.ph, dst.H, dst.W, od.pitch(), reinterpret_cast<bf16_t *>(outp));
-        } else {
-          RN_POOL(PK_MAX_F32);
-          hipLaunchKernelGGL(maxpool2d_c8i_kernel, grid, dim3(256), 0, s, src.buf, in.Cb(), B, src.H, src.W, in.pitch(), op.kh, op.sh, op.ph, dst.H, dst.W,
-                             od.pitch(), reinterpret_cast<float *>(outp));
-        }
-      } else {
-        if (g->bf16 && op.sh == 1 && op.sw == 1 && dst.H == src.H && dst.W == src.W && src.H * src.W <= 256) {
-          const int mpb = 256 / (src.H * src.W);
-          RN_POOL(PK_AVG_BF16_SMALL);
-          hipLaunchKernelGGL(avgpool2d_c8i_bf16_small_kernel, dim3((unsigned)((B + mpb - 1) / mpb), (unsigned)in.Cb()), dim3(256), 0, s,
-                             reinterpret_cast<const bf16_t *>(src.buf), B, src.H, src.W, in.pitch(), op.kh, op.kw, op.ph, op.pw, od.pitch(),
-                             reinterpret_cast<bf16_t *>(outp), op.pool_bias, op.relu);
-        } else if (g->bf16) {
-          RN_POOL(PK_AVG_BF16);
-          hipLaunchKernelGGL(avgpool2d_c8i_bf16_kernel, grid16, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(src.buf), in.Cb(), B, src.H, src.W,
-                             in.pitch(), op.kh, op.kw, op.sh, op.sw, op.ph, op.pw, dst.H, dst.W, od.pitch(), reinterpret_cast<bf16_t *>(outp), op.pool_bias, op.relu);
-        } else {
-          RN_POOL(PK_AVG_F32);
-          hipLaunchKernelGGL((avgpool2d_c8i_kernel<float>), grid, dim3(256), 0, s, src.buf, in.Cb(), B, src.H, src.W, in.pitch(), op.kh, op.kw, op.sh, op.sw,
-                             op.ph, op.pw, dst.H, dst.W, od.pitch(), reinterpret_cast<float *>(outp), op.pool_bias, op.relu);
-        }
-      }
-      MPN_CHECK_LAUNCH();
+      int rc = rn_pool_op(g, op, src, in, dst, od, outp, B, s);
+      if (rc) return rc;
     }
   }
   if (trunk) { int rc = need_c8i(g->feat_tensor); if (rc) return rc; }  // the ROI pooling reads the C8I map
@@ -3590,15 +2772,7 @@ static int graph_run(ResNetGraph *g, const std::vector<GOp> &ops, std::vector<GT
 int resnet_trunk_forward(ResNetGraph *g, const float *d_image, int H, int W, const int *swap, double scale, const double *mean,
                          const double *std, int has_std, hipStream_t s) {
   MPN_CHECK_ARG(g && d_image && H > 0 && W > 0);
-  const size_t plane = (size_t)H * W;
-  if (g->bf16)
-    hipLaunchKernelGGL(image_transform_c8i_bf16_kernel, dim3((unsigned)cdiv_sz(plane, 256)), dim3(256), 0, s, d_image, H, W, swap[0], swap[1], swap[2],
-                       scale, mean[0], mean[1], mean[2], has_std ? std[0] : 1.0, has_std ? std[1] : 1.0, has_std ? std[2] : 1.0, has_std,
-                       reinterpret_cast<bf16_t *>(g->img), (ActI{g->img, 1, 3, H, W}).pitch());
-  else
-    hipLaunchKernelGGL(image_transform_c8i_kernel, dim3((unsigned)cdiv_sz(plane, 256)), dim3(256), 0, s, d_image, H, W, swap[0], swap[1], swap[2], scale,
-                       mean[0], mean[1], mean[2], has_std ? std[0] : 1.0, has_std ? std[1] : 1.0, has_std ? std[2] : 1.0, has_std, g->img, g->img_planar);
-  MPN_CHECK_LAUNCH();
+  { int rc = rn_image_transform(g, d_image, H, W, swap, scale, mean, std, has_std, s); if (rc) return rc; }
   if (g->is_graph) {
     int rc = graph_dims(g->g_trunk, g->t_trunk, H, W);
     if (rc == MPN_OK) rc = graph_run(g, g->g_trunk, g->t_trunk, 1, s);
@@ -3612,17 +2786,8 @@ int resnet_trunk_forward(ResNetGraph *g, const float *d_image, int H, int W, con
   int rc = rn_conv(g->conv1, x, g->tb[0], nullptr, 1, s, &y);
   if (rc) return rc;
   const int OH = (y.H + 2 - 3) / 2 + 1, OW = (y.W + 2 - 3) / 2 + 1;
-  {
-    const size_t total = (size_t)y.Cb() * OH * OW * 2;
-    const ActI po{g->tb[1], 1, y.C, OH, OW};
-    if (g->bf16)
-      hipLaunchKernelGGL(maxpool2d_c8i_bf16_kernel, dim3((unsigned)cdiv_sz(total / 2, 256)), dim3(256), 0, s, reinterpret_cast<const bf16_t *>(y.p), y.Cb(), 1,
-                         y.H, y.W, y.pitch(), 3, 2, 1, OH, OW, po.pitch(), reinterpret_cast<bf16_t *>(g->tb[1]));
-    else
-      hipLaunchKernelGGL(maxpool2d_c8i_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, y.p, y.Cb(), 1, y.H, y.W, y.pitch(), 3, 2, 1, OH, OW,
-                         po.pitch(), g->tb[1]);
-    MPN_CHECK_LAUNCH();
-  }
+  rc = rn_stem_maxpool(g, y, OH, OW, s);
+  if (rc) return rc;
   ActI cur{g->tb[1], 1, y.C, OH, OW};
   for (auto &blk : g->trunk) {
     rc = rn_block(blk, cur, g->tb, s, &y);
@@ -3633,54 +2798,6 @@ int resnet_trunk_forward(ResNetGraph *g, const float *d_image, int H, int W, con
   return MPN_OK;
 }
 
-// The per-image preparation of the bf16 ROI pooling — the order-preserving int16 image of the feature map and, where a head fuses the
-// max-pool of its pooled input, its vertical range-max levels — for head `head` (-1: whatever ANY head needs).  Built once per trunk run
-// (the valid flags), on `s`.
-static int heads_prepare_impl(ResNetGraph *g, int head, hipStream_t s) {
-  const int Cb = (g->feat_c + 7) / 8;
-  if (!(g->bf16 && (g_bf16_fast_pool & 1) && Cb % 4 == 0)) return MPN_OK;
-  const bool fuse_mp = g->is_graph && (g_graph_fuse & 4) && g->roi_bins == 0;
-  const ActI fa{g->feat, 1, g->feat_c, g->feat_h, g->feat_w};
-  const size_t need = (size_t)Cb * fa.pitch() * 8;
-  if (g->feat_sorted_elems < need) {  // first use (or a larger image than any before): outside the steady state
-    float *q = reinterpret_cast<float *>(g->feat_sorted);
-    g->feat_sorted = nullptr; g->feat_sorted_elems = 0;
-    int rc = rn_regrow(g, &q, need * sizeof(bf16_t));
-    if (rc) return rc;
-    g->feat_sorted = reinterpret_cast<bf16_t *>(q); g->feat_sorted_elems = need; g->feat_sorted_valid = false;
-  }
-  bool any_mp = false;
-  if (fuse_mp)
-    for (int h = 0; h < (int)g->g_heads.size(); ++h)
-      if (head < 0 || h == head)
-        for (const GOp &op : g->g_heads[h]) any_mp = any_mp || op.from_rois;
-  const int want_levels = (any_mp && (g_graph_fuse & 64) && g->feat_h > 1) ? 31 - __builtin_clz((unsigned)g->feat_h) : 0;
-  if (want_levels > 0 && (g->feat_vmax_elems < need || g->feat_vmax_levels < want_levels)) {  // outside the steady state, as above
-    float *q = reinterpret_cast<float *>(g->feat_vmax);
-    g->feat_vmax = nullptr; g->feat_vmax_elems = 0; g->feat_vmax_levels = 0;
-    int rc = rn_regrow(g, &q, need * sizeof(bf16_t) * want_levels);
-    if (rc) return rc;
-    g->feat_vmax = reinterpret_cast<bf16_t *>(q); g->feat_vmax_elems = need; g->feat_vmax_levels = want_levels; g->feat_vmax_valid = false;
-  }
-  if (!g->feat_sorted_valid) {
-    hipLaunchKernelGGL(bf16_sortable_kernel, dim3((unsigned)cdiv_sz(need / 8, 256)), dim3(256), 0, s, reinterpret_cast<const u32x4 *>(g->feat), need / 8,
-                       reinterpret_cast<u32x4 *>(g->feat_sorted));
-    MPN_CHECK_LAUNCH();
-    g->feat_sorted_valid = true;
-    g->feat_vmax_valid = false;
-  }
-  if (want_levels > 0 && !g->feat_vmax_valid) {  // once per image: level l from level l - 1 (level 0 = the sortable map)
-    for (int l = 1; l <= want_levels; ++l) {
-      const u32x4 *prev = l == 1 ? reinterpret_cast<const u32x4 *>(g->feat_sorted)
-                                 : reinterpret_cast<const u32x4 *>(g->feat_vmax) + (size_t)(l - 2) * (g->feat_vmax_elems / 8);
-      hipLaunchKernelGGL(vmax_level_sorted_kernel, dim3((unsigned)cdiv_sz((size_t)g->feat_h * g->feat_w * Cb, 256)), dim3(256), 0, s, prev,
-                         reinterpret_cast<u32x4 *>(g->feat_vmax) + (size_t)(l - 1) * (g->feat_vmax_elems / 8), g->feat_h, g->feat_w, fa.pitch(), Cb, 1 << (l - 1));
-      MPN_CHECK_LAUNCH();
-    }
-    g->feat_vmax_valid = true;
-  }
-  return MPN_OK;
-}
 int resnet_heads_prepare(ResNetGraph *g, hipStream_t s) {
   MPN_CHECK_ARG(g && g->feat);
   return heads_prepare_impl(g, -1, s);
@@ -3691,81 +2808,16 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
                         hipStream_t s, int lane) {
   MPN_CHECK_ARG(g && g->feat && d_rois && d_feat_c8 && N > 0 && N <= g->max_rois && head >= 0 && head < (int)g->heads.size());
   MPN_CHECK_ARG(lane == 0 || (lane == 1 && g->has_lane2));
-  const int Cb = (g->feat_c + 7) / 8, PH = g->pooled;
+  const int PH = g->pooled;
   std::vector<GTensor> &t_head = lane ? g->t_head2 : g->t_head;
   float *const *const hb = lane ? g->hb2 : g->hb;
   float *const pool_dst = g->is_graph ? t_head[0].buf : hb[0];
-  const bool fuse_mp = g->is_graph && g->bf16 && (g_bf16_fast_pool & 1) && Cb % 4 == 0 && (g_graph_fuse & 4) && g->roi_bins == 0;  // max-pools of the pooled input: from the map (its kernel unions the CUDA branch's bins: the adaptive rule runs the max-pool as an ordinary op on the pooled batch)
+  const bool fuse_mp = roi_maxpool_fused(g);
   bool fc_gemm = false;  // the head starts with a fully-connected layer: pool straight into its GEMM operand
-  if (g->is_graph && !g->bf16 && g->fc_x && (g_graph_fuse & 8) && (g_bf16_fast_pool & 1) && Cb % 4 == 0)
+  if (g->is_graph && !g->bf16 && g->fc_x && (g_graph_fuse & 8) && fast_pool_ok(g))
     for (const GOp &op : g->g_heads[head]) fc_gemm = fc_gemm || op.fc_w != nullptr;
   if (g->is_graph) { int rc = graph_dims(g->g_heads[head], t_head, PH, PH); if (rc) return rc; }
-  {
-    const size_t total = (size_t)N * Cb * PH * PH * 2;
-    const ActI fa{g->feat, 1, g->feat_c, g->feat_h, g->feat_w}, pa{pool_dst, N, g->feat_c, PH, PH};
-    if (g->bf16 && (g_bf16_fast_pool & 1) && Cb % 4 == 0) {
-      { int rc_prep = heads_prepare_impl(g, head, s); if (rc_prep) return rc_prep; }  // (a no-op when resnet_heads_prepare already ran for this image)
-      const int want_levels = g->feat_vmax_valid ? g->feat_vmax_levels : 0;
-#ifdef MPN_DEBUG_HOOKS
-      if (g_tower_knock & 1) {}
-      else if ((g_pool_exp & 3) && Cb % 8 == 0) {  // mpn_debug_set_pool_exp (timing experiments): 1 = 8 channel blocks per thread / ordinary stores, 2 = 4 blocks / ordinary stores (rounds 3-5), 3 = 8 blocks / non-temporal
-        RN_POOL(PK_ROI_SORTED_EXP);
-        const dim3 g8((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 8)), g4((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4));
-#define MPN_POOL_ARGS reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale, reinterpret_cast<u32x4 *>(pool_dst), pa.pitch(), g->roi_bins
-        if ((g_pool_exp & 3) == 1) hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<8, false>), g8, dim3(256), 0, s, MPN_POOL_ARGS);
-        else if ((g_pool_exp & 3) == 2) hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<4, false>), g4, dim3(256), 0, s, MPN_POOL_ARGS);   // rounds 3-5: ordinary stores
-        else hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<8, true>), g8, dim3(256), 0, s, MPN_POOL_ARGS);
-#undef MPN_POOL_ARGS
-      } else
-#endif
-      // non-temporal stores: the 0.4-0.9 GB pooled tensor streams past the L2 instead of evicting the sorted map the launch gathers from
-      // (measured, profiles/r06_pool_exp.txt: configs[4] 24.28 -> 24.10 ms, configs[3] bf16 11.06 -> 10.99; 8 channel blocks per thread: slower)
-      {
-        RN_POOL(PK_ROI_SORTED);
-        hipLaunchKernelGGL((roi_pool_c8i_bf16_sorted_kernel<4, true>), dim3((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4)), dim3(256), 0, s,
-                           reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale,
-                           reinterpret_cast<u32x4 *>(pool_dst), pa.pitch(), g->roi_bins);
-      }
-      if (fuse_mp)
-        for (const GOp &op : g->g_heads[head]) {
-          if (!op.from_rois) continue;
-          MPN_CHECK_LAUNCH();
-          const GTensor &dst = t_head[op.dst];
-          const ActI od{dst.buf, N, dst.C, dst.H, dst.W};
-          char *outp = reinterpret_cast<char *>(dst.buf) + (size_t)(op.dst_c_off / 8) * od.pitch() * 8 * sizeof(bf16_t);  // plane offset = the concat
-          RN_POOL(want_levels > 0 ? PK_ROIMAX_SORTED_TABLES : PK_ROIMAX_SORTED);
-          hipLaunchKernelGGL(roi_maxpool_c8i_bf16_sorted_kernel<4>, dim3((unsigned)cdiv_sz((size_t)N * dst.H * dst.W, 256), (unsigned)(Cb / 4)), dim3(256), 0, s,
-                             reinterpret_cast<const u32x4 *>(g->feat_sorted), g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale,
-                             op.kh, op.sh, op.ph, dst.H, dst.W, reinterpret_cast<u32x4 *>(outp), od.pitch(),
-                             want_levels > 0 ? reinterpret_cast<const u32x4 *>(g->feat_vmax) : nullptr, g->feat_vmax_elems / 8, want_levels);
-        }
-    } else if (g->bf16) {
-      RN_POOL(PK_ROI_BF16);
-      hipLaunchKernelGGL(roi_pool_c8i_bf16_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, reinterpret_cast<const bf16_t *>(g->feat), Cb, g->feat_h,
-                         g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale, reinterpret_cast<bf16_t *>(pool_dst), pa.pitch(), g->roi_bins);
-    } else if (fc_gemm && (g_graph_fuse & 256)) {
-      RN_POOL(PK_ROI_PM);
-      // the fully-connected operand is the VGG pipeline's (bin, roi)-row matrix: its pooling kernel too (a wave = one (roi, bin) over 256
-      // channels of a pixel-major copy of the map, four ROIs per block leaving as whole 128-byte lines) — 37 -> 12 us on AlexNet
-      void *pm = nullptr;
-      { int rc_ws = scratch_get(SCR_MISC, (size_t)g->feat_h * g->feat_w * Cb * 8 * sizeof(float), s, &pm); if (rc_ws) return rc_ws; }
-      hipLaunchKernelGGL(c8i_to_pixel_major_kernel, dim3((unsigned)cdiv_sz((size_t)g->feat_h * g->feat_w * Cb * 2, 256)), dim3(256), 0, s, g->feat, Cb,
-                         (size_t)g->feat_h * g->feat_w, fa.pitch(), static_cast<float *>(pm));
-      MPN_CHECK_LAUNCH();
-      const Act fdim{nullptr, g->feat_c, g->feat_h, g->feat_w, 0, 0};
-      int rcp = roi_pool_pm(fdim, static_cast<const float *>(pm), d_rois, N, PH, PH, spatial_scale, RoiRule{1.0f, 0, g->roi_bins}, g->fc_x, s, roi_stride, round_up(N, 128));
-      if (rcp) return rcp;
-    } else if ((g_bf16_fast_pool & 1) && Cb % 4 == 0) {
-      RN_POOL(PK_ROI_ROWS4);
-      hipLaunchKernelGGL(roi_pool_c8i_rows_kernel<4>, dim3((unsigned)cdiv_sz((size_t)N * PH * PH, 256), (unsigned)(Cb / 4)), dim3(256), 0, s, g->feat, g->feat_h,
-                         g->feat_w, fa.pitch(), d_rois, roi_stride, N, PH, PH, spatial_scale, fc_gemm ? g->fc_x : pool_dst, pa.pitch(), fc_gemm ? round_up(N, 128) : 0, g->roi_bins);
-    } else {
-      RN_POOL(PK_ROI_F32);
-      hipLaunchKernelGGL(roi_pool_c8i_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, g->feat, Cb, g->feat_h, g->feat_w, fa.pitch(), d_rois, roi_stride,
-                         N, PH, PH, spatial_scale, pool_dst, pa.pitch(), g->roi_bins);
-    }
-    MPN_CHECK_LAUNCH();
-  }
+  { int rc = rn_roi_pool(g, head, t_head, pool_dst, d_rois, roi_stride, N, spatial_scale, fc_gemm, fuse_mp, s); if (rc) return rc; }
   ActI cur{pool_dst, N, g->feat_c, PH, PH}, y;
   if (g->is_graph) {
     int rc = graph_run(g, g->g_heads[head], t_head, N, s, fuse_mp, fc_gemm);
@@ -3784,366 +2836,13 @@ int resnet_head_forward(ResNetGraph *g, int head, const float *d_rois, int roi_s
     if (rc) return rc;
     cur = y;
   }
-  const size_t total = (size_t)N * cur.Cb() * 2;
-  if (g->bf16 && (g_bf16_fast_pool & 2) && (size_t)16 * cur.H * cur.W * 9 * sizeof(float) <= 64 * 1024) {
-    RN_POOL(PK_GAVG_BF16_LDS);
-    hipLaunchKernelGGL(avgpool_c8i_bf16_to_c8_lds_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)cur.Cb()), dim3(256), (size_t)16 * cur.H * cur.W * 9 * sizeof(float), s,
-                       reinterpret_cast<const bf16_t *>(cur.p), N, cur.H * cur.W, cur.pitch(), 1.0f / (float)(cur.H * cur.W), d_feat_c8, Mp);
-  } else if (g->bf16) {
-    RN_POOL(PK_GAVG_BF16);
-    hipLaunchKernelGGL(avgpool_c8i_bf16_to_c8_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, reinterpret_cast<const bf16_t *>(cur.p), N, cur.Cb(),
-                       cur.H * cur.W, cur.pitch(), 1.0f / (float)(cur.H * cur.W), d_feat_c8, Mp);
-  } else {
-    RN_POOL(PK_GAVG_F32);
-    hipLaunchKernelGGL(avgpool_c8i_to_c8_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, s, cur.p, N, cur.Cb(), cur.H * cur.W, cur.pitch(),
-                       1.0f / (float)(cur.H * cur.W), d_feat_c8, Mp);
-  }
-  MPN_CHECK_LAUNCH();
-  return MPN_OK;
+  return rn_global_avg(g, cur, N, d_feat_c8, Mp, s);
 }
 
 }  // namespace mpn
 
 #ifdef MPN_DEBUG_HOOKS
-// Kernel-only timing of ONE per-ROI bf16 convolution (rn_conv, per_roi dispatch) on a batch of B maps of H x W (tools/bench_conv_bf16.py):
-// random bf16 activations / weights (zero operands clock higher), optional residual; returns the average ms of `iters` launches.
-namespace mpn {
-__global__ void checksum_u16_kernel(const unsigned short *__restrict__ p, size_t n, unsigned long long *__restrict__ acc) {
-  unsigned long long local = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    local += (unsigned long long)p[i] * (unsigned long long)(i % 65521u + 1u);
-  atomicAdd(acc, local);
-}
-}  // namespace mpn
-// checksum_out (optional): a position-weighted 64-bit checksum of the (zero-initialised, then written) output tensor — equal checksums
-// under two kernel choices = the same bits
-extern "C" int mpn_debug_bench_conv_bf16(int Cin, int Cout, int KH, int KW, int sh, int sw, int ph, int pw, int B, int H, int W, int with_res, int iters,
-                                         float *ms_out, unsigned long long *checksum_out) {
-  using namespace mpn;
-  MPN_CHECK_ARG(Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && B > 0 && H > 0 && W > 0 && iters > 0 && ms_out);
-  ResNetGraph *g = new ResNetGraph();
-  g->bf16 = true;
-  RnConv c;
-  c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.sh = sh; c.sw = sw; c.ph = ph; c.pw = pw; c.K = KH; c.stride = sh; c.pad = ph;
-  const size_t nw = (size_t)Cout * Cin * KH * KW;
-  std::vector<float> hw(nw);
-  unsigned x = 2463534242u;
-  for (auto &v : hw) { x = x * 1664525u + 1013904223u; v = ((x >> 8) * (1.0f / 8388608.0f) - 1.0f) * 0.05f; }
-  float *d_w = nullptr;
-  int rc = rn_alloc(g, &d_w, nw * sizeof(float));
-  if (rc == MPN_OK && hipMemcpy(d_w, hw.data(), nw * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = MPN_EHIP;
-  if (rc == MPN_OK) rc = rn_pack(g, c, d_w, nullptr);
-  const int OH = (H + 2 * ph - KH) / sh + 1, OW = (W + 2 * pw - KW) / sw + 1;
-  const size_t ie = c8i_elems(B, Cin, H, W), oe = c8i_elems(B, Cout, OH, OW);
-  float *in = nullptr, *out = nullptr, *res = nullptr;
-  if (rc == MPN_OK) rc = rn_alloc(g, &in, ie * sizeof(bf16_t));
-  if (rc == MPN_OK) rc = rn_alloc(g, &out, oe * sizeof(bf16_t));
-  if (rc == MPN_OK && with_res) rc = rn_alloc(g, &res, oe * sizeof(bf16_t));
-  if (rc == MPN_OK) {
-    std::vector<unsigned short> hi(std::max(ie, oe));
-    for (auto &v : hi) { x = x * 1664525u + 1013904223u; v = (unsigned short)(0x3c00u + ((x >> 9) & 0x3ffu) + ((x >> 31) << 15)); }  // +-[0.0078, 0.031): finite bf16
-    { const char *fill = getenv("MPN_BENCH_FILL"); if (fill && fill[0] == 'z') for (auto &v : hi) v = 0; }  // DVFS experiments: zero activations clock higher
-    if (hipMemcpy(in, hi.data(), ie * sizeof(bf16_t), hipMemcpyHostToDevice) != hipSuccess) rc = MPN_EHIP;
-    if (rc == MPN_OK && res && hipMemcpy(res, hi.data(), oe * sizeof(bf16_t), hipMemcpyHostToDevice) != hipSuccess) rc = MPN_EHIP;
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (rc == MPN_OK && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = MPN_EHIP;
-  const ActI ai{in, B, Cin, H, W};
-  ActI o;
-  for (int i = 0; i < 2 && rc == MPN_OK; ++i) rc = rn_conv(c, ai, out, res, 1, nullptr, &o, true, true);
-  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
-  if (rc == MPN_OK && checksum_out) {
-    unsigned long long *d_acc = nullptr;
-    if (hipMalloc(&d_acc, 8) != hipSuccess || hipMemset(d_acc, 0, 8) != hipSuccess || hipMemset(out, 0, oe * sizeof(bf16_t)) != hipSuccess) rc = MPN_EHIP;
-    if (rc == MPN_OK) rc = rn_conv(c, ai, out, res, 1, nullptr, &o, true, true);
-    if (rc == MPN_OK) {
-      hipLaunchKernelGGL(checksum_u16_kernel, dim3(2048), dim3(256), 0, nullptr, reinterpret_cast<const unsigned short *>(out), oe, d_acc);
-      if (hipMemcpy(checksum_out, d_acc, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = MPN_EHIP;
-    }
-    if (d_acc) (void)hipFree(d_acc);
-  }
-  if (rc == MPN_OK) (void)hipEventRecord(e0, nullptr);
-  for (int i = 0; i < iters && rc == MPN_OK; ++i) rc = rn_conv(c, ai, out, res, 1, nullptr, &o, true, true);
-  if (rc == MPN_OK) {
-    (void)hipEventRecord(e1, nullptr);
-    float ms = 0.f;
-    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = MPN_EHIP;
-    *ms_out = ms / iters;
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  resnet_free(g);
-  return rc;
-}
-// Test hook (tests/test_gpu_conv_numerics.py): ONE convolution through rn_conv, on NCHW fp32 device operands x [B, Cin, H, W], w [Cout, Cin,
-// KH, KW], b [Cout] (optional), res [B, Cout, OH, OW] (optional), packed by rn_pack into a scratch graph as graph building packs them
-// (lin_w / col_w; with `mosaic`, fp32 3x3 / stride-1 / pad-1 layers also get the Winograd weights and mosaic images for max_rois maps, as
-// mpn_resnet_create sets them up).  bf16: x, res and the weights round to bf16 (RNE), as the graph stores them.  The C8I input's pad channel
-// planes and its rows from B*H*W up to the pitch hold the finite pattern pad_fill * (+-1 .. 5); so do the residual's.  The output goes to
-// channels [out_c_off, out_c_off + Cout) of an out_c-channel C8I tensor (out_c_off: a multiple of 8) whose every element first holds the
-// sentinel NaN 0x7fa5a5a5 (bf16: 0x7fa5).  The rn_conv call is repeated for the batch sizes n_b[0 .. n_rep - 1] (each the first maps of x;
-// a fresh layout per run, one graph: the mosaic images carry over); y [n_b[n_rep - 1], Cout, OH, OW] fp32 is the last run's output.  raw
-// (optional, raw_cap bytes): the last run's whole output buffer, raw_bytes (optional) its size.  form_out: mpn_debug_conv_last_form().
-namespace mpn {
-__global__ void dbg_nchw_to_c8i_kernel(const float *__restrict__ x, int B, int C, int H, int W, size_t pitch, size_t total, float pad_fill, int bf16,
-                                       void *__restrict__ out, int one_sign = 0) {  // one_sign: the pad pattern is pad_fill * (1 .. 5)
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int j = (int)(t & 7);
-  const size_t r = (t >> 3) % pitch;
-  const int c = (int)((t >> 3) / pitch) * 8 + j;
-  const size_t HW = (size_t)H * W;
-  float v = pad_fill * (float)(1 + (int)(t % 5)) * ((t & 8) && !one_sign ? -1.0f : 1.0f);
-  if (c < C && r < (size_t)B * HW) v = x[((r / HW) * C + c) * HW + r % HW];
-  if (bf16) static_cast<bf16_t *>(out)[t] = f2bf(v);
-  else static_cast<float *>(out)[t] = v;
-}
-__global__ void dbg_c8i_to_nchw_kernel(const void *__restrict__ in, int B, int C, int H, int W, size_t pitch, int cb0, int bf16, float *__restrict__ y) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t HW = (size_t)H * W;
-  if (t >= (size_t)B * C * HW) return;
-  const size_t b = t / ((size_t)C * HW), rem = t % ((size_t)C * HW);
-  const int c = (int)(rem / HW);
-  const size_t off = ((size_t)(cb0 + c / 8) * pitch + b * HW + rem % HW) * 8 + c % 8;
-  y[t] = bf16 ? bf2f(static_cast<const bf16_t *>(in)[off]) : static_cast<const float *>(in)[off];
-}
-__global__ void dbg_fill_u32_kernel(unsigned *p, size_t n, unsigned v) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) p[t] = v;
-}
-}  // namespace mpn
-extern "C" int mpn_debug_conv_last_form(void) { return mpn::g_dbg_conv_form; }
-extern "C" int mpn_debug_conv_form(const float *d_x, int Cin, int H, int W, const float *d_w, int Cout, int KH, int KW, int sh, int sw, int ph, int pw,
-                                   const float *d_b, const float *d_res, int relu, int norelu_c0, int norelu_c1, int bf16, int per_roi, int allow_gemm,
-                                   int mosaic, int max_rois, int n_rep, const int *n_b, int out_c, int out_c_off, float pad_fill, float *d_y, void *d_raw,
-                                   size_t raw_cap, size_t *raw_bytes, int *form_out) {
-  using namespace mpn;
-  MPN_CHECK_ARG(d_x && d_w && d_y && Cin > 0 && H > 0 && W > 0 && Cout > 0 && KH > 0 && KW > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0);
-  MPN_CHECK_ARG(n_rep >= 1 && n_b && out_c_off >= 0 && out_c_off % 8 == 0 && out_c >= out_c_off + Cout && norelu_c0 % 8 == 0 && norelu_c1 % 8 == 0);
-  for (int i = 0; i < n_rep; ++i) MPN_CHECK_ARG(n_b[i] > 0);
-  const int OH = (H + 2 * ph - KH) / sh + 1, OW = (W + 2 * pw - KW) / sw + 1;
-  MPN_CHECK_ARG(OH > 0 && OW > 0 && std::isfinite(pad_fill));
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  ResNetGraph *g = new ResNetGraph();
-  g->bf16 = bf16 != 0;
-  const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
-  RnConv c;
-  c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.sh = sh; c.sw = sw; c.ph = ph; c.pw = pw; c.K = KH; c.stride = sh; c.pad = ph;
-  c.norelu_c0 = norelu_c0; c.norelu_c1 = norelu_c1;
-  int rc = rn_pack(g, c, d_w, d_b);
-  if (rc == MPN_OK && mosaic && !g->bf16 && (g_graph_fuse & 128) && KH == 3 && KW == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && Cin % 8 == 0 &&
-      Cout % 8 == 0 && Cin >= 16 && max_rois > 0) {  // as mpn_resnet_create: the Winograd weights and the two zeroed mosaic images
-    rc = rn_alloc(g, &c.wino, conv_wino_elems(Cin, Cout) * sizeof(float));
-    if (rc == MPN_OK) rc = pack_conv_weights_wino(d_w, Cin, Cout, c.wino, nullptr);
-    const int mx = std::max(1, 32 / (W + 1)), rows = ((max_rois + mx - 1) / mx) * (H + 1), cols = mx * (W + 1);
-    if (rc == MPN_OK) rc = rn_alloc(g, &c.mos_in, act_bytes(Cin, rows, cols));
-    if (rc == MPN_OK) rc = rn_alloc(g, &c.mos_out, act_bytes(Cout, rows, cols));
-    if (rc == MPN_OK && (hipMemset(c.mos_in, 0, act_bytes(Cin, rows, cols)) != hipSuccess || hipMemset(c.mos_out, 0, act_bytes(Cout, rows, cols)) != hipSuccess))
-      rc = MPN_EHIP;
-    c.mos_h = H; c.mos_w = W; c.mos_mx = mx; c.mos_rows = rows; c.mos_cols = cols;
-  }
-  // the output's channel blocks: the wider tensor's, and room for a form that writes whole 128-channel panels from out_c_off on
-  const int ob_all = std::max(round_up(out_c, 128), out_c_off + round_up(Cout, 128)) / 8;
-  float *in = nullptr, *out = nullptr, *res = nullptr;
-  for (int i = 0; i < n_rep && rc == MPN_OK; ++i) {
-    const int B = n_b[i];
-    if (in) { (void)hipFree(in); in = nullptr; }
-    if (out) { (void)hipFree(out); out = nullptr; }
-    if (res) { (void)hipFree(res); res = nullptr; }
-    const size_t ie = c8i_elems(B, Cin, H, W), pitch_o = ((size_t)B * OH * OW + 127) / 128 * 128, oe = (size_t)ob_all * pitch_o * 8;
-    const size_t re = c8i_elems(B, Cout, OH, OW);
-    if (hipMalloc(&in, ie * esz) != hipSuccess || hipMalloc(&out, oe * esz) != hipSuccess || (d_res && hipMalloc(&res, re * esz) != hipSuccess)) {
-      rc = MPN_EHIP;
-      break;
-    }
-    const ActI ai0{in, B, Cin, H, W};
-    hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(ie, 256)), dim3(256), 0, nullptr, d_x, B, Cin, H, W, ai0.pitch(), ie, pad_fill, bf16, in);
-    MPN_CHECK_LAUNCH();
-    if (res) {
-      hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(re, 256)), dim3(256), 0, nullptr, d_res, B, Cout, OH, OW, pitch_o, re, pad_fill, bf16, res);
-      MPN_CHECK_LAUNCH();
-    }
-    if (g->bf16) {
-      hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe / 2, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(out), oe / 2, 0x7fa57fa5u);
-    } else {
-      hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(out), oe, 0x7fa5a5a5u);
-    }
-    MPN_CHECK_LAUNCH();
-    ActI ai{in, B, Cin, H, W};
-    if (Cin == 3 && B == 1) ai.planar = d_x;  // the image layer: the graph keeps the same pixels as [3][H][W] planes
-    ActI o;
-    g_dbg_conv_form = 0;
-    rc = rn_conv(c, ai, reinterpret_cast<float *>(reinterpret_cast<char *>(out) + (size_t)(out_c_off / 8) * pitch_o * 8 * esz), res, relu, nullptr, &o,
-                 allow_gemm != 0, per_roi != 0);
-    if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
-    if (rc == MPN_OK && i + 1 == n_rep) {
-      const size_t total = (size_t)B * Cout * OH * OW;
-      hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, out, B, Cout, OH, OW, pitch_o, out_c_off / 8, bf16, d_y);
-      MPN_CHECK_LAUNCH();
-      if (raw_bytes) *raw_bytes = oe * esz;
-      if (d_raw && raw_cap < oe * esz) { set_error("mpn_debug_conv_form: raw needs %zu bytes", oe * esz); rc = MPN_EINVAL; }
-      else if (d_raw) MPN_CHECK_HIP(hipMemcpy(d_raw, out, oe * esz, hipMemcpyDeviceToDevice));
-    }
-  }
-  if (form_out) *form_out = g_dbg_conv_form;
-  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
-  if (in) (void)hipFree(in);
-  if (out) (void)hipFree(out);
-  if (res) (void)hipFree(res);
-  resnet_free(g);
-  return rc;
-}
-
-// Test hooks (tests/test_gpu_graph_pool_numerics.py): the pooling, LRN and ROI-pooling launches of the graph executor, one at a time, through
-// the dispatch code the product runs (graph_parse / graph_dims / graph_run, resnet_head_forward) on a scratch graph.
-//
-// mpn_debug_graph_op: ONE op of kind 1 (max-pool), 2 (average pool; op->b = the commuted pool's bias, with op->relu) or 3 (LRN) on the NCHW fp32
-// device tensor x [B, C, H, W]; the op reads channels [op->src_c_off, + op->cin) of it (op->src / dst / dst_c_off / w / cout are ignored).  The
-// source is laid out as C8I (bf16: rounded RNE) with the finite one-signed pattern pad_fill * (1 .. 5) in the pad lanes of a ragged last channel block,
-// in its pad planes and in the rows from B*H*W up to the pitch; the destination is an out_c-channel tensor written at out_c_off whose every
-// element first holds the sentinel NaN 0x7fa5a5a5 (bf16: 0x7fa5).  y [B, op->cin, OH, OW] fp32 (y_cap elements), oh / ow the output size,
-// raw (optional, raw_cap bytes) the whole output buffer [round_up(out_c, 128) / 8][pitch][8], kernel_out the PoolKernel id that ran.
-extern "C" int mpn_debug_graph_op(const float *d_x, int B, int C, int H, int W, const mpn_graph_op *op_in, int bf16, int out_c, int out_c_off, float pad_fill,
-                                  float *d_y, size_t y_cap, int *oh_out, int *ow_out, void *d_raw, size_t raw_cap, size_t *raw_bytes, int *kernel_out) {
-  using namespace mpn;
-  MPN_CHECK_ARG(d_x && d_y && op_in && B > 0 && C > 0 && H > 0 && W > 0 && out_c > 0 && out_c_off >= 0 && std::isfinite(pad_fill));
-  MPN_CHECK_ARG(op_in->kind >= 1 && op_in->kind <= 3);
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  ResNetGraph *g = new ResNetGraph();
-  g->is_graph = true; g->bf16 = bf16 != 0;
-  const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
-  mpn_graph_op o = *op_in;
-  o.src = 0; o.dst = 1; o.dst_c_off = out_c_off; o.w = nullptr; o.cout = 0;
-  const int tc[2] = {C, out_c};
-  std::vector<GOp> ops;
-  int rc = graph_parse(g, 1, &o, 2, tc, ops, g->t_head, true);
-  if (rc == MPN_OK) rc = graph_dims(ops, g->t_head, H, W);
-  size_t oe = 0, pitch_o = 0;
-  int OH = 0, OW = 0;
-  if (rc == MPN_OK) {
-    GTensor &ti = g->t_head[0], &to = g->t_head[1];
-    OH = to.H; OW = to.W;
-    const ActI ai{nullptr, B, C, H, W}, ao{nullptr, B, out_c, OH, OW};
-    const size_t ie = c8i_elems(B, C, H, W);
-    pitch_o = ao.pitch(); oe = c8i_elems(B, out_c, OH, OW);
-    if ((size_t)B * o.cin * OH * OW > y_cap) { set_error("mpn_debug_graph_op: y needs %zu elements", (size_t)B * o.cin * OH * OW); rc = MPN_EINVAL; }
-    if (rc == MPN_OK) rc = rn_alloc(g, &ti.buf, ie * esz);
-    if (rc == MPN_OK) rc = rn_alloc(g, &to.buf, oe * esz);
-    if (rc == MPN_OK) {
-      hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(ie, 256)), dim3(256), 0, nullptr, d_x, B, C, H, W, ai.pitch(), ie, pad_fill, bf16, ti.buf, 1);
-      if (g->bf16) hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe / 2, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(to.buf), oe / 2, 0x7fa57fa5u);
-      else hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(oe, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(to.buf), oe, 0x7fa5a5a5u);
-      if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
-    }
-  }
-  g_dbg_pool_kernel[0] = 0;
-  if (rc == MPN_OK) rc = graph_run(g, ops, g->t_head, B, nullptr);
-  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
-  if (rc == MPN_OK) {
-    const size_t total = (size_t)B * o.cin * OH * OW;
-    hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, g->t_head[1].buf, B, o.cin, OH, OW, pitch_o, out_c_off / 8, bf16, d_y);
-    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
-  }
-  if (rc == MPN_OK) {
-    if (oh_out) *oh_out = OH;
-    if (ow_out) *ow_out = OW;
-    if (raw_bytes) *raw_bytes = oe * esz;
-    if (kernel_out) *kernel_out = g_dbg_pool_kernel[0];
-    if (d_raw && raw_cap < oe * esz) { set_error("mpn_debug_graph_op: raw needs %zu bytes", oe * esz); rc = MPN_EINVAL; }
-    else if (d_raw && hipMemcpy(d_raw, g->t_head[1].buf, oe * esz, hipMemcpyDeviceToDevice) != hipSuccess) rc = MPN_EHIP;
-  }
-  if (hipDeviceSynchronize() != hipSuccess && rc == MPN_OK) rc = MPN_EHIP;
-  resnet_free(g);
-  return rc;
-}
-// mpn_debug_head_pool: resnet_head_forward on a scratch graph head without convolutions — the ROI pooling of the one-map NCHW fp32 feature
-// [C, H, W] (laid out as above, pad_fill in its pad lanes / planes / rows) for the table d_rois [N][roi_stride] into head tensor 0, optionally ONE
-// max-pool op of it (op_in: kind 1 reading all C channels of tensor 0 into tensor 1; from_rois by graph_build's rule, so the fused kernel takes it
-// where resnet_head_forward fuses), and the closing average of tensor 0 into the C8 matrix d_c8 [Cb][Mp][8] (pre-filled with the sentinel).
-// Every head tensor first holds the sentinel.  d_pooled [N, C, pooled, pooled], d_mp [N, C, OH, OW] (with op_in; mp_cap elements) fp32;
-// kernels_out[4] = the PoolKernel ids of {graph_run's op, ROI pooling, fused max-pool, closing average} (0 = none ran), levels_out = the range-max
-// levels built.  The fully-connected route (roi_pool_pm) needs an fc_w op and is not reachable from here.
-extern "C" int mpn_debug_head_pool(const float *d_feat, int C, int H, int W, const float *d_rois, int roi_stride, int N, int pooled, float spatial_scale,
-                                   int roi_bins, int bf16, const mpn_graph_op *op_in, float pad_fill, int Mp, float *d_pooled, float *d_mp, size_t mp_cap,
-                                   int *oh_out, int *ow_out, float *d_c8, int *kernels_out, int *levels_out) {
-  using namespace mpn;
-  MPN_CHECK_ARG(d_feat && d_rois && d_pooled && d_c8 && C > 0 && H > 0 && W > 0 && N > 0 && pooled > 0 && Mp >= N && roi_stride >= 5);
-  MPN_CHECK_ARG((roi_bins == MPN_ROI_BINS_CAFFE || roi_bins == MPN_ROI_BINS_ADAPTIVE) && std::isfinite(pad_fill) && (!op_in || (op_in->kind == 1 && d_mp)));
-  MPN_CHECK_HIP(hipDeviceSynchronize());
-  ResNetGraph *g = new ResNetGraph();
-  g->is_graph = true; g->bf16 = bf16 != 0; g->feat_c = C; g->feat_h = H; g->feat_w = W; g->pooled = pooled; g->max_rois = N; g->roi_bins = roi_bins;
-  g->out_tensor = 0; g->heads.resize(1); g->g_heads.resize(1);
-  const size_t esz = g->bf16 ? sizeof(bf16_t) : sizeof(float);
-  const int Cb = (C + 7) / 8;
-  int rc = MPN_OK;
-  if (op_in) {
-    mpn_graph_op o = *op_in;
-    o.src = 0; o.dst = 1; o.dst_c_off = 0; o.src_c_off = 0; o.cin = C; o.w = nullptr; o.cout = 0;
-    const int tc[2] = {C, C};
-    rc = graph_parse(g, 1, &o, 2, tc, g->g_heads[0], g->t_head, true);
-    if (rc == MPN_OK)
-      for (GOp &op : g->g_heads[0])
-        if (MPN_GOP_POOLS_ROIS(op, g->t_head[0].C))
-          op.from_rois = true;
-  } else {
-    g->t_head.resize(1);
-    g->t_head[0].C = C;
-  }
-  if (rc == MPN_OK) rc = graph_dims(g->g_heads[0], g->t_head, pooled, pooled);
-  const size_t fe = c8i_elems(1, C, H, W);
-  float *feat = nullptr;
-  if (rc == MPN_OK) rc = rn_alloc(g, &feat, fe * esz);
-  if (rc == MPN_OK) {
-    const ActI fa{nullptr, 1, C, H, W};
-    hipLaunchKernelGGL(dbg_nchw_to_c8i_kernel, dim3((unsigned)cdiv_sz(fe, 256)), dim3(256), 0, nullptr, d_feat, 1, C, H, W, fa.pitch(), fe, pad_fill, bf16, feat, 1);
-    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
-    g->feat = feat;
-  }
-  for (size_t i = 0; rc == MPN_OK && i < g->t_head.size(); ++i) {
-    GTensor &t = g->t_head[i];
-    const size_t te = c8i_elems(N, t.C, t.H, t.W);
-    rc = rn_alloc(g, &t.buf, te * esz);
-    if (rc != MPN_OK) break;
-    hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(te * esz / 4, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(t.buf), te * esz / 4,
-                       g->bf16 ? 0x7fa57fa5u : 0x7fa5a5a5u);
-    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
-  }
-  if (rc == MPN_OK) {
-    const size_t ce = (size_t)Cb * Mp * 8;
-    hipLaunchKernelGGL(dbg_fill_u32_kernel, dim3((unsigned)cdiv_sz(ce, 256)), dim3(256), 0, nullptr, reinterpret_cast<unsigned *>(d_c8), ce, 0x7fa5a5a5u);
-    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
-  }
-  if (rc == MPN_OK && g->t_head.size() > 1 && (size_t)N * C * g->t_head[1].H * g->t_head[1].W > mp_cap) {
-    set_error("mpn_debug_head_pool: mp needs %zu elements", (size_t)N * C * g->t_head[1].H * g->t_head[1].W);
-    rc = MPN_EINVAL;
-  }
-  for (int i = 0; i < 4; ++i) g_dbg_pool_kernel[i] = 0;
-  if (rc == MPN_OK) rc = resnet_head_forward(g, 0, d_rois, roi_stride, N, spatial_scale, d_c8, Mp, nullptr, 0);
-  if (rc == MPN_OK && hipDeviceSynchronize() != hipSuccess) rc = MPN_EHIP;
-  if (rc == MPN_OK) {
-    const ActI pa{nullptr, N, C, pooled, pooled};
-    const size_t total = (size_t)N * C * pooled * pooled;
-    hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, g->t_head[0].buf, N, C, pooled, pooled, pa.pitch(), 0, bf16, d_pooled);
-    if (g->t_head.size() > 1) {
-      const GTensor &t = g->t_head[1];
-      const ActI ma{nullptr, N, C, t.H, t.W};
-      const size_t tot2 = (size_t)N * C * t.H * t.W;
-      hipLaunchKernelGGL(dbg_c8i_to_nchw_kernel, dim3((unsigned)cdiv_sz(tot2, 256)), dim3(256), 0, nullptr, t.buf, N, C, t.H, t.W, ma.pitch(), 0, bf16, d_mp);
-      if (oh_out) *oh_out = t.H;
-      if (ow_out) *ow_out = t.W;
-    }
-    if (hipGetLastError() != hipSuccess) rc = MPN_EHIP;
-    if (kernels_out) for (int i = 0; i < 4; ++i) kernels_out[i] = g_dbg_pool_kernel[i];
-    if (levels_out) *levels_out = g->feat_vmax_valid ? g->feat_vmax_levels : 0;
-  }
-  if (hipDeviceSynchronize() != hipSuccess && rc == MPN_OK) rc = MPN_EHIP;
-  resnet_free(g);
-  return rc;
-}
-extern "C" void mpn_debug_set_tower_knock(int v) { mpn::g_tower_knock = v; }
-extern "C" void mpn_debug_set_pool_exp(int v) { mpn::g_pool_exp = v; }
 extern "C" void mpn_debug_set_bf16_dma(int v) { mpn::g_bf16_dma = v; }
-extern "C" void mpn_debug_set_roi_invariant(int v) { mpn::g_roi_invariant = v; }
 extern "C" void mpn_debug_set_bf16_exp(int v) { mpn::g_bf16_exp = v; }
 extern "C" void mpn_debug_set_bf16_bdir(int v) { mpn::g_bf16_bdir = v; }
 extern "C" void mpn_debug_set_bf16_bdir_ver(int v) { mpn::g_bf16_bdir_ver = v; }
@@ -4151,9 +2850,7 @@ extern "C" void mpn_debug_set_bf16_bdir_abl(int v) { mpn::g_bf16_bdir_abl = v; }
 extern "C" void mpn_debug_set_bf16_nch(int v) { mpn::g_bf16_nch = v; }
 extern "C" void mpn_debug_set_bf16_dma_tn(int v) { mpn::g_bf16_dma_tn = v; }
 extern "C" void mpn_debug_set_bf16_split_target(int v) { mpn::g_bf16_split_target = v; }
-extern "C" void mpn_debug_set_bf16_fast_pool(int v) { mpn::g_bf16_fast_pool = v; }
-extern "C" void mpn_debug_set_graph_fuse(int v) { mpn::g_graph_fuse = v; }
 extern "C" void mpn_debug_set_fp32_pf(int v) { mpn::g_fp32_pf = v; }
 extern "C" void mpn_debug_set_bf16_trace(void *p, int kh) { mpn::g_bf16_trace = static_cast<unsigned long long *>(p); mpn::g_bf16_trace_kh = kh; }
 extern "C" void mpn_debug_set_split_max_tiles(int v) { mpn::g_split_max_tiles = v; }
-#endif  // MPN_DEBUG_HOOKS
+#endif

@@ -41,9 +41,11 @@ def test_product_library_has_no_test_hooks():
     for n in _declared("mpn.h"):
         assert re.search(r" T %s\b" % n, dsym), n
     # no process-global device scratch: the only device-pointer statics allowed are inside the registry (common.hip)
-    for f in ("common.hip", "boxes.hip", "nms.hip", "roi_pool.hip", "dense.hip", "resnet.hip", "pipeline.hip", "comm.hip", "cocoeval.hip",
-              "train.hip", "train_driver.hip"):  # csrc/Makefile's SRCS
-        txt = open(os.path.join(ROOT, "multipathnet_amd", "csrc", f)).read()
+    csrc = os.path.join(ROOT, "multipathnet_amd", "csrc")
+    srcs = re.search(r"^SRCS\s*=\s*(.+)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()  # every source of the library
+    assert "common.hip" in srcs and "resnet.hip" in srcs and all(f.endswith(".hip") for f in srcs), srcs
+    for f in srcs:
+        txt = open(os.path.join(csrc, f)).read()
         assert not re.search(r"^\s*static\s+(float|char|void)\s*\*\s*\w+\s*=\s*nullptr", txt, flags=re.M), f
 
 

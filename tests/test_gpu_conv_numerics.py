@@ -33,7 +33,7 @@ KNOB_DEFAULTS = dict(fp32_pf=1, bf16_dma=1, bf16_dma_tn=0, bf16_bdir=1, bf16_bdi
 SENT32, SENT16 = 0x7FA5A5A5, 0x7FA5
 NOSPLIT = dict(bf16_split_target=0)
 
-# form ids (mpn_debug_conv_last_form): enum ConvForm in resnet.hip
+# form ids (mpn_debug_conv_last_form): enum ConvForm in graph_internal.h
 KC1, KC2, KC3, KC4, PF, MOSAIC, IM2COL, GEMM_FC, GEMM_DIRECT, GEMM_RI = 1, 2, 3, 4, 5, 10, 11, 12, 13, 14
 BDIR, DMA_256x128, DMA_128x256, DMA_256x256, B_KP1, B_KP2 = 20, 21, 22, 23, 26, 27
 DMA_W8, BDIR8 = 29, 38  # debug-flavour experiments: the 8-wave LDS-DMA shape, the 256-cout B-direct kernel

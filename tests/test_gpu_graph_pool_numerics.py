@@ -1,4 +1,4 @@
-"""The graph executor's pooling, LRN and ROI-pooling kernels (resnet.hip), one launch at a time, against float64 restatements.
+"""The graph executor's pooling, LRN and ROI-pooling kernels (graph_pool.hip), one launch at a time, against float64 restatements.
 
 The kernels are reached through two debug entries (debug flavour only) that run the product's own dispatch on a scratch graph:
 mpn_debug_graph_op (graph_parse / graph_dims / graph_run on one max-pool, average-pool or LRN op) and mpn_debug_head_pool
@@ -55,7 +55,7 @@ LRN_FACTOR = 2.0  # the device powf and a contracted k + a * ssum, over the orac
 
 SENT32, SENT16 = 0x7FA5A5A5, 0x7FA5
 MPN_EINVAL = -1
-# enum PoolKernel (resnet.hip)
+# enum PoolKernel (graph_internal.h)
 MAX_F32, MAX_BF16, AVG_F32, AVG_BF16, AVG_BF16_SMALL, LRN = 1, 2, 3, 4, 5, 6
 ROI_F32, ROI_ROWS4, ROI_BF16, ROI_SORTED = 16, 17, 18, 19
 ROIMAX_SORTED, ROIMAX_SORTED_TABLES = 32, 33
