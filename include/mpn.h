@@ -833,7 +833,32 @@ int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w /*[Cout,Cin,
  *                          NULL); with or without a train_begin: the exact inverse of creation.
  * Debug tensors of the last step (mpn_frcnn_debug_tensor), row-major: "tower_train_x.<t>" [rows, Kcat_t, PH, PW], "tower_train_y6.<t>"
  * [rows, fc_dim], "tower_train_cat" [rows, T * fc_dim], "tower_train_cls" [rows, K*C], "tower_train_bbox" [rows, 4C], "tower_train_g_cls"
- * [rows, K*C] (the gradient at z).  Not here: phase 2 (conv layers through the skip pooling), ResNet / op-list towers, momentum export. */
+ * [rows, K*C] (the gradient at z).
+ *
+ * The optimiser state of a tower run, under mpn_frcnn_train_get_state / _set_state's rules:
+ *   mpn_mpnet_train_get_state  tower t's momentum in Torch layout — the shapes of mpn_mpnet_get_tower_weights: mix [c5, Kcat_t], fc6
+ *                          [F, c5 * PH * PW], fc7 [F, F], each with its bias.  Any pointer may be NULL (not wanted).
+ *   mpn_mpnet_train_set_state  the inverse: packs the momentum as creation packs the weights (pad lanes +0.0; get -> set -> get is exact).
+ *                          All six tensors are required: a NULL one answers MPN_EINVAL naming it.
+ *   mpn_mpnet_train_get_head_state / _set_head_state  the same for the K classifiers [K*C, (T-1) F] and the box regressor [4C, F] — the
+ *                          shapes of mpn_mpnet_get_head_weights — and the step counter the dropout masks read (*h_step: a HOST pointer, may be
+ *                          NULL; step >= 0, else MPN_EINVAL).  set: all four tensors are required.
+ *                          tower outside [0, T): MPN_EINVAL naming T.  Without an mpn_mpnet_train_begin: MPN_ESTATE.  A set with rows pending
+ *                          (a train_add without its step): MPN_ESTATE.  Every other handle kind: MPN_ESTATE with mpn_mpnet_train_begin's
+ *                          message.  A refused call changes nothing.
+ * The weights (mpn_mpnet_get_tower_weights / _get_head_weights), this state, the dropout rate and the seed are everything a tower run
+ * continues from: a new handle created from the weights, train_begin, set_dropout, the set_state calls give the bits of the
+ * uninterrupted run.
+ *
+ * The learning-rate drop on the momentum (train.lua:321-335: `dfdx:mul(state.decay)` beside `learningRate * decay`), both kinds:
+ *   mpn_frcnn_train_scale_momentum / mpn_mpnet_train_scale_momentum  v <- fl(v * factor) in fp32, one rounding per element, in place on
+ *                          EVERY momentum buffer the state holds — plain handle: fc6, fc7 and the head as far as the depth trains them, and
+ *                          every trained conv layer; tower handle: every tower's mix / fc6 / fc7 and both heads; weights and biases.
+ *                          factor must be finite and >= 0 (MPN_EINVAL otherwise): the pad lanes of the packed buffers stay +0.0.
+ *                          factor == 1.0f launches nothing; 0.0f is the reference's reset on a phase switch (train.lua:248-259).  With rows
+ *                          pending: MPN_ESTATE (the reference scales between epochs).  One streaming launch per buffer, each byte read
+ *                          and written once.  The exported state afterwards is np.float32(v) * np.float32(factor) bit for bit.
+ * Not here: phase 2 (conv layers through the skip pooling), ResNet / op-list towers. */
 int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight);
 int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_rois /*[n,4]*/,
                         const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);
@@ -844,6 +869,16 @@ int mpn_mpnet_train_set_head(mpn_frcnn *p, int k);
 int mpn_mpnet_get_tower_weights(mpn_frcnn *p, int t, float *d_mix_w, float *d_mix_b, float *d_fc6_w, float *d_fc6_b, float *d_fc7_w,
                                 float *d_fc7_b, void *stream);
 int mpn_mpnet_get_head_weights(mpn_frcnn *p, float *d_cls_w, float *d_cls_b, float *d_bbox_w, float *d_bbox_b, void *stream);
+int mpn_mpnet_train_get_state(mpn_frcnn *p, int tower, float *d_mix_v, float *d_mix_vb, float *d_fc6_v, float *d_fc6_vb,
+                              float *d_fc7_v, float *d_fc7_vb, void *stream);
+int mpn_mpnet_train_set_state(mpn_frcnn *p, int tower, const float *d_mix_v, const float *d_mix_vb, const float *d_fc6_v,
+                              const float *d_fc6_vb, const float *d_fc7_v, const float *d_fc7_vb, void *stream);
+int mpn_mpnet_train_get_head_state(mpn_frcnn *p, float *d_cls_v, float *d_cls_vb, float *d_bbox_v, float *d_bbox_vb,
+                                   long *h_step, void *stream);
+int mpn_mpnet_train_set_head_state(mpn_frcnn *p, const float *d_cls_v, const float *d_cls_vb, const float *d_bbox_v,
+                                   const float *d_bbox_vb, long step, void *stream);
+int mpn_frcnn_train_scale_momentum(mpn_frcnn *p, float factor, void *stream);
+int mpn_mpnet_train_scale_momentum(mpn_frcnn *p, float factor, void *stream);
 
 /* Drawing a training minibatch's rows on the device: DataSetCOCO:attachProposals with its crowd branch
  * (DataSetJSON.lua:280-390) and BatchProviderROI's setupOne + selectBBoxesOne (BatchProviderROI.lua:39-49, 98-101) for ONE image — what

@@ -124,6 +124,13 @@ def load(flavour=None):
     lib.mpn_frcnn_train_set_head.argtypes = [C.c_void_p, C.c_int]
     lib.mpn_mpnet_train_set_dropout.argtypes = [C.c_void_p, C.c_float, C.c_long]
     lib.mpn_mpnet_train_set_head.argtypes = [C.c_void_p, C.c_int]
+    # the optimiser state of a tower run and the learning-rate drop on the momentum (include/mpn.h)
+    lib.mpn_mpnet_train_get_state.argtypes = [C.c_void_p, C.c_int] + [f32p] * 6 + [C.c_void_p]
+    lib.mpn_mpnet_train_set_state.argtypes = [C.c_void_p, C.c_int] + [f32p] * 6 + [C.c_void_p]
+    lib.mpn_mpnet_train_get_head_state.argtypes = [C.c_void_p] + [f32p] * 4 + [C.POINTER(C.c_long), C.c_void_p]
+    lib.mpn_mpnet_train_set_head_state.argtypes = [C.c_void_p] + [f32p] * 4 + [C.c_long, C.c_void_p]
+    lib.mpn_frcnn_train_scale_momentum.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+    lib.mpn_mpnet_train_scale_momentum.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
     # the minibatch sampler (include/mpn.h): 64-bit seed / draw, the configuration by pointer, the two counts through a HOST int[2]
     vp, cfgp = C.c_void_p, C.POINTER(RoiSamplerCfg)
     lib.mpn_attach_proposals.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]

@@ -65,6 +65,11 @@ int linear_dgrad_c8(const float *d_g_c8, int g_Mp, int B, int N, const float *d_
 // Lanes col >= N of the last record are written +0.0.  One thread per 32-byte record.  DESIGN.md section 13.6.
 struct DropoutCfg { uint32_t threshold, seed_lo, seed_hi, layer, step; float scale; };
 int dropout_c8(float *d_y_c8, int Mp, int B, int N, const DropoutCfg &cfg, hipStream_t s);
+// dfdx:mul(factor) on one momentum buffer (train.lua:321-335, the learning-rate drop): v[i] = fl(v[i] * factor) for i < n, in place, one
+// rounding per element, pad lanes of a packed buffer included (factor finite and >= 0 keeps their +0.0).  One grid-stride launch: float4
+// records over the first n & ~3 elements, a scalar tail for the rest; d_v is 16-byte aligned (every allocation is).  Each byte is read
+// and written once: the kernel is bound by HBM.  DESIGN.md section 13.13.
+int scale_momentum(float *d_v, size_t n, float factor, hipStream_t s);
 // rows < M of a C8 matrix at row pitch Mp -> row-major [M, N] (c8_to_rowmajor with the pitch given)
 int c8_rows_to_rowmajor(const float *d_c8, int Mp, int M, int N, float *d_y, hipStream_t s);
 // The inverse of pack_linear_weights for output rows [n0, n1): d_w [n1 - n0, K] Torch layout, d_b [n1 - n0]; either may be null.

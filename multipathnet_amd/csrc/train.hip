@@ -17,6 +17,9 @@
 // and the 32 lanes of a half-wave store 1 KiB contiguous.
 #include "train.h"
 
+#include <algorithm>
+#include <cstdint>
+
 #include "dense.h"
 #include "philox.h"
 
@@ -570,6 +573,34 @@ int dropout_c8(float *d_y_c8, int Mp, int B, int N, const DropoutCfg &cfg, hipSt
   MPN_CHECK_ARG(d_y_c8 && B > 0 && N > 0 && Mp >= B);
   const int nq = cdiv(N, 8);
   hipLaunchKernelGGL(dropout_c8_kernel, dim3((unsigned)cdiv_sz((size_t)nq * B, 256)), dim3(256), 0, s, d_y_c8, Mp, B, N, nq, cfg);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The learning-rate drop's dfdx:mul(decay) (train.lua:321-335)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Grid-stride over the n4 = n / 4 float4 records, a wave reading and writing 1 KiB contiguous per trip; the n & 3 elements behind them
+// go to the first threads of block 0 one by one.  No LDS, nothing but one multiply per element between the load and the store.
+__global__ __launch_bounds__(256) void scale_momentum_kernel(float *__restrict__ v, size_t n4, int tail, float f) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  f32x4 *v4 = reinterpret_cast<f32x4 *>(v);
+  for (size_t i = t0; i < n4; i += stride) {
+    f32x4 x = v4[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = x[e] * f;
+    v4[i] = x;
+  }
+  if (t0 < (size_t)tail) v[n4 * 4 + t0] = v[n4 * 4 + t0] * f;
+}
+
+constexpr unsigned kScaleMaxBlocks = 4096;  // 16 blocks of 256 threads per CU of an MI355X: the longest buffers take a few trips each
+
+int scale_momentum(float *d_v, size_t n, float factor, hipStream_t s) {
+  MPN_CHECK_ARG(d_v && n > 0 && ((uintptr_t)d_v & 15) == 0);
+  const size_t n4 = n / 4;
+  const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>(cdiv_sz(n4, 256), 1), kScaleMaxBlocks);
+  hipLaunchKernelGGL(scale_momentum_kernel, dim3(blocks), dim3(256), 0, s, d_v, n4, (int)(n & 3), factor);
   MPN_CHECK_LAUNCH();
   return MPN_OK;
 }

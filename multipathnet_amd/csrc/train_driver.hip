@@ -1039,6 +1039,146 @@ extern "C" int mpn_mpnet_get_head_weights(mpn_frcnn *p, float *d_cls_w, float *d
   return rc;
 }
 
+// ---- the optimiser state of a tower run (mpn_mpnet_train_get_state / _set_state / _get_head_state / _set_head_state; DESIGN.md
+// section 13.13): a table row's momentum in the Torch layout of its weight, through the packers the weights themselves go through ----
+static int get_lin_state(const LinT &L, float *d_v, float *d_vb, hipStream_t s) {
+  return unpack_linear_weights(L.v, L.vb, L.K, L.N, L.inner, 0, L.N, d_v, d_vb, s);
+}
+static int set_lin_state(const LinT &L, const float *d_v, const float *d_vb, hipStream_t s) {
+  return pack_linear_weights(d_v, d_vb, L.K, L.N, L.inner, L.v, L.vb, s);
+}
+// a tower-state entry point up to its own arguments: a MultiPathNet handle that can train and has begun; setter: no rows pending
+static int tower_state_begin(mpn_frcnn *p, const char *fn, bool setter, TowerTrainState **t) {
+  int rc = refuse_train(p, true, fn);
+  TrainCore *c = nullptr;
+  if (rc == MPN_OK) rc = need_core(p, true, fn, &c);
+  if (rc) return rc;
+  if (setter && c->pending > 0) { set_error("%s: %d rows are pending: take the step (mpn_mpnet_train_step) first", fn, c->pending); return MPN_ESTATE; }
+  *t = static_cast<TowerTrainState *>(c);
+  return MPN_OK;
+}
+static int check_tower_index(const mpn_frcnn *p, const char *fn, int tower) {
+  const int T = (int)p->towers.size();
+  if (tower >= 0 && tower < T) return MPN_OK;
+  set_error("%s: invalid argument: tower %d is outside [0, T) of this handle's T = %d towers", fn, tower, T);
+  return MPN_EINVAL;
+}
+// a setter's tensors: every one is part of the state
+static int need_all_tensors(const char *fn, const float *const *q, const char *const *names, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!q[i]) { set_error("%s: invalid argument: %s is NULL: every tensor of the call is part of the state", fn, names[i]); return MPN_EINVAL; }
+  return MPN_OK;
+}
+static const char *const kTowerStateNames[6] = {"d_mix_v", "d_mix_vb", "d_fc6_v", "d_fc6_vb", "d_fc7_v", "d_fc7_vb"};
+static const char *const kTowerHeadStateNames[4] = {"d_cls_v", "d_cls_vb", "d_bbox_v", "d_bbox_vb"};
+
+extern "C" int mpn_mpnet_train_get_state(mpn_frcnn *p, int tower, float *d_mix_v, float *d_mix_vb, float *d_fc6_v, float *d_fc6_vb, float *d_fc7_v,
+                                         float *d_fc7_vb, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t;
+  int rc = tower_state_begin(p, __func__, false, &t);
+  if (rc == MPN_OK) rc = check_tower_index(p, __func__, tower);
+  if (rc) return rc;
+  float *const q[6] = {d_mix_v, d_mix_vb, d_fc6_v, d_fc6_vb, d_fc7_v, d_fc7_vb};
+  hipStream_t s = as_stream(stream);
+  for (int i = 0; i < 3 && rc == MPN_OK; ++i) rc = get_lin_state(t->lin[3 * tower + i], q[2 * i], q[2 * i + 1], s);
+  return rc;
+}
+
+extern "C" int mpn_mpnet_train_set_state(mpn_frcnn *p, int tower, const float *d_mix_v, const float *d_mix_vb, const float *d_fc6_v,
+                                         const float *d_fc6_vb, const float *d_fc7_v, const float *d_fc7_vb, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t;
+  int rc = tower_state_begin(p, __func__, true, &t);
+  if (rc == MPN_OK) rc = check_tower_index(p, __func__, tower);
+  const float *const q[6] = {d_mix_v, d_mix_vb, d_fc6_v, d_fc6_vb, d_fc7_v, d_fc7_vb};
+  if (rc == MPN_OK) rc = need_all_tensors(__func__, q, kTowerStateNames, 6);
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  for (int i = 0; i < 3 && rc == MPN_OK; ++i) rc = set_lin_state(t->lin[3 * tower + i], q[2 * i], q[2 * i + 1], s);
+  return rc;
+}
+
+extern "C" int mpn_mpnet_train_get_head_state(mpn_frcnn *p, float *d_cls_v, float *d_cls_vb, float *d_bbox_v, float *d_bbox_vb, long *h_step,
+                                              void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t;
+  int rc = tower_state_begin(p, __func__, false, &t);
+  if (rc) return rc;
+  hipStream_t s = as_stream(stream);
+  rc = get_lin_state(t->cls(), d_cls_v, d_cls_vb, s);
+  if (rc == MPN_OK) rc = get_lin_state(t->bbox(), d_bbox_v, d_bbox_vb, s);
+  if (rc == MPN_OK && h_step) *h_step = t->step;
+  return rc;
+}
+
+extern "C" int mpn_mpnet_train_set_head_state(mpn_frcnn *p, const float *d_cls_v, const float *d_cls_vb, const float *d_bbox_v,
+                                              const float *d_bbox_vb, long step, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t;
+  int rc = tower_state_begin(p, __func__, true, &t);
+  const float *const q[4] = {d_cls_v, d_cls_vb, d_bbox_v, d_bbox_vb};
+  if (rc == MPN_OK) rc = need_all_tensors(__func__, q, kTowerHeadStateNames, 4);
+  if (rc) return rc;
+  if (step < 0) { set_error("%s: invalid argument: step %ld is negative", __func__, step); return MPN_EINVAL; }
+  hipStream_t s = as_stream(stream);
+  rc = set_lin_state(t->cls(), d_cls_v, d_cls_vb, s);
+  if (rc == MPN_OK) rc = set_lin_state(t->bbox(), d_bbox_v, d_bbox_vb, s);
+  if (rc == MPN_OK) t->step = step;
+  return rc;
+}
+
+// ---- the learning-rate drop on the momentum (*_train_scale_momentum; train.lua:321-335 dfdx:mul(state.decay)) ----
+// every trained row of a layer table: the weight's momentum and the bias's, whole packed buffers (one launch each)
+static int scale_lin_momentum(const LinT *rows, int n, float factor, hipStream_t s) {
+  int rc = MPN_OK;
+  for (int i = 0; i < n && rc == MPN_OK; ++i) {
+    const LinT &L = rows[i];
+    if (!L.v) continue;
+    rc = scale_momentum(L.v, lin_wpk_elems(round_up(L.K, 64), L.N), factor, s);
+    if (rc == MPN_OK) rc = scale_momentum(L.vb, (size_t)lin_np(L.N), factor, s);
+  }
+  return rc;
+}
+
+static int train_scale_momentum(mpn_frcnn *p, bool mpnet, const char *fn, float factor, void *stream) {
+  int rc = refuse_train(p, mpnet, fn);
+  TrainCore *c = nullptr;
+  if (rc == MPN_OK) rc = need_core(p, mpnet, fn, &c);
+  if (rc) return rc;
+  if (!(std::isfinite(factor) && factor >= 0.0f) || std::signbit(factor)) {  // (-0.0f too: it would turn a pad lane's +0.0 into -0.0)
+    set_error("%s: invalid argument: factor %g is not a finite number >= 0 (-0.0 is not taken either)", fn, (double)factor);
+    return MPN_EINVAL;
+  }
+  if (c->pending > 0) {
+    set_error("%s: %d rows are pending: take the step (%s_train_step) first — the rate drops between epochs", fn, c->pending, kind_prefix(mpnet));
+    return MPN_ESTATE;
+  }
+  if (factor == 1.0f) return MPN_OK;  // v * 1 is v: nothing to launch
+  hipStream_t s = as_stream(stream);
+  if (mpnet) {
+    const TowerTrainState *t = p->tower_train;
+    return scale_lin_momentum(t->lin.data(), (int)t->lin.size(), factor, s);
+  }
+  const TrainState *t = p->train;
+  rc = scale_lin_momentum(t->fc, 3, factor, s);
+  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {
+    const ConvLayer &L = p->conv[t->first + j];
+    rc = scale_momentum(t->cl[j].v, conv_wpk_elems(L.Cin, L.Cout), factor, s);
+    if (rc == MPN_OK) rc = scale_momentum(t->cl[j].vb, (size_t)conv_coutp(L.Cout), factor, s);
+  }
+  return rc;
+}
+
+extern "C" int mpn_frcnn_train_scale_momentum(mpn_frcnn *p, float factor, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_scale_momentum(p, false, __func__, factor, stream);
+}
+extern "C" int mpn_mpnet_train_scale_momentum(mpn_frcnn *p, float factor, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  return train_scale_momentum(p, true, __func__, factor, stream);
+}
+
 // mpn_frcnn_debug_tensor's "tower_train_*" names, all of the last mpn_mpnet_train_step, row-major: "tower_train_x.<t>" the mix operand
 // [rows, Kcat_t, PH, PW] (valid until the next mpn_mpnet_train_add), "tower_train_y6.<t>" fc6's output behind the dropout [rows, F],
 // "tower_train_cat" [rows, T * F], "tower_train_cls" [rows, K * C], "tower_train_bbox" [rows, 4C], "tower_train_g_cls" [rows, K * C]

@@ -986,6 +986,7 @@ class FastRCNN(object):
         fc6 and fc7, the K integral classifiers and the box regressor.  fp32 handles only; train_begin keeps refusing these handles.
         dropout = 0.0: none; see tower_train_set_dropout."""
         check(self._lib.mpn_mpnet_train_begin(self._h, C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)), "mpn_mpnet_train_begin")
+        self._dropout = (0.0, int(seed))
         if dropout:
             self.tower_train_set_dropout(dropout, seed)
 
@@ -993,6 +994,7 @@ class FastRCNN(object):
         """nn.Dropout(rate) behind fc6 + ReLU and fc7 + ReLU of every tower from the next tower_train_step on: train_set_dropout's mask
         with layer = 2 * tower + (0 behind fc6, 1 behind fc7), so two towers never share one."""
         check(self._lib.mpn_mpnet_train_set_dropout(self._h, float(rate), int(seed)), "mpn_mpnet_train_set_dropout")
+        self._dropout = (float(rate), int(seed))
 
     def tower_train_set_head(self, k):
         """The integral loss's selector: the next tower_train_step's loss reads classifier k of n_integral (train_set_head's rule)."""
@@ -1012,6 +1014,54 @@ class FastRCNN(object):
 
     def tower_train_end(self):
         self._train_call("mpn_mpnet_train_end")
+
+    _TOWER_ORDER = ("mix_w", "mix_b", "fc6_w", "fc6_b", "fc7_w", "fc7_b")
+    _TOWER_HEAD_ORDER = ("cls_w", "cls_b", "bbox_w", "bbox_b")
+
+    def tower_train_state(self):
+        """The optimiser's state between tower_train_begin and tower_train_end: {"step": the step counter,
+        "towers": [{"mix_w", "mix_b", "fc6_w", "fc6_b", "fc7_w", "fc7_b"}, ...], "cls_w", "cls_b", "bbox_w", "bbox_b"} — the keys of
+        tower_weights(), the values the MOMENTUM of that tensor in Torch layout (device tensors).  With the weights, the dropout rate and
+        the seed it is what tower_train_load_state continues a run from, bit for bit."""
+        F, Cn, KC, PP = self.fc_dim, self.n_classes, self.n_integral * self.n_classes, self._cfg.pooled_h * self._cfg.pooled_w
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        S = {"towers": []}
+        if self.is_mpnet:   # (any other handle: the library names the cause below)
+            c5, nf = self._cout[len(self._cout) - 1], len(self._towers) - 1
+            for t, T in enumerate(self._towers):
+                V = dict(mix_w=z(c5, T["total_feat"]), mix_b=z(c5), fc6_w=z(F, c5 * PP), fc6_b=z(F), fc7_w=z(F, F), fc7_b=z(F))
+                check(self._lib.mpn_mpnet_train_get_state(self._h, t, *[_f(V[k]) for k in self._TOWER_ORDER], _stream()), "mpn_mpnet_train_get_state")
+                S["towers"].append(V)
+            S.update(cls_w=z(KC, nf * F), cls_b=z(KC), bbox_w=z(4 * Cn, F), bbox_b=z(4 * Cn))
+        step = C.c_long()
+        check(self._lib.mpn_mpnet_train_get_head_state(self._h, *[_f(S[k]) if k in S else None for k in self._TOWER_HEAD_ORDER], C.byref(step), _stream()),
+              "mpn_mpnet_train_get_head_state")
+        S["step"] = int(step.value)
+        return S
+
+    def tower_train_load_state(self, state):
+        """Restore what tower_train_state() returned (momentum tensors on any device; numpy arrays are taken too) into a handle that has
+        begun tower training: every tower's six tensors and the four head tensors must be there.  No rows may be pending."""
+        dev = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).to(self.device).contiguous()
+        ptr = lambda t: None if t is None else _f(t)
+        keep = []
+        for t, V in enumerate(state["towers"]):
+            Tn = [dev(V.get(k)) for k in self._TOWER_ORDER]
+            keep.append(Tn)
+            check(self._lib.mpn_mpnet_train_set_state(self._h, t, *[ptr(x) for x in Tn], _stream()), "mpn_mpnet_train_set_state")
+        Hn = [dev(state.get(k)) for k in self._TOWER_HEAD_ORDER]
+        check(self._lib.mpn_mpnet_train_set_head_state(self._h, *[ptr(x) for x in Hn], int(state["step"]), _stream()), "mpn_mpnet_train_set_head_state")
+        torch.cuda.current_stream().synchronize()   # the packers have read the (possibly temporary) device copies
+
+    def train_scale_momentum(self, factor):
+        """The learning-rate drop's `dfdx:mul(decay)` (train.lua:321-335) between train_begin and train_end: every momentum buffer of the
+        state — fc6 / fc7 / heads as far as the depth trains them, every trained conv layer, weights and biases — times `factor` in fp32,
+        in place (mpn_frcnn_train_scale_momentum).  factor finite and >= 0; 1.0 launches nothing; no rows may be pending."""
+        self._train_call("mpn_frcnn_train_scale_momentum", C.c_float(factor), _stream())
+
+    def tower_train_scale_momentum(self, factor):
+        """train_scale_momentum for a tower run: every tower's mix / fc6 / fc7 and both heads (mpn_mpnet_train_scale_momentum)."""
+        self._train_call("mpn_mpnet_train_scale_momentum", C.c_float(factor), _stream())
 
     def tower_weights(self):
         """The MultiPathNet handle's parameters as synthetic_mpnet_params shapes them (device tensors): the towers' and heads' current

@@ -236,56 +236,218 @@ def bbox_regression_stats(records, fg_threshold=0.5):
 _HEAD_KEYS = ("fc6_w", "fc6_b", "fc7_w", "fc7_b", "cls_w", "cls_b", "bbox_w", "bbox_b")
 
 
-def save_checkpoint(path, net):
-    """Everything a training run of a models.FastRCNN continues from, as ONE Torch7 table (t7.py) — the reference writes the pair
+def save_checkpoint(path, net, epoch=None, learning_rate=None):
+    """Everything a training run of a models.FastRCNN or models.MultiPathNet continues from, as ONE Torch7 table (t7.py) — the reference writes the pair
     model_<epoch>.t7 + optimState_<epoch>.t7 (train.lua:188-198).  Between train_begin and train_end.  Flat keys:
       "fc6_w" .. "bbox_b", "conv_w.<l>", "conv_b.<l>"       the weights (net.head_weights() + net.trunk_weights())
       "v.fc6_w" .. "v.bbox_b", "v.conv_w.<l>", "v.conv_b.<l>"  the momentum of every TRAINED tensor (net.train_state(); the others are absent)
       "step", "n_conv", "dropout", "seed"                   the step counter, the trunk's depth, the dropout rate and its seed (a decimal
                                                             string: a Torch7 number is a double, a seed has 64 bits)
       "n_integral"                                          K, only where net holds K > 1 integral classifiers ("cls_w" [K*C, F], "cls_b"
-                                                            [K*C] and their momentum stacked in head order): a K = 1 file has no such key"""
-    torch.cuda.synchronize()
-    host = lambda t: t.detach().cpu().numpy()
-    Wt, St = dict(net.head_weights()), net.train_state()
-    Wt.update(net.trunk_weights())
-    tab = {k: host(Wt[k]) for k in _HEAD_KEYS}
-    n_conv = len(Wt["conv_w"])
-    for l in range(n_conv):
-        tab["conv_w.%d" % l], tab["conv_b.%d" % l] = host(Wt["conv_w"][l]), host(Wt["conv_b"][l])
-    for k in _HEAD_KEYS:
-        if St[k] is not None:
-            tab["v." + k] = host(St[k])
-    for l in range(n_conv):
-        if St["conv_w"][l] is not None:
-            tab["v.conv_w.%d" % l], tab["v.conv_b.%d" % l] = host(St["conv_w"][l]), host(St["conv_b"][l])
+                                                            [K*C] and their momentum stacked in head order): a K = 1 file has no such key
+      "epoch", "learningRate"                               only where given: the epoch the file closes and the rate the next one runs at
+                                                            (`fit` writes both, behind the rate drop)
+    A MultiPathNet net (between tower_train_begin and tower_train_end) gives mpnet_checkpoint_table's keys instead, "kind" = "mpnet"
+    among them; a plain file has no "kind"."""
+    if torch.cuda.is_available():   # (the copies to the host below wait for the device anyway; a stand-in net in a test has none)
+        torch.cuda.synchronize()
     rate, seed = net._dropout
-    tab.update({"step": St["step"], "n_conv": n_conv, "dropout": float(rate), "seed": str(int(seed))})
-    if getattr(net, "n_integral", 1) > 1:
-        tab["n_integral"] = int(net.n_integral)
+    if getattr(net, "is_mpnet", False):
+        tab = mpnet_checkpoint_table(net.tower_weights(), net.tower_train_state(), rate, seed, epoch, learning_rate)
+    else:
+        Wt = dict(net.head_weights())
+        Wt.update(net.trunk_weights())
+        tab = plain_checkpoint_table(Wt, net.train_state(), rate, seed, getattr(net, "n_integral", 1), epoch, learning_rate)
     t7.save(path, tab)
 
 
-def load_checkpoint(path):
-    """-> {"weights": {...head_weights() keys, "conv_w": [...], "conv_b": [...]}, "state": what FastRCNN.train_load_state takes,
-    "dropout": rate, "seed": int} with host torch tensors ("weights" also carries "n_integral" where the file does: K > 1 integral
-    classifiers).  Update a parameter dict with "weights" to create the FastRCNN, then
-    train_begin (the same depth), train_set_dropout(dropout, seed), train_load_state(state) — or `resume`."""
-    tab = t7.load(path)
-    n_conv = int(tab["n_conv"])
+def _host(t):
+    """a host numpy array of a tensor on either side (or of an array)"""
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def _run_keys(tab, rate, seed, step, epoch, learning_rate):
+    """what every checkpoint carries beside tensors: the seed as a decimal string (a Torch7 number is a double, a seed has 64 bits)"""
+    tab.update({"step": int(step), "dropout": float(rate), "seed": str(int(seed))})
+    if epoch is not None:
+        tab["epoch"] = int(epoch)
+    if learning_rate is not None:
+        tab["learningRate"] = float(learning_rate)
+    return tab
+
+
+def plain_checkpoint_table(weights, state, rate, seed, n_integral=1, epoch=None, learning_rate=None):
+    """save_checkpoint's table of a plain FastRCNN from plain tensors / arrays on either side (no GPU needed): `weights` =
+    head_weights() + trunk_weights(), `state` = train_state()."""
+    tab = {k: _host(weights[k]) for k in _HEAD_KEYS}
+    n_conv = len(weights["conv_w"])
+    for l in range(n_conv):
+        tab["conv_w.%d" % l], tab["conv_b.%d" % l] = _host(weights["conv_w"][l]), _host(weights["conv_b"][l])
+    for k in _HEAD_KEYS:
+        if state[k] is not None:
+            tab["v." + k] = _host(state[k])
+    for l in range(n_conv):
+        if state["conv_w"][l] is not None:
+            tab["v.conv_w.%d" % l], tab["v.conv_b.%d" % l] = _host(state["conv_w"][l]), _host(state["conv_b"][l])
+    tab["n_conv"] = n_conv
+    if n_integral > 1:
+        tab["n_integral"] = int(n_integral)
+    return _run_keys(tab, rate, seed, state["step"], epoch, learning_rate)
+
+
+_TOWER_KEYS = ("mix_w", "mix_b", "fc6_w", "fc6_b", "fc7_w", "fc7_b")
+_TOWER_GEOMETRY = ("region", "use4", "use3")
+_TOWER_HEAD_KEYS = ("cls_w", "cls_b", "bbox_w", "bbox_b")
+
+
+def mpnet_checkpoint_table(weights, state, rate, seed, epoch=None, learning_rate=None):
+    """save_checkpoint's table of a MultiPathNet from plain tensors / arrays on either side (no GPU needed): `weights` = tower_weights(),
+    `state` = tower_train_state().  Flat keys:
+      "kind" = "mpnet", "n_towers", "n_integral", "n_classes", "n_conv"
+      "tower.<t>.mix_w" .. "tower.<t>.fc7_b", "tower.<t>.region" / ".use4" / ".use3"   tower t's weights and its geometry (numbers)
+      "cls_w", "cls_b", "bbox_w", "bbox_b"                  the K classifiers stacked, the box regressor
+      "conv_w.<l>", "conv_b.<l>"                            the frozen trunk: the reference's model_<n>.t7 holds the whole model
+      "bbox_mean", "bbox_std", "conv345_norm"               nn.BBoxNorm's statistics where the net has them; opt.model_conv345_norm
+      "v.tower.<t>.<name>", "v.cls_w" .. "v.bbox_b"         the momentum of every trained tensor
+      "step", "dropout", "seed", "epoch", "learningRate"    as in a plain file"""
+    tow = weights["towers"]
+    tab = {"kind": "mpnet", "n_towers": len(tow), "n_integral": int(weights["n_integral"]), "n_classes": int(weights["n_classes"])}
+    for t, T in enumerate(tow):
+        for k in _TOWER_KEYS:
+            tab["tower.%d.%s" % (t, k)] = _host(T[k])
+            tab["v.tower.%d.%s" % (t, k)] = _host(state["towers"][t][k])
+        for k in _TOWER_GEOMETRY:
+            tab["tower.%d.%s" % (t, k)] = int(T[k])
+    for k in _TOWER_HEAD_KEYS:
+        tab[k], tab["v." + k] = _host(weights[k]), _host(state[k])
+    n_conv = len(weights["conv_w"])
+    for l in range(n_conv):
+        tab["conv_w.%d" % l], tab["conv_b.%d" % l] = _host(weights["conv_w"][l]), _host(weights["conv_b"][l])
+    tab["n_conv"] = n_conv
+    for k in ("bbox_mean", "bbox_std"):
+        if weights.get(k) is not None:
+            tab[k] = np.asarray(_host(weights[k]), np.float64)   # (Python floats at creation: a DoubleTensor keeps them as they are)
+    tab["conv345_norm"] = bool(weights.get("conv345_norm", True))
+    return _run_keys(tab, rate, seed, state["step"], epoch, learning_rate)
+
+
+def _read_run_keys(tab, out):
+    out.update({"dropout": float(tab["dropout"]), "seed": int(tab["seed"])})
+    if "epoch" in tab:
+        out["epoch"] = int(tab["epoch"])
+    if "learningRate" in tab:
+        out["learningRate"] = float(tab["learningRate"])
+    return out
+
+
+def checkpoint_read(tab):
+    """load_checkpoint behind t7.load: a checkpoint table (as t7.load returns it, or as *_checkpoint_table built it) -> load_checkpoint's
+    result with host torch tensors.  A table without "kind" is a plain FastRCNN's."""
     ten = lambda k: torch.from_numpy(np.array(tab[k])) if k in tab else None
-    weights = {k: ten(k) for k in _HEAD_KEYS}
-    weights["conv_w"], weights["conv_b"] = [ten("conv_w.%d" % l) for l in range(n_conv)], [ten("conv_b.%d" % l) for l in range(n_conv)]
+    n_conv = int(tab["n_conv"])
+    weights = {"conv_w": [ten("conv_w.%d" % l) for l in range(n_conv)], "conv_b": [ten("conv_b.%d" % l) for l in range(n_conv)]}
+    if tab.get("kind") == "mpnet":
+        nt = int(tab["n_towers"])
+        weights["towers"] = []
+        state = {"towers": [], "step": int(tab["step"])}
+        for t in range(nt):
+            T = {k: ten("tower.%d.%s" % (t, k)) for k in _TOWER_KEYS}
+            T.update({k: int(tab["tower.%d.%s" % (t, k)]) for k in _TOWER_GEOMETRY})
+            T["total_feat"] = int(T["mix_w"].shape[1])
+            weights["towers"].append(T)
+            state["towers"].append({k: ten("v.tower.%d.%s" % (t, k)) for k in _TOWER_KEYS})
+        for k in _TOWER_HEAD_KEYS:
+            weights[k], state[k] = ten(k), ten("v." + k)
+        weights["n_integral"], weights["n_classes"] = int(tab["n_integral"]), int(tab["n_classes"])
+        for k in ("bbox_mean", "bbox_std"):
+            if k in tab:
+                weights[k] = [float(x) for x in np.asarray(tab[k]).reshape(-1)]
+        weights["conv345_norm"] = bool(tab.get("conv345_norm", True))
+        return _read_run_keys(tab, {"kind": "mpnet", "weights": weights, "state": state})
+    if "kind" in tab:
+        raise ValueError("checkpoint of an unknown kind %r" % (tab["kind"],))
+    weights.update({k: ten(k) for k in _HEAD_KEYS})
     if "n_integral" in tab:
         weights["n_integral"] = int(tab["n_integral"])
     state = {k: ten("v." + k) for k in _HEAD_KEYS}
     state["conv_w"], state["conv_b"] = [ten("v.conv_w.%d" % l) for l in range(n_conv)], [ten("v.conv_b.%d" % l) for l in range(n_conv)]
     state["step"] = int(tab["step"])
-    return {"weights": weights, "state": state, "dropout": float(tab["dropout"]), "seed": int(tab["seed"])}
+    return _read_run_keys(tab, {"weights": weights, "state": state})
+
+
+def load_checkpoint(path):
+    """-> {"weights": {...head_weights() keys, "conv_w": [...], "conv_b": [...]}, "state": what FastRCNN.train_load_state takes,
+    "dropout": rate, "seed": int} with host torch tensors ("weights" also carries "n_integral" where the file does: K > 1 integral
+    classifiers; "epoch" and "learningRate" where the file has them).  Update a parameter dict with "weights" to create the FastRCNN,
+    then train_begin (the same depth), train_set_dropout(dropout, seed), train_load_state(state) — or `resume`.
+    A MultiPathNet file ("kind" = "mpnet", also returned): "weights" is a dict models.MultiPathNet(...) is built from (tower_weights()'
+    keys), "state" what tower_train_load_state takes; then tower_train_begin and `resume`."""
+    return checkpoint_read(t7.load(path))
 
 
 def resume(net, ckpt):
     """opt.resume: restore load_checkpoint's dropout stream and optimiser state into `net` — a FastRCNN created from ckpt["weights"] on
-    which train_begin (the same depth, momentum, weight decay) has been called."""
-    net.train_set_dropout(ckpt["dropout"], ckpt["seed"])
-    net.train_load_state(ckpt["state"])
+    which train_begin (the same depth, momentum, weight decay) has been called; or a MultiPathNet created from them on which
+    tower_train_begin has."""
+    if getattr(net, "is_mpnet", False):
+        net.tower_train_set_dropout(ckpt["dropout"], ckpt["seed"])
+        net.tower_train_load_state(ckpt["state"])
+    else:
+        net.train_set_dropout(ckpt["dropout"], ckpt["seed"])
+        net.train_load_state(ckpt["state"])
+
+
+def fit(net, batch_fn, n_epochs, epoch_size, lr, step, decay, snapshot=0, save_dir=None, validate=None, log=None, start=None):
+    """The epoch loop of train.lua:221-360 (the engine's hooks) on a net that has begun training — train_begin on a plain FastRCNN,
+    tower_train_begin on a MultiPathNet; `fit` picks train_* or tower_train_* by net.is_mpnet.  Phase 1 only (phase2_epoch = -1, the
+    shipped recipe).
+      batch_fn(epoch, it)   adds minibatch `it` of epoch `epoch` (both 1-based, as in the reference's log lines) to `net` itself with
+                            train_add* / tower_train_add*; returns the integral head k the step trains, or None (no set_head call).
+                            Which images enter a batch is the caller's: nothing is loaded, decoded or chosen here.
+      lr, step, decay       the rate of the first epoch; after every epoch e with e % step == 0: lr *= decay in Python double arithmetic
+                            (Lua's), then *_train_scale_momentum(decay) — the reference's dfdx:mul(decay).
+      log(dict)             after every epoch, behind the drop: {"epoch", "learningRate", "train_loss", "primary_loss", "bboxregr_loss"},
+                            the means over the epoch's steps (train_loss = cls + bbox; the box loss carries bbox_weight).  The steps' two
+                            losses are added up on the device and read back once per epoch: no synchronisation per iteration.
+      snapshot, save_dir    snapshot > 0: after every epoch e with e % snapshot == 0, save_checkpoint(save_dir/model_<e>.t7) with the epoch
+                            and the rate BEHIND the drop, then validate(net, e), whose result is logged as {"epoch", "validate"}.
+                            After the last epoch: model_final.t7 and a last validate(net, "final") (save_dir None: nothing is written).
+      start                 a load_checkpoint(...) result of such a file: resume(net, start), then epochs start["epoch"] + 1 .. n_epochs at
+                            the stored rate.
+    With a batch_fn that depends on (epoch, it) alone, a resumed fit gives the bits of the uninterrupted one: the weights, the momentum,
+    the step counter and the dropout stream are all in the file.  DeviceRoiSampler makes that easy — its `draw` is a counter the caller
+    passes, e.g. draw = ((epoch - 1) * epoch_size + (it - 1)) * images_per_batch + image, with no generator state to carry.
+    -> the rate after the last epoch."""
+    import os
+    mp = bool(getattr(net, "is_mpnet", False))
+    set_head, take_step = (net.tower_train_set_head, net.tower_train_step) if mp else (net.train_set_head, net.train_step)
+    scale = net.tower_train_scale_momentum if mp else net.train_scale_momentum
+    log = log if log is not None else (lambda rec: None)
+    lr, first = float(lr), 1
+    if start is not None:
+        resume(net, start)
+        first, lr = int(start["epoch"]) + 1, float(start["learningRate"])
+
+    def save_and_validate(tag, epoch):
+        if save_dir is not None:
+            save_checkpoint(os.path.join(save_dir, "model_%s.t7" % tag), net, epoch=epoch, learning_rate=lr)
+        if validate is not None:
+            log({"epoch": epoch, "validate": validate(net, tag)})
+
+    for e in range(first, int(n_epochs) + 1):
+        total = None
+        for it in range(1, int(epoch_size) + 1):
+            k = batch_fn(e, it)
+            if k is not None:
+                set_head(int(k))
+            loss = take_step(lr)
+            total = loss if total is None else total + loss   # on the device, in step order
+        if e % int(step) == 0:
+            lr = lr * float(decay)
+            scale(float(decay))
+        cls_l, box_l = (float(v) / int(epoch_size) for v in total.cpu())
+        log({"epoch": e, "learningRate": lr, "train_loss": cls_l + box_l, "primary_loss": cls_l, "bboxregr_loss": box_l})
+        if snapshot and e % int(snapshot) == 0:
+            save_and_validate(str(e), e)
+    save_and_validate("final", int(n_epochs))
+    return lr

@@ -18,9 +18,12 @@ the five MPN_TOWERS, fc_dim 4096, C 81, K 6; mpn_mpnet_train_*): ms of mpn_mpnet
 2 x 64 rows, step i on classifier i mod K, beside the step's derived floor — every trained weight and its momentum read and written once.
 --device-sampler measures instead the whole iteration at depth 2 with each image's rows chosen from 2000
 proposals, drawn on the device (train_add_sampled) and, alternating in the same run, on the host (numpy + uploads + train_add).
+--scale-momentum measures instead the learning-rate drop's momentum scaling per call — the VGG-16 towers and the
+plain handle at MPN_TRAIN_TRUNK(--trunk-layers, 9 without it) — beside its HBM floor and beside get -> multiply -> set on the plain handle.
 One JSON line per measurement.
 
     python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6] [--model mpnet] [--device-sampler]
+                                [--scale-momentum]
 """
 import argparse
 import ctypes as C
@@ -139,8 +142,75 @@ def bench_sampled(a):
                           "host_threads": torch.get_num_threads(), "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
+def bench_scale(a):
+    """--scale-momentum: *_train_scale_momentum per call — the learning-rate drop's dfdx:mul(decay), DESIGN.md section 13.13 — on the
+    VGG-16 towers and on the plain handle at MPN_TRAIN_TRUNK(k) (k = --trunk-layers, 9 without it): HIP events around a window of
+    --steps calls after --warmup, beside the floor — every momentum byte read and written once at 6.3 TB/s — and, on the plain handle,
+    the only alternative a host had before: train_state() -> multiply -> train_load_state()."""
+    import torch
+    from multipathnet_amd import models
+    name = torch.cuda.get_device_name(0)
+
+    def window(fn):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for _ in range(a.warmup):
+            fn()
+        e[0].record()
+        for _ in range(a.steps):
+            fn()
+        e[1].record()
+        e[1].synchronize()
+        return e[0].elapsed_time(e[1]) / a.steps
+
+    def numel(S):
+        flat = []
+        for v in S.values():
+            if isinstance(v, dict):
+                flat += list(v.values())
+            elif isinstance(v, list):
+                for x in v:
+                    flat += list(x.values()) if isinstance(x, dict) else [x]
+            else:
+                flat.append(v)
+        return sum(int(x.numel()) for x in flat if isinstance(x, torch.Tensor))
+
+    def report(what, ms, n, **kw):
+        gb = 2 * 4 * n / 1e9   # read + write
+        print(json.dumps(dict({"what": what, "ms_per_call": round(ms, 4), "momentum_elements": n, "gbytes_moved": round(gb, 3),
+                               "gbytes_per_s": round(gb / (ms * 1e-3), 1), "floor_ms_at_6.3TBps": round(gb / 6.3e3 * 1e3, 4), "calls": a.steps,
+                               "device": name}, **kw)), flush=True)
+
+    P = models.synthetic_mpnet_params(seed=557)
+    net = models.MultiPathNet(P, max_h=H, max_w=W, max_rois=IMAGES * ROWS)
+    del P
+    net.tower_train_begin(momentum=0.9, weight_decay=5e-4)
+    n = numel(net.tower_train_state())
+    report("mpnet_train_scale_momentum", window(lambda: net.tower_train_scale_momentum(0.5)), n, towers=5)
+    net.tower_train_end()
+    net.close()
+    del net
+    torch.cuda.empty_cache()
+
+    k = a.trunk_layers or 9
+    net = models.FastRCNN(models.synthetic_params(seed=557), max_h=H, max_w=W, max_rois=IMAGES * ROWS)
+    net.train_begin(trunk_layers=k, momentum=0.9, weight_decay=5e-4)
+    n = numel(net.train_state())
+    report("frcnn_train_scale_momentum", window(lambda: net.train_scale_momentum(0.5)), n, depth="MPN_TRAIN_TRUNK(%d)" % k)
+
+    def get_multiply_set():
+        S = net.train_state()
+        mul = lambda v: v * 0.5 if isinstance(v, torch.Tensor) else v
+        S = {key: ([mul(x) for x in v] if isinstance(v, list) else mul(v)) for key, v in S.items()}
+        net.train_load_state(S)
+
+    report("frcnn_get_multiply_set", window(get_multiply_set), n, depth="MPN_TRAIN_TRUNK(%d)" % k)
+    net.train_end()
+    net.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scale-momentum", action="store_true", help="instead: *_train_scale_momentum per call on both models, and get -> multiply -> set on the plain handle")
     ap.add_argument("--device-sampler", action="store_true", help="instead: the iteration with the rows drawn on the device (train_add_sampled) against the host-sampled one")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -152,6 +222,8 @@ def main():
     import torch
     from multipathnet_amd import _lib, models
     assert torch.cuda.is_available(), "bench_train needs a HIP device"
+    if a.scale_momentum:
+        return bench_scale(a)
     if a.device_sampler:
         return bench_sampled(a)
     if a.model == "mpnet":
