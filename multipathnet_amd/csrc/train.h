@@ -105,7 +105,10 @@ size_t conv_wgrad_part_elems(int Cin, int Cout, int H, int W);
 // v_mfma_f32_32x32x2_f32 over the pixels in row-major pairs, cut into segments of kWgradSegPx pixels, each accumulated from zero by its
 // own block into d_part; conv_wgrad_reduce_kernel then adds the segments in ascending order in groups of kWgradSegGroup, adds the group
 // sums in ascending order (up to kWgradSegGroup segments: one group, the plain ascending sum) and (accumulate) adds that sum to d_dw:
-// the order depends on (Cin, Cout, H, W) alone.  X's halo must be zero (it is the padding); G's halo is never read.
+// the order depends on (Cin, Cout, H, W) alone.  X's halo must be zero (it is the padding); G's halo and the pad channels of its last
+// block are never read.  d_part: slab s = segment s in the `wpk` layout, whole 32-byte records of the couts < Cout only — a pad cout's
+// records are not written, the pad-cin lanes of a written record hold the sums over X's pad channels (+0.0 for a real map); the
+// segment sum reads neither.
 int conv3x3_wgrad(const Act &x, const Act &g, float *d_part, float *d_dw, int accumulate, hipStream_t s);
 // db[co] (+)= sum_{y,x} G[co][y][x]: 32 interleaved pixel-ascending partial sums, then a fixed tree (as sgd_bias_kernel)
 int conv_bias_grad(const Act &g, float *d_db, int accumulate, hipStream_t s);

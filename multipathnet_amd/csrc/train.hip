@@ -765,7 +765,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(ConvWgradArgs a) 
   }
 }
 
-// dW (+)= (g[0] + g[1]) + ... with g[i] = ((part[8 i] + part[8 i + 1]) + ...) + part[8 i + 7] (train.h kWgradSegGroup); lanes outside the layer (pad couts, pad cins: never written by the kernel above) get +0.0
+// dW (+)= (g[0] + g[1]) + ... with g[i] = ((part[8 i] + part[8 i + 1]) + ...) + part[8 i + 7] (train.h kWgradSegGroup); lanes outside the layer get
+// +0.0 without a read of `part`: the records of pad couts are never written by the kernel above (stale), the pad-cin lanes of a real
+// cout's record hold its sums over X's pad channels
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float *__restrict__ part, size_t stride, int nseg, int Cin, int Cout, int CoutP,
                                                                 size_t total, float *__restrict__ dw, int accumulate) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
