@@ -858,8 +858,62 @@ int mpn_frcnn_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w /*[Cout,Cin,
  *                          factor == 1.0f launches nothing; 0.0f is the reference's reset on a phase switch (train.lua:248-259).  With rows
  *                          pending: MPN_ESTATE (the reference scales between epochs).  One streaming launch per buffer, each byte read
  *                          and written once.  The exported state afterwards is np.float32(v) * np.float32(factor) bit for bit.
- * Not here: phase 2 (conv layers through the skip pooling), ResNet / op-list towers. */
+ *
+ * Phase 2, first step: the conv block above the last pooling layer trained together with the towers (DESIGN.md section 13.15;
+ * models/model_utils.lua:184-207 setPhase2 restricted to conv5_1 .. conv5_3 of VGG-16).
+ *   mpn_mpnet_train_begin_conv  mpn_mpnet_train_begin that also trains the trunk's last conv_layers = k conv layers, k in 0..K, K = the conv
+ *                          layers behind the trunk's last pool_after layer capped at MPN_TRAIN_MAX_CONV, as for MPN_TRAIN_CONV.  k = 0 IS
+ *                          mpn_mpnet_train_begin: the same state, the same launches, the same bits.  k < 0 or k > K: MPN_EINVAL naming K;
+ *                          every other refusal is mpn_mpnet_train_begin's; the allocation is all or nothing.  With k > 0 at most
+ *                          MPN_TRAIN_MAX_IMAGES images may be pending: one more mpn_mpnet_train_add / _add_sampled answers MPN_EINVAL and
+ *                          changes nothing.
+ *   mpn_mpnet_get_trunk_weights  conv layer `layer`'s weights [Cout,Cin,3,3] and bias [Cout] in Torch layout (either may be NULL), with or
+ *                          without training: the exact inverse of creation (mpn_frcnn_get_trunk_weights keeps refusing these handles).
+ *   mpn_mpnet_train_get_trunk_state / _set_trunk_state  a TRAINED conv layer's momentum in those shapes, under the rules of
+ *                          mpn_frcnn_train_get_trunk_state / _set_trunk_state: get: either pointer may be NULL; set: both are needed; a
+ *                          layer that is not trained: MPN_EINVAL naming the trained range; a set with rows pending: MPN_ESTATE.
+ *                          mpn_mpnet_train_scale_momentum scales these buffers too.
+ * The step for k > 0, in section 13.9's notation — B pending rows of I images, gm_t the (unmasked) gradient at tower t's mix output, y_t the
+ * stored operand, c5 the last conv layer's channels, PP = PH * PW.  Only slab 0 of every operand, the conv5 slab (columns [0, c5) of
+ * Kcat_t), gets a gradient: the conv4 / conv3 slabs' and the layers below the last pooling layer are not trained.
+ *   1. gx_t[(bin,m), c] = sum_n gm_t[(bin,m), n] Wmix_t[n, c], c < c5, on the valid rows (PP segments of B rows at pitch Mp; the rows
+ *      between two segments may hold anything, NaN included: they reach no valid result), n ascending in the order of the Linear layers'
+ *      input gradient (four contiguous ranges of n, each ascending in pairs, their sums added in range order), before any weight is
+ *      updated.  It is that kernel itself, run once per tower over the rows from the first segment's first to the last segment's last.
+ *   2. nn.Normalize(2) x 1000 backward per (row, tower): with x the c5 * PP pooled values, s = 1000 / sqrt(sum x^2 + 1e-10) and
+ *      y = s x the stored operand,  dx = s * (gx - y * (y . gx) / 1000^2).  Both sums (x . x for s, y . gx) run over the entries
+ *      e = (c / 8 * PP + bin) * 8 + c % 8 in ONE order that depends on (c5, PP) alone: 256 partial sums, partial t taking the entries
+ *      e = t, t + 256, t + 512, .. ascending from +0.0 with one fused multiply-add each, then the tree
+ *      for (h = 128; h >= 1; h /= 2) part[t] += part[t + h] for t < h.  s is recomputed from x, which mpn_mpnet_train_add keeps beside the
+ *      argmax; the training forward's bits are untouched.  conv345_unnormalized: dx = gx (the conv5 factor is 1).
+ *   3. argmax, per Foveal region used, pending row, channel and bin: the FIRST strict maximum of the bin's window in row-major scan, -1 for
+ *      an empty window (the ROI pooling's own rule), written by mpn_mpnet_train_add behind the pending rows; towers that pool the same
+ *      region share it.  The forward keeps pooling from the range-max tables.
+ *   4. the gradient map of image i at the last conv layer's output: per cell (c, y, x) ONE fp32 chain from +0.0 — towers ascending, inside a
+ *      tower the image's rows ascending, inside a row the bins ascending, each term adding dx_t[n, c, bin] wherever
+ *      argmax_t[n, c, bin] == y * W + x.  No atomics; every interior cell is written, the halo is zero.  Then the mask [conv5 output > 0]:
+ *      nn.Normalize sits between the pooling and the ReLU, so the gradient at a pooled zero is not zero until here.
+ *   5. the chain of MPN_TRAIN_CONV(k) above, layer by layer in its orders: db, dW, the input gradient (here always on the direct
+ *      convolution kernel, never the Winograd one: DESIGN.md section 13.15) masked with the ReLU of the layer below, summed over
+ *      the images in train_add order; optim.sgd on the master pack, then the Winograd pack (and a first layer's
+ *      K = 36 pack) rebuilt in place — the forms a MultiPathNet handle's creation derives from the conv weights are the plain handle's —,
+ *      so that every form is bit-identical to what creation builds from mpn_mpnet_get_trunk_weights' output.  detect and captured graphs
+ *      see the new weights at once.
+ *   6. every input gradient of the step, the towers' and the convs', is computed before any update; the step is deterministic and
+ *      bit-reproducible with dropout on or off.
+ * mpn_mpnet_train_begin_conv(k > 0) allocates, all or nothing: per tower two [c5, PP, Mp] gradient slabs (one unnormalised), per region
+ * used the raw pools and the argmax [max_rois, c5, PP], the rows' Foveal table, MPN_TRAIN_MAX_IMAGES gradient maps, and the conv block's
+ * buffers as MPN_TRAIN_CONV(k) (the saved maps, two gradient maps, per layer momentum, gradient and the input gradient's packs).
+ * Debug tensors after such a step, valid until the next mpn_mpnet_train_add: "tower_train_argmax.<region>" [B, c5, PH, PW] (item 3, as
+ * floats), "tower_train_gx5.<t>" and "tower_train_dx5.<t>" [B, c5, PH, PW] (items 1 and 2 for tower t), "tower_train_g5.<i>" [c5, h, w]
+ * (item 4's map of image i behind the mask), "tower_train_act.<i>.<j>" (the saved maps, as "train_act.<i>.<j>").
+ * Not here: the conv layers below the last pooling layer and the conv4 / conv3 slabs' gradients (the rest of phase 2), ResNet / op-list
+ * towers, MPN_FC_SPLIT3, more than one GPU. */
 int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight);
+int mpn_mpnet_train_begin_conv(mpn_frcnn *p, int conv_layers, float momentum, float weight_decay, float bbox_weight);
+int mpn_mpnet_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w /*[Cout,Cin,3,3]*/, float *d_b /*[Cout]*/, void *stream);
+int mpn_mpnet_train_get_trunk_state(mpn_frcnn *p, int layer, float *d_v /*[Cout,Cin,3,3]*/, float *d_vb /*[Cout]*/, void *stream);
+int mpn_mpnet_train_set_trunk_state(mpn_frcnn *p, int layer, const float *d_v, const float *d_vb, void *stream);
 int mpn_mpnet_train_add(mpn_frcnn *p, const float *d_image, int H, int W, const float *d_rois /*[n,4]*/,
                         const float *d_gt /*[n,4]*/, const int *d_labels /*[n], 0 = background*/, int n, void *stream);
 int mpn_mpnet_train_step(mpn_frcnn *p, float lr, float *d_loss /*[2]: cls, bbox*/, void *stream);

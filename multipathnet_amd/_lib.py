@@ -129,6 +129,10 @@ def load(flavour=None):
     lib.mpn_mpnet_train_set_state.argtypes = [C.c_void_p, C.c_int] + [f32p] * 6 + [C.c_void_p]
     lib.mpn_mpnet_train_get_head_state.argtypes = [C.c_void_p] + [f32p] * 4 + [C.POINTER(C.c_long), C.c_void_p]
     lib.mpn_mpnet_train_set_head_state.argtypes = [C.c_void_p] + [f32p] * 4 + [C.c_long, C.c_void_p]
+    lib.mpn_mpnet_train_begin_conv.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    lib.mpn_mpnet_get_trunk_weights.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
+    lib.mpn_mpnet_train_get_trunk_state.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
+    lib.mpn_mpnet_train_set_trunk_state.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_void_p]
     lib.mpn_frcnn_train_scale_momentum.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
     lib.mpn_mpnet_train_scale_momentum.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
     # the minibatch sampler (include/mpn.h): 64-bit seed / draw, the configuration by pointer, the two counts through a HOST int[2]

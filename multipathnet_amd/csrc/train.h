@@ -143,4 +143,31 @@ int unpack_conv_weights(const float *d_wpk, const float *d_bpk, int Cin, int Cou
 // dX = conv3x3_c8p(G, d_wpk_t, d_zero_b, Cin, relu 0, ..., d_wino_t): the forward's kernels.
 int pack_conv_weights_dgrad(const float *d_w, int Cin, int Cout, float *d_tmp, float *d_wpk_t, float *d_zero_b, float *d_wino_t, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// MultiPathNet's conv5 block through the skip pooling (mpn_mpnet_train_begin_conv): the backward of
+// nn.Normalize(2) x mul on one tower's conv5 slab and the Foveal ROI poolings' backward summed over the towers.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int kNormBwdThreads = 256;
+// Per row n < B of ONE tower's conv5 slab — C channels x PP bins as C8 records [ceil(C/8)][PP][Mp][8], record r = cb * PP + bin at
+// (r * Mp + n) * 8 (Mp here is the operand's row pitch between two bins) — with x the raw pooled values, y = s x the stored operand,
+// s = mul / sqrt(sum x^2 + 1e-10) and g the gradient at y:
+//   dx = s * (g - y * (sum_e y_e g_e) / mul^2)       (d_dx_c8: g's layout, a buffer of its own).
+// Both sums run over the entries e = r * 8 + lane, e < ceil(C/8) * PP * 8, lanes of channels >= C skipped, in ONE order that depends on
+// (C, PP) alone: thread t of kNormBwdThreads adds its entries e = t, t + 256, t + 512, ... ascending from +0.0 with one fused
+// multiply-add per entry (fma(x, x, acc); fma(y, g, acc)), then the 256 partial sums go through the tree
+//   for (h = 128; h >= 1; h /= 2) part[t] += part[t + h]   (t < h).
+// One block per row: one reduction pass and one elementwise pass over the row's slab.  Rows >= B are neither read nor written.
+int normalize_backward_c8(const float *d_x_c8, const float *d_y_c8, const float *d_g_c8, float *d_dx_c8, int Mp, int B, int C, int PP, float mul, hipStream_t s);
+
+// inn.ROIPooling:updateGradInput of ONE tower's Foveal region as roi_pool_backward's per-cell gather, ADDED to what the map holds:
+//   out[c][y][x] = out[c][y][x] + sum over the rows n in [n0, n1) ascending and, inside a row, the bins ascending of g[n][c][bin] wherever
+//   argmax[n][c][bin] == y * W + x — one fp32 chain per cell that starts at the cell's current value.  Called tower after tower on a
+// zeroed map it IS the chain "towers ascending, rows ascending, bins ascending from +0.0" of the step's contract; no atomics.
+// The operands are roi_pool_backward's (by_batch = 0, B = 1: every field of `a` means what it means there), but row n's window is
+// a.rois + n * roi_stride (a Foveal table row holds four regions of 5 floats: roi_stride = 20, a.rois shifted to the region).
+int roi_pool_backward_add(const RoiBwd &a, int roi_stride, hipStream_t s);
+
+// out[i] = (float)in[i] (an argmax tensor as a debug tensor: exact below 2^24)
+int int_to_float(const int32_t *d_in, size_t n, float *d_out, hipStream_t s);
+
 }  // namespace mpn

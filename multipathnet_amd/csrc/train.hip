@@ -1028,6 +1028,110 @@ int pack_conv_weights_dgrad(const float *d_w, int Cin, int Cout, float *d_tmp, f
   return d_wino_t ? pack_conv_weights_wino(d_tmp, Cout, Cin, d_wino_t, s) : MPN_OK;
 }
 
+// =================================================================================================================================
+// MultiPathNet's conv5 block through the skip pooling (train.h)
+// =================================================================================================================================
+// One block per row.  Pass 1: thread t walks its entries ascending (stride 256 floats = 32 records: a wave reads 8 records of 32 bytes,
+// Mp * 32 bytes apart — the layout's row pitch, not the kernel's choice) into two partial sums, the LDS tree adds them.  Pass 2: the
+// same walk, elementwise.  y and g are read twice (the second time from L2), x once, dx is written once.
+__global__ __launch_bounds__(kNormBwdThreads) void normalize_backward_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ g, float *__restrict__ dx,
+                                                                             int Mp, int C, int PP, int E, float mul) {
+  __shared__ float pss[kNormBwdThreads], pd[kNormBwdThreads];
+  const int t = threadIdx.x;
+  const size_t n8 = (size_t)blockIdx.x * 8;
+  float ss = 0.0f, d = 0.0f;
+  for (int e = t; e < E; e += kNormBwdThreads) {
+    const int r = e >> 3, lane = e & 7;
+    if ((r / PP) * 8 + lane >= C) continue;  // a pad lane of the last channel block
+    const size_t off = (size_t)r * Mp * 8 + n8 + lane;
+    const float xv = x[off];
+    ss = fmaf(xv, xv, ss);
+    d = fmaf(y[off], g[off], d);
+  }
+  pss[t] = ss; pd[t] = d;
+  __syncthreads();
+  for (int h = kNormBwdThreads / 2; h >= 1; h >>= 1) {
+    if (t < h) { pss[t] += pss[t + h]; pd[t] += pd[t + h]; }
+    __syncthreads();
+  }
+  const float sc = mul / sqrtf(pss[0] + 1e-10f), coef = pd[0] / (mul * mul);
+  for (int e = t; e < E; e += kNormBwdThreads) {
+    const int r = e >> 3, lane = e & 7;
+    if ((r / PP) * 8 + lane >= C) continue;
+    const size_t off = (size_t)r * Mp * 8 + n8 + lane;
+    dx[off] = sc * (g[off] - y[off] * coef);
+  }
+}
+
+int normalize_backward_c8(const float *d_x_c8, const float *d_y_c8, const float *d_g_c8, float *d_dx_c8, int Mp, int B, int C, int PP, float mul, hipStream_t s) {
+  MPN_CHECK_ARG(d_x_c8 && d_y_c8 && d_g_c8 && d_dx_c8 && B > 0 && Mp >= B && C > 0 && PP > 0 && mul > 0.0f);
+  hipLaunchKernelGGL(normalize_backward_kernel, dim3((unsigned)B), dim3(kNormBwdThreads), 0, s, d_x_c8, d_y_c8, d_g_c8, d_dx_c8, Mp, C, PP, cdiv(C, 8) * PP * 8, mul);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// roi_pool_backward_kernel's walk for one map and one tower's region, the chain continued from the cell's value (train.h).  One thread
+// per (c, y, x) cell, x fastest; the cell's own record lane is read and written by this thread alone.
+__global__ __launch_bounds__(256) void roi_pool_backward_add_kernel(RoiBwd a, int roi_stride) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)a.C * a.H * a.W) return;
+  const int x = (int)(t % a.W), y = (int)((t / a.W) % a.H), c = (int)(t / ((size_t)a.W * a.H));
+  const int cell = y * a.W + x, PP = a.PH * a.PW;
+  const float *gc = a.g + (long)(c >> 3) * a.g_cb + (long)(c & 7) * a.g_c;
+  float *o = a.out + (long)(c >> 3) * a.o_cb + (long)(c & 7) * a.o_c + (long)y * a.o_y + (long)x * a.o_x;
+  float sum = *o;
+  for (int n = a.n0; n < a.n1; ++n) {
+    const float *ro = a.rois + (size_t)n * roi_stride;
+    unsigned phm = 0xffffffffu, pwm = 0xffffffffu;
+    if (a.windows) {
+      phm = pwm = 0u;
+      int hs, he, ws, we;
+      for (int ph = 0; ph < a.PH; ++ph) {
+        roi_bin_bounds(ro, a.scale, a.rr, a.H, a.W, a.PH, a.PW, ph, 0, hs, he, ws, we);
+        if (y >= hs && y < he) phm |= 1u << ph;
+      }
+      if (!phm) continue;
+      for (int pw = 0; pw < a.PW; ++pw) {
+        roi_bin_bounds(ro, a.scale, a.rr, a.H, a.W, a.PH, a.PW, 0, pw, hs, he, ws, we);
+        if (x >= ws && x < we) pwm |= 1u << pw;
+      }
+      if (!pwm) continue;
+    }
+    const int32_t *am = a.argmax + ((size_t)n * a.C + c) * PP;
+    const float *gn = gc + (long)n * a.g_n;
+    for (int ph = 0; ph < a.PH; ++ph) {
+      if (!((phm >> (ph & 31)) & 1u)) continue;
+      for (int pw = 0; pw < a.PW; ++pw) {
+        if (!((pwm >> (pw & 31)) & 1u)) continue;
+        const int bin = ph * a.PW + pw;
+        if (am[bin] == cell) sum += gn[(long)bin * a.g_bin];
+      }
+    }
+  }
+  *o = sum;
+}
+
+int roi_pool_backward_add(const RoiBwd &a, int roi_stride, hipStream_t s) {
+  MPN_CHECK_ARG(a.g && a.argmax && a.rois && a.out && a.B == 1 && !a.by_batch && a.C > 0 && a.H > 0 && a.W > 0 && a.PH > 0 && a.PW > 0 && a.n0 >= 0 && a.n1 >= a.n0);
+  MPN_CHECK_ARG(roi_stride >= 5 && (!a.windows || (a.PH <= 32 && a.PW <= 32)));
+  const size_t cells = (size_t)a.C * a.H * a.W;
+  hipLaunchKernelGGL(roi_pool_backward_add_kernel, dim3((unsigned)cdiv_sz(cells, 256)), dim3(256), 0, s, a, roi_stride);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+__global__ void int_to_float_kernel(const int32_t *__restrict__ in, size_t n, float *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (float)in[i];
+}
+
+int int_to_float(const int32_t *d_in, size_t n, float *d_out, hipStream_t s) {
+  MPN_CHECK_ARG(d_in && d_out && n > 0);
+  hipLaunchKernelGGL(int_to_float_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, s, d_in, n, d_out);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
 }  // namespace mpn
 
 // ---- module-level C entry points (NCHW Torch layouts) -----------------------------------------------------------------------------

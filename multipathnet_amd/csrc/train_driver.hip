@@ -1,7 +1,8 @@
 // train_driver.hip — training a VGG Fast R-CNN handle on the device (include/mpn.h mpn_frcnn_train_*): the ROI
 // head with the trunk frozen, or with the trunk's last conv layers (MPN_TRAIN_CONV(k), MPN_TRAIN_TRUNK(k)); and the towers of a
-// MultiPathNet handle with the trunk frozen (mpn_mpnet_train_*; section 13.9) — two trainers over one core and one layer table
-// (section 13.12).  Host code only: the kernels are train.hip's (train.h) and the detect path's (dense.h); the handle and what is
+// MultiPathNet handle with the trunk frozen (mpn_mpnet_train_*; section 13.9) or with the conv block above the last pooling layer
+// trained through the skip pooling (mpn_mpnet_train_begin_conv; section 13.15) — two trainers over one core, one layer table
+// (section 13.12) and one conv block.  Host code only: the kernels are train.hip's (train.h) and the detect path's (dense.h); the handle and what is
 // shared with pipeline.hip: pipeline.h.  The state-free debug pass-throughs to the kernels: train_debug.hip.
 #include <cmath>
 #include <algorithm>
@@ -63,39 +64,48 @@ struct LinT {
   int nseg = 1;                        // > 1 (MultiPathNet's mix, PP): the valid rows are nseg segments of B at pitch Mp — the forward runs over all
 };                                     // nseg * Mp rows, the update is sgd_wgrad_seg_c8 / sgd_bias_seg_c8
 
-// The training state of a plain handle: exists between train_begin and train_end
-struct TrainState : TrainCore {
-  LinT fc[3] = {};                     // fc6 (x: the ROI-pooled rows of the pending images), fc7, the fused cls + bbox head
-  int n_fc = 1;                        // how many of them, counted from the head down, are trained
-  float *head = nullptr;               // the head's output, row-major [B, (K+4)C]
-  float *vtmp = nullptr;               // mpn_frcnn_train_set_state: cls and bbox momentum joined as creation joins the weights, [(K+4)C, F] + [(K+4)C]
-  // ---- depth >= MPN_TRAIN_CONV(1): the conv layers conv[first] .. conv[first + kconv - 1] — above the last pooling layer, or
-  // (MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
+// The conv block of a training state — the trunk's trained conv layers conv[first] .. conv[first + kconv - 1], their saved maps and
+// what their backward pass works in.  Both kinds' states hold one: the plain handle's at depth >=
+// MPN_TRAIN_CONV(1), the tower handle's under mpn_mpnet_train_begin_conv(k > 0).  The layers lie above the last pooling layer, or
+// (plain handle, MPN_TRAIN_TRUNK(k), k > K) with pooling layers among them: then every map has its own size (train_map)
+struct ConvBlock {
   struct ConvT {
     float *v = nullptr, *vb = nullptr;       // momentum: `wpk` layout, [CoutP]
     float *dw = nullptr, *db = nullptr;      // the step's gradients, summed over the images in train_add order
     float *wpk_t = nullptr, *wino_t = nullptr, *zero_b = nullptr;  // the input gradient's convolution (pack_conv_weights_dgrad); wino_t where Cout >= 16
   };
   int kconv = 0, first = 0;
+  bool dgrad_wino = true;              // the input gradients run on the forward's Winograd kernel where Cout >= 16.  The tower handle's block
+                                       // takes the direct kernels instead (the Winograd form's rounding reached the
+                                       // weight gradient of the layer below at 2.5 x the fp32 yardstick); the plain handle keeps its bits
   std::vector<ConvT> cl;               // [kconv], cl[j] goes with conv[first + j]
-  float *dx6 = nullptr;                // gradient at the pooled features, fc[0].x's layout
-  int32_t *argmax = nullptr;           // [max_rois, C, PH, PW] of the pending rows
-  float *prois = nullptr;              // [max_rois, 5] the pending rows' projected ROIs (the bins' windows)
   float *acts = nullptr;               // per image: the block's input map and the kconv trained layers' outputs (before the pool where pooled), whole C8P planes,
                                        // then the pooled map of every pooled trained layer but the last (the next trained layer's input)
   size_t act_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, pool_off[MPN_TRAIN_MAX_TRUNK + 1] = {}, act_img = 0; // floats: map j / pooled map j inside an image's slot; between two images' slots
   float *gmap[2] = {nullptr, nullptr}; // the gradient maps of the image being worked on (ping-pong through the layers)
   size_t gmap_bytes = 0;
   float *wtmp = nullptr, *part = nullptr;  // a layer's weights in Torch layout (x 2: W, W'); conv3x3_wgrad's partial sums
-  int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>")
+  int n_img = 0, last_img = 0;         // images pending; images of the last step (debug tensors "train_act.<i>.<j>", "tower_train_act.<i>.<j>")
   int img_h[MPN_TRAIN_MAX_IMAGES] = {}, img_w[MPN_TRAIN_MAX_IMAGES] = {}, img_row0[MPN_TRAIN_MAX_IMAGES] = {}, img_rows[MPN_TRAIN_MAX_IMAGES] = {};  // final map size, row range
   int img_nh[MPN_TRAIN_MAX_IMAGES] = {}, img_nw[MPN_TRAIN_MAX_IMAGES] = {};  // network-input size (every layer's map size follows from it)
 };
-using ConvT = TrainState::ConvT;
+using ConvT = ConvBlock::ConvT;
+
+// The training state of a plain handle: exists between train_begin and train_end
+struct TrainState : TrainCore, ConvBlock {
+  LinT fc[3] = {};                     // fc6 (x: the ROI-pooled rows of the pending images), fc7, the fused cls + bbox head
+  int n_fc = 1;                        // how many of them, counted from the head down, are trained
+  float *head = nullptr;               // the head's output, row-major [B, (K+4)C]
+  float *vtmp = nullptr;               // mpn_frcnn_train_set_state: cls and bbox momentum joined as creation joins the weights, [(K+4)C, F] + [(K+4)C]
+  // ---- depth >= MPN_TRAIN_CONV(1): the conv block (ConvBlock) and what the ROI pooling's backward reads
+  float *dx6 = nullptr;                // gradient at the pooled features, fc[0].x's layout
+  int32_t *argmax = nullptr;           // [max_rois, C, PH, PW] of the pending rows
+  float *prois = nullptr;              // [max_rois, 5] the pending rows' projected ROIs (the bins' windows)
+};
 
 // The training state of a MultiPathNet handle's towers (mpn_mpnet_train_*): exists between mpn_mpnet_train_begin
 // and mpn_mpnet_train_end.  Every activation and gradient of a step lives here, none in detect's buffers.
-struct TowerTrainState : TrainCore {
+struct TowerTrainState : TrainCore, ConvBlock {
   // The layers in forward order: per tower t its mix, fc6, fc7 (rows 3 t ..), then the K classifiers and the box regressor.
   //   mix: x the operand [Kcat64/8][PP * Mp][8], rows (bin, roi), the normalised ROI pools side by side; K = Kcat, the tower's concat width
   //        (conv5 [+ conv4] [+ conv3]); y [c5P/8][PP * Mp][8] == fc6's operand [.. >= K6_64/8][Mp][8]; no ReLU between the two
@@ -105,6 +115,16 @@ struct TowerTrainState : TrainCore {
   std::vector<int> bwd;                          // the rows in the backward pass's order: the heads, then per tower fc7, fc6, mix
   float *cat = nullptr, *dcat = nullptr;         // the towers' fc7 outputs side by side [T * F/8][Mp][8] (behind the dropout); the gradient there
   float *seg_part = nullptr;                     // sgd_wgrad_seg_c8's partial sums (the widest tower's)
+  // ---- mpn_mpnet_train_begin_conv(k > 0): the conv block (ConvBlock) and what lies between it and the mix layers
+  std::vector<float *> gx;                       // [T] the gradient at tower t's conv5 slab [c5P/8][PP * Mp][8] (the operand's rows), before nn.Normalize's backward ...
+  std::vector<float *> dx5;                      // ... and behind it (conv345_unnormalized: the same buffer, the factor is 1)
+  std::vector<int> regions;                      // the distinct Foveal regions of the towers, ascending
+  std::vector<float *> xraw;                     // [regions] conv5's raw ROI max-pools over the region, the operand's layout (nn.Normalize's input)
+  std::vector<int32_t *> argmax;                 // [regions] [max_rois, c5, PH, PW] of the pending rows
+  float *pfov = nullptr;                         // [max_rois, 20] the pending rows' Foveal table (the bins' windows)
+  float *g5 = nullptr;                           // per image: the gradient map at conv5's output behind the ReLU mask (debug tensor "tower_train_g5.<i>"), g5_img floats apart
+  size_t g5_img = 0;
+  int region_slot(int region) const { return (int)(std::find(regions.begin(), regions.end(), region) - regions.begin()); }
   LinT &mix(int t) { return lin[3 * t]; }
   LinT &fc6(int t) { return lin[3 * t + 1]; }
   LinT &cls() { return lin[lin.size() - 2]; }    // y_rm [B, K*C], g: train_loss_split's two gradient matrices
@@ -304,25 +324,30 @@ static void layer_map_size(const mpn_frcnn *p, int l, int H, int W, int *h, int 
 }
 // Saved map j of the trained block for an H x W network input, at `base` (an image's slot): j = 0 the input of conv[first], j = 1..k the
 // post-ReLU output of conv[first + j - 1] before its pool; pooled: the pooled output of that layer (1 <= j < k, the layer pooled)
-static Act train_map(const mpn_frcnn *p, const TrainState *t, float *base, int j, bool pooled, int H, int W) {
+static Act train_map(const mpn_frcnn *p, const ConvBlock *t, float *base, int j, bool pooled, int H, int W) {
   const int l = j == 0 ? t->first : t->first + j - 1;
   int h, w;
   layer_map_size(p, pooled ? l + 1 : l, H, W, &h, &w);
   return make_act(base ? base + (pooled ? t->pool_off[j] : t->act_off[j]) : nullptr, j == 0 ? p->conv[l].Cin : p->conv[l].Cout, h, w);  // (no base: the geometry alone)
 }
 // the input map of trained layer j (1..k): saved map j - 1, or its pooled form where the layer below is pooled
-static Act train_in_map(const mpn_frcnn *p, const TrainState *t, float *base, int j, int H, int W) {
+static Act train_in_map(const mpn_frcnn *p, const ConvBlock *t, float *base, int j, int H, int W) {
   return train_map(p, t, base, j - 1, j > 1 && p->conv[t->first + j - 2].pool, H, W);
 }
 
+// K: the conv layers behind the trunk's last pooling layer (none when the trunk has no pooling layer: the block's input would be the
+// image), capped at MPN_TRAIN_MAX_CONV
+static int conv_layers_above_last_pool(const mpn_frcnn *p) {
+  const int n_conv = (int)p->conv.size();
+  int Kmax = 0;
+  while (Kmax < n_conv && !p->conv[n_conv - 1 - Kmax].pool) ++Kmax;
+  if (Kmax == n_conv) Kmax = 0;
+  return std::min(Kmax, (int)MPN_TRAIN_MAX_CONV);
+}
 // MPN_TRAIN_* -> the trained layers: the last n_fc Linear layers and, below fc6, the conv layers conv[first] .. conv[first + kconv - 1]
 // (kconv == 0: none) — or a refusal
 static int parse_train_depth(const mpn_frcnn *p, int depth, TrainState *t) {
-  const int n_conv = (int)p->conv.size();
-  int Kmax = 0;  // conv layers behind the trunk's last pooling layer (none when the trunk has no pooling layer: the block's input would be the image)
-  while (Kmax < n_conv && !p->conv[n_conv - 1 - Kmax].pool) ++Kmax;
-  if (Kmax == n_conv) Kmax = 0;
-  if (Kmax > MPN_TRAIN_MAX_CONV) Kmax = MPN_TRAIN_MAX_CONV;
+  const int n_conv = (int)p->conv.size(), Kmax = conv_layers_above_last_pool(p);
   int k = depth > MPN_TRAIN_FC6 ? depth - MPN_TRAIN_FC6 : 0;
   if (depth >= MPN_TRAIN_TRUNK(0)) {  // k <= K: no pooling layer among them, MPN_TRAIN_CONV(k) — the same code, the same bits; k > K: pooling layers among the trained ones
     const int lim = std::min(n_conv - 1, (int)MPN_TRAIN_MAX_TRUNK);
@@ -344,7 +369,7 @@ static int parse_train_depth(const mpn_frcnn *p, int depth, TrainState *t) {
 
 // Where the conv block's saved maps lie in an image's slot of `acts` (act_off, pool_off, act_img), each at its own layer's size for a
 // max_h x max_w input, and the size of a gradient map: the largest of the saved maps' sizes (and the final map's)
-static void layout_train_maps(const mpn_frcnn *p, TrainState *t) {
+static void layout_train_maps(const mpn_frcnn *p, ConvBlock *t) {
   const mpn_frcnn_config &c = p->cfg;
   const int k = t->kconv;
   int mh = c.max_h, mw = c.max_w;
@@ -364,6 +389,7 @@ static void layout_train_maps(const mpn_frcnn *p, TrainState *t) {
   t->act_img = off;
 }
 
+static bool alloc_conv_block(const mpn_frcnn *p, ConvBlock *t, DeviceOwner &own);
 // The Linear layers' table, every buffer of the state and (kconv > 1, on the NULL stream) the input gradient's weight forms.
 // false: something failed (t's DeviceOwner holds what was made)
 static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
@@ -388,8 +414,17 @@ static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
   if (!k) return ok;
   ok = ok && alloc0(&t->dx6, (size_t)(round_up(p->K6, 64) / 8) * rec) && alloc0(&t->prois, M * 5 * sizeof(float));
   ok = ok && t->own.alloc(&t->argmax, M * p->feat_c * PP * sizeof(int32_t), true) == MPN_OK;
+  return ok && alloc_conv_block(p, t, t->own);
+}
+
+// The conv block's buffers for its kconv > 0 layers: the images' saved maps, the two gradient maps, per layer momentum, gradient sums
+// and (on the NULL stream) the input gradient's weight forms.  false: something failed (`own` holds what was made)
+static bool alloc_conv_block(const mpn_frcnn *p, ConvBlock *t, DeviceOwner &own) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int k = t->kconv;
+  auto alloc0 = [&](float **q, size_t bytes) -> bool { return own.alloc(q, bytes, true) == MPN_OK; };
   layout_train_maps(p, t);
-  ok = ok && alloc0(&t->acts, t->act_img * MPN_TRAIN_MAX_IMAGES * sizeof(float));
+  bool ok = alloc0(&t->acts, t->act_img * MPN_TRAIN_MAX_IMAGES * sizeof(float));
   ok = ok && alloc0(&t->gmap[0], t->gmap_bytes) && alloc0(&t->gmap[1], t->gmap_bytes);
   size_t wmax = 0, pmax = 0;
   t->cl.resize(k);
@@ -400,7 +435,7 @@ static bool alloc_train_state(const mpn_frcnn *p, TrainState *t) {
     ok = alloc0(&T.v, we) && alloc0(&T.vb, be) && alloc0(&T.dw, we) && alloc0(&T.db, be);
     if (j > 0) {  // a trained layer lies below: this layer hands a gradient down
       ok = ok && alloc0(&T.wpk_t, conv_wpk_elems(L.Cout, L.Cin) * sizeof(float)) && alloc0(&T.zero_b, (size_t)conv_coutp(L.Cin) * sizeof(float));
-      if (L.Cout >= 16) ok = ok && alloc0(&T.wino_t, conv_wino_elems(L.Cout, L.Cin) * sizeof(float));
+      if (t->dgrad_wino && L.Cout >= 16) ok = ok && alloc0(&T.wino_t, conv_wino_elems(L.Cout, L.Cin) * sizeof(float));
     }
     wmax = std::max(wmax, (size_t)L.Cout * L.Cin * 9);
     int lh, lw;
@@ -504,9 +539,10 @@ static int add_check(mpn_frcnn *p, bool mpnet, const char *fn, int H0, int W0, i
     set_error("%s: %dx%d image (scaled to %dx%d) exceeds the pipeline's %dx%d", fn, H0, W0, *H, *W, c.max_h, c.max_w);
     return MPN_EINVAL;
   }
-  const TrainState *t = mpnet ? nullptr : p->train;
+  const ConvBlock *t = mpnet ? static_cast<const ConvBlock *>(p->tower_train) : p->train;
   if (t && t->kconv && t->n_img >= MPN_TRAIN_MAX_IMAGES) {
-    set_error("%s: %d images are pending: a step at depth MPN_TRAIN_CONV(k) takes at most MPN_TRAIN_MAX_IMAGES = %d images", fn, t->n_img, MPN_TRAIN_MAX_IMAGES);
+    set_error("%s: %d images are pending: a step %s takes at most MPN_TRAIN_MAX_IMAGES = %d images", fn, t->n_img,
+              mpnet ? "that trains conv layers (mpn_mpnet_train_begin_conv, k > 0)" : "at depth MPN_TRAIN_CONV(k)", MPN_TRAIN_MAX_IMAGES);
     return MPN_EINVAL;
   }
   return MPN_OK;
@@ -591,6 +627,27 @@ extern "C" int mpn_mpnet_train_add_sampled(mpn_frcnn *p, const float *d_image, i
   return train_add_sampled(p, true, __func__, d_image, H0, W0, d_proposals, n, d_gt, d_gt_labels, g, d_crowds, n_crowd, cfg, seed, draw, flip, h_counts, stream);
 }
 
+// What the conv block's backward pass reads of the image whose trunk pass has just run (final map `feat`, network input H x W), into
+// the next image slot: the block's input map, every trained layer's output, and the image's record — its n rows start at row0
+static int save_conv_maps(mpn_frcnn *p, ConvBlock *t, const Act &feat, int H, int W, int row0, int n, hipStream_t s) {
+  const int i = t->n_img, k = t->kconv;
+  float *slot = t->acts + (size_t)i * t->act_img;
+  for (int j = 0; j <= k; ++j) {
+    const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones
+    // j == 0: what conv[first] read; j >= 1: the layer's output before its pool (the last layer's unpooled output is the final map)
+    const float *src = j == 0 ? (L.pool ? L.pooled : L.out) : ((j == k && !L.pool) ? feat.p : L.out);
+    const Act a = train_map(p, t, slot, j, false, H, W);
+    MPN_CHECK_HIP(hipMemcpyAsync(a.p, src, act_bytes(a.C, a.H, a.W), hipMemcpyDeviceToDevice, s));
+    if (j >= 1 && j < k && L.pool) {
+      const Act ap = train_map(p, t, slot, j, true, H, W);
+      MPN_CHECK_HIP(hipMemcpyAsync(ap.p, L.pooled, act_bytes(ap.C, ap.H, ap.W), hipMemcpyDeviceToDevice, s));
+    }
+  }
+  t->img_h[i] = feat.H; t->img_w[i] = feat.W; t->img_nh[i] = H; t->img_nw[i] = W; t->img_row0[i] = row0; t->img_rows[i] = n;
+  ++t->n_img;
+  return MPN_OK;
+}
+
 // The plain handle's add: the frozen trunk, the ROI pooling of these rows behind the pending ones, what the conv block's backward pass
 // reads, the rows' copies
 static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int H0, int W0, int H, int W, double sc, const float *d_rois,
@@ -614,42 +671,73 @@ static int frcnn_add_rows(mpn_frcnn *p, TrainState *t, const float *d_image, int
                    t->kconv ? t->argmax + (size_t)t->pending * p->feat_c * c.pooled_h * c.pooled_w : nullptr, s, 5, p->Mp);
   if (rc) return rc;
   if (t->kconv) {  // what the conv block's backward pass reads: the block's input, every trained layer's output, the rows' windows
-    const int i = t->n_img, h = feat.H, w = feat.W, k = t->kconv;
-    float *slot = t->acts + (size_t)i * t->act_img;
-    for (int j = 0; j <= k; ++j) {
-      const ConvLayer &L = p->conv[t->first + j - 1];   // j == 0: the layer below the trained ones
-      // j == 0: what conv[first] read; j >= 1: the layer's output before its pool (the last layer's unpooled output is the final map)
-      const float *src = j == 0 ? (L.pool ? L.pooled : L.out) : ((j == k && !L.pool) ? feat.p : L.out);
-      const Act a = train_map(p, t, slot, j, false, H, W);
-      MPN_CHECK_HIP(hipMemcpyAsync(a.p, src, act_bytes(a.C, a.H, a.W), hipMemcpyDeviceToDevice, s));
-      if (j >= 1 && j < k && L.pool) {
-        const Act ap = train_map(p, t, slot, j, true, H, W);
-        MPN_CHECK_HIP(hipMemcpyAsync(ap.p, L.pooled, act_bytes(ap.C, ap.H, ap.W), hipMemcpyDeviceToDevice, s));
-      }
-    }
     MPN_CHECK_HIP(hipMemcpyAsync(t->prois + (size_t)t->pending * 5, p->rois, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    t->img_h[i] = h; t->img_w[i] = w; t->img_nh[i] = H; t->img_nw[i] = W; t->img_row0[i] = t->pending; t->img_rows[i] = n;
-    ++t->n_img;
+    if ((rc = save_conv_maps(p, t, feat, H, W, t->pending, n, s)) != MPN_OK) return rc;
   }
   return append_rows(*t, __func__, d_rois, d_gt, d_labels, n, s);
 }
 
+// The conv block's backward pass for image i from where its gradient map is laid: G = the gradient at the last trained layer's output
+// (masked with that layer's ReLU) in gmap[cur], a zero-haloed map, the other gradient map zeroed too.  Last trained layer to first:
+// the bias and weight gradients (added to the step's sums from the second image on) and the input gradient masked with the ReLU of the
+// layer below.  No weight is touched.  Both kinds' steps end in it.
+static int conv_chain_backward(mpn_frcnn *p, ConvBlock *t, int i, Act G, int cur, hipStream_t s) {
+  const int nh = t->img_nh[i], nw = t->img_nw[i], k = t->kconv;
+  float *slot = t->acts + (size_t)i * t->act_img;
+  bool relaid = false;  // a pooling layer has been crossed: the caller's memset no longer is the halo of the maps' sizes
+  int rc = MPN_OK;
+  for (int j = k; j >= 1 && rc == MPN_OK; --j) {
+    const ConvLayer &L = p->conv[t->first + j - 1];
+    const ConvT &T = t->cl[j - 1];
+    const Act X = train_in_map(p, t, slot, j, nh, nw);
+    if (L.pool) {  // G is the gradient at the pooled output: route it to the pre-pool map's maxima, masked with that map's ReLU
+      const Act Y = train_map(p, t, slot, j, false, nh, nw);
+      Act Gl = make_act(t->gmap[cur ^ 1], L.Cout, Y.H, Y.W);
+      rc = c8p_zero_halos(&Gl, 1, s);
+      if (rc == MPN_OK) rc = maxpool2x2_backward_c8p(Y, G, Gl, 1, s);
+      if (rc != MPN_OK) break;
+      G = Gl; cur ^= 1; relaid = true;
+    }
+    rc = conv_bias_grad(G, T.db, i > 0, s);
+    if (rc == MPN_OK) rc = conv3x3_wgrad(X, G, t->part, T.dw, i > 0, s);
+    if (rc != MPN_OK || j == 1) break;
+    Act dX = make_act(t->gmap[cur ^ 1], L.Cin, X.H, X.W);
+    if (relaid) rc = c8p_zero_halos(&dX, 1, s);
+    if (rc == MPN_OK) rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
+    if (rc == MPN_OK && !p->conv[t->first + j - 2].pool) rc = relu_mask_c8p(dX, X, s);  // (a pooled layer below: its pool's backward masks)
+    G = dX; cur ^= 1;
+  }
+  return rc;
+}
+
+// optim.sgd on the block's layers behind a step's backward pass: the master `wpk` in place, then every form derived from it; the
+// pending images become the last step's
+static int conv_block_update(mpn_frcnn *p, ConvBlock *t, const TrainCore &c, float lr, int rc, hipStream_t s) {
+  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {
+    const ConvLayer &L = p->conv[t->first + j];
+    const ConvT &T = t->cl[j];
+    rc = conv_sgd(L.wpk, T.v, T.dw, L.Cin, L.Cout, lr, c.momentum, c.weight_decay, s);
+    if (rc == MPN_OK) rc = vec_sgd(L.bpk, T.vb, T.db, L.Cout, lr, c.momentum, s);
+    if (rc == MPN_OK) rc = refresh_conv_forms(L, T, t->wtmp, true, s);
+  }
+  t->last_img = t->n_img; t->n_img = 0;
+  return rc;
+}
+
 // The backward pass below fc6 (depth MPN_TRAIN_CONV(k)): the gradient at the pooled features, then per image — in train_add order — the
-// ROI-pooling backward into a zero-haloed gradient map and, last trained layer to first, the bias and weight gradients (added to the
-// step's sums) and the input gradient masked with the ReLU of the layer below.  No weight is touched: the caller updates afterwards.
-// MPN_TRAIN_TRUNK(k): every layer at its own size; at a pooled layer the gradient at its pooled output first goes through
+// ROI-pooling backward into a zero-haloed gradient map and conv_chain_backward: last trained layer to first, the bias and weight gradients
+// (added to the step's sums) and the input gradient masked with the ReLU of the layer below.  No weight is touched: the caller updates
+// afterwards.  MPN_TRAIN_TRUNK(k): every layer at its own size; at a pooled layer the gradient at its pooled output first goes through
 // maxpool2x2_backward_c8p (fused with the ReLU mask of the pre-pool map, so the input gradient handed to a pooled layer is not masked
 // on its own) into the other gradient map, whose halo is laid for the larger size first — as is every map written after it.
 static int train_conv_backward(mpn_frcnn *p, TrainState *t, int B, hipStream_t s) {
   const mpn_frcnn_config &c = p->cfg;
-  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp, k = t->kconv;
+  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp;
   // dx6 = (g6 W6) .* [x6 > 0]: fc6's packed chunk order is x6's.  The mask is the last conv layer's ReLU mask (pooled values are map values)
   const LinT &L6 = t->fc[0];
   int rc = linear_dgrad_c8(L6.g, Mp, B, L6.N, L6.w, L6.K, L6.x, t->dx6, Mp, s);
   for (int i = 0; i < t->n_img && rc == MPN_OK; ++i) {
-    const int h = t->img_h[i], w = t->img_w[i], nh = t->img_nh[i], nw = t->img_nw[i];
-    float *slot = t->acts + (size_t)i * t->act_img;
-    bool relaid = false;  // a pooling layer has been crossed: the memset below no longer is the halo of the maps' sizes
+    const int h = t->img_h[i], w = t->img_w[i];
     for (float *gm : t->gmap) MPN_CHECK_HIP(hipMemsetAsync(gm, 0, t->gmap_bytes, s));  // the halo is the input gradient's padding
     int cur = 0;
     Act G = make_act(t->gmap[cur], p->feat_c, h, w);
@@ -661,27 +749,7 @@ static int train_conv_backward(mpn_frcnn *p, TrainState *t, int B, hipStream_t s
     a.scale = c.spatial_scale; a.rr = RoiRule{1.0f, 0, c.roi_bin_rule};
     a.out = G.p + ((size_t)G.Wp + 1) * 8;
     rc = roi_pool_backward(a, s);
-    for (int j = k; j >= 1 && rc == MPN_OK; --j) {
-      const ConvLayer &L = p->conv[t->first + j - 1];
-      const ConvT &T = t->cl[j - 1];
-      const Act X = train_in_map(p, t, slot, j, nh, nw);
-      if (L.pool) {  // G is the gradient at the pooled output: route it to the pre-pool map's maxima, masked with that map's ReLU
-        const Act Y = train_map(p, t, slot, j, false, nh, nw);
-        Act Gl = make_act(t->gmap[cur ^ 1], L.Cout, Y.H, Y.W);
-        rc = c8p_zero_halos(&Gl, 1, s);
-        if (rc == MPN_OK) rc = maxpool2x2_backward_c8p(Y, G, Gl, 1, s);
-        if (rc != MPN_OK) break;
-        G = Gl; cur ^= 1; relaid = true;
-      }
-      rc = conv_bias_grad(G, T.db, i > 0, s);
-      if (rc == MPN_OK) rc = conv3x3_wgrad(X, G, t->part, T.dw, i > 0, s);
-      if (rc != MPN_OK || j == 1) break;
-      Act dX = make_act(t->gmap[cur ^ 1], L.Cin, X.H, X.W);
-      if (relaid) rc = c8p_zero_halos(&dX, 1, s);
-      if (rc == MPN_OK) rc = conv3x3_c8p(G, T.wpk_t, T.zero_b, L.Cin, 0, dX, Act{}, s, T.wino_t);
-      if (rc == MPN_OK && !p->conv[t->first + j - 2].pool) rc = relu_mask_c8p(dX, X, s);  // (a pooled layer below: its pool's backward masks)
-      G = dX; cur ^= 1;
-    }
+    if (rc == MPN_OK) rc = conv_chain_backward(p, t, i, G, cur, s);
   }
   return rc;
 }
@@ -721,14 +789,7 @@ extern "C" int mpn_frcnn_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   if (rc == MPN_OK) rc = lin_dgrad(t->fc, kPlainBwd, 3, *t, B, Mp, s);  // down to the lowest trained layer
   if (rc == MPN_OK && t->kconv) rc = train_conv_backward(p, t, B, s);
   if (rc == MPN_OK) rc = lin_update(t->fc, kPlainBwd, 3, *t, B, Mp, lr, nullptr, s);
-  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {  // the conv block: the master `wpk` in place, then every form derived from it
-    const ConvLayer &L = p->conv[t->first + j];
-    const ConvT &T = t->cl[j];
-    rc = conv_sgd(L.wpk, T.v, T.dw, L.Cin, L.Cout, lr, t->momentum, t->weight_decay, s);
-    if (rc == MPN_OK) rc = vec_sgd(L.bpk, T.vb, T.db, L.Cout, lr, t->momentum, s);
-    if (rc == MPN_OK) rc = refresh_conv_forms(L, T, t->wtmp, true, s);
-  }
-  t->last_img = t->n_img; t->n_img = 0;
+  rc = conv_block_update(p, t, *t, lr, rc, s);
   step_end(*t);
   return rc;
 }
@@ -826,17 +887,31 @@ extern "C" int mpn_frcnn_train_set_state(mpn_frcnn *p, const float *d_fc6_v, con
   return rc;
 }
 
-// conv[layer] as a trained layer of the state: its ConvT, or a refusal naming the trained range
-static int trained_conv(mpn_frcnn *p, const char *fn, int layer, TrainState **t_out, ConvT **T_out) {
-  TrainState *t = p->train;
-  if (!t) { set_error("%s: no mpn_frcnn_train_begin on this handle", fn); return MPN_ESTATE; }
+// conv[layer] as a trained layer of a state's conv block: its ConvT, or a refusal naming the trained range
+static int block_layer(ConvBlock *t, const char *fn, int layer, ConvT **T_out) {
   if (layer < t->first || layer >= t->first + t->kconv || !t->kconv) {
     if (t->kconv) set_error("%s: conv layer %d is not trained at this depth (layers %d .. %d are): it has no momentum", fn, layer, t->first, t->first + t->kconv - 1);
     else set_error("%s: conv layer %d is not trained at this depth (no conv layer is): it has no momentum", fn, layer);
     return MPN_EINVAL;
   }
-  *t_out = t; *T_out = &t->cl[layer - t->first];
+  *T_out = &t->cl[layer - t->first];
   return MPN_OK;
+}
+static int trained_conv(mpn_frcnn *p, const char *fn, int layer, TrainState **t_out, ConvT **T_out) {
+  TrainState *t = p->train;
+  if (!t) { set_error("%s: no mpn_frcnn_train_begin on this handle", fn); return MPN_ESTATE; }
+  *t_out = t;
+  return block_layer(t, fn, layer, T_out);
+}
+// every trained conv layer's momentum, weight and bias (*_train_scale_momentum)
+static int scale_conv_momentum(const mpn_frcnn *p, const ConvBlock *t, float factor, hipStream_t s) {
+  int rc = MPN_OK;
+  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {
+    const ConvLayer &L = p->conv[t->first + j];
+    rc = scale_momentum(t->cl[j].v, conv_wpk_elems(L.Cin, L.Cout), factor, s);
+    if (rc == MPN_OK) rc = scale_momentum(t->cl[j].vb, (size_t)conv_coutp(L.Cout), factor, s);
+  }
+  return rc;
 }
 
 extern "C" int mpn_frcnn_train_get_trunk_state(mpn_frcnn *p, int layer, float *d_v, float *d_vb, void *stream) {
@@ -923,21 +998,58 @@ static bool alloc_tower_train_state(const mpn_frcnn *p, TowerTrainState *t) {
   for (LinT &L : t->lin) ok = ok && alloc_momentum(t->own, L);  // every layer is trained
   t->bwd = {3 * T, 3 * T + 1};
   for (int i = 0; i < T; ++i) t->bwd.insert(t->bwd.end(), {3 * i + 2, 3 * i + 1, 3 * i});
-  return ok && alloc0(&t->seg_part, part * sizeof(float)) && alloc_core(p, *t);
+  ok = ok && alloc0(&t->seg_part, part * sizeof(float)) && alloc_core(p, *t);
+  if (!t->kconv) return ok;
+  // the conv block and what lies between it and the mix layers: per tower the gradient at its conv5 slab before and behind
+  // nn.Normalize's backward, per distinct Foveal region conv5's raw pools and their argmax, the rows' windows, per image the map
+  const size_t slab = (size_t)((c5 + 7) / 8) * PP * rec;
+  for (int i = 0; i < T; ++i) if (std::find(t->regions.begin(), t->regions.end(), p->towers[i].region) == t->regions.end()) t->regions.push_back(p->towers[i].region);
+  std::sort(t->regions.begin(), t->regions.end());
+  t->gx.assign(T, nullptr); t->dx5.assign(T, nullptr);
+  t->xraw.assign(t->regions.size(), nullptr); t->argmax.assign(t->regions.size(), nullptr);
+  for (int i = 0; i < T && ok; ++i) {
+    ok = alloc0(&t->gx[i], slab);
+    if (p->conv345_norm) ok = ok && alloc0(&t->dx5[i], slab);
+    else t->dx5[i] = t->gx[i];  // conv345_unnormalized: MulConstant(1) on the conv5 slab
+  }
+  for (size_t r = 0; r < t->regions.size() && ok; ++r)
+    ok = alloc0(&t->xraw[r], slab) && t->own.alloc(&t->argmax[r], M * c5 * PP * sizeof(int32_t), true) == MPN_OK;
+  ok = ok && alloc0(&t->pfov, M * 20 * sizeof(float));
+  int mh = c.max_h, mw = c.max_w;
+  final_map_size(p, &mh, &mw);
+  t->g5_img = act_bytes(c5, mh, mw) / sizeof(float);
+  ok = ok && alloc0(&t->g5, t->g5_img * MPN_TRAIN_MAX_IMAGES * sizeof(float));
+  return ok && alloc_conv_block(p, t, t->own);
 }
 
-extern "C" int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight) {
-  MPN_CHECK_ARG(p != nullptr);
-  int rc = begin_refusals(p, true, __func__);
+// mpn_mpnet_train_begin and mpn_mpnet_train_begin_conv behind their `p != nullptr` (fn: the entry point's name)
+static int mpnet_train_begin(mpn_frcnn *p, const char *fn, int conv_layers, float momentum, float weight_decay, float bbox_weight) {
+  int rc = begin_refusals(p, true, fn);
   if (rc) return rc;
+  const int K = conv_layers_above_last_pool(p);
+  if (conv_layers < 0 || conv_layers > K) {
+    set_error("%s: invalid argument: conv_layers = %d, but k runs from 0 to K = %d on this trunk: the conv layers above its last pooling layer (a pooling layer has no backward pass here)",
+              fn, conv_layers, K);
+    return MPN_EINVAL;
+  }
   std::unique_ptr<TowerTrainState> t(new TowerTrainState());
-  if ((rc = begin_core(*t, __func__, momentum, weight_decay, bbox_weight)) != MPN_OK) return rc;
+  if ((rc = begin_core(*t, fn, momentum, weight_decay, bbox_weight)) != MPN_OK) return rc;
+  t->kconv = conv_layers; t->first = (int)p->conv.size() - conv_layers; t->dgrad_wino = false;
   if (!alloc_tower_train_state(p, t.get()) || hipDeviceSynchronize() != hipSuccess) {
-    set_error("mpn_mpnet_train_begin: allocating the momentum / activation / gradient buffers failed: %s", hipGetErrorString(hipGetLastError()));
+    set_error("%s: allocating the momentum / activation / gradient buffers failed: %s", fn, hipGetErrorString(hipGetLastError()));
     return MPN_ENOMEM;
   }
   p->tower_train = t.release();  // all or nothing: published last
   return MPN_OK;
+}
+
+extern "C" int mpn_mpnet_train_begin(mpn_frcnn *p, float momentum, float weight_decay, float bbox_weight) {
+  MPN_CHECK_ARG(p != nullptr);
+  return mpnet_train_begin(p, __func__, 0, momentum, weight_decay, bbox_weight);
+}
+extern "C" int mpn_mpnet_train_begin_conv(mpn_frcnn *p, int conv_layers, float momentum, float weight_decay, float bbox_weight) {
+  MPN_CHECK_ARG(p != nullptr);
+  return mpnet_train_begin(p, __func__, conv_layers, momentum, weight_decay, bbox_weight);
 }
 
 extern "C" int mpn_mpnet_train_end(mpn_frcnn *p) {
@@ -986,7 +1098,57 @@ static int mpnet_add_rows(mpn_frcnn *p, TowerTrainState *t, const float *d_image
       cb_off += maps[m].Cb();
     }
   }
+  if (t->kconv) {  // what the backward pass below the operand reads: per region conv5's raw pools (nn.Normalize's input) and their argmax —
+    // roi_pool_c8, whose pooled values are the range-max tables' —, the rows' windows, the block's maps
+    for (size_t r = 0; r < t->regions.size(); ++r) {
+      rc = roi_pool_c8(feat, p->fov + 5 * t->regions[r], n, c.pooled_h, c.pooled_w, scales[0], RoiRule{1.0f, 0, c.roi_bin_rule}, t->xraw[r] + (size_t)t->pending * 8,
+                       t->argmax[r] + (size_t)t->pending * p->feat_c * PP, s, 20, Mp);
+      if (rc) return rc;
+    }
+    MPN_CHECK_HIP(hipMemcpyAsync(t->pfov + (size_t)t->pending * 20, p->fov, (size_t)n * 20 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = save_conv_maps(p, t, feat, H, W, t->pending, n, s)) != MPN_OK) return rc;
+  }
   return append_rows(*t, __func__, d_rois, d_gt, d_labels, n, s);
+}
+
+// The backward pass below the mix layers (mpn_mpnet_train_begin_conv, k > 0).  Per tower: the mix layer's input
+// gradient on its conv5 columns — linear_dgrad_c8 with K = c5 (the packed weight's first c5 / 8 chunks are the conv5 slab's) in ONE
+// launch over the (PP - 1) * Mp + B rows from the first segment's first row to the last segment's last: a row's result depends on that
+// row alone, so the stale rows between two segments cost Mp / B of the work and touch nothing valid — and nn.Normalize's backward on
+// the valid rows.  Per image, in train_add order: the five Foveal poolings' backward added tower after tower into one zeroed map
+// (roi_pool_backward_add: one chain per cell), the ReLU mask of conv5's output, then conv_chain_backward.  No weight is touched.
+static int tower_conv_backward(mpn_frcnn *p, TowerTrainState *t, int B, hipStream_t s) {
+  const mpn_frcnn_config &c = p->cfg;
+  const int PP = c.pooled_h * c.pooled_w, Mp = p->Mp, c5 = p->feat_c, T = (int)p->towers.size();
+  int rc = MPN_OK;
+  for (int i = 0; i < T && rc == MPN_OK; ++i) {
+    const LinT &L = t->mix(i);
+    rc = linear_dgrad_c8(L.g, PP * Mp, (PP - 1) * Mp + B, L.N, L.w, c5, nullptr, t->gx[i], PP * Mp, s);
+    if (rc == MPN_OK && p->conv345_norm)
+      rc = normalize_backward_c8(t->xraw[t->region_slot(p->towers[i].region)], L.x, t->gx[i], t->dx5[i], Mp, B, c5, PP, 1000.0f, s);
+  }
+  for (int i = 0; i < t->n_img && rc == MPN_OK; ++i) {
+    const int h = t->img_h[i], w = t->img_w[i];
+    Act G = make_act(t->g5 + (size_t)i * t->g5_img, c5, h, w);
+    MPN_CHECK_HIP(hipMemsetAsync(G.p, 0, t->g5_img * sizeof(float), s));  // the chain's +0.0 and the halo (the input gradient's padding)
+    for (float *gm : t->gmap) MPN_CHECK_HIP(hipMemsetAsync(gm, 0, t->gmap_bytes, s));
+    for (int tw = 0; tw < T && rc == MPN_OK; ++tw) {
+      RoiBwd a{};
+      a.g = t->dx5[tw]; a.argmax = t->argmax[t->region_slot(p->towers[tw].region)]; a.rois = t->pfov + 5 * p->towers[tw].region;
+      a.by_batch = 0; a.n0 = t->img_row0[i]; a.n1 = a.n0 + t->img_rows[i];
+      a.B = 1; a.C = c5; a.H = h; a.W = w; a.PH = c.pooled_h; a.PW = c.pooled_w; a.windows = (c.pooled_h <= 32 && c.pooled_w <= 32) ? 1 : 0;
+      a.g_n = 8; a.g_cb = (long)PP * Mp * 8; a.g_c = 1; a.g_bin = (long)Mp * 8;
+      a.o_b = 0; a.o_cb = (long)G.plane(); a.o_c = 1; a.o_y = (long)G.Wp * 8; a.o_x = 8;
+      a.scale = c.spatial_scale; a.rr = RoiRule{1.0f, 0, c.roi_bin_rule};
+      a.out = G.p + ((size_t)G.Wp + 1) * 8;
+      rc = roi_pool_backward_add(a, 20, s);
+    }
+    // the pooled values are conv5's post-ReLU values, but nn.Normalize sits between the pooling and the ReLU: the gradient at a pooled
+    // zero is not zero until this mask
+    if (rc == MPN_OK) rc = relu_mask_c8p(G, train_map(p, t, t->acts + (size_t)i * t->act_img, t->kconv, false, t->img_nh[i], t->img_nw[i]), s);
+    if (rc == MPN_OK) rc = conv_chain_backward(p, t, i, G, 1, s);  // (cur = 1: the first input gradient goes to gmap[0])
+  }
+  return rc;
 }
 
 extern "C" int mpn_mpnet_train_step(mpn_frcnn *p, float lr, float *d_loss, void *stream) {
@@ -1004,7 +1166,9 @@ extern "C" int mpn_mpnet_train_step(mpn_frcnn *p, float lr, float *d_loss, void 
   rc = train_loss_split(t->cls().y_rm, t->bbox().y_rm, B, p->cfg.n_classes, p->n_integral, t->head_k, t->rois, t->gt, t->labels, loss_cfg(p, *t), t->cls().g,
                         t->bbox().g, Mp, d_loss ? d_loss : t->loss, s);
   if (rc == MPN_OK) rc = lin_dgrad(t->lin.data(), t->bwd.data(), n, *t, B, Mp, s);
+  if (rc == MPN_OK && t->kconv) rc = tower_conv_backward(p, t, B, s);  // every input gradient of the step before any update
   if (rc == MPN_OK) rc = lin_update(t->lin.data(), t->bwd.data(), n, *t, B, Mp, lr, t->seg_part, s);
+  rc = conv_block_update(p, t, *t, lr, rc, s);
   step_end(*t);
   return rc;
 }
@@ -1128,6 +1292,38 @@ extern "C" int mpn_mpnet_train_set_head_state(mpn_frcnn *p, const float *d_cls_v
   return rc;
 }
 
+// ---- the conv block of a tower run: the trunk's weights back in Torch layout, the trained layers' momentum (mpn_frcnn_get_trunk_weights'
+// and mpn_frcnn_train_get_trunk_state / _set_trunk_state's rules on a MultiPathNet handle) ----
+extern "C" int mpn_mpnet_get_trunk_weights(mpn_frcnn *p, int layer, float *d_w, float *d_b, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  if (int rc = refuse_not_mpnet(p, "mpn_mpnet_get_trunk_weights")) return rc;
+  if (layer < 0 || layer >= (int)p->conv.size()) { set_error("mpn_mpnet_get_trunk_weights: layer %d of a %d-layer trunk", layer, (int)p->conv.size()); return MPN_EINVAL; }
+  const ConvLayer &L = p->conv[layer];
+  return unpack_conv_weights(L.wpk, L.bpk, L.Cin, L.Cout, d_w, d_b, as_stream(stream));
+}
+
+extern "C" int mpn_mpnet_train_get_trunk_state(mpn_frcnn *p, int layer, float *d_v, float *d_vb, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t; ConvT *T;
+  int rc = tower_state_begin(p, __func__, false, &t);
+  if (rc == MPN_OK) rc = block_layer(t, __func__, layer, &T);
+  if (rc) return rc;
+  const ConvLayer &L = p->conv[layer];
+  return unpack_conv_weights(T->v, T->vb, L.Cin, L.Cout, d_v, d_vb, as_stream(stream));
+}
+
+extern "C" int mpn_mpnet_train_set_trunk_state(mpn_frcnn *p, int layer, const float *d_v, const float *d_vb, void *stream) {
+  MPN_CHECK_ARG(p != nullptr);
+  TowerTrainState *t; ConvT *T;
+  int rc = tower_state_begin(p, __func__, false, &t);
+  if (rc == MPN_OK) rc = block_layer(t, __func__, layer, &T);
+  if (rc) return rc;
+  if (t->pending > 0) { set_error("%s: %d rows are pending: take the step (mpn_mpnet_train_step) first", __func__, t->pending); return MPN_ESTATE; }
+  if (!d_v || !d_vb) { set_error("%s: %s is NULL: a trained layer's state is its weight and its bias momentum", __func__, d_v ? "d_vb" : "d_v"); return MPN_EINVAL; }
+  const ConvLayer &L = p->conv[layer];
+  return pack_conv_weights(d_v, d_vb, L.Cin, L.Cout, T->v, T->vb, as_stream(stream));
+}
+
 // ---- the learning-rate drop on the momentum (*_train_scale_momentum; train.lua:321-335 dfdx:mul(state.decay)) ----
 // every trained row of a layer table: the weight's momentum and the bias's, whole packed buffers (one launch each)
 static int scale_lin_momentum(const LinT *rows, int n, float factor, hipStream_t s) {
@@ -1158,16 +1354,12 @@ static int train_scale_momentum(mpn_frcnn *p, bool mpnet, const char *fn, float 
   hipStream_t s = as_stream(stream);
   if (mpnet) {
     const TowerTrainState *t = p->tower_train;
-    return scale_lin_momentum(t->lin.data(), (int)t->lin.size(), factor, s);
+    rc = scale_lin_momentum(t->lin.data(), (int)t->lin.size(), factor, s);
+    return rc == MPN_OK ? scale_conv_momentum(p, t, factor, s) : rc;
   }
   const TrainState *t = p->train;
   rc = scale_lin_momentum(t->fc, 3, factor, s);
-  for (int j = 0; j < t->kconv && rc == MPN_OK; ++j) {
-    const ConvLayer &L = p->conv[t->first + j];
-    rc = scale_momentum(t->cl[j].v, conv_wpk_elems(L.Cin, L.Cout), factor, s);
-    if (rc == MPN_OK) rc = scale_momentum(t->cl[j].vb, (size_t)conv_coutp(L.Cout), factor, s);
-  }
-  return rc;
+  return rc == MPN_OK ? scale_conv_momentum(p, t, factor, s) : rc;
 }
 
 extern "C" int mpn_frcnn_train_scale_momentum(mpn_frcnn *p, float factor, void *stream) {
@@ -1188,8 +1380,45 @@ int mpn::tower_train_debug_tensor(mpn_frcnn *p, const char *name, const float **
   const mpn_frcnn_config &c = p->cfg;
   const int R = t->last_rows, F = c.fc_dim, C = c.n_classes, KC = p->n_integral * C, T = (int)p->towers.size(), PP = c.pooled_h * c.pooled_w, Mp = p->Mp;
   const char *tail = name + 12;
-  int ti = -1;
+  int ti = -1, ii = -1, ji = -1;
   const bool is_x = sscanf(tail, "x.%d", &ti) == 1, is_y6 = !is_x && sscanf(tail, "y6.%d", &ti) == 1;
+  // the conv block's tensors (mpn_mpnet_train_begin_conv, k > 0; valid until the next mpn_mpnet_train_add): "tower_train_argmax.<region>",
+  // "tower_train_gx5.<t>" / "tower_train_dx5.<t>" [rows, c5, PH, PW], "tower_train_g5.<i>" [c5, h, w], "tower_train_act.<i>.<j>"
+  const bool is_am = !strncmp(tail, "argmax.", 7), is_gx = !strncmp(tail, "gx5.", 4), is_dx = !strncmp(tail, "dx5.", 4), is_g5 = !strncmp(tail, "g5.", 3),
+             is_act = !strncmp(tail, "act.", 4);
+  if (is_am || is_gx || is_dx || is_g5 || is_act) {
+    if (!t->kconv) { set_error("mpn_frcnn_debug_tensor: '%s' needs a mpn_mpnet_train_step after mpn_mpnet_train_begin_conv with conv_layers > 0", name); return MPN_ESTATE; }
+    const int c5 = p->feat_c;
+    size_t nt = 0;
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    int rc = MPN_OK;
+    if (is_am) {
+      if (sscanf(tail + 7, "%d", &ti) != 1 || t->region_slot(ti) >= (int)t->regions.size()) { set_error("mpn_frcnn_debug_tensor: '%s': no tower of this handle pools that Foveal region", name); return MPN_EINVAL; }
+      nt = (size_t)R * c5 * PP;
+      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+      rc = int_to_float(t->argmax[t->region_slot(ti)], nt, p->dbg, nullptr);
+    } else if (is_gx || is_dx) {
+      if (sscanf(tail + 4, "%d", &ti) != 1 || ti < 0 || ti >= T) { set_error("mpn_frcnn_debug_tensor: '%s': the handle has towers 0..%d", name, T - 1); return MPN_EINVAL; }
+      nt = (size_t)R * c5 * PP;
+      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+      rc = launch_unpack_pooled(is_gx ? t->gx[ti] : t->dx5[ti], R, c5, PP, Mp, p->dbg);
+    } else {
+      const int got = is_g5 ? sscanf(tail + 3, "%d", &ii) : sscanf(tail + 4, "%d.%d", &ii, &ji);
+      if (got != (is_g5 ? 1 : 2) || ii < 0 || ii >= t->last_img || (is_act && (ji < 0 || ji > t->kconv))) {
+        set_error("mpn_frcnn_debug_tensor: '%s': the last step had %d images and maps 0..%d", name, t->last_img, t->kconv);
+        return MPN_EINVAL;
+      }
+      const Act a = is_g5 ? make_act(t->g5 + (size_t)ii * t->g5_img, c5, t->img_h[ii], t->img_w[ii])
+                          : train_map(p, t, t->acts + (size_t)ii * t->act_img, ji, false, t->img_nh[ii], t->img_nw[ii]);
+      nt = (size_t)a.C * a.H * a.W;
+      if (int rcd = grow_dbg(p, nt * sizeof(float))) return rcd;
+      rc = c8p_to_nchw(a, p->dbg, nullptr);
+    }
+    if (rc) return rc;
+    MPN_CHECK_HIP(hipDeviceSynchronize());
+    *d_ptr = p->dbg; *n_elems = nt;
+    return MPN_OK;
+  }
   if ((is_x || is_y6) && (ti < 0 || ti >= T)) { set_error("mpn_frcnn_debug_tensor: '%s': the handle has towers 0..%d", name, T - 1); return MPN_EINVAL; }
   size_t n = 0;
   if (is_x) n = (size_t)R * t->mix(ti).K * PP;

@@ -971,21 +971,30 @@ class FastRCNN(object):
 
     def trunk_weights(self):
         """The trunk's current conv weights and biases in Torch layout, {"conv_w": [...], "conv_b": [...]} as synthetic_params names them
-        (device tensors): with head_weights() everything a new FastRCNN of the trained network needs."""
+        (device tensors): with head_weights() everything a new FastRCNN of the trained network needs.  On a MultiPathNet handle
+        (mpn_mpnet_get_trunk_weights): the trunk as tower_train_begin(conv_layers=k) has trained it; tower_weights() carries it too."""
+        entry = "mpn_mpnet_get_trunk_weights" if self.is_mpnet else "mpn_frcnn_get_trunk_weights"
         ws, bs, cin = [], [], 3
         for l, co in enumerate(self._cout):
             w = torch.empty((co, cin, 3, 3), dtype=torch.float32, device=self.device)
             b = torch.empty(co, dtype=torch.float32, device=self.device)
-            check(self._lib.mpn_frcnn_get_trunk_weights(self._h, l, _f(w), _f(b), _stream()), "mpn_frcnn_get_trunk_weights")
+            check(getattr(self._lib, entry)(self._h, l, _f(w), _f(b), _stream()), entry)
             ws.append(w); bs.append(b); cin = co
         return {"conv_w": ws, "conv_b": bs}
 
     # ---- training a MultiPathNet handle's towers, trunk frozen (mpn_mpnet_train_*, include/mpn.h; DESIGN.md section 13.9) ----
-    def tower_train_begin(self, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0, dropout=0.0, seed=555):
+    def tower_train_begin(self, momentum=0.9, weight_decay=5e-4, bbox_weight=1.0, dropout=0.0, seed=555, conv_layers=0):
         """Start training the towers of a MultiPathNet handle (models/multipathnet.lua phase 1: the trunk frozen): every tower's 1x1 mix,
         fc6 and fc7, the K integral classifiers and the box regressor.  fp32 handles only; train_begin keeps refusing these handles.
-        dropout = 0.0: none; see tower_train_set_dropout."""
-        check(self._lib.mpn_mpnet_train_begin(self._h, C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)), "mpn_mpnet_train_begin")
+        dropout = 0.0: none; see tower_train_set_dropout.  conv_layers = k > 0 (mpn_mpnet_train_begin_conv) also
+        trains the trunk's last k conv layers through the towers' skip pooling, k <= K = the conv layers above the last pooling layer
+        (VGG-16: 3, conv5_1 .. conv5_3 — the first step of the reference's phase 2); a step then takes at most 8 images."""
+        if conv_layers:
+            check(self._lib.mpn_mpnet_train_begin_conv(self._h, int(conv_layers), C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)),
+                  "mpn_mpnet_train_begin_conv")
+        else:
+            check(self._lib.mpn_mpnet_train_begin(self._h, C.c_float(momentum), C.c_float(weight_decay), C.c_float(bbox_weight)), "mpn_mpnet_train_begin")
+        self._tower_conv_layers = int(conv_layers)
         self._dropout = (0.0, int(seed))
         if dropout:
             self.tower_train_set_dropout(dropout, seed)
@@ -1037,6 +1046,13 @@ class FastRCNN(object):
         check(self._lib.mpn_mpnet_train_get_head_state(self._h, *[_f(S[k]) if k in S else None for k in self._TOWER_HEAD_ORDER], C.byref(step), _stream()),
               "mpn_mpnet_train_get_head_state")
         S["step"] = int(step.value)
+        k, n = getattr(self, "_tower_conv_layers", 0), len(self._cout)
+        if k:   # the trained conv layers' momentum, as train_state() names it (None for a layer that is not trained)
+            S["conv_w"], S["conv_b"] = [None] * n, [None] * n
+            for l in range(n - k, n):
+                w, b = z(self._cout[l], self._conv_cin(l), 3, 3), z(self._cout[l])
+                check(self._lib.mpn_mpnet_train_get_trunk_state(self._h, l, _f(w), _f(b), _stream()), "mpn_mpnet_train_get_trunk_state")
+                S["conv_w"][l], S["conv_b"][l] = w, b
         return S
 
     def tower_train_load_state(self, state):
@@ -1051,6 +1067,13 @@ class FastRCNN(object):
             check(self._lib.mpn_mpnet_train_set_state(self._h, t, *[ptr(x) for x in Tn], _stream()), "mpn_mpnet_train_set_state")
         Hn = [dev(state.get(k)) for k in self._TOWER_HEAD_ORDER]
         check(self._lib.mpn_mpnet_train_set_head_state(self._h, *[ptr(x) for x in Hn], int(state["step"]), _stream()), "mpn_mpnet_train_set_head_state")
+        cw, cb = state.get("conv_w") or [], state.get("conv_b") or []
+        for l in range(len(cw)):   # (tower_train_begin(conv_layers=k): the trained conv layers' momentum)
+            if cw[l] is None and cb[l] is None:
+                continue
+            w, b = dev(cw[l]), dev(cb[l])
+            keep.append((w, b))
+            check(self._lib.mpn_mpnet_train_set_trunk_state(self._h, l, ptr(w), ptr(b), _stream()), "mpn_mpnet_train_set_trunk_state")
         torch.cuda.current_stream().synchronize()   # the packers have read the (possibly temporary) device copies
 
     def train_scale_momentum(self, factor):
@@ -1065,7 +1088,7 @@ class FastRCNN(object):
 
     def tower_weights(self):
         """The MultiPathNet handle's parameters as synthetic_mpnet_params shapes them (device tensors): the towers' and heads' current
-        weights in Torch layout, the frozen trunk as creation took it.  MultiPathNet(net.tower_weights(), ...) rebuilds the same network."""
+        weights in Torch layout, the trunk's current conv weights (trunk_weights()).  MultiPathNet(net.tower_weights(), ...) rebuilds the same network."""
         if not self.is_mpnet:
             check(self._lib.mpn_mpnet_get_head_weights(self._h, None, None, None, None, _stream()), "mpn_mpnet_get_head_weights")  # (names the cause)
         F, Cn, KC, PP = self.fc_dim, self.n_classes, self.n_integral * self.n_classes, self._cfg.pooled_h * self._cfg.pooled_w
@@ -1073,6 +1096,7 @@ class FastRCNN(object):
         z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
         P = dict(self._mpnet_fixed)
         P = {k: v for k, v in P.items() if v is not None}
+        P.update(self.trunk_weights())   # (the trunk as it is now: tower_train_begin(conv_layers=k) trains its last layers)
         P["towers"] = []
         for t, T in enumerate(self._towers):
             W = dict(T, mix_w=z(c5, T["total_feat"]), mix_b=z(c5), fc6_w=z(F, c5 * PP), fc6_b=z(F), fc7_w=z(F, F), fc7_b=z(F))

@@ -309,6 +309,8 @@ def mpnet_checkpoint_table(weights, state, rate, seed, epoch=None, learning_rate
       "conv_w.<l>", "conv_b.<l>"                            the frozen trunk: the reference's model_<n>.t7 holds the whole model
       "bbox_mean", "bbox_std", "conv345_norm"               nn.BBoxNorm's statistics where the net has them; opt.model_conv345_norm
       "v.tower.<t>.<name>", "v.cls_w" .. "v.bbox_b"         the momentum of every trained tensor
+      "conv_layers", "v.conv_w.<l>", "v.conv_b.<l>"         only where the run trains conv layers (tower_train_begin(conv_layers=k), k > 0):
+                                                            k and the momentum of the trunk's last k layers; a file without them is k = 0
       "step", "dropout", "seed", "epoch", "learningRate"    as in a plain file"""
     tow = weights["towers"]
     tab = {"kind": "mpnet", "n_towers": len(tow), "n_integral": int(weights["n_integral"]), "n_classes": int(weights["n_classes"])}
@@ -328,6 +330,11 @@ def mpnet_checkpoint_table(weights, state, rate, seed, epoch=None, learning_rate
         if weights.get(k) is not None:
             tab[k] = np.asarray(_host(weights[k]), np.float64)   # (Python floats at creation: a DoubleTensor keeps them as they are)
     tab["conv345_norm"] = bool(weights.get("conv345_norm", True))
+    trained = [l for l, v in enumerate(state.get("conv_w") or []) if v is not None]   # tower_train_begin(conv_layers=k): the last k layers
+    if trained:
+        tab["conv_layers"] = len(trained)
+        for l in trained:
+            tab["v.conv_w.%d" % l], tab["v.conv_b.%d" % l] = _host(state["conv_w"][l]), _host(state["conv_b"][l])
     return _run_keys(tab, rate, seed, state["step"], epoch, learning_rate)
 
 
@@ -363,7 +370,10 @@ def checkpoint_read(tab):
             if k in tab:
                 weights[k] = [float(x) for x in np.asarray(tab[k]).reshape(-1)]
         weights["conv345_norm"] = bool(tab.get("conv345_norm", True))
-        return _read_run_keys(tab, {"kind": "mpnet", "weights": weights, "state": state})
+        k = int(tab.get("conv_layers", 0))
+        if k:
+            state["conv_w"], state["conv_b"] = [ten("v.conv_w.%d" % l) for l in range(n_conv)], [ten("v.conv_b.%d" % l) for l in range(n_conv)]
+        return _read_run_keys(tab, {"kind": "mpnet", "weights": weights, "state": state, "conv_layers": k})
     if "kind" in tab:
         raise ValueError("checkpoint of an unknown kind %r" % (tab["kind"],))
     weights.update({k: ten(k) for k in _HEAD_KEYS})
@@ -381,14 +391,15 @@ def load_checkpoint(path):
     classifiers; "epoch" and "learningRate" where the file has them).  Update a parameter dict with "weights" to create the FastRCNN,
     then train_begin (the same depth), train_set_dropout(dropout, seed), train_load_state(state) — or `resume`.
     A MultiPathNet file ("kind" = "mpnet", also returned): "weights" is a dict models.MultiPathNet(...) is built from (tower_weights()'
-    keys), "state" what tower_train_load_state takes; then tower_train_begin and `resume`."""
+    keys), "state" what tower_train_load_state takes, "conv_layers" the k the run trains (0 for a file written without it); then
+    tower_train_begin(conv_layers=k) and `resume`."""
     return checkpoint_read(t7.load(path))
 
 
 def resume(net, ckpt):
     """opt.resume: restore load_checkpoint's dropout stream and optimiser state into `net` — a FastRCNN created from ckpt["weights"] on
     which train_begin (the same depth, momentum, weight decay) has been called; or a MultiPathNet created from them on which
-    tower_train_begin has."""
+    tower_train_begin(conv_layers=ckpt["conv_layers"]) has."""
     if getattr(net, "is_mpnet", False):
         net.tower_train_set_dropout(ckpt["dropout"], ckpt["seed"])
         net.tower_train_load_state(ckpt["state"])
@@ -399,8 +410,9 @@ def resume(net, ckpt):
 
 def fit(net, batch_fn, n_epochs, epoch_size, lr, step, decay, snapshot=0, save_dir=None, validate=None, log=None, start=None):
     """The epoch loop of train.lua:221-360 (the engine's hooks) on a net that has begun training — train_begin on a plain FastRCNN,
-    tower_train_begin on a MultiPathNet; `fit` picks train_* or tower_train_* by net.is_mpnet.  Phase 1 only (phase2_epoch = -1, the
-    shipped recipe).
+    tower_train_begin on a MultiPathNet; `fit` picks train_* or tower_train_* by net.is_mpnet.  One phase per call (phase2_epoch = -1, the
+    shipped recipe): what is trained — the towers alone or, tower_train_begin(conv_layers=k), the trunk's last conv layers with them — is
+    what the net has begun; the checkpoints carry k and those layers' momentum.
       batch_fn(epoch, it)   adds minibatch `it` of epoch `epoch` (both 1-based, as in the reference's log lines) to `net` itself with
                             train_add* / tower_train_add*; returns the integral head k the step trains, or None (no set_head call).
                             Which images enter a batch is the caller's: nothing is loaded, decoded or chosen here.

@@ -16,13 +16,15 @@ more small kernels per step and a scale in two input gradients); 0, the default,
 --model mpnet measures instead the tower training of a MultiPathNet handle (models.synthetic_mpnet_params: VGG-16,
 the five MPN_TOWERS, fc_dim 4096, C 81, K 6; mpn_mpnet_train_*): ms of mpn_mpnet_train_step alone and of the whole iteration on the same
 2 x 64 rows, step i on classifier i mod K, beside the step's derived floor — every trained weight and its momentum read and written once.
+--conv-layers k with it also trains the trunk's last k conv layers through the towers' skip pooling (3: conv5_1 ..
+conv5_3): the same two times; 0, the default, is the tower training above.
 --device-sampler measures instead the whole iteration at depth 2 with each image's rows chosen from 2000
 proposals, drawn on the device (train_add_sampled) and, alternating in the same run, on the host (numpy + uploads + train_add).
 --scale-momentum measures instead the learning-rate drop's momentum scaling per call — the VGG-16 towers and the
 plain handle at MPN_TRAIN_TRUNK(--trunk-layers, 9 without it) — beside its HBM floor and beside get -> multiply -> set on the plain handle.
 One JSON line per measurement.
 
-    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6] [--model mpnet] [--device-sampler]
+    python tools/bench_train.py [--steps 20] [--warmup 5] [--trunk-layers 9] [--dropout 0.5] [--integral 6] [--model mpnet [--conv-layers 3]] [--device-sampler]
                                 [--scale-momentum]
 """
 import argparse
@@ -63,7 +65,7 @@ def bench_mpnet(a):
         sum(int(P[k].numel()) for k in ("cls_w", "cls_b", "bbox_w", "bbox_b"))
     gb = 4 * trained * 4 / 1e9   # w read + w write + v read + v write
     del P
-    net.tower_train_begin(momentum=0.9, weight_decay=5e-4, dropout=a.dropout)
+    net.tower_train_begin(momentum=0.9, weight_decay=5e-4, dropout=a.dropout, conv_layers=a.conv_layers)
     e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     step_ms, iter_ms = [], []
     for i in range(a.warmup + a.steps):
@@ -80,7 +82,7 @@ def bench_mpnet(a):
             iter_ms.append(e[0].elapsed_time(e[2]))
     net.tower_train_end()
     net.close()
-    print(json.dumps({"what": "mpnet_train_step", "towers": 5, "dropout": a.dropout, "integral": K, "rows": IMAGES * ROWS,
+    print(json.dumps({"what": "mpnet_train_step", "towers": 5, "conv_layers": a.conv_layers, "dropout": a.dropout, "integral": K, "rows": IMAGES * ROWS,
                       "ms_step_median": round(float(np.median(step_ms)), 3), "ms_step_min": round(float(np.min(step_ms)), 3),
                       "ms_iteration_median": round(float(np.median(iter_ms)), 3), "gbytes_weights_and_momentum": round(gb, 2),
                       "floor_ms_at_6.3TBps": round(gb / 6.3e3 * 1e3, 3), "steps": a.steps, "device": torch.cuda.get_device_name(0)}), flush=True)
@@ -217,6 +219,7 @@ def main():
     ap.add_argument("--trunk-layers", type=int, default=0, help="also measure MPN_TRAIN_TRUNK(k) (9: conv3_1 and up, the reference's configuration)")
     ap.add_argument("--dropout", type=float, default=0.0, help="dropout rate behind fc6 / fc7 (0.5: the reference's default; 0: none)")
     ap.add_argument("--integral", type=int, default=1, help="K classifiers of the integral loss, trained in turn (6: the reference's scripts; 1: the plain head)")
+    ap.add_argument("--conv-layers", type=int, default=0, help="--model mpnet: also train the trunk's last k conv layers through the skip pooling (3: conv5_1 .. conv5_3)")
     ap.add_argument("--model", choices=("vgg", "mpnet"), default="vgg", help="mpnet: the tower training of a MultiPathNet handle (mpn_mpnet_train_*)")
     a = ap.parse_args()
     import torch
