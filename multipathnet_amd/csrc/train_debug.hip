@@ -281,6 +281,51 @@ extern "C" int mpn_debug_pack_conv_weights_wino(const float *d_w, size_t n_w, in
   }
   return pack_conv_weights_wino(d_w, Cin, Cout, d_wino, nullptr);
 }
+
+// tests/test_gpu_train_phase2_kernels_numerics.py (debug flavour only): the kernels between the mix layers and
+// the conv block (mpn_mpnet_train_begin_conv) under the same rules.
+// x, y, g, dx: one tower's conv5 slab [ceil(C/8)][PP][Mp][8] each
+extern "C" int mpn_debug_normalize_backward_c8(const float *d_x_c8, size_t n_x, const float *d_y_c8, size_t n_y, const float *d_g_c8, size_t n_g, float *d_dx_c8,
+                                               size_t n_dx, int Mp, int B, int C, int PP, float mul) {
+  if (B > 0 && Mp >= B && C > 0 && PP > 0) {
+    const size_t slab = (size_t)cdiv(C, 8) * PP * Mp * 8;
+    DBG_NEED(d_x_c8, n_x, slab);
+    DBG_NEED(d_y_c8, n_y, slab);
+    DBG_NEED(d_g_c8, n_g, slab);
+    DBG_NEED(d_dx_c8, n_dx, slab);
+  }
+  return normalize_backward_c8(d_x_c8, d_y_c8, d_g_c8, d_dx_c8, Mp, B, C, PP, mul, nullptr);
+}
+
+// The trainer's layout alone (layout 1 of mpn_debug_roi_pool_backward): g the C8 matrix at pitch Mp >= N, out the interior of ONE C8P map
+// as make_act lays it out; row n's window is d_rois + n * roi_stride.  B = 1 and by_batch = 0 are set here and n1 <= N is checked here
+// (the wrapper does not know N); a roi_stride below 5 and the window limits are the wrapper's to refuse.
+extern "C" int mpn_debug_roi_pool_backward_add(const float *d_g, size_t n_g, const int32_t *d_argmax, size_t n_argmax, const float *d_rois, size_t n_rois, int N,
+                                               int roi_stride, int Mp, int n0, int n1, int C, int H, int W, int PH, int PW, int windows, float scale,
+                                               int bin_rule, float *d_out, size_t n_out) {
+  MPN_CHECK_ARG(N > 0 && n0 >= 0 && n1 >= n0 && n1 <= N && Mp >= N && (bin_rule == 0 || bin_rule == 1));
+  RoiBwd a{};
+  if (C > 0 && H > 0 && W > 0 && PH > 0 && PW > 0) {
+    const size_t PP = (size_t)PH * PW;
+    if (roi_stride >= 5) DBG_NEED(d_rois, n_rois, (size_t)(N - 1) * roi_stride + 5);
+    DBG_NEED(d_argmax, n_argmax, (size_t)N * C * PP);
+    DBG_NEED(d_g, n_g, (size_t)cdiv(C, 8) * PP * Mp * 8);
+    DBG_NEED(d_out, n_out, dbg_act(C, H, W));
+    const Act G = make_act(d_out, C, H, W);
+    a.g_n = 8; a.g_cb = (long)PP * Mp * 8; a.g_c = 1; a.g_bin = (long)Mp * 8;
+    a.o_b = 0; a.o_cb = (long)G.plane(); a.o_c = 1; a.o_y = (long)G.Wp * 8; a.o_x = 8;
+    a.out = d_out ? G.p + ((size_t)G.Wp + 1) * 8 : nullptr;
+  }
+  a.g = d_g; a.argmax = d_argmax; a.rois = d_rois; a.by_batch = 0; a.n0 = n0; a.n1 = n1; a.B = 1; a.C = C; a.H = H; a.W = W; a.PH = PH; a.PW = PW;
+  a.windows = windows; a.scale = scale; a.rr = RoiRule{1.0f, 0, bin_rule};
+  return roi_pool_backward_add(a, roi_stride, nullptr);
+}
+
+extern "C" int mpn_debug_int_to_float(const int32_t *d_in, size_t n_in, size_t n, float *d_out, size_t n_out) {
+  DBG_NEED(d_in, n_in, n);
+  DBG_NEED(d_out, n_out, n);
+  return int_to_float(d_in, n, d_out, nullptr);
+}
 #undef DBG_NEED
 
 #endif

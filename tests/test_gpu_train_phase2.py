@@ -219,6 +219,18 @@ def test_gradient_against_float64(dev, name, case, norm):
     assert not bad, bad
 
 
+def test_last_layer_of_44_channels_is_refused(dev):
+    """Network D (a last conv layer of 44 channels, K = 1) was to run through test_gradient_against_float64 at B70_two_images.  No
+    handle is made for such a trunk: creation refuses feat_c % 8 != 0, before any training state exists.  So the driver never runs
+    the Normalize backward, the gather or the mix layer's input gradient with a pad lane in the conv5 slab; their C % 8 != 0 cases in
+    tests/test_gpu_train_phase2_kernels_numerics.py check the kernels' own contract."""
+    from multipathnet_amd._lib import MpnError
+    assert NETS["D"]["c5"] == 44 and NETS["D"]["cfg"][-1] == 44 and NETS["D"]["K"] == 1
+    with pytest.raises(MpnError) as e:
+        _net(P2.params("D"), "D")
+    assert "mpn_mpnet_create" in str(e.value) and "invalid argument: p->feat_c % 8 == 0" in str(e.value), str(e.value)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 2. three SGD steps (momentum 0.9, wd 5e-4): network C with dropout 0.5 and the classifiers alternating 0, 1, 0; network B plain.
 #    Then: a second fresh handle gives the same bits; a net rebuilt from the exported weights detects bit-identically; a graph

@@ -28,6 +28,8 @@ STD, MEAN = [0.1, 0.1, 0.2, 0.2], [0.0, 0.0, 0.0, 0.0]   # models.synthetic_para
 NETS = {
     "B": dict(cfg=[8, 16, "P", 16, 24, "P", 24, 24, "P", 40, "P", 48], c5=48, fc=256, C=7, K=1, k=1, layers=[7]),
     "C": dict(cfg=[8, 16, "P", 16, 24, "P", 24, 24, "P", 40, "P", 48, 12, 48], c5=48, fc=128, C=5, K=2, k=3, layers=[7, 8, 9]),
+    # a last layer of 44 channels: a handle refuses such a trunk (feat_c % 8), tests/test_gpu_train_phase2.py asserts the refusal
+    "D": dict(cfg=[8, 16, "P", 16, 24, "P", 24, 24, "P", 40, "P", 44], c5=44, fc=128, C=5, K=1, k=1, layers=[7]),
 }
 GRAD_BATCHES = {"B70_two_images": [(33, 9), (37, 11)], "B128_one_image": [(128, 40)], "B1": [(1, 0)]}
 _params = {}
@@ -128,24 +130,38 @@ def normalize_backward64(x, y, g, mul=MUL):
     return s[:, None, None] * (g - y * (d / (mul * mul))[:, None, None])
 
 
+def norm_entries(C, PP):
+    """E = ceil(C / 8) * PP * 8: the entries both sums walk (the slab's records times 8 lanes, pad lanes of the last channel block counted)"""
+    return -(-C // 8) * PP * 8
+
+
 def _entry_order(a):
-    """[B, c5, PP] -> [B, L, 256]: entry e = (c / 8 * PP + bin) * 8 + c % 8 at [e / 256, e % 256], zeros behind the last (c5 a multiple of 8)"""
-    B, c5, PP = a.shape
-    assert c5 % 8 == 0
-    e = a.reshape(B, c5 // 8, 8, PP).transpose(0, 1, 3, 2).reshape(B, -1)
+    """[B, C, PP] -> ([B, L, 256] values, [L, 256] bool `real`): entry e = (c / 8 * PP + bin) * 8 + c % 8 at [e / 256, e % 256], e <
+    ceil(C / 8) * PP * 8.  `real` is False at the pad lanes of the last channel block (c >= C) and behind the last entry: those are
+    SKIPPED by _fma_sum, not added as zeros (fma(0, 0, acc) would give the same bits; the kernel's `continue` is what is restated)."""
+    B, C, PP = a.shape
+    Cb = -(-C // 8)
+    full = np.zeros((B, Cb * 8, PP), a.dtype)
+    full[:, :C] = a
+    e = full.reshape(B, Cb, 8, PP).transpose(0, 1, 3, 2).reshape(B, -1)
+    ok = np.broadcast_to((np.arange(Cb * 8) < C).reshape(Cb, 1, 8), (Cb, PP, 8)).reshape(-1)
+    assert e.shape[1] == norm_entries(C, PP)
     L = -(-e.shape[1] // NORM_THREADS)
-    pad = np.zeros((B, L * NORM_THREADS), a.dtype)
-    pad[:, :e.shape[1]] = e
-    return pad.reshape(B, L, NORM_THREADS)
+    pad, real = np.zeros((B, L * NORM_THREADS), a.dtype), np.zeros(L * NORM_THREADS, bool)
+    pad[:, :e.shape[1]], real[:e.shape[1]] = e, ok
+    return pad.reshape(B, L, NORM_THREADS), real.reshape(L, NORM_THREADS)
 
 
 def _fma_sum(a, b):
-    """the stated order: 256 partial sums, partial t over the entries t, t + 256, .. ascending with one fused multiply-add each (the
-    product of two fp32 values is exact in float64; rounding the float64 sum to fp32 is the fma up to a double rounding), then the tree"""
-    A, Bv = _entry_order(np.asarray(a, F32)).astype(np.float64), _entry_order(np.asarray(b, F32)).astype(np.float64)
+    """the stated order: 256 partial sums, partial t over the entries t, t + 256, .. ascending with one fused multiply-add each, then the
+    tree.  The product of two fp32 values is exact in float64; the float64 sum product + partial is then rounded to fp32.  For operands
+    of full mantissa that is the fma only up to a double rounding (test_train_phase2_kernels_ref_cpu.py shows a counter-example); for
+    operands of at most 12 significant bits in [2^-6, 2^3] (bit_exact_draw) the float64 sum is exact and this IS the fma."""
+    (A, real), (Bv, _) = _entry_order(np.asarray(a, F32)), _entry_order(np.asarray(b, F32))
+    A, Bv = A.astype(np.float64), Bv.astype(np.float64)
     part = np.zeros((A.shape[0], NORM_THREADS), F32)
     for l in range(A.shape[1]):
-        part = (A[:, l] * Bv[:, l] + part.astype(np.float64)).astype(F32)
+        part = np.where(real[l][None, :], (A[:, l] * Bv[:, l] + part.astype(np.float64)).astype(F32), part)
     h = NORM_THREADS // 2
     while h >= 1:
         part = (part[:, :h] + part[:, h:2 * h]).astype(F32)
@@ -156,22 +172,29 @@ def _fma_sum(a, b):
 def normalize_backward_f32(x, y, g, mul=MUL):
     """train.h normalize_backward_c8 in numpy fp32, operation by operation"""
     x, y, g = (np.asarray(a, F32) for a in (x, y, g))
-    s = (F32(mul) / np.sqrt((_fma_sum(x, x) + F32(1e-10)).astype(F32)).astype(F32)).astype(F32)
-    coef = (_fma_sum(y, g) / F32(F32(mul) * F32(mul))).astype(F32)
+    return normalize_backward_tail(_fma_sum(x, x), _fma_sum(y, g), y, g, mul)
+
+
+def normalize_backward_tail(ss, d, y, g, mul=MUL):
+    """what the kernel does with its two sums ss = sum x^2 and d = sum y g ([B] fp32), operation by operation"""
+    ss, d, y, g = (np.asarray(a, F32) for a in (ss, d, y, g))
+    s = (F32(mul) / np.sqrt((ss + F32(1e-10)).astype(F32)).astype(F32)).astype(F32)
+    coef = (d / F32(F32(mul) * F32(mul))).astype(F32)
     inner = (g - (y * coef[:, None, None]).astype(F32)).astype(F32)
     return (s[:, None, None] * inner).astype(F32)
 
 
 def normalize_backward_bound(x, y, g, mul=MUL):
-    """Elementwise bound of |fp32 result - normalize_backward64| for fp32 inputs, from the stated order.  With E = c5 * PP entries a
-    partial sum is a chain of L = ceil(E / 256) fused multiply-adds and the tree adds 8 levels, so each sum carries at most L + 8
+    """Elementwise bound of |fp32 result - normalize_backward64| for fp32 inputs, from the stated order.  With E = ceil(C / 8) * PP * 8
+    entries (pad lanes counted: they take a slot of the walk, though no rounding) a partial sum is a chain of at most L = ceil(E / 256)
+    fused multiply-adds and the tree adds 8 levels, so each sum carries at most L + 8
     roundings: the sum of squares (all terms >= 0) a relative error (L + 8) u, the dot product an absolute error (L + 8) u sum|y g|.
       s:     (L + 8) u / 2 through the root, + u for the 1e-10 add, + u for the root, + u for the division        =: es (relative)
       coef:  D / mul^2, mul^2 exact, one division: relative u on top of D's absolute error dD = (L + 8) u sum|y g|
       inner: g - y coef: the product's u and the subtraction's u; dx = s * inner: u.
     |dx - dx64| <= (es + 2u) |dx64| + s |y| (2u |D| + dD) / mul^2, times 1.01 for the second-order terms."""
     x, y, g = (np.asarray(a, np.float64) for a in (x, y, g))
-    L = -(-(x.shape[1] * x.shape[2]) // NORM_THREADS)
+    L = -(-norm_entries(x.shape[1], x.shape[2]) // NORM_THREADS)
     n = L + 8
     s = mul / np.sqrt((x * x).sum((1, 2)) + 1e-10)
     D, aD = (y * g).sum((1, 2)), np.abs(y * g).sum((1, 2))
