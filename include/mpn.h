@@ -313,7 +313,7 @@ typedef struct mpn_frcnn_config {
   double tf_scale;         /* ImageTransformer: scale, mean[3], std[3] (std[0]==0 -> none), swap[3] */
   double tf_mean[3];
   double tf_std[3];
-  int tf_swap[3];
+  int tf_swap[3];         /* output channel j reads image plane tf_swap[j]; a value outside 0..2 is refused at create */
   float bbox_mean[4];      /* BBoxNorm (std[0]==0 -> module absent) */
   float bbox_std[4];
   float nms_thresh;        /* 0.3 */

@@ -56,7 +56,8 @@ int nchw_to_c8p(const float *d_in, int C, int H, int W, Act out, hipStream_t s);
 int c8p_to_nchw(Act in, float *d_out, hipStream_t s);
 int rowmajor_to_c8(const float *d_x, int M, int K, float *d_c8, hipStream_t s);
 int c8_to_rowmajor(const float *d_c8, int M, int N, float *d_y, hipStream_t s);
-// image transformer fused with the NCHW->C8P conversion (channels 3..7 zero)
+// image transformer fused with the NCHW->C8P conversion (channels 3..7 zero).  swap[j] is the image plane output channel j reads: taken as
+// given, the caller has checked 0 <= swap[j] < 3 (pipeline.hip check_config for the handles)
 int image_transform_c8p(const float *d_in, int H, int W, const int *swap, double scale, const double *mean,
                         const double *std, int has_std, Act out, hipStream_t s);
 // the same for one level of an image pyramid: the H x W image top-left in the out.H x out.W canvas, every other interior pixel 0

@@ -900,3 +900,21 @@ int heads_prepare_impl(ResNetGraph *g, int head, hipStream_t s) {
 extern "C" void mpn_debug_set_pool_exp(int v) { mpn::g_pool_exp = v; }
 extern "C" void mpn_debug_set_bf16_fast_pool(int v) { mpn::g_bf16_fast_pool = v; }
 #endif
+
+#ifdef MPN_DEBUG_HOOKS
+// tests/test_gpu_layout_kernels.py: c8i_to_pixel_major_kernel alone, with rn_roi_pool's grid.  Rules: layout_debug.h.
+#include "layout_debug.h"
+// one C x H x W map in C8I [ceil(C / 8)][pitch][8] -> [H * W][ceil(C / 8) * 8]
+extern "C" int mpn_debug_c8i_to_pixel_major(const float *d_c8i, size_t c8i_bytes, int C, int H, int W, float *d_pm, size_t pm_bytes) {
+  using namespace mpn;
+  MPN_CHECK_ARG(C > 0 && H > 0 && W > 0);
+  const ActI fa{const_cast<float *>(d_c8i), 1, C, H, W};
+  const int Cb = fa.Cb();
+  LDBG_BUF(d_c8i, c8i_bytes, (size_t)Cb * fa.pitch() * 8 * sizeof(float), 16);
+  LDBG_BUF(d_pm, pm_bytes, (size_t)H * W * Cb * 8 * sizeof(float), 16);
+  hipLaunchKernelGGL(c8i_to_pixel_major_kernel, dim3((unsigned)cdiv_sz((size_t)H * W * Cb * 2, 256)), dim3(256), 0, nullptr, d_c8i, Cb, (size_t)H * W, fa.pitch(),
+                     d_pm);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+#endif

@@ -401,6 +401,8 @@ static int check_config(const CreateArgs &a) {
   MPN_CHECK_ARG(cfg->pooled_h > 0 && cfg->pooled_w > 0 && cfg->n_classes > 1);
   MPN_CHECK_ARG(cfg->max_h > 0 && cfg->max_w > 0 && cfg->max_rois > 0 && cfg->max_rois <= MPN_NMS_MAX_BOXES);
   MPN_CHECK_ARG(cfg->top_k > 0);
+  // the image transforms (dense.h image_transform_c8p, the graph's rn_image_transform) index the image's three planes by tf_swap unchecked
+  for (int j = 0; j < 3; ++j) MPN_CHECK_ARG(cfg->tf_swap[j] >= 0 && cfg->tf_swap[j] < 3);
   if (!(cfg->fc_arith == MPN_FC_FP32 || (cfg->fc_arith == MPN_FC_SPLIT3 && !graph_net))) { set_error("mpn_frcnn_config.fc_arith: %d (MPN_FC_SPLIT3 is for mpn_frcnn_create / mpn_mpnet_create pipelines)", cfg->fc_arith); return MPN_EINVAL; }
   if (cfg->roi_bin_rule != MPN_ROI_BINS_CAFFE && cfg->roi_bin_rule != MPN_ROI_BINS_ADAPTIVE) { set_error("mpn_frcnn_config.roi_bin_rule: %d is not an MPN_ROI_BINS_* value", cfg->roi_bin_rule); return MPN_EINVAL; }
   for (int l = 0; !graph_net && l < cfg->n_conv; ++l) MPN_CHECK_ARG(a.conv_w[l] != nullptr);
@@ -2036,3 +2038,89 @@ extern "C" int mpn_frcnn_debug_tensor(mpn_frcnn *p, const char *name, const floa
   *n_elems = n;
   return MPN_OK;
 }
+
+#ifdef MPN_DEBUG_HOOKS
+// tests/test_gpu_layout_kernels.py: this file's glue kernels one launch at a time, with the grids their call
+// sites above use, on the null stream.  Rules: layout_debug.h.
+#include "layout_debug.h"
+
+// dst [M, ncols] = columns [col0, col0 + ncols) of src [M, ld]
+extern "C" int mpn_debug_copy_cols(const float *d_src, size_t src_bytes, int ld, int col0, int M, int ncols, float *d_dst, size_t dst_bytes) {
+  MPN_CHECK_ARG(M > 0 && ncols > 0 && col0 >= 0 && ld >= col0 + ncols);
+  LDBG_BUF(d_src, src_bytes, ((size_t)(M - 1) * ld + col0 + ncols) * sizeof(float), 4);
+  LDBG_BUF(d_dst, dst_bytes, (size_t)M * ncols * sizeof(float), 4);
+  const size_t n = (size_t)M * ncols;
+  hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)cdiv_sz(n, 256)), dim3(256), 0, nullptr, d_src, ld, col0, M, ncols, d_dst);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// rank `rank` of `world`: its tables sc [P * n_local, C], bb [P * n_local, 4C] (n_local from shard_bounds; null when it is 0) -> its
+// row record [P * chunk * 5C], chunk = ceil(N / world) as mpn_frcnn_shard_head computes it
+extern "C" int mpn_debug_shard_pack_rows(const float *d_sc, size_t sc_bytes, const float *d_bb, size_t bb_bytes, int N, int world, int rank, int P, int C,
+                                         float *d_rec, size_t rec_bytes) {
+  MPN_CHECK_ARG(N > 0 && world >= 1 && rank >= 0 && rank < world && P > 0 && C > 0);
+  const int chunk = (N + world - 1) / world;
+  int lo, hi;
+  shard_bounds(N, world, rank, &lo, &hi);
+  const int n_local = hi - lo;
+  if (n_local > 0) {
+    LDBG_BUF(d_sc, sc_bytes, (size_t)P * n_local * C * sizeof(float), 4);
+    LDBG_BUF(d_bb, bb_bytes, (size_t)P * n_local * 4 * C * sizeof(float), 4);
+  }
+  const size_t total = (size_t)P * chunk * 5 * C;
+  LDBG_BUF(d_rec, rec_bytes, total * sizeof(float), 4);
+  hipLaunchKernelGGL(shard_pack_rows_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, d_sc, d_bb, n_local, P, C, chunk, d_rec);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// all ranks' row records [world][P * chunk * 5C] -> sc [P * N, C], bb [P * N, 4C]
+extern "C" int mpn_debug_shard_unpack_rows(const float *d_all, size_t all_bytes, int N, int world, int P, int C, float *d_sc, size_t sc_bytes, float *d_bb,
+                                           size_t bb_bytes) {
+  MPN_CHECK_ARG(N > 0 && world >= 1 && P > 0 && C > 0);
+  const int chunk = (N + world - 1) / world;
+  const size_t rec_floats = (size_t)P * chunk * 5 * C, total = (size_t)P * N * 5 * C;
+  LDBG_BUF(d_all, all_bytes, (size_t)world * rec_floats * sizeof(float), 4);
+  LDBG_BUF(d_sc, sc_bytes, (size_t)P * N * C * sizeof(float), 4);
+  LDBG_BUF(d_bb, bb_bytes, (size_t)P * N * 4 * C * sizeof(float), 4);
+  hipLaunchKernelGGL(shard_unpack_rows_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, d_all, N, world, P, C, chunk, rec_floats, d_sc, d_bb);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// keep / voted [n_cls, rows, 5], kidx [n_cls, rows], n_keep [n_cls] -> the class record of `rank` (shard_class_rec_floats); d_voted null: no voting
+extern "C" int mpn_debug_shard_pack_classes(const float *d_keep, size_t keep_bytes, const int *d_kidx, size_t kidx_bytes, const int *d_n_keep,
+                                            size_t n_keep_bytes, const float *d_voted, size_t voted_bytes, int n_cls, int world, int rank, int rows,
+                                            float *d_rec, size_t rec_bytes) {
+  MPN_CHECK_ARG(n_cls > 0 && world >= 1 && rank >= 0 && rank < world && rows > 0 && n_cls <= 65535);
+  const int cmax = (n_cls + world - 1) / world;
+  int c0, c1;
+  shard_bounds(n_cls, world, rank, &c0, &c1);
+  LDBG_BUF(d_keep, keep_bytes, (size_t)n_cls * rows * 5 * sizeof(float), 4);
+  LDBG_BUF(d_kidx, kidx_bytes, (size_t)n_cls * rows * sizeof(int), 4);
+  LDBG_BUF(d_n_keep, n_keep_bytes, (size_t)n_cls * sizeof(int), 4);
+  if (d_voted) LDBG_BUF(d_voted, voted_bytes, (size_t)n_cls * rows * 5 * sizeof(float), 4);
+  LDBG_BUF(d_rec, rec_bytes, shard_class_rec_floats(cmax, rows, d_voted != nullptr) * sizeof(float), 4);
+  hipLaunchKernelGGL(shard_pack_classes_kernel, dim3(cdiv(rows, 256), cmax), dim3(256), 0, nullptr, d_keep, d_kidx, d_n_keep, d_voted, c0, c1, rows, cmax, d_rec);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// all ranks' class records -> the per-class tables
+extern "C" int mpn_debug_shard_unpack_classes(const float *d_all, size_t all_bytes, int n_cls, int world, int rows, float *d_keep, size_t keep_bytes,
+                                              int *d_kidx, size_t kidx_bytes, int *d_n_keep, size_t n_keep_bytes, float *d_voted, size_t voted_bytes) {
+  MPN_CHECK_ARG(n_cls > 0 && world >= 1 && rows > 0 && n_cls <= 65535);
+  const int cmax = (n_cls + world - 1) / world;
+  const size_t rec_floats = shard_class_rec_floats(cmax, rows, d_voted != nullptr);
+  LDBG_BUF(d_all, all_bytes, (size_t)world * rec_floats * sizeof(float), 4);
+  LDBG_BUF(d_keep, keep_bytes, (size_t)n_cls * rows * 5 * sizeof(float), 4);
+  LDBG_BUF(d_kidx, kidx_bytes, (size_t)n_cls * rows * sizeof(int), 4);
+  LDBG_BUF(d_n_keep, n_keep_bytes, (size_t)n_cls * sizeof(int), 4);
+  if (d_voted) LDBG_BUF(d_voted, voted_bytes, (size_t)n_cls * rows * 5 * sizeof(float), 4);
+  hipLaunchKernelGGL(shard_unpack_classes_kernel, dim3(cdiv(rows, 256), n_cls), dim3(256), 0, nullptr, d_all, n_cls, world, rows, cmax, rec_floats, d_keep,
+                     d_kidx, d_n_keep, d_voted);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+#endif

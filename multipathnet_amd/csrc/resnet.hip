@@ -2854,3 +2854,83 @@ extern "C" void mpn_debug_set_fp32_pf(int v) { mpn::g_fp32_pf = v; }
 extern "C" void mpn_debug_set_bf16_trace(void *p, int kh) { mpn::g_bf16_trace = static_cast<unsigned long long *>(p); mpn::g_bf16_trace_kh = kh; }
 extern "C" void mpn_debug_set_split_max_tiles(int v) { mpn::g_split_max_tiles = v; }
 #endif
+
+#ifdef MPN_DEBUG_HOOKS
+// tests/test_gpu_layout_kernels.py: this file's layout and packing kernels one launch at a time, with the grids
+// rn_pack and rn_conv use, on the null stream.  Rules: layout_debug.h.
+#include "layout_debug.h"
+
+// N maps of C x H x W in C8I (pitch = N * H * W rounded up to 128) <-> the mosaic laid out for `cap` >= N maps, mx per mosaic row:
+// a C8P image of mos_rows = ceil(cap / mx) * (H + 1) by mos_cols = mx * (W + 1) pixels.  to_mosaic = 1: c8i_to_mosaic_kernel, 0: back.
+extern "C" int mpn_debug_c8i_mosaic(float *d_c8i, size_t c8i_bytes, float *d_mos, size_t mos_bytes, int C, int N, int cap, int H, int W, int mx, int to_mosaic) {
+  using namespace mpn;
+  MPN_CHECK_ARG(C > 0 && N > 0 && cap >= N && H > 0 && W > 0 && mx > 0 && (to_mosaic == 0 || to_mosaic == 1));
+  const ActI in{d_c8i, N, C, H, W};
+  const int mos_rows = ((cap + mx - 1) / mx) * (H + 1), mos_cols = mx * (W + 1);
+  const int Hp = act_hp(mos_rows), Wp = act_wp(mos_cols);
+  LDBG_BUF(d_c8i, c8i_bytes, (size_t)in.Cb() * in.pitch() * 8 * sizeof(float), 16);
+  LDBG_BUF(d_mos, mos_bytes, act_bytes(C, mos_rows, mos_cols), 16);
+  const size_t recs = (size_t)N * H * W;
+  if (to_mosaic)
+    hipLaunchKernelGGL(c8i_to_mosaic_kernel, dim3((unsigned)cdiv_sz(recs * in.Cb() * 2, 256)), dim3(256), 0, nullptr, d_c8i, in.Cb(), N, H, W, in.pitch(), mx, Hp, Wp,
+                       d_mos);
+  else
+    hipLaunchKernelGGL(mosaic_to_c8i_kernel, dim3((unsigned)cdiv_sz(recs * in.Cb() * 2, 256)), dim3(256), 0, nullptr, d_mos, in.Cb(), N, H, W, mx, Hp, Wp, in.pitch(),
+                       d_c8i);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// d_img [3][H][W] -> the C8 matrix [round_up(KH * KW * 3, 64) / 8][pitch = OH * OW rounded up to 128][8]
+extern "C" int mpn_debug_im2col3_c8i(const float *d_img, size_t img_bytes, int H, int W, int KH, int KW, int stride, int pad, float *d_col, size_t col_bytes) {
+  using namespace mpn;
+  MPN_CHECK_ARG(H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && H + 2 * pad >= KH && W + 2 * pad >= KW);
+  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
+  const int nkb = round_up(KH * KW * 3, 64) / 8;
+  const size_t P = (size_t)OH * OW, pitch = (P + 127) / 128 * 128;
+  LDBG_BUF(d_img, img_bytes, (size_t)3 * H * W * sizeof(float), 4);
+  LDBG_BUF(d_col, col_bytes, (size_t)nkb * pitch * 8 * sizeof(float), 16);
+  hipLaunchKernelGGL(im2col3_c8i_kernel, dim3((unsigned)cdiv_sz(P * nkb, 256)), dim3(256), 0, nullptr, d_img, H, W, KH, KW, stride, stride, pad, pad, OH, OW, nkb, pitch,
+                     d_col);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// d_w [Cout][3][KK] -> d_o [Cout][KK * 3]
+extern "C" int mpn_debug_permute_w3(const float *d_w, size_t w_bytes, int Cout, int KK, float *d_o, size_t o_bytes) {
+  using namespace mpn;
+  MPN_CHECK_ARG(Cout > 0 && KK > 0);
+  LDBG_BUF(d_w, w_bytes, (size_t)Cout * 3 * KK * sizeof(float), 4);
+  LDBG_BUF(d_o, o_bytes, (size_t)Cout * 3 * KK * sizeof(float), 4);
+  hipLaunchKernelGGL(permute_w3_kernel, dim3((unsigned)cdiv(Cout * KK * 3, 256)), dim3(256), 0, nullptr, d_w, Cout, KK, d_o);
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+
+// d_w [Cout][Cin][KK], d_b [Cout] or null -> fp32: d_wpk [KK][ceil(Cin / 8)][CoutP][8] floats and d_bpk [CoutP];
+// bf16: d_wpk [KK][nch2][CoutP][8] 16-bit values, nch2 = ceil(Cin / 8) rounded up to even (rn_pack fills the bias by copies: d_b, d_bpk unused)
+extern "C" int mpn_debug_pack_conv_graph(const float *d_w, size_t w_bytes, const float *d_b, size_t b_bytes, int Cin, int Cout, int KK, int bf16, void *d_wpk,
+                                         size_t wpk_bytes, float *d_bpk, size_t bpk_bytes) {
+  using namespace mpn;
+  MPN_CHECK_ARG(Cin > 0 && Cout > 0 && KK > 0 && (bf16 == 0 || bf16 == 1));
+  const int CoutP = round_up(Cout, 128);
+  LDBG_BUF(d_w, w_bytes, (size_t)Cout * Cin * KK * sizeof(float), 4);
+  if (bf16) {
+    const int nch2 = round_up((Cin + 7) / 8, 2);
+    const size_t total = (size_t)KK * nch2 * CoutP * 8;
+    LDBG_BUF(d_wpk, wpk_bytes, total * sizeof(bf16_t), 2);
+    hipLaunchKernelGGL(pack_conv_bf16_kernel, dim3((unsigned)cdiv_sz(total, 256)), dim3(256), 0, nullptr, d_w, Cin, Cout, KK, nch2, CoutP, static_cast<bf16_t *>(d_wpk));
+  } else {
+    const int nch = (Cin + 7) / 8;
+    const size_t total = (size_t)KK * nch * CoutP * 8;
+    if (d_b) LDBG_BUF(d_b, b_bytes, (size_t)Cout * sizeof(float), 4);
+    LDBG_BUF(d_wpk, wpk_bytes, total * sizeof(float), 4);
+    LDBG_BUF(d_bpk, bpk_bytes, (size_t)CoutP * sizeof(float), 4);
+    const size_t threads = total > (size_t)CoutP ? total : (size_t)CoutP;
+    hipLaunchKernelGGL(pack_conv_generic_kernel, dim3((unsigned)cdiv_sz(threads, 256)), dim3(256), 0, nullptr, d_w, d_b, Cin, Cout, KK, nch, CoutP,
+                       static_cast<float *>(d_wpk), d_bpk);
+  }
+  MPN_CHECK_LAUNCH();
+  return MPN_OK;
+}
+#endif
