@@ -269,7 +269,10 @@ int mpn_select_scored(const float *d_scores, const float *d_bbox, int N, int C, 
  * Writes *d_thresh (device float) and compacts survivors into d_out [max_out, 6] =
  * {x1,y1,x2,y2,score,class(1-based, as float)} class-major.  *d_n_out receives the UNTRUNCATED number of survivors:
  * when it exceeds max_out (many ties at the threshold), only the first max_out rows were written and the caller
- * knows rows were dropped (utils.keep_top_k itself never truncates). */
+ * knows rows were dropped (utils.keep_top_k itself never truncates).
+ * Arguments: k >= 1, 0 <= n_cls <= 1024, m_stride >= 0, max_out >= 0; anything else answers MPN_EINVAL and launches nothing
+ * (both entries).  Counts above m_stride are read as m_stride, negative counts as 0.  -0.0f and 0.0f are one score.  NaN scores
+ * are not supported: utils.keep_top_k sorts them with a comparison that gives no defined order. */
 int mpn_keep_top_k(const float *d_keep, const int *d_n_keep, int n_cls, int m_stride, int k, float *d_thresh,
                    float *d_out, int max_out, int *d_n_out, void *stream);
 /* The same on tables whose rows are in NON-INCREASING score order inside every class — what mpn_nms_batched emits (each greedy round picks the

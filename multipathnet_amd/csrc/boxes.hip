@@ -223,6 +223,15 @@ constexpr int kTopkLdsKeys = 32768;  // 128 KiB of the CU's 160 KiB
 constexpr int kTopkMaxCls = 1024;
 constexpr int kTopkCand = 2048;   // keep_top_k: candidate list of the radix select (keys of the bin the first pass picked)
 
+// The upper end of the bin the radix select narrowed to: lo = the bin's first key (a key of the bin exists, so lo <= hi).  Written as a
+// comparison of DISTANCES: `min(hi, lo + (1 << shift) - 1)` wraps past 2^32 when the keys' range is at least 2^31 wide (shift = 24) and the
+// bin starts above 0xff000000 — scores from -1.0 to +inf, say — which left hi < lo, ended the select a pass early and returned the bin's
+// lowest key (FLT_MAX's, with +inf in the same bin) as the threshold.
+__device__ __forceinline__ unsigned topk_bin_hi(unsigned lo, unsigned hi, int shift) {
+  const unsigned span = (1u << shift) - 1u;
+  return hi - lo > span ? lo + span : hi;
+}
+
 __device__ __forceinline__ int topk_class_of(const int *__restrict__ cls_off, int n_cls, int i) {  // last c with cls_off[c] <= i
   int lo = 0, hi = n_cls - 1;
   while (lo < hi) {
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(1024) void keep_top_k_kernel(const float *__restric
     }
     __syncthreads();
     lo += sel_bin << shift;
-    hi = min(hi, lo + ((1u << shift) - 1u));
+    hi = topk_bin_hi(lo, hi, shift);
     // (the next pass's hist zeroing is ordered after every thread's read of sel_bin by the barrier that follows it)
     if (!use_cand && hi > lo && sel_cnt <= (unsigned)kTopkCand) {
       for (int i = tid; i < total; i += blockDim.x) {
@@ -514,7 +523,7 @@ __global__ __launch_bounds__(1024) void keep_top_k_sorted_kernel(const float *__
     }
     __syncthreads();
     lo += sel_bin << shift;
-    hi = min(hi, lo + ((1u << shift) - 1u));
+    hi = topk_bin_hi(lo, hi, shift);
     __syncthreads();  // every thread has read sel_bin before the next pass rewrites it
   }
   const unsigned thr_key = lo;

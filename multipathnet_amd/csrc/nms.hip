@@ -148,6 +148,15 @@ __device__ __forceinline__ unsigned nms_f2key(float f) {
   unsigned u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// The ONE sort key of every NMS form (the chain's sort, the dense rank kernel, the fused kernel): ascending key = descending score, then
+// ascending row.  -0.0f and 0.0f are EQUAL for nms.c:77's '>' (and for a stable sort on the score): they get one key, so that a +-0 pair is
+// a TIED pair — counted in `bad`, flagged, and resolved by the array order in the tie paths, whose run tests compare floats — instead of
+// every +0.0 row sorting before every -0.0 row.
+__device__ __forceinline__ unsigned long long nms_sort_key(float s, unsigned row) {
+  unsigned u = __float_as_uint(s);
+  if ((u << 1) == 0u) u = 0u;
+  return ((unsigned long long)(~nms_f2key(__uint_as_float(u))) << 32) | row;
+}
 
 constexpr int kSortMax = 8192;  // 64 KiB of LDS keys
 constexpr int kTieMax = 4096;   // nms_tie_kernel: one 64-bit alive/occupancy word per lane
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(const float *__restrict_
     if (i < m) {
       float s = src[5 * (size_t)i + 4];
       if (s != s) hasnan = 1;  // NaN: let the exact sweep kernel reproduce the reference's behaviour
-      k = ((unsigned long long)(~nms_f2key(s)) << 32) | (unsigned)i;
+      k = nms_sort_key(s, (unsigned)i);
     }
     keys[i] = k;
   }
@@ -1227,10 +1236,8 @@ __global__ __launch_bounds__(1024) void nms_fused_kernel(const float *__restrict
   u64 key = ~0ull;
   if (tid < m) {
     const float sc = src[5 * (size_t)tid + 4];
-    unsigned u = __float_as_uint(sc);
-    if ((u << 1) == 0u) u = 0u;          // -0.0f and 0.0f are EQUAL for nms.c:77's '>': one key, so that the array order decides between them
-    if (sc != sc) u = 0xff800000u;       // a NaN score is never picked (nms.c:77: `NaN > bestS` is false): it sorts with the unpickable rows, as -inf
-    key = ((u64)(~nms_f2key(__uint_as_float(u))) << 32) | (unsigned)tid;
+    // a NaN score is never picked (nms.c:77: `NaN > bestS` is false): it sorts with the unpickable rows, as -inf
+    key = nms_sort_key(sc != sc ? __uint_as_float(0xff800000u) : sc, (unsigned)tid);  // (-0.0f and 0.0f share a key: nms_sort_key)
   }
   FUSED_STAMP(1);
   for (int k = 2; k <= nt; k <<= 1)
@@ -1720,12 +1727,12 @@ __global__ __launch_bounds__(256) void dense_rank_scatter_kernel(const float *__
   __shared__ unsigned long long tile[1024];
   const int i = blockIdx.x * 256 + threadIdx.x;
   unsigned long long mine = ~0ull;
-  if (i < m) mine = ((unsigned long long)(~nms_f2key(scored[5 * (size_t)i + 4])) << 32) | (unsigned)i;
+  if (i < m) mine = nms_sort_key(scored[5 * (size_t)i + 4], (unsigned)i);
   int rank = 0;
   for (int j0 = 0; j0 < m; j0 += 1024) {
     for (int t = threadIdx.x; t < 1024; t += 256) {
       const int j = j0 + t;
-      tile[t] = j < m ? (((unsigned long long)(~nms_f2key(scored[5 * (size_t)j + 4])) << 32) | (unsigned)j) : ~0ull;
+      tile[t] = j < m ? nms_sort_key(scored[5 * (size_t)j + 4], (unsigned)j) : ~0ull;
     }
     __syncthreads();
     const int n = min(1024, m - j0);
